@@ -363,6 +363,7 @@ class ScoreLoop:
         self.pending = [None] * nbuf
         self._gather_ms = None
         self.graph, self.G = None, 8
+        self.last = None   # the score rows the most recent step wrote (`outputs`)
         if gather == "graph":
             if SAME_GPU:   # the rehearsal's host-buffer gather cannot be captured
                 _fault("capture")
@@ -436,12 +437,14 @@ class ScoreLoop:
         if self.gather == "graph":  # a stray step outside whole replays: in order
             self._launch(self.local[0])
             gather_scores(self.full[0], self.local[0])
+            self.last = self.local[0]
             return
         b = (i // K) % len(self.local)
         if self.overlap and i % K == 0 and self.pending[b] is not None:
             self.pending[b].wait()  # this buffer's previous gather must be done before the sweep rewrites it (a stream wait)
             self.pending[b] = None
         out = self.local[b][(i % K) * B:(i % K + 1) * B]
+        self.last = out
         st = Ct.c_void_p(torch.cuda.current_stream(self.dev).cuda_stream)
         self._lib.check(self.lib.dcx_score_grad(w["model"]._h, self.qp, B, None, Ct.c_void_p(out.data_ptr()), self.gp, st))
         if self.gather == "none" or not (i % K == K - 1 or i == last):
@@ -466,6 +469,8 @@ class ScoreLoop:
         if self.graph is not None:
             for _ in range(n // self.G):
                 self.graph.replay()
+            if n >= self.G:
+                self.last = self.local[(self.G - 1) % 2]
             n = n % self.G
         for i in range(n):
             self.step(i, n - 1)
@@ -487,6 +492,10 @@ class ScoreLoop:
             torch.cuda.synchronize(self.dev)
             self._gather_ms = e0.elapsed_time(e1) / n
         return self._gather_ms
+
+    def outputs(self):
+        """what a caller of dcx_score_grad receives from the last step: this rank's scores [B, C] and gradient [B, dof]"""
+        return {"scores": self.last, "grad": self.grad}
 
 
 class TrajLoop:
@@ -516,6 +525,14 @@ class TrajLoop:
 
     def gather_ms(self):
         return None
+
+    def outputs(self):
+        """what ShardedAdamRun.finish() handed back after the last step, and the paths the iterations left.  They depend on
+        every iteration run so far, the untimed settle iterations included (their number comes from a timing): `iterations`
+        says how many that was"""
+        summ, bvp, lop = self.summary
+        return {"summaries": summ, "best_valid_path": bvp, "lowest_path": lop, "path": self.run_obj.t["path"],
+                "iterations": torch.tensor([self.run_obj.it], dtype=torch.float64)}
 
 
 def hwmon_read(dev_index=0):
@@ -735,6 +752,29 @@ def cold_launch_us(loop, dev, n=20, idle_s=1.0, rounds=3):
             "mean_first": round(sum(a for a, _ in res) / len(res), 2), "settled": round(settled, 2),
             "what": "the headline launch right after the GPU sat idle: mean of the first / next 20 launches, and 20 launches behind "
                     f"{SETTLE_MS:.0f} ms of load (what `value` is measured at)"}
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(loop, dirpath):
+    """--dump-outputs: the arrays of the loop's last step as DIR/<name>.npy (float32, float64 where the path computed float64).
+    Beyond DUMP_LIMIT_BYTES in all, every array keeps the same fixed, seeded sample of its rows (DIR/rows.npy holds their
+    indices); the inputs come from fixed seeds, so two builds given the same arguments can be compared file for file."""
+    arrs = {}
+    for k, v in loop.outputs().items():
+        a = v.detach().cpu().numpy() if torch.is_tensor(v) else np.asarray(v)
+        arrs[k] = a.astype(np.float64 if a.dtype == np.float64 else np.float32)
+    total = sum(a.nbytes for a in arrs.values())
+    if total > DUMP_LIMIT_BYTES:
+        n = max(a.shape[0] for a in arrs.values())
+        keep = max(1, int(n * DUMP_LIMIT_BYTES / (total + 8 * n)))   # (rows.npy counts too)
+        rows = np.sort(np.random.default_rng(12345).choice(n, size=keep, replace=False))
+        arrs = {k: (a[rows] if a.shape[0] == n else a) for k, a in arrs.items()}
+        arrs["rows"] = rows.astype(np.float64)
+    os.makedirs(dirpath, exist_ok=True)
+    for k, a in arrs.items():
+        np.save(os.path.join(dirpath, k + ".npy"), a)
 
 
 def measure(loop, steps, warmup, dev, multi):
@@ -1041,7 +1081,12 @@ def main():
                     help="headline, N=1: skip the short measurements of the other BASELINE configurations (`configs` in the line)")
     ap.add_argument("--force-dist", action="store_true",
                     help="exercise the N>1 code path (process group + all-gather) even with one rank")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed (rank 0's scores and gradient; config #5: "
+                         "the run's summaries and paths) as DIR/<name>.npy, at most 64 MB in all")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
     if args.no_gather:
         args.gather = "none"
 
@@ -1114,6 +1159,8 @@ def main():
 
     w, loop = build(args.scaling, args.gather)
     wall, kern_ms, n_settle = measure(loop, args.steps, args.warmup, dev, multi)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(loop, args.dump_outputs)
     gather_ms = loop.gather_ms()
     B, C, dof = w["B"], w["C"], w["dof"]
 

@@ -139,10 +139,15 @@ def test_tree_description_is_validated_before_any_device_work():
                                              dict(type=fd.DCX_J_PRISMATIC, q=1, fixed=ident, axis=(0, 0, 1))])],
                             [(0, 0, (0, 0, 0)), (0, 1, (0.1, 0, 0))])
 
+    # a well-formed tree is launched where a GPU exists: q and X must then be device memory, not a host buffer
+    buf = torch.zeros(64, device="cuda") if torch.cuda.is_available() else (ctypes.c_float * 64)()
+    p = ctypes.c_void_p(buf.data_ptr()) if torch.is_tensor(buf) else ctypes.cast(buf, ctypes.c_void_p)
+
     def rc_of(desc):
-        buf = (ctypes.c_float * 64)()
-        p = ctypes.cast(buf, ctypes.c_void_p)
-        return lib.dcx_fkine(0, ctypes.byref(desc), p, 1, p, None), lib.dcx_last_error().decode()
+        rc = lib.dcx_fkine(0, ctypes.byref(desc), p, 1, p, None)
+        if torch.is_tensor(buf):
+            torch.cuda.synchronize()
+        return rc, lib.dcx_last_error().decode()
 
     rc, msg = rc_of(good())
     assert rc in (0, 4), msg  # fine, or "no device" on a CPU box — never an argument error

@@ -59,3 +59,27 @@ def test_bare_gpus_n_becomes_its_own_launcher():
     assert r.returncode != 0 and r.stdout.strip() == ""
     assert "local_rank: 0" in r.stderr and "local_rank: 1" in r.stderr, r.stderr[-1500:]
     assert "no CPU fallback" in r.stderr
+
+
+def test_dump_outputs_keep_a_fixed_sample_under_the_limit(tmp_path, monkeypatch):
+    """bench.dump_outputs: float32 .npy per array; beyond the size limit every array keeps the same seeded rows (rows.npy)"""
+    import numpy as np
+    import torch
+    sys.path.insert(0, ROOT)
+    import bench
+
+    class Loop:
+        def outputs(self):
+            return {"scores": torch.arange(1000.0).reshape(1000, 1), "grad": torch.arange(7000.0, dtype=torch.float64).reshape(1000, 7)}
+    bench.dump_outputs(Loop(), str(tmp_path / "full"))
+    full = {k: np.load(tmp_path / "full" / f"{k}.npy") for k in ("scores", "grad")}
+    assert sorted(os.listdir(tmp_path / "full")) == ["grad.npy", "scores.npy"]
+    assert full["scores"].dtype == np.float32 and full["grad"].dtype == np.float64 and full["grad"].shape == (1000, 7)
+    monkeypatch.setattr(bench, "DUMP_LIMIT_BYTES", 20000)
+    for run in ("a", "b"):
+        bench.dump_outputs(Loop(), str(tmp_path / run))
+    a, b = ({k: np.load(tmp_path / run / f"{k}.npy") for k in ("scores", "grad", "rows")} for run in ("a", "b"))
+    assert sum(v.nbytes for v in a.values()) <= 20000 and all(np.array_equal(a[k], b[k]) for k in a)
+    rows = a["rows"].astype(np.int64)
+    assert len(rows) > 100 and np.all(np.diff(rows) > 0)
+    assert np.array_equal(a["scores"], full["scores"][rows]) and np.array_equal(a["grad"], full["grad"][rows])

@@ -236,3 +236,33 @@ def test_the_line_survives_a_hang_in_the_side_measurements():
     assert r.returncode == 0, r.stderr[-2000:]
     d = _one_line(r.stdout)
     assert d["n_gpus"] == 2 and d["multi"]["ranks"] == 2 and d["value"] > 0 and "variants" not in d
+
+
+def test_dump_outputs_are_the_last_steps_results(tmp_path):
+    """--dump-outputs DIR: the scores and gradient the timed path computed in its last step, as float32 .npy files; the
+    same arguments give the same files, and they match the CPU oracle on the workload's (seeded) inputs"""
+    import numpy as np
+    import torch
+    sys.path.insert(0, ROOT)
+    import bench
+    from oracle import oracle
+    args = ["--no-cpu-baseline", "--no-configs", "--workload", "cfg2", "--batch", "4096"]
+    dumps = []
+    for run, steps in (("a", 7), ("b", 13)):
+        d = _run(args + ["--dump-outputs", str(tmp_path / run)], steps=steps)
+        assert d["steps"] == steps and d["ms_per_step"] > 0
+        dumps.append({k: np.load(tmp_path / run / f"{k}.npy") for k in ("scores", "grad")})
+    a, b = dumps
+    assert sorted(os.listdir(tmp_path / "a")) == ["grad.npy", "scores.npy"]
+    assert a["scores"].shape == (4096, 1) and a["grad"].shape == (4096, 7) and a["scores"].dtype == np.float32
+    assert all(np.array_equal(a[k], b[k]) for k in a)
+    w = bench.make_workload("cfg2", 4096, torch.device("cuda"))
+    so, go, _ = oracle.score_grad(w["desc"], *w["kspec"], w["sup"].cpu().numpy(), w["W"].numpy(), w["q_cpu"].numpy())
+    for got, want in ((a["scores"], so), (a["grad"], go)):
+        assert np.abs(got - want).max() <= 1e-5 * np.abs(want).max()
+    # config #5: what ShardedAdamRun.finish() hands back, the paths, and how many iterations produced them
+    _run(["--no-cpu-baseline", "--no-configs", "--workload", "cfg5", "--dump-outputs", str(tmp_path / "traj")])
+    t = {f[:-4]: np.load(tmp_path / "traj" / f) for f in os.listdir(tmp_path / "traj")}
+    assert sorted(t) == ["best_valid_path", "iterations", "lowest_path", "path", "summaries"]
+    assert t["summaries"].shape == (256, 4) and t["path"].shape == t["lowest_path"].shape == (256, 50, 7)
+    assert t["iterations"].dtype == np.float64 and t["iterations"][0] >= 10 + 3 and np.isfinite(t["path"]).all()
