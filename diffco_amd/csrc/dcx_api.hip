@@ -27,16 +27,12 @@ struct dcx_model {
     float* rows_dev = nullptr;     // [S_active][RS]
     float* rows_p2_dev = nullptr;  // the PAIR-INTERLEAVED copy of rows_dev the two-rows-per-instruction sweeps read (score_kernel.h pair2,
                                    // p2_applies models only; padded to an even row count with a zero-weight row)
-    float* rows_x2_dev = nullptr;  // the pair-interleaved copy of rows_xf_dev for the expanded sweeps that take two rows per packed
-                                   // instruction (score_kernel.h X2, x2_applies models only)
     float* rows_xf_dev = nullptr;  // what the expanded-form sweeps read (score_kernel.h): the rows shifted by `centre`,
                                    // |s - c|^2 in their last column
-    unsigned short* aplanes_dev = nullptr;  // XM sweep (score_kernel.h): the centred supports as bf16 planes, MFMA A-operand layout
     float* centre_dev = nullptr;   // [Dt]: the support centroid for features an FK transform produced, zero for raw inputs
     int64_t S_in = 0;
     int32_t S_active = 0;
     int64_t cap = 0;               // supports the row storage holds (dcx_model_create_ex capacity; dcx_model_update refills in place)
-    size_t aplanes_cap = 0;
     float fold = 1.0f;             // factor folded into the row weights: 1/eps (Polyharmonic(1)), (2/gamma)^2 (RQ2), else 1
     int32_t* info_dev = nullptr;   // 16 bytes the packing kernel reports in (kept rows, max |s - c|^2) ...
     int32_t* info_host = nullptr;  // ... and their pinned host copy
@@ -274,7 +270,7 @@ int fk_device_copy(int device, const dcx_fk_desc& fk, FkProg** out) {
 // path calls getenv.  -1 = "use the rule".
 struct Knobs {
     std::atomic<int64_t> ys{-1}, nw{-1}, min_rows{-1}, split_finish_kernel{-1}, inlaunch_tiles{-1}, jac_per_class{-1},
-        mfma{-1}, traj_fused{-1}, xf{-1}, jac_one_sweep{-1}, train_grid{-1}, fkk{-1}, jt_waves{-1}, hess_ys{-1}, hess_form{-1}, xm{-1},
+        traj_fused{-1}, xf{-1}, jac_one_sweep{-1}, train_grid{-1}, fkk{-1}, jt_waves{-1}, hess_ys{-1}, hess_form{-1},
         traj_ys{-1}, traj_across{-1}, owner_poll{-1}, solve_threads{-1}, qt{-1}, giveup_inject{-1}, skew{-1}, skew8{-1};
     Knobs() {
         auto rd = [](const char* name, std::atomic<int64_t>& dst, bool flag) {
@@ -286,7 +282,6 @@ struct Knobs {
         rd("DCX_SPLIT_FINISH_KERNEL", split_finish_kernel, true);
         rd("DCX_INLAUNCH_TILES", inlaunch_tiles, false);
         rd("DCX_JAC_PER_CLASS", jac_per_class, true);
-        rd("DCX_MFMA", mfma, false);
         rd("DCX_TRAJ_FUSED", traj_fused, false);
         rd("DCX_XF", xf, false);
         rd("DCX_JAC_ONE_SWEEP", jac_one_sweep, false);
@@ -295,7 +290,6 @@ struct Knobs {
         rd("DCX_JT_WAVES", jt_waves, false);
         rd("DCX_HESS_YS", hess_ys, false);
         rd("DCX_HESS_FORM", hess_form, false);
-        rd("DCX_XM", xm, false);
         rd("DCX_TRAJ_YS", traj_ys, false);
         rd("DCX_TRAJ_ACROSS", traj_across, false);
         rd("DCX_OWNER_POLL", owner_poll, false);
@@ -303,10 +297,6 @@ struct Knobs {
         rd("DCX_QT", qt, false);
         rd("DCX_SKEW", skew, false);
         rd("DCX_SKEW8", skew8, false);
-#ifndef DCX_WITH_MATRIX_FORMS
-        if (mfma > 0) mfma = -1;   // (forms this build does not carry)
-        if (xm > 0) xm = -1;
-#endif
     }
 };
 Knobs& knobs() {
@@ -591,7 +581,7 @@ int run_score(const dcx_model* m, const float* q, int64_t B, const float* upstre
     size_t qt_lds = 0;
     // (a knob that asks for a particular form of the split launch or of the sweep - tests, A/B tools - is honoured: the rule yields)
     const Knobs& kn0 = knobs();
-    const bool asked_otherwise = kn0.ys >= 1 || kn0.xf >= 0 || kn0.mfma > 0 || kn0.xm > 0 || kn0.owner_poll >= 0 || kn0.split_finish_kernel > 0 ||
+    const bool asked_otherwise = kn0.ys >= 1 || kn0.xf >= 0 || kn0.owner_poll >= 0 || kn0.split_finish_kernel > 0 ||
                                  kn0.inlaunch_tiles >= 0 || kn0.min_rows >= 1;
     if (const int64_t kq = kn0.qt; kq != 0 && (kq > 0 || !asked_otherwise) && qt_applies(m->Dt, m->Cc, m->kf, mode) && nz == 1 &&
                                    m->S_active >= 64 && B <= 16LL * m->n_cu) {
@@ -684,12 +674,7 @@ int run_score(const dcx_model* m, const float* q, int64_t B, const float* upstre
     // Expanded form of the sweep (score_kernel.h XF) wherever it is compiled (Polyharmonic(1), rows <= 37 floats): 13-17 %
     // faster for chip-filling batches, 1-3 % for split launches (profiles/r02_xf_probe.txt).  Knob xf = 0: direct form.
     a.xf = xf_able ? 1 : 0;
-    // MFMA form of the gradient fold: compiled for even D <= 16 with the two specialised kernel functions; needs every
-    // wave to own a slice of the LDS reduction scratch (nw > 1, parallel fold)
-    a.mfma = (mode != MODE_SCORE && (m->Cc == 1 || m->Cc == 5 || m->Cc == 8) && (m->Dt == 12 || m->Dt == 16) && (m->Dt % 2) == 0 && m->kf != KF_GEN && g.nw > 1 && g.red_slots == g.nw &&
-              knobs().mfma != 0 && knobs().mfma > 0) ? 1 : 0;
     if (qt) {   // 16-configuration blocks, the direct form on the model's own rows
-        a.mfma = 0;
         a.xf = 0;
         a.qt = 1;
         a.qt_per = qt_per;
@@ -715,25 +700,9 @@ int run_score(const dcx_model* m, const float* q, int64_t B, const float* upstre
         a.qt_front = (int32_t)((int64_t)QT_SLICES * g.nw * qt_per * (kq >= 100 ? std::min<int64_t>(kq - 100, 100) : 45) / 100);
         nblk = (B + 15) / 16;
     }
-    if (a.mfma) a.xf = 0;
     if (a.xf) {  // the XF kernel: the centred rows and the centroid
         a.rows = m->rows_xf_dev;
         a.centre = m->centre_dev;
-    }
-    // XM: the expanded form's distance on the matrix cores (score_kernel.h sweep_rows, XM).  Slices then start on the
-    // 16-row blocks of the A planes.
-    a.xm = (a.xf && mode == MODE_GRAD_ROW && m->aplanes_dev != nullptr && xm_applies(m->Dt, m->Cc, m->kf) && knobs().xm > 0) ? 1 : 0;
-    if (a.xm) {
-        a.s_skew = 0;   // (slices on the 16-row blocks of the A planes)
-        a.aplanes = m->aplanes_dev;
-        a.s_super = (a.s_super + 15) / 16 * 16;
-        a.s_chunk = ((a.s_super + g.nw - 1) / g.nw + 15) / 16 * 16;
-    } else if (a.xf && m->rows_x2_dev != nullptr && x2_applies(m->Dt, m->Cc, m->kf)) {
-        // the expanded form with two rows per packed instruction (score_kernel.h X2): the pair-interleaved centred rows, slices
-        // that start on even rows
-        a.rows = m->rows_x2_dev;
-        a.s_super = (a.s_super + 1) & ~1;
-        a.s_chunk = ((a.s_super + g.nw - 1) / g.nw + 1) & ~1;
     }
     // J^T on several waves (fk_device.h dh2_vjp_waves): the step table, a parallel fold (its scratch rows 1 .. nw-1 hold 12
     // columns per point step), and not the finish-kernel mode.  Knob jt_waves = 0: wave 0 alone (tests: identical bits).
@@ -816,15 +785,15 @@ int dcx_debug_set(const char* name, int64_t value) {
     if (!name) return fail(DCX_ERR_INVALID, "knob name is NULL");
     Knobs& k = knobs();
     const std::string n(name);
+    // the matrix-core forms were removed; their knobs stay valid names whose only settings are the form
+    // every launch takes: off (0) and the rule (-1)
+    if (n == "mfma" || n == "xm")
+        return value > 0 ? fail(DCX_ERR_UNSUPPORTED, "the matrix-core forms of the sweep were removed (measured slower, profiles/r03_mfma_ab.txt)")
+                         : DCX_OK;
     std::atomic<int64_t>* dst = n == "ys" ? &k.ys : n == "nw" ? &k.nw : n == "min_rows" ? &k.min_rows
         : n == "split_finish_kernel" ? &k.split_finish_kernel : n == "inlaunch_tiles" ? &k.inlaunch_tiles
-        : n == "jac_per_class" ? &k.jac_per_class : n == "mfma" ? &k.mfma : n == "traj_fused" ? &k.traj_fused : n == "xf" ? &k.xf : n == "jac_one_sweep" ? &k.jac_one_sweep : n == "train_grid" ? &k.train_grid : n == "fkk" ? &k.fkk : n == "jt_waves" ? &k.jt_waves : n == "hess_ys" ? &k.hess_ys : n == "hess_form" ? &k.hess_form : n == "xm" ? &k.xm : n == "traj_ys" ? &k.traj_ys : n == "traj_across" ? &k.traj_across : n == "owner_poll" ? &k.owner_poll : n == "solve_threads" ? &k.solve_threads : n == "qt" ? &k.qt : n == "giveup_inject" ? &k.giveup_inject : n == "skew" ? &k.skew : n == "skew8" ? &k.skew8 : nullptr;
+        : n == "jac_per_class" ? &k.jac_per_class : n == "traj_fused" ? &k.traj_fused : n == "xf" ? &k.xf : n == "jac_one_sweep" ? &k.jac_one_sweep : n == "train_grid" ? &k.train_grid : n == "fkk" ? &k.fkk : n == "jt_waves" ? &k.jt_waves : n == "hess_ys" ? &k.hess_ys : n == "hess_form" ? &k.hess_form : n == "traj_ys" ? &k.traj_ys : n == "traj_across" ? &k.traj_across : n == "owner_poll" ? &k.owner_poll : n == "solve_threads" ? &k.solve_threads : n == "qt" ? &k.qt : n == "giveup_inject" ? &k.giveup_inject : n == "skew" ? &k.skew : n == "skew8" ? &k.skew8 : nullptr;
     if (!dst) return fail(DCX_ERR_INVALID, "unknown knob: " + n);
-#ifndef DCX_WITH_MATRIX_FORMS
-    if ((dst == &k.mfma || dst == &k.xm) && value > 0)
-        return fail(DCX_ERR_UNSUPPORTED, "this build of libdcx does not carry the matrix-core forms of the sweep (measured slower, "
-                                         "profiles/r03_mfma_ab.txt): make EXTRA=-DDCX_WITH_MATRIX_FORMS");
-#endif
     *dst = value;
     return DCX_OK;
 }
@@ -839,17 +808,13 @@ int dcx_device_count(void) {
 
 // ---- the model's rows: storage for `cap` supports, filled from host staging or by the packing kernel ---------------------
 static constexpr double kXfRqRule = 32.0;   // RQ2 takes the expanded form iff gamma * max |s - c|^2 <= this (see model_fill_host)
-static size_t rows_tail_floats(const dcx_model* m) { return 8 * (size_t)m->RS + 16; }  // the MFMA B-operand loads run up to 7 rows + 15 floats ahead
-static size_t aplane_shorts(int64_t rows) { return ((size_t)(rows + 15) / 16 + 2) * 3 * 16 * 4 * 8; }
+static size_t rows_tail_floats(const dcx_model* m) { return 8 * (size_t)m->RS + 16; }  // readable zeros behind the last row for the sweeps' look-ahead loads
 
 static void model_free_rows(dcx_model* m) {
     if (m->rows_dev) (void)hipFree(m->rows_dev);
     if (m->rows_xf_dev) (void)hipFree(m->rows_xf_dev);
     if (m->rows_p2_dev) (void)hipFree(m->rows_p2_dev);
-    if (m->rows_x2_dev) (void)hipFree(m->rows_x2_dev);
-    if (m->aplanes_dev) (void)hipFree(m->aplanes_dev);
-    m->rows_dev = m->rows_xf_dev = m->rows_p2_dev = m->rows_x2_dev = nullptr;
-    m->aplanes_dev = nullptr;
+    m->rows_dev = m->rows_xf_dev = m->rows_p2_dev = nullptr;
     m->cap = 0;
 }
 
@@ -860,11 +825,10 @@ static int model_alloc_rows(dcx_model* m, int64_t cap) {
     // the new buffers first, the old ones freed only when both exist: a failed growth leaves the model as it was (ADVICE r4:
     // freeing first left rows_dev null beside the old S_active, and the next launch read through it)
     const size_t floats = (size_t)cap * m->RS + rows_tail_floats(m);
-    float *rows = nullptr, *rows_xf = nullptr, *rows_p2 = nullptr, *rows_x2 = nullptr;
+    float *rows = nullptr, *rows_xf = nullptr, *rows_p2 = nullptr;
     hipError_t e = hipMalloc((void**)&rows, floats * sizeof(float));
     if (e == hipSuccess) e = hipMalloc((void**)&rows_xf, floats * sizeof(float));
     if (e == hipSuccess && p2_applies(m->Dt, m->Cc, m->kf)) e = hipMalloc((void**)&rows_p2, (floats + m->RS) * sizeof(float));
-    if (e == hipSuccess && x2_applies(m->Dt, m->Cc, m->kf) && xf_applies(m->Dt, m->Cc, m->kf)) e = hipMalloc((void**)&rows_x2, (floats + m->RS) * sizeof(float));
     if (e == hipSuccess && !m->centre_dev) e = hipMalloc((void**)&m->centre_dev, (size_t)m->Dt * sizeof(float));
     if (e == hipSuccess && !m->info_dev) e = hipMalloc((void**)&m->info_dev, 16);
     if (e == hipSuccess && !m->info_host) e = hipHostMalloc((void**)&m->info_host, 16, hipHostMallocDefault);
@@ -879,14 +843,12 @@ static int model_alloc_rows(dcx_model* m, int64_t cap) {
         if (rows) (void)hipFree(rows);
         if (rows_xf) (void)hipFree(rows_xf);
         if (rows_p2) (void)hipFree(rows_p2);
-        if (rows_x2) (void)hipFree(rows_x2);
         return fail_hip(e, "device allocation of the model");
     }
     model_free_rows(m);
     m->rows_dev = rows;
     m->rows_xf_dev = rows_xf;
     m->rows_p2_dev = rows_p2;
-    m->rows_x2_dev = rows_x2;
     m->cap = cap;
     return DCX_OK;
 }
@@ -924,7 +886,7 @@ static int model_fill_device(dcx_model* m, const float* feat_dev, const float* w
     return DCX_OK;
 }
 
-// Host inputs (or the XM planes asked for: their bf16 split is done here): staged and packed on the host, one copy per array
+// Host inputs: staged and packed on the host, one copy per array
 // into the model's storage.  pack_rows_kernel restates exactly this arithmetic.
 static int model_fill_host(dcx_model* m, const float* support_feat, const float* weights, int64_t S, hipStream_t stream) {
     const int32_t D = m->D, C = m->C, Cl = m->Cc;
@@ -991,53 +953,11 @@ static int model_fill_host(dcx_model* m, const float* support_feat, const float*
     // Panda, gamma 2 .. 80: 2e-6 / 2.5e-6 against float64 at 29, 3.5e-6 / 7e-6 at 58, 1e-5 at 117; the direct form
     // stays at 3e-7 .. 1e-6): 32 keeps it a factor of four inside the 1e-5 bar.  Larger gamma or workspace: direct form.
     m->xf_rq_ok = (m->kf == KF_RQ2 && m->fk.kind != DCX_FK_NONE && (double)m->kp0 * ss_max <= kXfRqRule) ? 1 : 0;
-    std::vector<unsigned short> aplanes;
-    if (kept > 0) {
-        // XM sweep: the centred coordinates split into three bf16 planes by truncation and laid out as the A operands of
-        // v_mfma_f32_16x16x32_bf16: [16-row block][chunk c][support m][k'][8], K slot 8 k' + e of chunk c = term 2c + slot / 16,
-        // feature slot % 16; terms hi.hi hi.mid mid.hi hi.lo lo.hi mid.mid take the s planes hi mid hi lo hi mid
-        if (xm_applies(m->Dt, C, m->kf)) {
-            const int splane_of_term[6] = {0, 1, 0, 2, 0, 1};
-            aplanes.assign(aplane_shorts(kept), 0);
-            for (int32_t j = 0; j < kept; ++j) {
-                unsigned short pl[3][16] = {};
-                for (int k = 0; k < D; ++k) {
-                    float r = rows_xf[(size_t)j * m->RS + k];
-                    for (int p = 0; p < 3; ++p) {
-                        uint32_t u;
-                        std::memcpy(&u, &r, 4);
-                        u &= 0xFFFF0000u;
-                        float h;
-                        std::memcpy(&h, &u, 4);
-                        pl[p][k] = (unsigned short)(u >> 16);
-                        r -= h;
-                    }
-                }
-                for (int c = 0; c < 3; ++c)
-                    for (int kq = 0; kq < 4; ++kq)
-                        for (int e2 = 0; e2 < 8; ++e2) {
-                            const int slot = 8 * kq + e2, term = 2 * c + slot / 16, kk = slot % 16;
-                            aplanes[((((size_t)(j / 16) * 3 + c) * 16 + (j % 16)) * 4 + kq) * 8 + e2] = pl[splane_of_term[term]][kk];
-                        }
-            }
-        }
-    }
     rows.resize(rows.size() + rows_tail_floats(m), 0.0f);
     rows_xf.resize(rows.size(), 0.0f);
     hipError_t e = hipMemcpy(m->rows_dev, rows.data(), rows.size() * sizeof(float), hipMemcpyHostToDevice);
     if (e == hipSuccess) e = hipMemcpy(m->rows_xf_dev, rows_xf.data(), rows_xf.size() * sizeof(float), hipMemcpyHostToDevice);
     if (e == hipSuccess) e = hipMemcpy(m->centre_dev, centre.data(), centre.size() * sizeof(float), hipMemcpyHostToDevice);
-    if (e == hipSuccess && !aplanes.empty()) {
-        if (m->aplanes_dev && m->aplanes_cap < aplanes.size()) {
-            (void)hipFree(m->aplanes_dev);
-            m->aplanes_dev = nullptr;
-        }
-        if (!m->aplanes_dev) {
-            m->aplanes_cap = aplane_shorts(m->cap);
-            e = hipMalloc((void**)&m->aplanes_dev, m->aplanes_cap * sizeof(unsigned short));
-        }
-        if (e == hipSuccess) e = hipMemcpy(m->aplanes_dev, aplanes.data(), aplanes.size() * sizeof(unsigned short), hipMemcpyHostToDevice);
-    }
     if (e != hipSuccess) return fail_hip(e, "upload of the model's rows");
     return DCX_OK;
 }
@@ -1065,17 +985,11 @@ static int refuse_capture(hipStream_t stream) {
 }
 
 static int model_fill(dcx_model* m, const float* support_feat, const float* weights, int64_t S, hipStream_t stream) {
-    // the XM planes (knob xm > 0: measurements only) are split on the host
-    const bool on_device = S > 0 && is_device_ptr(support_feat) && is_device_ptr(weights) &&
-                           !(knobs().xm > 0 && xm_applies(m->Dt, m->Cc, m->kf));
+    const bool on_device = S > 0 && is_device_ptr(support_feat) && is_device_ptr(weights);
     int rc = on_device ? model_fill_device(m, support_feat, weights, S, stream) : model_fill_host(m, support_feat, weights, S, stream);
     if (rc == DCX_OK && m->rows_p2_dev) {   // the pair-interleaved copy (stream-ordered behind the rows it reads)
         hipError_t e = launch_interleave_rows(m->rows_dev, m->rows_p2_dev, (int32_t)m->S_active, m->RS, (int32_t)rows_tail_floats(m), stream);
         if (e != hipSuccess) return fail_hip(e, "interleaving of the support rows");
-    }
-    if (rc == DCX_OK && m->rows_x2_dev) {   // ... and of the centred rows
-        hipError_t e = launch_interleave_rows(m->rows_xf_dev, m->rows_x2_dev, (int32_t)m->S_active, m->RS, (int32_t)rows_tail_floats(m), stream);
-        if (e != hipSuccess) return fail_hip(e, "interleaving of the centred support rows");
     }
     return rc;
 }
@@ -1198,9 +1112,7 @@ void dcx_model_destroy(dcx_model* m) {
     if (m->rows_dev) (void)hipFree(m->rows_dev);
     if (m->rows_xf_dev) (void)hipFree(m->rows_xf_dev);
     if (m->rows_p2_dev) (void)hipFree(m->rows_p2_dev);
-    if (m->rows_x2_dev) (void)hipFree(m->rows_x2_dev);
     if (m->centre_dev) (void)hipFree(m->centre_dev);
-    if (m->aplanes_dev) (void)hipFree(m->aplanes_dev);
     if (m->info_dev) (void)hipFree(m->info_dev);
     if (m->info_host) (void)hipHostFree(m->info_host);
     if (m->giveup_host) (void)hipHostFree(m->giveup_host);
@@ -1528,10 +1440,6 @@ static int traj_run(const dcx_model* m, const dcx_traj_state* st, const dcx_traj
             if (a.sc.xf) {
                 a.sc.rows = m->rows_xf_dev;
                 a.sc.centre = m->centre_dev;
-                if (m->rows_x2_dev && x2_applies(m->Dt, m->Cc, m->kf)) {   // (two rows per packed instruction: score_kernel.h X2)
-                    a.sc.rows = m->rows_x2_dev;
-                    traj_p2 = true;
-                }
             } else if (m->rows_p2_dev && p2_applies(m->Dt, m->Cc, m->kf)) {
                 a.sc.rows = m->rows_p2_dev;
                 traj_p2 = true;

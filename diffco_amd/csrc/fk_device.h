@@ -605,7 +605,6 @@ __device__ __attribute__((noinline)) void fk_tree_chain(fk_cptr fk, T* sXcol, T*
     }
 }
 
-#ifndef DCX_VJP_MATRIX_ADJOINT
 template <class T>
 __device__ __attribute__((noinline)) void fk_tree_vjp(fk_cptr fk, const T* sFcol, const T* sGcol, T* gqRow) {
     const int dof = rfl(fk->dof);
@@ -703,112 +702,6 @@ __device__ __attribute__((noinline)) void fk_tree_vjp(fk_cptr fk, const T* sFcol
         }
     }
 }
-#else
-template <class T>
-__device__ __attribute__((noinline)) void fk_tree_vjp(fk_cptr fk, const T* sFcol, const T* sGcol, T* gqRow) {
-    const int dof = rfl(fk->dof);
-    // Reverse-mode sweep through T_j = T_parent(j) F_j M_j(v_j) over the tree; joints driven by the same q (mimic)
-    // simply accumulate.  With N = T_parent F_j:
-    //   revolute : R_j = R_N Rz(v), t_j = t_N   ->  dL/dv = <R_N^T GR, dRz/dv>,  G_RN = GR Rz^T
-    //   prismatic: R_j = R_N, t_j = t_N + R_N a v -> dL/dv = Gt . (R_N a),        G_RN = GR + Gt (a v)^T
-    //   through F: G_R(j-1) = G_RN F_R^T + Gt F_t^T,  R_(j-1) = R_N F_R^T,  Gt unchanged
-    for (int i = 0; i < dof; ++i) gqRow[i] = 0.f;  // the sweep reads frames, not q
-    const int stride = rfl(fk->out_stride) * 64, njt = rfl(fk->n_joints);
-    const int f_leaf = rfl(fk->f_leaf), f_adj = rfl(fk->f_adj), n_branch = rfl(fk->n_branch);
-    T* sFw = const_cast<T*>(sFcol);  // the adjoint sums of branch nodes live in the frames area
-    for (int e = 0; e < 12 * n_branch; ++e) sFw[(f_adj + e) * 64] = 0.f;
-    T r00 = 1.f, r01 = 0.f, r02 = 0.f, r10 = 0.f, r11 = 1.f, r12 = 0.f, r20 = 0.f, r21 = 0.f, r22 = 1.f;
-    T G00 = 0.f, G01 = 0.f, G02 = 0.f, G10 = 0.f, G11 = 0.f, G12 = 0.f, G20 = 0.f, G21 = 0.f, G22 = 0.f;
-    T T0 = 0.f, T1 = 0.f, T2 = 0.f;
-    // nodes in reverse depth-first order: every child has been processed before its parent
-    for (int j = njt - 1; j >= 0; --j) {
-        const int leaf = rfl(fk->tj[j].leaf), park = rfl(fk->tj[j].park);
-        if (leaf >= 0) {  // no child handed its state over in registers: restart from this node's own rotation
-            const T* fr = sFcol + (f_leaf + 9 * leaf) * 64;
-            r00 = fr[0]; r01 = fr[64]; r02 = fr[128]; r10 = fr[192]; r11 = fr[256]; r12 = fr[320];
-            r20 = fr[384]; r21 = fr[448]; r22 = fr[512];
-            G00 = G01 = G02 = G10 = G11 = G12 = G20 = G21 = G22 = 0.f;
-            T0 = T1 = T2 = 0.f;
-        }
-        if (park >= 0) {  // plus what the children that started from the parked frame sent back
-            const T* ad = sFcol + (f_adj + 12 * park) * 64;
-            G00 += ad[0]; G01 += ad[64]; G02 += ad[128]; T0 += ad[192];
-            G10 += ad[256]; G11 += ad[320]; G12 += ad[384]; T1 += ad[448];
-            G20 += ad[512]; G21 += ad[576]; G22 += ad[640]; T2 += ad[704];
-        }
-        const int pb = rfl(fk->tj[j].pt_begin), pe = rfl(fk->tj[j].pt_end);
-        for (int p = pb; p < pe; ++p) {
-            const T* gin = sGcol + rfl(fk->points[p].out_k) * 64;
-            const T g0 = gin[0], g1 = gin[stride], g2 = gin[2 * stride];
-            const float ox = fk->points[p].ox, oy = fk->points[p].oy, oz = fk->points[p].oz;
-            T0 += g0; T1 += g1; T2 += g2;
-            G00 = fma3(g0, ox, G00); G01 = fma3(g0, oy, G01); G02 = fma3(g0, oz, G02);
-            G10 = fma3(g1, ox, G10); G11 = fma3(g1, oy, G11); G12 = fma3(g1, oz, G12);
-            G20 = fma3(g2, ox, G20); G21 = fma3(g2, oy, G21); G22 = fma3(g2, oz, G22);
-        }
-        const int type = rfl(fk->tj[j].type), slot = rfl(fk->tj[j].slot);
-        if (type == TJ_REV) {
-            const T s = sFcol[(2 * slot) * 64], c = sFcol[(2 * slot + 1) * 64];
-            // R_N = R_j Rz^T: columns 0, 1 rotate back
-            const T p00 = fma3(r00, c, -r01 * s), p01 = fma3(r01, c, r00 * s);
-            const T p10 = fma3(r10, c, -r11 * s), p11 = fma3(r11, c, r10 * s);
-            const T p20 = fma3(r20, c, -r21 * s), p21 = fma3(r21, c, r20 * s);
-            // A = R_N^T GR, rows 0 and 1, columns 0 and 1 (dRz/dv = [[-s, -c, 0], [c, -s, 0], [0, 0, 0]])
-            const T A00 = fma3(p00, G00, fma3(p10, G10, p20 * G20)), A01 = fma3(p00, G01, fma3(p10, G11, p20 * G21));
-            const T A10 = fma3(p01, G00, fma3(p11, G10, p21 * G20)), A11 = fma3(p01, G01, fma3(p11, G11, p21 * G21));
-            const T dv = (c * A10 - s * A11) - (s * A00 + c * A01);
-            gqRow[rfl(fk->tj[j].q_index)] += fk->tj[j].scale * dv;
-            // G_RN = GR Rz^T
-            const T h00 = fma3(G00, c, -G01 * s), h01 = fma3(G01, c, G00 * s);
-            const T h10 = fma3(G10, c, -G11 * s), h11 = fma3(G11, c, G10 * s);
-            const T h20 = fma3(G20, c, -G21 * s), h21 = fma3(G21, c, G20 * s);
-            G00 = h00; G01 = h01; G10 = h10; G11 = h11; G20 = h20; G21 = h21;
-            r00 = p00; r01 = p01; r10 = p10; r11 = p11; r20 = p20; r21 = p21;
-        } else if (type == TJ_PRISM) {
-            const T v = sFcol[(2 * slot) * 64];
-            const float ax = fk->tj[j].ax, ay = fk->tj[j].ay, az = fk->tj[j].az;
-            const T w0 = fma3(r00, ax, fma3(r01, ay, r02 * az)), w1 = fma3(r10, ax, fma3(r11, ay, r12 * az)),
-                        w2 = fma3(r20, ax, fma3(r21, ay, r22 * az));
-            gqRow[rfl(fk->tj[j].q_index)] += fk->tj[j].scale * fma3(T0, w0, fma3(T1, w1, T2 * w2));
-            const T dx = ax * v, dy = ay * v, dz = az * v;
-            G00 = fma3(T0, dx, G00); G01 = fma3(T0, dy, G01); G02 = fma3(T0, dz, G02);
-            G10 = fma3(T1, dx, G10); G11 = fma3(T1, dy, G11); G12 = fma3(T1, dz, G12);
-            G20 = fma3(T2, dx, G20); G21 = fma3(T2, dy, G21); G22 = fma3(T2, dz, G22);
-        }
-        // back through the constant transform F
-        const auto* F = fk->tj[j].F;
-        const float f00 = F[0], f01 = F[1], f02 = F[2], f03 = F[3], f10 = F[4], f11 = F[5], f12 = F[6], f13 = F[7];
-        const float f20 = F[8], f21 = F[9], f22 = F[10], f23 = F[11];
-        const T n00 = fma3(G00, f00, fma3(G01, f01, fma3(G02, f02, T0 * f03)));
-        const T n01 = fma3(G00, f10, fma3(G01, f11, fma3(G02, f12, T0 * f13)));
-        const T n02 = fma3(G00, f20, fma3(G01, f21, fma3(G02, f22, T0 * f23)));
-        const T n10 = fma3(G10, f00, fma3(G11, f01, fma3(G12, f02, T1 * f03)));
-        const T n11 = fma3(G10, f10, fma3(G11, f11, fma3(G12, f12, T1 * f13)));
-        const T n12 = fma3(G10, f20, fma3(G11, f21, fma3(G12, f22, T1 * f23)));
-        const T n20 = fma3(G20, f00, fma3(G21, f01, fma3(G22, f02, T2 * f03)));
-        const T n21 = fma3(G20, f10, fma3(G21, f11, fma3(G22, f12, T2 * f13)));
-        const T n22 = fma3(G20, f20, fma3(G21, f21, fma3(G22, f22, T2 * f23)));
-        G00 = n00; G01 = n01; G02 = n02; G10 = n10; G11 = n11; G12 = n12; G20 = n20; G21 = n21; G22 = n22;
-        const T q00 = fma3(r00, f00, fma3(r01, f01, r02 * f02)), q01 = fma3(r00, f10, fma3(r01, f11, r02 * f12)),
-                    q02 = fma3(r00, f20, fma3(r01, f21, r02 * f22));
-        const T q10 = fma3(r10, f00, fma3(r11, f01, r12 * f02)), q11 = fma3(r10, f10, fma3(r11, f11, r12 * f12)),
-                    q12 = fma3(r10, f20, fma3(r11, f21, r12 * f22));
-        const T q20 = fma3(r20, f00, fma3(r21, f01, r22 * f02)), q21 = fma3(r20, f10, fma3(r21, f11, r22 * f12)),
-                    q22 = fma3(r20, f20, fma3(r21, f21, r22 * f22));
-        r00 = q00; r01 = q01; r02 = q02; r10 = q10; r11 = q11; r12 = q12; r20 = q20; r21 = q21; r22 = q22;
-        // (R, GR, Gt) now refer to the parent frame.  A child that started from a parked frame adds its adjoint to the
-        // parent's sum; a child that continued in registers just carries on; a root's parent adjoint is dropped.
-        const int start = rfl(fk->tj[j].start);
-        if (start >= 0) {
-            T* ad = sFw + (f_adj + 12 * start) * 64;
-            ad[0] += G00; ad[64] += G01; ad[128] += G02; ad[192] += T0;
-            ad[256] += G10; ad[320] += G11; ad[384] += G12; ad[448] += T1;
-            ad[512] += G20; ad[576] += G21; ad[640] += G22; ad[704] += T2;
-        }
-    }
-}
-
-#endif
 
 // ---- DCX_FK_DH walks that read the program with SCALAR loads -------------------------------------------------------------
 // fk_forward_chain / fk_vjp interpret the program from its LDS copy: every wave-uniform field arrives in a VGPR and goes
@@ -1014,11 +907,10 @@ __device__ inline void fk_forward_chain(fk_cptr fk, const T* sQrow, T* sXcol, T*
                 const T s = sFcol[(2 * j) * 64], c = sFcol[(2 * j + 1) * 64];
                 const float a = fk->joints[j].a, d = fk->joints[j].d;
                 const float sa = fk->joints[j].sin_alpha, ca = fk->joints[j].cos_alpha;
-#ifndef DCX_FK_DH_MATRIX
                 // T <- T * Rz(theta) * Trans(a, 0, d) * Rx(alpha)   (utils.DH2mat, factor by factor: columns 0, 1 of R mix by
                 // theta, the origin moves by a along the new column 0 and by d along column 2, columns 1, 2 mix by alpha):
                 // 30 operations per joint where the product with the assembled 3x4 block takes 39 - the chain is a lone
-                // wave's phase, bound by its instruction count.  -DDCX_FK_DH_MATRIX restores the block form.
+                // wave's phase, bound by its instruction count.
                 const T n00 = fma3(r00, c, r01 * s), n10 = fma3(r10, c, r11 * s), n20 = fma3(r20, c, r21 * s);
                 const T u0 = fma3(r01, c, -(r00 * s)), u1 = fma3(r11, c, -(r10 * s)), u2 = fma3(r21, c, -(r20 * s));
                 t0 = fma3(n00, a, fma3(r02, d, t0));
@@ -1026,21 +918,6 @@ __device__ inline void fk_forward_chain(fk_cptr fk, const T* sQrow, T* sXcol, T*
                 t2 = fma3(n20, a, fma3(r22, d, t2));
                 const T n01 = fma3(u0, ca, r02 * sa), n11 = fma3(u1, ca, r12 * sa), n21 = fma3(u2, ca, r22 * sa);
                 const T n02 = fma3(r02, ca, -(u0 * sa)), n12 = fma3(r12, ca, -(u1 * sa)), n22 = fma3(r22, ca, -(u2 * sa));
-#else
-                // T <- T * [[c, -s ca,  s sa, a c], [s, c ca, -c sa, a s], [0, sa, ca, d]]   (utils.DH2mat)
-                const T m01 = -s * ca, m02 = s * sa, m11 = c * ca, m12 = -c * sa;
-                const T ac = a * c, as = a * s;
-                t0 = fma3(r00, ac, fma3(r01, as, fma3(r02, d, t0)));
-                t1 = fma3(r10, ac, fma3(r11, as, fma3(r12, d, t1)));
-                t2 = fma3(r20, ac, fma3(r21, as, fma3(r22, d, t2)));
-                const T n00 = fma3(r00, c, r01 * s), n10 = fma3(r10, c, r11 * s), n20 = fma3(r20, c, r21 * s);
-                const T n01 = fma3(r00, m01, fma3(r01, m11, r02 * sa));
-                const T n11 = fma3(r10, m01, fma3(r11, m11, r12 * sa));
-                const T n21 = fma3(r20, m01, fma3(r21, m11, r22 * sa));
-                const T n02 = fma3(r00, m02, fma3(r01, m12, r02 * ca));
-                const T n12 = fma3(r10, m02, fma3(r11, m12, r12 * ca));
-                const T n22 = fma3(r20, m02, fma3(r21, m12, r22 * ca));
-#endif
                 r00 = n00; r01 = n01; r02 = n02; r10 = n10; r11 = n11; r12 = n12; r20 = n20; r21 = n21; r22 = n22;
                 const int pb = rfl(fk->joints[j].pt_begin), pe = rfl(fk->joints[j].pt_end);
                 for (int p = pb; p < pe; ++p) {
@@ -1119,7 +996,6 @@ __device__ inline void fk_vjp(fk_cptr fk, const T* sQrow, const T* sFcol, const 
     if (kind == DCX_FK_DH) {
         for (int i = 0; i < dof; ++i) gqRow[i] = 0.f;  // DH reads frames, not q
         const int nch = rfl(fk->n_chains), njt = rfl(fk->n_joints);
-#ifndef DCX_VJP_MATRIX_ADJOINT
         // Reverse sweep of a WRENCH (force f, moment n about the frame origin) expressed in the coordinates of the current
         // frame, from the tip of the chain to its base.  With A_j = Rz(theta_j) Trans(a, 0, d) Rx(alpha):
         //   points of frame j (offset o, upstream g):  l = R_j^T g ;  f += l ;  n += o x l
@@ -1128,10 +1004,10 @@ __device__ inline void fk_vjp(fk_cptr fk, const T* sQrow, const T* sFcol, const 
         //   through Rz(theta):                         f <- Rz f1 ;  n <- Rz n1 ;  R_{j-1} = R_j Rx^T Rz^T (recomputed)
         // Six adjoint components instead of the twelve (GR 3x3, Gt) of the matrix chain rule, and the joint derivative
         // costs nothing: ~44 instead of ~100 operations per joint (the lone wave's J^T phase of a block).
-        // Like the matrix form - and unlike the world-frame z x (p - o), which differences accumulated positions - the
+        // Like the matrix chain rule - and unlike the world-frame z x (p - o), which differences accumulated positions - the
         // STRUCTURAL zeros come out exactly: they live in the DH constants (Baxter's last joint, a = 0 with the control
         // point on the joint axis: n stays 0 and n1.z = sa*0 + ca*0 + 0*f1.y = 0), so an optimiser such as Adam is not
-        // handed 1e-8 of round-off to normalise into full-size steps.  -DDCX_VJP_MATRIX_ADJOINT restores the matrix form.
+        // handed 1e-8 of round-off to normalise into full-size steps.
         for (int ch = 0; ch < nch; ++ch) {
             const T* fr = sFcol + (2 * njt + 9 * ch) * 64;
             T r00 = fr[0], r01 = fr[64], r02 = fr[128], r10 = fr[192], r11 = fr[256], r12 = fr[320];
@@ -1180,72 +1056,6 @@ __device__ inline void fk_vjp(fk_cptr fk, const T* sQrow, const T* sFcol, const 
                 DCX_FK_TS(7 + (j < 8 ? j : 8), 1);
             }
         }
-#else
-        // Reverse-mode sweep through T_j = T_{j-1} A_j(theta_j), exactly the chain rule autograd applies to
-        // the reference's bmm chain.  Unlike the geometric form z x (p - o) it reproduces STRUCTURAL zeros
-        // exactly (e.g. Baxter's last joint, a = 0 and the control point on the joint axis): an optimiser
-        // such as Adam would otherwise amplify 1e-8 round-off on such a joint into full-size steps.
-        //   GR, Gt : adjoints of the current frame's rotation / translation
-        //   dL/dtheta_j = <R_{j-1}^T GR, dA_R/dtheta> + <R_{j-1}^T Gt, da_t/dtheta>
-        //   GR <- GR A_R^T + Gt a_t^T ;  Gt unchanged ;  R_{j-1} = R_j A_R^T (recomputed, not stored)
-        for (int ch = 0; ch < nch; ++ch) {
-            const T* fr = sFcol + (2 * njt + 9 * ch) * 64;
-            T r00 = fr[0], r01 = fr[64], r02 = fr[128], r10 = fr[192], r11 = fr[256], r12 = fr[320];
-            T r20 = fr[384], r21 = fr[448], r22 = fr[512];
-            T G00 = 0.f, G01 = 0.f, G02 = 0.f, G10 = 0.f, G11 = 0.f, G12 = 0.f, G20 = 0.f, G21 = 0.f, G22 = 0.f;
-            T T0 = 0.f, T1 = 0.f, T2 = 0.f;
-            const int jb = rfl(fk->chain_begin[ch]), je = rfl(fk->chain_end[ch]);
-            for (int j = je - 1; j >= jb; --j) {
-                const int pb = rfl(fk->joints[j].pt_begin), pe = rfl(fk->joints[j].pt_end);
-                for (int p = pb; p < pe; ++p) {
-                    const T* gin = sGcol + (rfl(fk->points[p].out_k) & (kPointBare - 1)) * 64;
-                    const T g0 = gin[0], g1 = gin[64], g2 = gin[128];
-                    const float ox = fk->points[p].ox, oy = fk->points[p].oy, oz = fk->points[p].oz;
-                    T0 += g0; T1 += g1; T2 += g2;
-                    G00 = fma3(g0, ox, G00); G01 = fma3(g0, oy, G01); G02 = fma3(g0, oz, G02);
-                    G10 = fma3(g1, ox, G10); G11 = fma3(g1, oy, G11); G12 = fma3(g1, oz, G12);
-                    G20 = fma3(g2, ox, G20); G21 = fma3(g2, oy, G21); G22 = fma3(g2, oz, G22);
-                }
-                const T s = sFcol[(2 * j) * 64], c = sFcol[(2 * j + 1) * 64];
-                const float a = fk->joints[j].a, d = fk->joints[j].d;
-                const float sa = fk->joints[j].sin_alpha, ca = fk->joints[j].cos_alpha;
-                // A_R = [[c, -s ca, s sa], [s, c ca, -c sa], [0, sa, ca]],  a_t = (a c, a s, d)
-                const T a00 = c, a01 = -s * ca, a02 = s * sa, a10 = s, a11 = c * ca, a12 = -c * sa;
-                const T at0 = a * c, at1 = a * s;
-                // R_{i-1} = R_i A_R^T
-                const T p00 = fma3(r00, a00, fma3(r01, a01, r02 * a02)), p01 = fma3(r00, a10, fma3(r01, a11, r02 * a12)),
-                            p02 = fma3(r01, sa, r02 * ca);
-                const T p10 = fma3(r10, a00, fma3(r11, a01, r12 * a02)), p11 = fma3(r10, a10, fma3(r11, a11, r12 * a12)),
-                            p12 = fma3(r11, sa, r12 * ca);
-                const T p20 = fma3(r20, a00, fma3(r21, a01, r22 * a02)), p21 = fma3(r20, a10, fma3(r21, a11, r22 * a12)),
-                            p22 = fma3(r21, sa, r22 * ca);
-                // M = R_{i-1}^T GR (rows 0,1 only: dA_R/dtheta has a zero third row), u = R_{i-1}^T Gt
-                const T M00 = fma3(p00, G00, fma3(p10, G10, p20 * G20)), M01 = fma3(p00, G01, fma3(p10, G11, p20 * G21)),
-                            M02 = fma3(p00, G02, fma3(p10, G12, p20 * G22));
-                const T M10 = fma3(p01, G00, fma3(p11, G10, p21 * G20)), M11 = fma3(p01, G01, fma3(p11, G11, p21 * G21)),
-                            M12 = fma3(p01, G02, fma3(p11, G12, p21 * G22));
-                const T u0 = fma3(p00, T0, fma3(p10, T1, p20 * T2)), u1 = fma3(p01, T0, fma3(p11, T1, p21 * T2));
-                // dA_R/dtheta = [[-s, -c ca, c sa], [c, -s ca, s sa], [0,0,0]] = [[-a10, -a11, -a12], [a00, a01, a02], 0]
-                // da_t/dtheta = (-a s, a c, 0)
-                const T dth = (M10 * a00 + M11 * a01 + M12 * a02) - (M00 * a10 + M01 * a11 + M02 * a12)
-                                  + (u1 * at0 - u0 * at1);
-                gqRow[rfl(fk->joints[j].q_index)] += dth;
-                // GR <- GR A_R^T + Gt a_t^T
-                const T n00 = fma3(G00, a00, fma3(G01, a01, fma3(G02, a02, T0 * at0)));
-                const T n01 = fma3(G00, a10, fma3(G01, a11, fma3(G02, a12, T0 * at1)));
-                const T n02 = fma3(G01, sa, fma3(G02, ca, T0 * d));
-                const T n10 = fma3(G10, a00, fma3(G11, a01, fma3(G12, a02, T1 * at0)));
-                const T n11 = fma3(G10, a10, fma3(G11, a11, fma3(G12, a12, T1 * at1)));
-                const T n12 = fma3(G11, sa, fma3(G12, ca, T1 * d));
-                const T n20 = fma3(G20, a00, fma3(G21, a01, fma3(G22, a02, T2 * at0)));
-                const T n21 = fma3(G20, a10, fma3(G21, a11, fma3(G22, a12, T2 * at1)));
-                const T n22 = fma3(G21, sa, fma3(G22, ca, T2 * d));
-                G00 = n00; G01 = n01; G02 = n02; G10 = n10; G11 = n11; G12 = n12; G20 = n20; G21 = n21; G22 = n22;
-                r00 = p00; r01 = p01; r02 = p02; r10 = p10; r11 = p11; r12 = p12; r20 = p20; r21 = p21; r22 = p22;
-                DCX_FK_TS(7 + (j < 8 ? j : 8), 1);
-            }
-        }
-#endif
     } else if (kind == DCX_FK_TREE) {
         fk_tree_vjp(fk, sFcol, sGcol, gqRow);
     } else if (kind == DCX_FK_SE2) {

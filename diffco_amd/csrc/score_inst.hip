@@ -26,23 +26,6 @@ namespace {
 constexpr int kD = DCX_INST_D;
 constexpr int kMaxT = kD <= 16 ? 1024 : (kD <= 48 ? 512 : 256);
 
-// widths / modes that carry the MFMA form of the gradient fold (sweep_rows_mfma)
-// (one, five and eight classes: the developer knob takes it for those models, dcx_api.hip; with C > 1 the weight
-// contraction K . W runs on the matrix cores beside the gradient fold)
-// Round 5: NOT in the shipped library.  Both matrix-core forms (MF: the gradient fold / K . W on v_mfma_f32_16x16x4_f32; XM: the
-// distance GEMM as bf16 x 3 on v_mfma_f32_16x16x32_bf16) measured 4 - 47 % slower than the VALU forms (profiles/r03_mfma_ab.txt);
-// they are compiled by `make EXTRA=-DDCX_WITH_MATRIX_FORMS` (tools/build_variant.sh matrix ...) for the parity tests' "mfma" leg
-// and the A/B tools, and dcx_debug_set("mfma" / "xm", 1) answers DCX_ERR_UNSUPPORTED without them.
-#ifdef DCX_WITH_MATRIX_FORMS
-template <int KF, int CC, int MODE>
-constexpr bool kHasMfma = (kD == 12 || kD == 16) && (CC == 1 || CC == 5 || CC == 8) && (MODE != MODE_SCORE) && (KF != KF_GEN);
-constexpr bool kHasXm = true;
-#else
-template <int KF, int CC, int MODE>
-constexpr bool kHasMfma = false;
-constexpr bool kHasXm = false;
-#endif
-
 // Shapes with an expanded form (score_kernel.h, XF: Polyharmonic(1), rows of <= 37 floats) run it by default, on the
 // centred row pairs the host passes with it (ScoreArgs::centre).  The direct form is compiled for them as well and
 // selected per launch by ScoreArgs::xf (dcx_debug_set("xf", 0)): the parity tests run every case in both forms,
@@ -61,16 +44,10 @@ hipError_t go(int nw, size_t lds, int64_t nblk, const ScoreArgs& a, hipStream_t 
         return hipGetLastError();
     };
     if constexpr (qt_applies(kD, CC, KF, MODE)) {   // the quarter tile (16 configurations per block, rows from LDS): nblk counts ITS blocks
-        if (a.qt) return launch(score_kernel<kD, KF, CC, MODE, kMaxT, false, false, false, true>);
-    }
-    if constexpr (kHasXm && xf_applies(kD, CC, KF) && xm_applies(kD, CC, KF) && MODE == MODE_GRAD_ROW) {
-        if (!a.mfma && a.xf && a.xm) return launch(score_kernel<kD, KF, CC, MODE, kMaxT, false, true, true>);
+        if (a.qt) return launch(score_kernel<kD, KF, CC, MODE, kMaxT, false, true>);
     }
     if constexpr (xf_applies(kD, CC, KF)) {
-        if (!a.mfma && a.xf) return launch(score_kernel<kD, KF, CC, MODE, kMaxT, false, true>);
-    }
-    if constexpr (kHasMfma<KF, CC, MODE>) {
-        if (a.mfma) return launch(score_kernel<kD, KF, CC, MODE, kMaxT, true>);
+        if (a.xf) return launch(score_kernel<kD, KF, CC, MODE, kMaxT, true>);
     }
     return launch(score_kernel<kD, KF, CC, MODE, kMaxT>);
 }

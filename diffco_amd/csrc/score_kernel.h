@@ -70,8 +70,6 @@ struct ScoreArgs {
                               // grad + z * dof (all Jacobian rows at once: the per-class sweeps of a small batch run side by side)
     int64_t grad_stride;      // floats between consecutive configurations' gradient rows (dof, or C*dof for jac)
     float* partial;           // split launch: per (tile, y) partial sums [(tile*ys + y)][ACC][64]; null = finish in-kernel
-    const unsigned short* aplanes;  // XM sweep: the centred supports as bf16 planes laid out as MFMA A operands (xm_applies)
-    int32_t xm;               // 1: the launch takes the distance of the expanded form from the matrix cores (score_kernel<..., XM>)
     unsigned int* tile_done;  // split launch: per-tile arrival counters (zero between launches).  Non-null: the LAST of a
                               // tile's ys blocks to arrive adds the partial rows and finishes in this launch; null: a
                               // second launch (score_finish_kernel) does
@@ -89,7 +87,6 @@ struct ScoreArgs {
     unsigned int ts_block;
 #endif
     float kp0, kp1;           // kernel parameters
-    int32_t mfma;             // 1: the launch uses the MFMA form of the gradient fold (score_kernel<..., MF = true>)
     int32_t xf;               // 1: the launch uses the expanded form of the sweep (score_kernel<..., XF = true>)
     int32_t fkk;              // DCX_FK_DH only: 1 = the FK walks read the program with scalar loads (fk_*_dh_k), 2 = the step
                               // table (fk_device.h dh2_*; `dh` below); 0 = every kind: FkProg interpreted from its LDS copy
@@ -343,37 +340,10 @@ __host__ __device__ inline LdsPlan lds_plan(int dof, int d_fk, int frame_floats,
 #ifndef DCX_MINW_SLACK
 #define DCX_MINW_SLACK 0
 #endif
-// The XM sweep (round 3): the expanded form with its distance GEMM x . s^T on v_mfma_f32_16x16x32_bf16 in split operands
-// (sweep_rows, XM).  One class, Polyharmonic(1), even D <= 16 (a term's 16 K slots hold the features).
-// (compiled for the two widths it was measured at: profiles/r03_mfma_ab.txt - measured slower, kept as evidence)
-constexpr bool xm_applies(int D, int CC, int KF) { return KF == 1 /* KF_POLY1 */ && CC == 1 && (D == 12 || D == 16); }
-// Does the EXPANDED form of this shape take two rows per packed instruction (sweep_rows, X2; round 6)?  One class, the two
-// specialised kernel functions, even D <= DCX_XF2_MAX_D (2 D gradient accumulators).  Such a model's centred rows are stored
-// pair-interleaved as well (dcx_api.hip rows_x2), its expanded sweeps run on even-aligned slices.
-// MEASURED, NOT SHIPPED (default 0; `make EXTRA="-DDCX_XF2=1 -DDCX_XF2_MINW=4"` builds it - profiles/r06_xf2.txt): the body needs ~70
-// VGPRs.  Under the sweep kernel's 64-register budget (two 16-wave blocks per CU) it spills into the loop; given 128 registers a
-// CU holds ONE block, whose prologue and epilogue nothing overlaps any more: headline 85.0 -> 104.0 us at B = 65536, 1200 -> 1217 us
-// at B = 1 M, while the launches that run one block per CU anyway gain 3 - 5 % (B = 8192: 19.1 -> 18.6 us, config #5's persistent
-// kernel 28.2 -> 27.4 us per iteration).  Not worth a second expanded form of every narrow kernel.
-#ifndef DCX_XF2
-#define DCX_XF2 0
-#endif
-#ifndef DCX_XF2_MAX_D
-#define DCX_XF2_MAX_D 12
-#endif
-constexpr bool x2_applies(int D, int CC, int KF) {
-    return DCX_XF2 && CC == 1 && (D % 2) == 0 && D >= 4 && D <= DCX_XF2_MAX_D && (KF == 1 /* KF_POLY1 */ || KF == 0 /* KF_RQ2 */) &&
-           4 * (D + 2) <= DCX_P0_MAX_SINGLE;
-}
-#ifndef DCX_XF2_MINW
-#define DCX_XF2_MINW 8   // waves per SIMD the register allocator must leave room for in such a kernel (8 = 64 VGPRs)
-#endif
-constexpr int sweep_min_waves(int D, int CC, int KF, bool MF = false, bool XM = false, bool QT = false, bool XF = false) {
+constexpr int sweep_min_waves(int D, int CC, int KF, bool QT = false) {
     if (QT) return 4;  // one block per CU (the rows fill its LDS), at most 16 waves: two row buffers in VGPRs + the direct body
-    if (XM) return 4;  // 48 VGPRs of loop-invariant B fragments + 16 distances in flight: 128 VGPRs
-    if (XF && x2_applies(D, CC, KF)) return DCX_XF2_MINW;
-    // KF_GEN calls powf/logf; the MFMA form adds 16 accumulator registers per contraction + the operand fragments
-    const int need = 3 * D + 2 * CC + 16 + DCX_MINW_SLACK + (KF == 2 ? 40 : 0) + (MF ? (CC > 1 ? 48 : 24) : 0);
+    // KF_GEN calls powf/logf
+    const int need = 3 * D + 2 * CC + 16 + DCX_MINW_SLACK + (KF == 2 ? 40 : 0);
     return need <= 64 ? 8 : need <= 72 ? 7 : need <= 80 ? 6 : need <= 96 ? 5 : need <= 128 ? 4 : need <= 168 ? 3 : need <= 256 ? 2 : 1;
 }
 
@@ -498,7 +468,7 @@ constexpr bool p2_applies(int D, int CC, int KF) {
 // at few waves per SIMD trade one packed add per row for a shorter dependent chain)
 // NS (several classes, MODE_GRAD_UP): no score accumulation - a caller that already holds this batch's class scores (the persistent
 // trajectory kernel's second sweep) saves the CC fma per pair; sc[] comes back untouched
-template <int D, int KF, int CC, int MODE, bool XF = false, int NACC = 0, bool XM = false, bool NS = false>
+template <int D, int KF, int CC, int MODE, bool XF = false, int NACC = 0, bool NS = false>
 __device__ __forceinline__ void sweep_rows(const ScoreArgs& a, const float (&x)[D], const float (&up)[CC], int j0, int j1,
                                            float (&sc)[CC], float (&gx)[D]) {
     static_assert(!NS || (CC > 1 && MODE == MODE_GRAD_UP), "NS: the gradient sweep of a multi-class model");
@@ -815,291 +785,7 @@ __device__ __forceinline__ void sweep_rows(const ScoreArgs& a, const float (&x)[
     // alive for every width by parking SGPRs in VGPR lanes: D=24 +37 %, D=42 +75 %, D=60 +97 % VALU instructions
     // (v_writelane / v_readlane) inside the sweep.
     static_assert(!XFA || PARTS <= 1, "expanded form: whole rows only");
-    constexpr bool X2 = XFA && !XM && x2_applies(D, CC, KF);
-    if constexpr (X2) {
-    // ---- X2 (round 6): the expanded form, two rows per packed instruction ----------------------------------------------------------
-    // The expanded body above packs a row's features two by two: D/2 v_pk_fma for the distance and D/2 for the gradient, an add of
-    // the two halves, and a scalar chain per row (seed, clamp, rsq, coefficient, score, sum of coefficients, near test): 20 VALU
-    // instructions per row at D = 12.  Here the two rows of a stage ride in the two halves of every packed register instead (the
-    // centred rows are stored pair-interleaved: element e of the even row at b[2 e], of the odd row at b[2 e + 1], so every operand
-    // pair is an aligned SGPR pair of the stage's one load): D + D v_pk_fma per TWO rows, no add of halves, the chain's adds and
-    // multiplies packed (clamp, rsq and near test stay one per row: no packed form exists) - 34 per two rows at D = 12 - and the
-    // expanded gradient H in 2 D accumulators (even rows' sums in .x, odd rows' in .y; one add per feature at the end).  The bare
-    // body (tools/sweep_body_ubench.hip): 39.3 ns per wave-row per SIMD against 44.2 at 4 waves per SIMD, 40.0 against 41.1 at 8.
-    // A row's distance is ONE fma chain over its features here (xx + ss first), and the rare near-pair block below reproduces
-    // exactly that chain in scalar fma before it takes the expanded term out and puts the direct one in (the same semantics as
-    // fix_near above).  j0 is even (the host's slicing); a slice that ends on the model's odd last row runs into the zero-weight
-    // padding row (d2 = |x - c|^2 there: finite, coefficient 0).
-    if (j0 < j1) {
-        constexpr int R2 = 2 * L::RS;
-        v2f h2[GRAD ? D : 1], sc2x = {0.0f, 0.0f}, as2 = {0.0f, 0.0f};
-        if constexpr (GRAD) {
-#pragma unroll
-            for (int k = 0; k < D; ++k) h2[k] = v2f{0.0f, 0.0f};
-        }
-        float xmk[D];
-#pragma unroll
-        for (int k = 0; k < D; ++k) xmk[k] = -2.0f * x[k];
-        float upc = 1.0f;
-        if constexpr (MODE == MODE_GRAD_UP) upc = up[0];
-        auto load2 = [&](float (&dst)[R2], int j) __attribute__((always_inline)) {
-            cfloat_ptr r = rows + (size_t)j * RSTRIDE;
-#pragma unroll
-            for (int e = 0; e < R2; ++e) dst[e] = r[e];
-        };
-        // the rare block, one row (half HF of the stage): out with the expanded term of the near lanes, in with the direct one
-        auto fix2 = [&](const float (&b)[R2], auto hf) __attribute__((always_inline)) {
-            constexpr int HF = decltype(hf)::value;
-            float d2 = xx + b[2 * L::SS_OFF + HF];
-#pragma unroll
-            for (int k = 0; k < D; ++k) d2 = fmaf(xmk[k], b[2 * k + HF], d2);
-            const float d2c = fmaxf(d2, thr);
-            const bool nr = d2c <= thr;
-            float val, g;
-            sweep_eval<KF, true>(d2c, a, val, g);
-            const float w = b[2 * L::W_OFF + HF];
-            float coef = g * w;
-            if constexpr (MODE == MODE_GRAD_UP) coef *= upc;
-            const float cneg = nr ? -coef : 0.0f;
-            // this row's half of a packed accumulator: v <- fma(p, q, v)
-            auto hfma = [&](v2f& v, float p_, float q_) __attribute__((always_inline)) {
-                if constexpr (HF) v.y = fmaf(p_, q_, v.y);
-                else v.x = fmaf(p_, q_, v.x);
-            };
-            if constexpr (KF == KF_POLY1 && MODE == MODE_GRAD_ROW) hfma(sc2x, cneg, d2c);
-            else hfma(sc2x, nr ? -w : 0.0f, val);
-            float dk[D];
-            float da = 0.0f, db = 0.0f;
-#pragma unroll
-            for (int k = 0; k < D; ++k) {
-                dk[k] = -0.5f * xmk[k] - b[2 * k + HF];     // x = -0.5 * (-2 x), exact
-                if (k & 1) db = fmaf(dk[k], dk[k], db);
-                else da = fmaf(dk[k], dk[k], da);
-            }
-            float vald, gd;
-            kernel_eval<KF>(da + db, a, vald, gd);          // (the direct sweep's distance: even / odd features, then the two halves)
-            hfma(sc2x, w, nr ? vald : 0.0f);
-            if constexpr (GRAD) {
-                float cdir = gd * w;
-                if constexpr (MODE == MODE_GRAD_UP) cdir *= upc;
-                const float cd = nr ? -cdir : 0.0f;          // H carries MINUS the gradient
-#pragma unroll
-                for (int k = 0; k < D; ++k) {
-                    hfma(h2[k], cneg, b[2 * k + HF]);
-                    hfma(h2[k], cd, dk[k]);
-                }
-                if constexpr (HF) as2.y += cneg;
-                else as2.x += cneg;
-            }
-        };
-        auto body2 = [&](const float (&b)[R2]) __attribute__((always_inline)) {
-#pragma unroll
-            for (int e = 2 * USED; e < R2; ++e) asm volatile("" ::"s"(b[e]));
-            v2f acc = v2f{xx, xx} + v2f{b[2 * L::SS_OFF], b[2 * L::SS_OFF + 1]};
-#pragma unroll
-            for (int k = 0; k < D; ++k) acc = __builtin_elementwise_fma(v2f{xmk[k], xmk[k]}, v2f{b[2 * k], b[2 * k + 1]}, acc);
-            v2f d2c = acc, val, g;
-            if constexpr (KF == KF_POLY1) d2c = v2f{fmaxf(acc.x, thr), fmaxf(acc.y, thr)};
-            {
-                float v0, g0, v1, g1;
-                sweep_eval<KF, true>(d2c.x, a, v0, g0);
-                sweep_eval<KF, true>(d2c.y, a, v1, g1);
-                val = v2f{v0, v1};
-                g = v2f{g0, g1};
-            }
-            const v2f w2 = {b[2 * L::W_OFF], b[2 * L::W_OFF + 1]};
-            v2f coef = g * w2;
-            if constexpr (MODE == MODE_GRAD_UP) coef = coef * v2f{upc, upc};
-            // one class, row weight, Polyharmonic(1): w r = (w / r) d2 - the score rides on the gradient coefficient
-            if constexpr (KF == KF_POLY1 && MODE == MODE_GRAD_ROW) sc2x = __builtin_elementwise_fma(coef, d2c, sc2x);
-            else sc2x = __builtin_elementwise_fma(w2, val, sc2x);
-            if constexpr (GRAD) {
-#pragma unroll
-                for (int k = 0; k < D; ++k) h2[k] = __builtin_elementwise_fma(coef, v2f{b[2 * k], b[2 * k + 1]}, h2[k]);
-                as2 += coef;
-            }
-            if constexpr (KF == KF_POLY1) {
-                if (__builtin_expect(__builtin_amdgcn_ballot_w64(fminf(d2c.x, d2c.y) <= thr) != 0, 0)) {
-                    fix2(b, std::integral_constant<int, 0>{});
-                    fix2(b, std::integral_constant<int, 1>{});
-                }
-            }
-        };
-        // fold the run's x * sum(c) into H in place: H <- H + (-2 x) (A / 2), per half
-        auto flush2 = [&]() __attribute__((always_inline)) {
-            if constexpr (GRAD) {
-                const v2f ah = {0.5f * as2.x, 0.5f * as2.y};
-#pragma unroll
-                for (int k = 0; k < D; ++k) h2[k] = __builtin_elementwise_fma(v2f{xmk[k], xmk[k]}, ah, h2[k]);
-                as2 = v2f{0.0f, 0.0f};
-            }
-        };
-        float ab[R2], cd[R2];
-        const int j1e = (j1 + 1) & ~1;
-        const int jl = j1e - 2;
-        load2(ab, j0);
-        int j = j0;
-        for (; j + 3 < j1e; j += 4) {
-            __builtin_amdgcn_s_waitcnt(0xC07F);
-            __builtin_amdgcn_sched_barrier(0);
-            load2(cd, j + 2);
-            __builtin_amdgcn_sched_barrier(0);
-            body2(ab);
-            __builtin_amdgcn_sched_barrier(0);
-            __builtin_amdgcn_s_waitcnt(0xC07F);
-            __builtin_amdgcn_sched_barrier(0);
-            load2(ab, (j + 4 < j1e) ? j + 4 : jl);
-            __builtin_amdgcn_sched_barrier(0);
-            body2(cd);
-            __builtin_amdgcn_sched_barrier(0);
-            if constexpr (GRAD) {
-                if ((j & (DCX_XF_FLUSH - 4)) == 0) flush2();  // once per DCX_XF_FLUSH rows, whatever j0's alignment
-            }
-        }
-        if (j < j1e) body2(ab);   // one stage left; ab holds it
-        flush2();
-        sc[0] += sc2x.x + sc2x.y;
-        if constexpr (GRAD) {
-#pragma unroll
-            for (int k = 0; k < D; ++k) gx[k] -= h2[k].x + h2[k].y;
-        }
-    }
-    } else if constexpr (XM) {
-    // ---- XM: the expanded form with x . s^T on the matrix cores (round 3) ---------------------------------------------------
-    // d2 = (|x|^2 + |s_j|^2) + sum_k (-2 x_k) s_jk: the one contraction of the sweep whose per-lane operand is loop
-    // invariant.  -2x is split ONCE per lane into three bf16 planes (hi, mid, lo by truncation: 24 bits) and turned into
-    // the B fragments of the four 16-configuration tiles with the 4 x 4 lane transpose; the supports were split on the
-    // host and laid out as A operands (dcx_model_create, `aplanes`).  The six plane products that matter (hi.hi, hi.mid,
-    // mid.hi, hi.lo, lo.hi, mid.mid) sit side by side along K (6 terms x 16 slots = three v_mfma_f32_16x16x32_bf16 per
-    // tile), accumulated in fp32 inside the instruction: the sum carries the 2^-24 (|x| |s|) error of the fp32 expanded
-    // form.  Per 16 supports and wave: 12 MFMAs + 16 lane swaps give every lane its 16 dot products; the rest of the
-    // pair body (clamp, 1 / r, score, fold, near pairs) is the XF one, two rows per scalar-load stage.  Measured in
-    // isolation (tools/contraction_ubench.hip, "pair body"): 82-86 cycles per wave-row against 96-98.
-    static_assert(XFA && CC == 1 && D <= 16 && (D % 2) == 0, "XM: one class, even D <= 16, expanded form");
-    if (j0 < j1) {
-        typedef unsigned int v4u __attribute__((ext_vector_type(4)));
-        typedef __bf16 v8bf __attribute__((ext_vector_type(8)));
-        typedef float v4f_ __attribute__((ext_vector_type(4)));
-        const int lane_ = (int)__builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u));
-        auto frags = [&](unsigned int c0, unsigned int c1, unsigned int c2, unsigned int c3, unsigned int (&f)[4]) __attribute__((always_inline)) {
-            auto s02 = __builtin_amdgcn_permlane32_swap(c0, c2, false, false);
-            auto s13 = __builtin_amdgcn_permlane32_swap(c1, c3, false, false);
-            auto t01 = __builtin_amdgcn_permlane16_swap(s02[0], s13[0], false, false);
-            auto t23 = __builtin_amdgcn_permlane16_swap(s02[1], s13[1], false, false);
-            f[0] = t01[0]; f[1] = t01[1]; f[2] = t23[0]; f[3] = t23[1];
-        };
-        v4u bfrag[4][3];
-        {
-            unsigned int pk[3][8];  // [plane][feature pair], features past D are zero
-#pragma unroll
-            for (int p = 0; p < 8; ++p) {
-                float r0 = (2 * p < D) ? -2.0f * x[2 * p < D ? 2 * p : 0] : 0.0f;
-                float r1 = (2 * p + 1 < D) ? -2.0f * x[2 * p + 1 < D ? 2 * p + 1 : 0] : 0.0f;
-#pragma unroll
-                for (int pl = 0; pl < 3; ++pl) {
-                    const unsigned int u0 = __float_as_uint(r0) & 0xFFFF0000u, u1 = __float_as_uint(r1) & 0xFFFF0000u;
-                    pk[pl][p] = __builtin_amdgcn_perm(u1, u0, 0x07060302u);
-                    r0 -= __uint_as_float(u0);
-                    r1 -= __uint_as_float(u1);
-                }
-            }
-            constexpr int xplane_of_term[6] = {0, 0, 1, 0, 2, 1};  // terms: hi.hi hi.mid mid.hi hi.lo lo.hi mid.mid (x plane)
-#pragma unroll
-            for (int c = 0; c < 3; ++c)
-#pragma unroll
-                for (int e = 0; e < 4; ++e) {
-                    // lane (n, k'): k' = 0, 1 -> term 2c, features 8 k' + 2e, + 1;  k' = 2, 3 -> term 2c + 1
-                    unsigned int f[4];
-                    frags(pk[xplane_of_term[2 * c]][e], pk[xplane_of_term[2 * c]][4 + e], pk[xplane_of_term[2 * c + 1]][e],
-                          pk[xplane_of_term[2 * c + 1]][4 + e], f);
-#pragma unroll
-                    for (int t = 0; t < 4; ++t) bfrag[t][c][e] = f[t];
-                }
-        }
-        // one row with its distance term from the matrix cores; returns the clamped distance
-        auto pair_m = [&](const auto& r, float dot) __attribute__((always_inline)) -> float {
-            const float d2 = fmaxf((xx + r[L::SS_OFF]) + dot, thr);
-            apply_x(r, d2, std::integral_constant<int, 1>{}, true);
-            return d2;
-        };
-        auto stage_m = [&](const auto& r0, const auto& r1, float dt0, float dt1) __attribute__((always_inline)) {
-            const float d0 = pair_m(r0, dt0), d1 = pair_m(r1, dt1);
-            const auto m0 = __builtin_amdgcn_ballot_w64(d0 <= thr);
-            const auto m1 = __builtin_amdgcn_ballot_w64(d1 <= thr);
-            if (__builtin_expect((m0 | m1) != 0, 0)) {
-                fix_near(r0, d0);
-                fix_near(r1, d1);
-            }
-        };
-        float rowA[L::RS], rowB[L::RS], rowC[L::RS], rowD[L::RS];
-        const int jl = j1 - 1;
-        int j = j0;
-        // rows in front of the first 16-row block of the A planes (slices start on a block boundary except where a caller's
-        // slicing does not: then at most 15 rows): the XF body
-        for (; j < j1 && (j & 15) != 0; ++j) {
-            load_row(rowA, j);
-            __builtin_amdgcn_s_waitcnt(0xC07F);
-            single_x(rowA);
-        }
-        if (j + 16 <= j1) {
-            // A operand of a 16-row block: lane (m, k') reads 16 bytes of [block][chunk][support m][k']
-            const v4u* ap = reinterpret_cast<const v4u*>(a.aplanes) + (lane_ & 15) * 4 + (lane_ >> 4);
-            v4u a0 = ap[(size_t)(j >> 4) * 192], a1 = ap[(size_t)(j >> 4) * 192 + 64], a2 = ap[(size_t)(j >> 4) * 192 + 128];
-            load_row(rowA, j);
-            load_row(rowB, j + 1);
-            for (; j + 16 <= j1; j += 16) {
-                const size_t nb = (size_t)((j >> 4) + 1) * 192;   // (the planes are padded by two blocks)
-                const v4u n0 = ap[nb], n1 = ap[nb + 64], n2 = ap[nb + 128];
-                float dot[16];
-                {
-                    v4f_ d[4];
-#pragma unroll
-                    for (int t = 0; t < 4; ++t) {
-                        v4f_ c = {0.f, 0.f, 0.f, 0.f};  // small terms first
-                        c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(v8bf, a2), __builtin_bit_cast(v8bf, bfrag[t][2]), c, 0, 0, 0);
-                        c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(v8bf, a1), __builtin_bit_cast(v8bf, bfrag[t][1]), c, 0, 0, 0);
-                        c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(v8bf, a0), __builtin_bit_cast(v8bf, bfrag[t][0]), c, 0, 0, 0);
-                        d[t] = c;
-                    }
-#pragma unroll
-                    for (int i = 0; i < 4; ++i) {
-                        unsigned int f[4];
-                        frags(__float_as_uint(d[0][i]), __float_as_uint(d[1][i]), __float_as_uint(d[2][i]), __float_as_uint(d[3][i]), f);
-#pragma unroll
-                        for (int g = 0; g < 4; ++g) dot[4 * g + i] = __uint_as_float(f[g]);
-                    }
-                }
-                a0 = n0; a1 = n1; a2 = n2;
-#pragma unroll
-                for (int q = 0; q < 16; q += 4) {
-                    __builtin_amdgcn_s_waitcnt(0xC07F);
-                    __builtin_amdgcn_sched_barrier(0);
-                    load_row(rowC, j + q + 2);
-                    load_row(rowD, j + q + 3);
-                    __builtin_amdgcn_sched_barrier(0);
-                    stage_m(rowA, rowB, dot[q], dot[q + 1]);
-                    __builtin_amdgcn_sched_barrier(0);
-                    __builtin_amdgcn_s_waitcnt(0xC07F);
-                    __builtin_amdgcn_sched_barrier(0);
-                    load_row(rowA, (j + q + 4 < j1) ? j + q + 4 : jl);
-                    load_row(rowB, (j + q + 5 < j1) ? j + q + 5 : jl);
-                    __builtin_amdgcn_sched_barrier(0);
-                    stage_m(rowC, rowD, dot[q + 2], dot[q + 3]);
-                    __builtin_amdgcn_sched_barrier(0);
-                }
-                if constexpr (GRAD) {
-                    if ((j & 48) == 0) flush_x();  // once per 64 rows
-                }
-            }
-        }
-        // what is left of the slice (< 16 rows): the XF body
-        for (; j < j1; ++j) {
-            load_row(rowA, j);
-            __builtin_amdgcn_s_waitcnt(0xC07F);
-            single_x(rowA);
-        }
-    }
-    } else if constexpr (P2 && DCX_PAIR2_LOADS) {
+    if constexpr (P2 && DCX_PAIR2_LOADS) {
     // pair2's own pipeline: the two rows of a stage are ONE piece of memory (pair-interleaved, see above), so they arrive by one
     // scalar load of 2 RS floats (one address computation per stage instead of one per row: with 12 VALU instructions per pair the
     // scalar unit, which the four SIMDs of a CU share, had become nearly as busy as the vector one).  j0 is even (the host's
@@ -1213,20 +899,6 @@ __device__ __forceinline__ void sweep_rows(const ScoreArgs& a, const float (&x)[
                 return;
             }
             --exp_real_loads;
-#endif
-#if defined(DCX_EXP_LOAD_DWORDS)   // timing experiment only (wrong results): fetch this many dwords per row, whatever its width
-            static_assert(PARTS != 1 || DCX_EXP_LOAD_DWORDS <= 16 || RSTRIDE >= 32, "build with DCX_ROW_ALIGN_MULTI=32");
-            if constexpr (PARTS == 1) {
-                float extra = 0.0f;
-#pragma unroll
-                for (int e = 0; e < (DCX_EXP_LOAD_DWORDS < LEN ? DCX_EXP_LOAD_DWORDS : LEN); ++e) dst[e] = r[e];
-#pragma unroll
-                for (int e = DCX_EXP_LOAD_DWORDS; e < LEN; ++e) dst[e] = dst[e - DCX_EXP_LOAD_DWORDS];
-#pragma unroll
-                for (int e = LEN; e < DCX_EXP_LOAD_DWORDS; ++e) extra += r[e];   // dwords beyond the row: fetched and folded into one operand
-                if constexpr (DCX_EXP_LOAD_DWORDS > LEN) dst[LEN - 1] += 1e-30f * extra;
-                return;
-            }
 #endif
 #pragma unroll
             for (int e = 0; e < LEN; ++e) dst[e] = r[e];
@@ -1375,9 +1047,7 @@ __device__ __forceinline__ void sweep_rows(const ScoreArgs& a, const float (&x)[
         }
     }
 
-    if constexpr (X2) {
-        // (flushed and merged inside its own block above)
-    } else if constexpr (XFA && GRAD) {
+    if constexpr (XFA && GRAD) {
         flush_x();
 #pragma unroll
         for (int k = 0; k + 1 < D; k += 2) {
@@ -1499,222 +1169,6 @@ __device__ __forceinline__ void sweep_rows_lds(const ScoreArgs& a, const float (
     }
 }
 
-// ---- the sweep with the (configurations x supports) . (supports x features) contraction on the matrix cores ------
-// The gradient fold  gX[b, :] = sum_j coef_bj (x_b - s_j)  is  x_b * (sum_j coef_bj) - (coef[B, S] . s[S, D])[b, :].
-// The second term is a dense GEMM; here it runs on v_mfma_f32_16x16x4_f32 (exact fp32, an fmaf chain in k order — the
-// same arithmetic as the VALU form) while the VALU keeps the per-pair work that is not GEMM-shaped (differences,
-// squared distance, kernel function).  The VALU and matrix pipes issue side by side, so the D fma per pair of the
-// gradient accumulation leave the critical pipe altogether.
-//   * A operand (16 configurations x 4 supports): the four coefficients a lane computed for supports j .. j+3 sit in
-//     four VGPRs; a 4x4 transpose of the 16-lane groups (2 v_permlane32_swap + 2 v_permlane16_swap) turns them into
-//     the A fragments of the wave's four 16-configuration tiles.
-//   * B operand (4 supports x 16 columns): one dword per lane straight from the support rows (lane l reads column
-//     l % 16 of row j + l / 16), prefetched one step ahead.  Columns >= D are never read back.
-//   * the expanded form cancels (x * sum(coef) against coef . s), so it is only ever applied to SHORT runs of
-//     supports: every MF_FLUSH steps the four accumulators go through this wave's LDS scratch back to the
-//     lane-per-configuration layout, are combined with x * sum(coef) of the same run, and restart from zero.  A run's
-//     partial sums stay within 4 * MF_FLUSH supports' worth of magnitude, so the rounding of the subtraction is
-//     ~1e-6 of the result even when every weight has the same sign (distance-regression models).
-#ifndef DCX_MF_FLUSH
-#define DCX_MF_FLUSH 16
-#endif
-typedef float v4f __attribute__((ext_vector_type(4)));
-
-template <int D, int KF, int CC, int MODE>
-__device__ __forceinline__ void sweep_rows_mfma(const ScoreArgs& a, const float (&x)[D], const float (&up)[CC], int j0, int j1,
-                                                float (&sc)[CC], float (&gx)[D], float* wscr, int lane) {
-    using L = RowLayout<D, CC>;
-    static_assert(D <= 16 && (D % 2) == 0 && MODE != MODE_SCORE, "MFMA sweep: even D <= 16, gradient modes");
-    constexpr int PITCH = D + 1;  // odd pitch: conflict-free ds_read across configurations
-    cfloat_ptr rows = (cfloat_ptr)(uintptr_t)a.rows;
-    const float* rows_g = a.rows;
-    const int grp = lane >> 4, col = lane & 15;
-    v4f acc[4];
-    // C > 1: the weight contraction K[configurations x supports] . W[supports x classes] runs on the matrix cores too
-    // (KW): the kernel values of a step are transposed like the coefficients, the B operand is the W block of the same
-    // four rows (classes past C read as zero), one accumulator per 16-configuration tile
-    constexpr bool KW = CC > 1;
-    v4f accS[4];
-#pragma unroll
-    for (int t = 0; t < 4; ++t) acc[t] = accS[t] = v4f{0.f, 0.f, 0.f, 0.f};
-    float asum = 0.0f;
-    float near2 = 1e-30f;  // pairs closer than 0.1 |x| take the direct form (see pair): the expanded sweep's threshold.  At the
-                           // first version's 1e-3 |x| the fold lost 2e-5 on queries planted 0.001-0.1 |x| from a support
-                           // (tests/test_gpu_parity.py::test_expanded_form_around_the_near_threshold)
-#pragma unroll
-    for (int k = 0; k < D; ++k) near2 = fmaf(DCX_XF_TAU * x[k], x[k], near2);
-
-    // one support row: score accumulation on the VALU, returns the gradient coefficient
-    auto pair = [&](const float (&r)[L::RS], float& val) __attribute__((always_inline)) -> float {
-        v2f d2a = {0.0f, 0.0f};
-#pragma unroll
-        for (int k = 0; k + 1 < D; k += 2) {
-            const v2f xv = {x[k], x[k + 1]};
-            const v2f rv = {r[k], r[k + 1]};
-            const v2f dv = xv - rv;
-            d2a = __builtin_elementwise_fma(dv, dv, d2a);
-        }
-        const float d2 = d2a.x + d2a.y;
-        float g;
-        sweep_eval<KF>(d2 + d2_seed<KF>(a), a, val, g);
-        if constexpr (!KW) sc[0] = fmaf(r[L::W_OFF], val, sc[0]);
-        float coef;
-        if constexpr (MODE == MODE_GRAD_ROW) {
-            coef = g * r[CC > 1 ? L::WSUM_OFF : L::W_OFF];
-        } else {
-            float wb = 0.0f;
-#pragma unroll
-            for (int c = 0; c < CC; ++c) wb = fmaf(up[c], r[L::W_OFF + c], wb);
-            coef = g * wb;
-        }
-        // A query (almost) on top of a support: coef ~ 1/r is huge and the expanded form would subtract two huge
-        // numbers.  Such a pair takes the direct form  gx += coef * (x - s)  here and leaves the GEMM with a zero
-        // coefficient (r == 0 contributes exactly zero, like the VALU sweep).  Rare: one wave-uniform branch per row.
-        if (__builtin_expect(__builtin_amdgcn_ballot_w64(d2 < near2) != 0, 0)) {
-            if (d2 < near2) {
-#pragma unroll
-                for (int k = 0; k < D; ++k) gx[k] = fmaf(coef, x[k] - r[k], gx[k]);
-                coef = 0.0f;
-            }
-        }
-        asum += coef;
-        return coef;
-    };
-    constexpr int USED = D + CC + (CC > 1 ? 1 : 0);
-    auto load_row = [&](float (&dst)[L::RS], int j) __attribute__((always_inline)) {
-        cfloat_ptr r = rows + (size_t)j * L::RS;
-#pragma unroll
-        for (int e = 0; e < USED; ++e) dst[e] = r[e];
-    };
-    // accumulators -> lane-per-configuration layout through this wave's LDS scratch; gx += x * asum - (coef . s)
-    auto flush = [&]() __attribute__((always_inline)) {
-        if (col < D) {
-#pragma unroll
-            for (int t = 0; t < 4; ++t) {
-#pragma unroll
-                for (int i = 0; i < 4; ++i) wscr[(16 * t + 4 * grp + i) * PITCH + col] = acc[t][i];
-            }
-        }
-        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");
-        __builtin_amdgcn_wave_barrier();
-#pragma unroll
-        for (int k = 0; k < D; ++k) gx[k] = fmaf(x[k], asum, gx[k] - wscr[lane * PITCH + k]);
-        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");
-        __builtin_amdgcn_wave_barrier();
-        if constexpr (KW) {   // the score tiles: lane (n, g) holds class n of configurations 16 t + 4 g + i
-            if (col < CC) {
-#pragma unroll
-                for (int t = 0; t < 4; ++t) {
-#pragma unroll
-                    for (int i = 0; i < 4; ++i) wscr[(16 * t + 4 * grp + i) * PITCH + col] = accS[t][i];
-                }
-            }
-            __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");
-            __builtin_amdgcn_wave_barrier();
-#pragma unroll
-            for (int c = 0; c < CC; ++c) sc[c] += wscr[lane * PITCH + c];
-            __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");
-            __builtin_amdgcn_wave_barrier();
-        }
-#pragma unroll
-        for (int t = 0; t < 4; ++t) acc[t] = accS[t] = v4f{0.f, 0.f, 0.f, 0.f};
-        asum = 0.0f;
-    };
-    // four per-lane values of a step (one per support row) -> the A fragments of the four 16-configuration tiles
-    auto frags = [&](float c0, float c1, float c2, float c3, float (&f)[4]) __attribute__((always_inline)) {
-        auto s02 = __builtin_amdgcn_permlane32_swap(__float_as_uint(c0), __float_as_uint(c2), false, false);
-        auto s13 = __builtin_amdgcn_permlane32_swap(__float_as_uint(c1), __float_as_uint(c3), false, false);
-        auto t01 = __builtin_amdgcn_permlane16_swap(s02[0], s13[0], false, false);
-        auto t23 = __builtin_amdgcn_permlane16_swap(s02[1], s13[1], false, false);
-        f[0] = __uint_as_float(t01[0]); f[1] = __uint_as_float(t01[1]);
-        f[2] = __uint_as_float(t23[0]); f[3] = __uint_as_float(t23[1]);
-    };
-    auto contract_kw = [&](float v0, float v1, float v2, float v3, float bw) __attribute__((always_inline)) {
-        float f[4];
-        frags(v0, v1, v2, v3, f);
-#pragma unroll
-        for (int t = 0; t < 4; ++t) accS[t] = __builtin_amdgcn_mfma_f32_16x16x4f32(f[t], bw, accS[t], 0, 0, 0);
-    };
-    // the four coefficients of a step -> A fragments of the four 16-configuration tiles, then the MFMAs
-    auto contract = [&](float c0, float c1, float c2, float c3, float bv) __attribute__((always_inline)) {
-        auto s02 = __builtin_amdgcn_permlane32_swap(__float_as_uint(c0), __float_as_uint(c2), false, false);
-        auto s13 = __builtin_amdgcn_permlane32_swap(__float_as_uint(c1), __float_as_uint(c3), false, false);
-        auto t01 = __builtin_amdgcn_permlane16_swap(s02[0], s13[0], false, false);
-        auto t23 = __builtin_amdgcn_permlane16_swap(s02[1], s13[1], false, false);
-        acc[0] = __builtin_amdgcn_mfma_f32_16x16x4f32(__uint_as_float(t01[0]), bv, acc[0], 0, 0, 0);
-        acc[1] = __builtin_amdgcn_mfma_f32_16x16x4f32(__uint_as_float(t01[1]), bv, acc[1], 0, 0, 0);
-        acc[2] = __builtin_amdgcn_mfma_f32_16x16x4f32(__uint_as_float(t23[0]), bv, acc[2], 0, 0, 0);
-        acc[3] = __builtin_amdgcn_mfma_f32_16x16x4f32(__uint_as_float(t23[1]), bv, acc[3], 0, 0, 0);
-    };
-
-    if (j0 < j1) {
-        float rowA[L::RS], rowB[L::RS], rowC[L::RS], rowD[L::RS];
-        const int jl = j1 - 1;  // clamp target for the look-ahead loads (harmless re-reads at the end)
-        // B operand: lane l reads column l % 16 of row j + l / 16.  A uniform base that advances by four rows per step
-        // plus a constant per-lane offset (saddr + voffset addressing, no per-step vector address arithmetic).  Rows
-        // past this wave's slice are real rows of the next slice or the zeroed tail padding of the row array
-        // (dcx_model_create pads it): they only ever meet a zero coefficient.
-        const float* bp = rows_g + (size_t)j0 * L::RS;
-        const int boff = grp * L::RS + col;
-        const int woff = grp * L::RS + L::W_OFF + (col < CC ? col : 0);  // B operand of the weight contraction
-        const float wmask = (col < CC) ? 1.0f : 0.0f;
-        load_row(rowA, j0);
-        load_row(rowB, (j0 + 1 < j1) ? j0 + 1 : jl);
-        float bcur = bp[boff];
-        float wcur = KW ? bp[woff] * wmask : 0.0f;
-        float v0, v1, v2, v3;
-        int j = j0, since = 0;
-        for (; j + 3 < j1; j += 4) {
-            bp += 4 * L::RS;
-            const float bnext = bp[boff];
-            float wnext = 0.0f;
-            if constexpr (KW) wnext = bp[woff] * wmask;
-            __builtin_amdgcn_s_waitcnt(0xC07F);
-            __builtin_amdgcn_sched_barrier(0);
-            load_row(rowC, j + 2);
-            load_row(rowD, j + 3);
-            __builtin_amdgcn_sched_barrier(0);
-            const float c0 = pair(rowA, v0);
-            const float c1 = pair(rowB, v1);
-            __builtin_amdgcn_sched_barrier(0);
-            __builtin_amdgcn_s_waitcnt(0xC07F);
-            __builtin_amdgcn_sched_barrier(0);
-            load_row(rowA, (j + 4 < j1) ? j + 4 : jl);
-            load_row(rowB, (j + 5 < j1) ? j + 5 : jl);
-            __builtin_amdgcn_sched_barrier(0);
-            const float c2 = pair(rowC, v2);
-            const float c3 = pair(rowD, v3);
-            contract(c0, c1, c2, c3, bcur);
-            if constexpr (KW) contract_kw(v0, v1, v2, v3, wcur);
-            __builtin_amdgcn_sched_barrier(0);
-            bcur = bnext;
-            wcur = wnext;
-            if (++since == DCX_MF_FLUSH) {
-                flush();
-                since = 0;
-            }
-        }
-        // up to three rows left (rowA / rowB hold rows j and j+1): absent rows contribute a zero coefficient
-        if (j < j1) {
-            v1 = v2 = 0.0f;
-            float c0 = pair(rowA, v0), c1 = 0.0f, c2 = 0.0f;
-            if (j + 1 < j1) c1 = pair(rowB, v1);
-            if (j + 2 < j1) {
-                load_row(rowC, j + 2);
-                c2 = pair(rowC, v2);
-            }
-            contract(c0, c1, c2, 0.0f, bcur);
-            if constexpr (KW) contract_kw(v0, v1, v2, 0.0f, wcur);
-        }
-        flush();
-    }
-    if constexpr (kGradScale<KF> != 1.0f) {
-#pragma unroll
-        for (int k = 0; k < D; ++k) gx[k] *= kGradScale<KF>;
-    }
-}
-
-
 // The parallel cross-wave fold: the nw waves of a block have left their ACC partial sums per lane in sRed[w][e][64]; every
 // wave folds a few of the accumulators over the nw rows - row 0 first, then 1, 2, ..., the order a single wave would use,
 // so the sums do not depend on nw's parallelism - into row 0.  The block sizes the launch rules pick are compiled in: all nw
@@ -1748,13 +1202,13 @@ __device__ __forceinline__ void fold_partial_rows(float* sRed, int wave, int lan
 }
 
 
-template <int D, int KF, int CC, int MODE, int MAXT, bool MF = false, bool XF = false, bool XM = false, bool QT = false>
-__global__ __launch_bounds__(MAXT, sweep_min_waves(D, CC, KF, MF, XM, QT, XF)) void score_kernel(const ScoreArgs a) {
+template <int D, int KF, int CC, int MODE, int MAXT, bool XF = false, bool QT = false>
+__global__ __launch_bounds__(MAXT, sweep_min_waves(D, CC, KF, QT)) void score_kernel(const ScoreArgs a) {
     extern __shared__ __attribute__((aligned(16))) float smem[];
     constexpr bool GRAD = (MODE != MODE_SCORE);
     constexpr int ACC = (GRAD ? D : 0) + CC;
     constexpr int TILE = QT ? 16 : 64;   // configurations per block (QT: lane l works for configuration l & 15)
-    static_assert(!QT || (!MF && !XF && !XM && qt_applies(D, CC, KF, MODE)), "the quarter tile: direct form, one class, row weights");
+    static_assert(!QT || (!XF && qt_applies(D, CC, KF, MODE)), "the quarter tile: direct form, one class, row weights");
 
     int lane = threadIdx.x & 63;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
@@ -1766,7 +1220,6 @@ __global__ __launch_bounds__(MAXT, sweep_min_waves(D, CC, KF, MF, XM, QT, XF)) v
     float* sQ = smem + lp.q;
     float* sX = smem + lp.x;
     float* sF = smem + lp.f;
-    float* sRed = smem + lp.red;
 
     // QT: all the rows go into LDS, slice by slice (4 nw slices of qt_per rows; short slices end in zero rows: weight 0) - the
     // first qt_front rows with the q rows below (their loads ride on the same round trip), the rest by the waves that have no
@@ -1818,9 +1271,6 @@ __global__ __launch_bounds__(MAXT, sweep_min_waves(D, CC, KF, MF, XM, QT, XF)) v
     }
     __syncthreads();
     DCX_TS(1);
-#if defined(DCX_ABLATE) && (DCX_ABLATE & 2)  // timing ablation only (wrong results): no FK
-    if (wave == 0) for (int k = 0; k < a.d_fk; ++k) sX[k * 64 + lane] = sQ[lane * dof + (k % dof)];
-#else
     fk_trig_sel(fw, a.dh, sQ + lane * dof, sF + lane, wave, nw);   // all waves: sin/cos of the joint angles
     __syncthreads();
     DCX_TS(6);
@@ -1833,7 +1283,6 @@ __global__ __launch_bounds__(MAXT, sweep_min_waves(D, CC, KF, MF, XM, QT, XF)) v
     } else {
         stage_rows(1, a.qt_front, kQtSlices * nw * a.qt_per);
     }
-#endif
     __syncthreads();
 
     DCX_TS(2);
@@ -1883,10 +1332,6 @@ __global__ __launch_bounds__(MAXT, sweep_min_waves(D, CC, KF, MF, XM, QT, XF)) v
     const int yend = (ybase + a.s_super < a.S) ? (ybase + a.s_super) : a.S;
     int j0, j1;
     wave_slice(wave, nw, a.s_chunk, a.s_skew, ybase, yend, j0, j1);
-#ifdef DCX_EXP_SAME_SLICE   // timing experiment only (wrong results): every wave of a block sweeps the SAME rows (scalar-cache hits)
-    j1 -= j0 - ybase;
-    j0 = ybase;
-#endif
 
     DCX_TSB(1);
     if constexpr (QT) {
@@ -1898,11 +1343,8 @@ __global__ __launch_bounds__(MAXT, sweep_min_waves(D, CC, KF, MF, XM, QT, XF)) v
         for (int h = 0; h < g; ++h) base += 16 * (a.qt_per_g[h] * RSQ + 4);
         const float* slice = smem + a.qt_off + base + ((wave & 3) * kQtSlices + (lane >> 4)) * (per * RSQ + 4);
         sweep_rows_lds<D, KF, GRAD>(a, x, slice, per, sc[0], gx);
-    } else if constexpr (MF) {
-        // this wave's slice of the reduction scratch doubles as its transpose buffer (X is dead, the fold comes later)
-        sweep_rows_mfma<D, KF, CC, MODE>(a, x, up, j0, j1, sc, gx, sRed + (size_t)wave * ACC * 64, lane);
     } else {
-        sweep_rows<D, KF, CC, MODE, XF, 0, XM>(a, x, up, j0, j1, sc, gx);
+        sweep_rows<D, KF, CC, MODE, XF>(a, x, up, j0, j1, sc, gx);
     }
     DCX_TS(3);
     {   // ---- epilogue: everything below reads the kernel arguments afresh (reload_args) and re-derives what it needs ----
@@ -2114,17 +1556,6 @@ __global__ __launch_bounds__(MAXT, sweep_min_waves(D, CC, KF, MF, XM, QT, XF)) v
                 }
                 float* gq = smem + lp.q;
                 float* scr = (QT && r1_done) ? smem + b.qt_scr + lane : sRed + (size_t)ACC * 64 + lane;
-#if defined(DCX_ABLATE) && (DCX_ABLATE & 4)  // timing ablation only (wrong results): no J^T on the several-wave path either
-                if (wave != 0) return;
-                for (int i = 0; i < dof; ++i) gq[lane * dof + i] = sRed[(CC + (i % b.d_fk)) * 64 + lane] * scale;
-                if (true) {
-                    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");
-                    __builtin_amdgcn_wave_barrier();
-                    float* gdst0 = b.grad + b0 * b.grad_stride;
-                    for (int i = lane; i < nb * dof; i += 64) gdst0[(int64_t)(i / dof) * b.grad_stride + (i % dof)] = gq[i];
-                    return;
-                }
-#endif
                 if (!r1_done) {  // unsplit launches (and blocks too small to run it beside the counter)
                     dh2_vjp_r1_sel(fw.dh, dhb, sF + lane, scr, wave);
                     __syncthreads();
@@ -2298,11 +1729,7 @@ __global__ __launch_bounds__(MAXT, sweep_min_waves(D, CC, KF, MF, XM, QT, XF)) v
         // J^T gX per lane.  The gradient row is built in place of the lane's own q row: every
         // fk_vjp branch reads what it needs from the q row before its first write to gq.
         float* gq = smem + lp.q;
-#if defined(DCX_ABLATE) && (DCX_ABLATE & 1)  // timing ablation only (wrong results): no J^T
-        for (int i = 0; i < dof; ++i) gq[lane * dof + i] = sG[(i % b.d_fk) * 64 + lane];
-#else
         fk_vjp_sel(fw, dhb, sQ + lane * dof, sF + lane, sG + lane, gq + lane * dof, dof);
-#endif
         DCX_TS(5);
         // rows -> HBM, coalesced (LDS ops of one wave complete in order; no other wave is alive)
         __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");

@@ -506,7 +506,7 @@ __global__ __launch_bounds__(MAXT, (MAXT / 256 > 0 ? MAXT / 256 : 1)) void traj_
                 for (int c = 0; c < CC; ++c) sc[c] = 0.0f;
 #pragma unroll
                 for (int k = 0; k < D; ++k) gx[k] = 0.0f;
-                sweep_rows<D, KF, CC, MODE_GRAD_UP, XF, DCX_TRAJ_NACC, false, true>(sa, x, up, j0, j1, sc, gx);   // (NS: the scores are known)
+                sweep_rows<D, KF, CC, MODE_GRAD_UP, XF, DCX_TRAJ_NACC, true>(sa, x, up, j0, j1, sc, gx);   // (NS: the scores are known)
             }
             grad_folded = !resweep;             // a speculation that held (or no gradient at all): the totals are in row 0 already
             regrad = spec_full && resweep;      // a speculation that failed: its second gradient travels through words of its own

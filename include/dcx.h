@@ -33,7 +33,7 @@
 extern "C" {
 #endif
 
-#define DCX_VERSION 109 /* 0.1.8: the optimisers' collision term for several classes under per-class margins (dcx_score_hinge_grad_mc, dcx_traj_adam_run_mc, dcx_traj_adam_step_mc), dcx_dh_frames / dcx_euler_frames (utils.DH2mat / euler2mat); 0.1.7: dcx_escape_adam (the escape loop of scripts/escape.py on the stream); 0.1.6: dcx_debug_clock_probe; the matrix-core forms are a build option (dcx_debug_set("mfma" / "xm", 1) -> DCX_ERR_UNSUPPORTED without them); owner-polls words tagged per launch, give-up reported by the model's next launch; 0.1.5: dcx_model_create_ex / dcx_model_update (rows packed on the device); 0.1.4: dcx_train_perceptron_ex (per-call flags); 0.1.3: dcx_fk_desc carries the DCX_FK_TREE section; 32 control points, D <= 96 */
+#define DCX_VERSION 109 /* 0.1.8: the optimisers' collision term for several classes under per-class margins (dcx_score_hinge_grad_mc, dcx_traj_adam_run_mc, dcx_traj_adam_step_mc), dcx_dh_frames / dcx_euler_frames (utils.DH2mat / euler2mat); 0.1.7: dcx_escape_adam (the escape loop of scripts/escape.py on the stream); 0.1.6: dcx_debug_clock_probe; the matrix-core forms left the default build (since removed: dcx_debug_set("mfma" / "xm", 1) -> DCX_ERR_UNSUPPORTED); owner-polls words tagged per launch, give-up reported by the model's next launch; 0.1.5: dcx_model_create_ex / dcx_model_update (rows packed on the device); 0.1.4: dcx_train_perceptron_ex (per-call flags); 0.1.3: dcx_fk_desc carries the DCX_FK_TREE section; 32 control points, D <= 96 */
 
 /* ---- status codes ---------------------------------------------------------------- */
 #define DCX_OK 0
@@ -146,8 +146,8 @@ int dcx_device_count(void);
 /* Developer knobs for tests and A/B tools: override one of the launch-geometry rules (they change how the work
  * is split over blocks, never what is computed).  name: "ys" (support super-chunks per tile), "nw" (waves per
  * block), "min_rows" (supports per wave slice), "split_finish_kernel" (1 = finish split launches with a second
- * launch), "inlaunch_tiles", "jac_per_class" (1 = one launch per class in dcx_score_jac), "mfma" (0 = never use the
- * MFMA contraction, 1 = use it wherever it is compiled), "xf" (0 = the sweep in its direct form everywhere, 1 / rule =
+ * launch), "inlaunch_tiles", "jac_per_class" (1 = one launch per class in dcx_score_jac), "mfma" and "xm" (the
+ * matrix-core forms, removed: 0 and rule are accepted, 1 answers DCX_ERR_UNSUPPORTED), "xf" (0 = the sweep in its direct form everywhere, 1 / rule =
  * the expanded form wherever it is compiled and the model qualifies: Polyharmonic(1), or RQKernel(p = 2) behind an FK
  * transform with gamma * max |s - centroid|^2 <= 32; rows of <= 37 floats; the two forms agree to ~1e-6; 2 = also for RQ
  * models outside that rule: measurements only),
@@ -162,8 +162,7 @@ int dcx_device_count(void);
  * the rule takes it when every block of the launch is resident at once), "hess_ys" (blocks per tile of dcx_score_hess; 1 =
  * never split the supports), "hess_form" (dcx_score_hess: 0 = one lane per (configuration, direction) sweeps the supports, 1 = the
  * moments form - one lane per configuration sweeps gradient, coefficient sum and the symmetric D x D matrix, the direction lanes
- * read M dx - wherever it is compiled (D <= 16); rule = from B = 1024; same Hessian to fp32 round-off), "xm" (1 = the expanded form takes its distance GEMM from the matrix cores, bf16x3 split
- * operands, where compiled: one class, Polyharmonic(1), even D <= 16; agrees with the VALU form to ~1e-6, measured slower),
+ * read M dx - wherever it is compiled (D <= 16); rule = from B = 1024; same Hessian to fp32 round-off),
  * "solve_threads" (dcx_solve's workgroup size: 256 or 512; rule = 256 up to 736 unknowns; same pivots, same arithmetic),
  * "qt" (small batches of a one-class D = 12 / 24 model as tiles of 16 configurations that sweep all the rows from an LDS copy
  * instead of the split launch: 0 = never, 1 = wherever it is compiled and fits with >= 4 waves; rule = at most 16

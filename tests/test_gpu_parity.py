@@ -7,8 +7,6 @@ output must be <= 1e-5 plus the reference's own distance from the referee (its t
 form is up to ~1e-4 off for large coordinates); HIP vs the fp32 oracle <= 1e-5.
 """
 
-import os
-
 import numpy as np
 import pytest
 import torch
@@ -16,17 +14,6 @@ import torch
 from helpers import CASE_ROBOT, FK_NAMES, KIND, case_kernel, desc_for, load, make_robot, relerr
 
 pytestmark = pytest.mark.gpu
-
-# The matrix-core forms of the sweep (measured slower, profiles/r03_mfma_ab.txt) are not in the shipped library; they live in
-# diffco_amd/libdcx_matrix.so, which build() makes for the widths that have them (12 and 16).  A process loads ONE libdcx, so the
-# third leg of this file ("mfma") and the tests that need `xm` / `mfma` exist only in a process started with DCX_LIB pointing at that
-# library - tests/test_gpu_matrix_forms.py starts it (round 6: the leg used to skip under the driver).
-MATRIX_LIB = "matrix" in os.path.basename(os.environ.get("DCX_LIB", ""))
-
-
-def matrix_only(fn):
-    """collected only in the process that runs against the matrix-forms library"""
-    return fn if MATRIX_LIB else None
 
 TOL = 1e-5
 TOL_ORACLE = 1e-5  # the fp32 oracle sums S terms sequentially; it is itself ~5e-6 from the referee at S=10k
@@ -40,29 +27,13 @@ def _n(t):
     return t.detach().cpu().numpy()
 
 
-@pytest.fixture(autouse=True, params=["expanded", "direct"] + (["mfma"] if MATRIX_LIB else []))
+@pytest.fixture(autouse=True, params=["expanded", "direct"])
 def fold_pipe(request, knob):
-    """every test of this file runs three times: the sweep in its expanded form (score_kernel.h XF, the default; shapes
-    without one — every kernel but Polyharmonic(1), rows wider than 37 floats — take the direct form), in its direct form
-    (differences), and with the
-    gradient fold on the matrix cores (v_mfma_f32_16x16x4_f32, knob mfma = 1; shapes without an MFMA instantiation
-    take the default form)"""
+    """every test of this file runs twice: the sweep in its expanded form (score_kernel.h XF, the default; shapes
+    without one — every kernel but Polyharmonic(1), rows wider than 37 floats — take the direct form) and in its direct form
+    (differences)"""
     knob("xf", 0 if request.param == "direct" else 1)
-    if request.param == "mfma":
-        knob("mfma", 1)   # (only in the process that loaded libdcx_matrix.so: see MATRIX_LIB)
-    else:
-        knob("mfma", 0)
     yield request.param
-
-
-def _need_mfma(knob):
-    """knob mfma = 1 (tests under @matrix_only)"""
-    knob("mfma", 1)
-
-
-def _need_xm(knob):
-    """knob xm = 1 (tests under @matrix_only)"""
-    knob("xm", 1)
 
 
 @pytest.fixture(scope="module")
@@ -167,7 +138,7 @@ def test_score_grad_vs_oracle_and_reference(ops, name):
 
 
 @pytest.mark.parametrize("name", ["cfg2_baxter_poly1", "cfg3_baxter_rq_c5", "misc_dualpanda_rq"])
-def test_support_slicing_is_invariant(ops, name, knob, fold_pipe):
+def test_support_slicing_is_invariant(ops, name, knob):
     """every launch geometry — waves per block (support slices meeting in LDS) x support super-chunks across
     blocks (split launch + finish kernel) — gives the same answer"""
     d = load(name)
@@ -185,12 +156,9 @@ def test_support_slicing_is_invariant(ops, name, knob, fold_pipe):
             outs.append((_n(s), _n(g), _n(s0), _n(jac)))
     knob("nw", -1)
     knob("ys", -1)
-    # (under the "mfma" parametrisation one wave per block has no matrix-core form and takes the default one: for an RQ model
-    # that is the expanded sweep since round 4, 2e-6 from the direct arithmetic of the matrix-core form - two forms are compared)
-    tol = 8e-6 if (fold_pipe == "mfma" and "rq" in name) else 3e-6
     for o in outs[1:]:
         for a, b in zip(o, outs[0]):
-            assert relerr(a, b) < tol
+            assert relerr(a, b) < 3e-6
 
 
 @pytest.mark.parametrize("name", ["cfg2_baxter_poly1", "cfg3_baxter_rq_c5", "cfg2_panda_poly1"])
@@ -288,8 +256,7 @@ def test_expanded_form_around_the_near_threshold(ops, knob, D, C):
     """the expanded sweep's near-pair machinery under load: every query sits at a chosen relative distance
     r / |x| in [1e-7, 1] from one support (the threshold is r / |x| = 0.1), many per wave, on both sides of it, plus exact
     coincidences — score and gradient against the float64 oracle at the 1e-5 bar, in the expanded AND the direct form, and
-    a configuration's result must not depend on its wave-mates (shuffled batch, bit for bit).  The matrix-core fold
-    runs the same gauntlet through the file's third parametrisation."""
+    a configuration's result must not depend on its wave-mates (shuffled batch, bit for bit)."""
     from diffco_amd import _fkdesc
     from oracle import oracle
     g = torch.Generator().manual_seed(100 * D + C)
@@ -310,7 +277,7 @@ def test_expanded_form_around_the_near_threshold(ops, knob, D, C):
                                   q.numpy().astype(np.float64), upstream=None if up is None else _n(up).astype(np.float64),
                                   dtype=np.float64)
     res = {}
-    for form in (1, 0):   # under the "mfma" parametrisation form 0 is the matrix-core fold where it is compiled
+    for form in (1, 0):
         knob("xf", form)
         s, gr = m.score_grad_raw(q.cuda(), up)
         assert torch.isfinite(s).all() and torch.isfinite(gr).all()
@@ -320,110 +287,6 @@ def test_expanded_form_around_the_near_threshold(ops, knob, D, C):
         assert torch.equal(sp, s[perm]) and torch.equal(gp, gr[perm]), form
         res[form] = (s, gr)
     assert relerr(_n(res[1][0]), _n(res[0][0])) < 6e-6 and relerr(_n(res[1][1]), _n(res[0][1])) < 6e-6
-
-
-@matrix_only
-@pytest.mark.parametrize("D", [4, 6, 8, 12, 16])
-def test_distance_gemm_on_the_matrix_cores_around_the_near_threshold(ops, knob, D):
-    """XM (knob xm = 1): the expanded form's x . s^T as a bf16x3 split-operand GEMM on v_mfma_f32_16x16x32_bf16 - the
-    near-threshold gauntlet of the expanded form (queries at 1e-7 .. 1 relative distance from a support, exact
-    coincidences, many per wave) against the float64 oracle, every compiled width, and bit-exact batch-order invariance"""
-    from diffco_amd import _fkdesc
-    from oracle import oracle
-    g = torch.Generator().manual_seed(7 * D)
-    S, B = 333, 4096          # 333: head / tail rows outside the 16-row blocks in every slice
-    sup = (torch.rand((S, D), generator=g) * 2 - 1) * 1.5
-    W = torch.randn((S, 1), generator=g)
-    j = torch.randint(0, S, (B,), generator=g)
-    u = torch.randn((B, D), generator=g)
-    u = u / u.norm(dim=1, keepdim=True)
-    rel = 10.0 ** (torch.rand((B, 1), generator=g) * 7 - 7)
-    rel[::97] = 0.0
-    q = sup[j] + rel * sup[j].norm(dim=1, keepdim=True) * u
-    desc = _fkdesc.none_desc(D)
-    m = ops.ScoreModel(desc, 1, 1.0, 1.0, sup.cuda(), W.cuda())
-    so, go, _ = oracle.score_grad(desc, 1, 1.0, 1.0, sup.numpy().astype(np.float64), W.numpy().astype(np.float64),
-                                  q.numpy().astype(np.float64), dtype=np.float64)
-    knob("xf", 1)
-    knob("mfma", 0)
-    _need_xm(knob)
-    s, gr = m.score_grad_raw(q.cuda())
-    assert torch.isfinite(s).all() and torch.isfinite(gr).all()
-    assert relerr(_n(s), so) < TOL and relerr(_n(gr), go) < TOL, (relerr(_n(s), so), relerr(_n(gr), go))
-    perm = torch.randperm(B, generator=g).cuda()
-    sp, gp = m.score_grad_raw(q.cuda()[perm].contiguous())
-    assert torch.equal(sp, s[perm]) and torch.equal(gp, gr[perm])
-    knob("xm", 0)
-    s0, g0 = m.score_grad_raw(q.cuda())
-    assert relerr(_n(s), _n(s0)) < 6e-6 and relerr(_n(gr), _n(g0)) < 6e-6
-
-
-@matrix_only
-@pytest.mark.parametrize("name", ["baxter_left", "panda", "baxter_dual"])
-@pytest.mark.parametrize("B", [1, 200, 4096, 30000])
-def test_distance_gemm_on_the_matrix_cores_with_fk(ops, knob, name, B):
-    """XM on FK-produced (centred) features: the Baxter arm (12 features; Panda's 21 and the dual arm's 24 are outside the
-    XM widths and must silently take the VALU expanded form), split and unsplit launches, against the VALU expanded form and
-    the float64 oracle"""
-    from oracle import oracle
-    rob = make_robot(name)
-    g = torch.Generator().manual_seed(len(name) + B)
-    lim = rob.limits.float()
-    S = 700
-    rnd = lambda n: torch.rand((n, rob.dof), generator=g) * (lim[:, 1] - lim[:, 0]) + lim[:, 0]  # noqa: E731
-    sq, q = rnd(S), rnd(B).cuda()
-    desc = rob.fk_desc()
-    sup = rob.fkine(sq.cuda()).reshape(S, -1)
-    W = torch.randn((S, 1), generator=g)
-    m = ops.ScoreModel(desc, 1, 1.0, 1.0, sup, W.cuda())
-    knob("xf", 1)
-    knob("mfma", 0)
-    knob("xm", 0)
-    s0, g0 = m.score_grad_raw(q)
-    _need_xm(knob)
-    s1, g1 = m.score_grad_raw(q)
-    s1b, g1b = m.score_grad_raw(q)
-    assert torch.equal(s1, s1b) and torch.equal(g1, g1b)
-    assert relerr(_n(s1), _n(s0)) < 4e-6 and relerr(_n(g1), _n(g0)) < 4e-6
-    n64 = min(B, 512)
-    so, go, _ = oracle.score_grad(desc, 1, 1.0, 1.0, _n(sup).astype(np.float64), W.numpy().astype(np.float64),
-                                  _n(q[:n64]).astype(np.float64), dtype=np.float64)
-    assert relerr(_n(s1[:n64]), so) < TOL and relerr(_n(g1[:n64]), go) < TOL
-
-
-@matrix_only
-@pytest.mark.parametrize("C,kspec", [(5, (0, 10.0, 2.0)), (8, (0, 10.0, 2.0)), (8, (1, 1.0, 1.0)), (1, (1, 1.0, 1.0))])
-@pytest.mark.parametrize("B", [200, 4096, 20000])
-def test_matrix_core_form_of_the_weight_contraction(ops, knob, C, kspec, B):
-    """K[B,S] . W[S,C] and the gradient fold on v_mfma_f32_16x16x4_f32 (knob mfma = 1; C = 1, 5 and 8 are instantiated)
-    against the VALU form of the same launch and against the float64 oracle, Baxter features, an explicit upstream and
-    the all-ones one, ragged batches, split and unsplit launches"""
-    from diffco_amd import model
-    from oracle import oracle
-    rob = model.BaxterLeftArmFK()
-    desc = rob.fk_desc()
-    g = torch.Generator().manual_seed(17 * C + B)
-    lo, hi = rob.limits[:, 0], rob.limits[:, 1]
-    S = 700
-    sq = torch.rand((S, 7), generator=g) * (hi - lo) + lo
-    q = (torch.rand((B, 7), generator=g) * (hi - lo) + lo).cuda()
-    W = torch.randn((S, C), generator=g)
-    sup = ops.fkine(desc, sq.cuda()).reshape(S, -1)
-    m = ops.ScoreModel(desc, *kspec, sup, W.cuda())
-    ups = [None] + ([torch.randn((B, C), generator=g).cuda()] if C > 1 else [])
-    n64 = min(B, 1024)
-    for up in ups:
-        so, go, _ = oracle.score_grad(desc, *kspec, _n(sup).astype(np.float64), W.numpy().astype(np.float64),
-                                      _n(q[:n64]).astype(np.float64), upstream=None if up is None else _n(up[:n64]).astype(np.float64),
-                                      dtype=np.float64)
-        knob("mfma", 0)
-        s0, g0 = m.score_grad_raw(q, up)
-        _need_mfma(knob)
-        s1, g1 = m.score_grad_raw(q, up)
-        assert relerr(_n(s1[:n64]), so) < TOL and relerr(_n(g1[:n64]), go) < TOL, (relerr(_n(s1[:n64]), so), relerr(_n(g1[:n64]), go))
-        assert relerr(_n(s1), _n(s0)) < 4e-6 and relerr(_n(g1), _n(g0)) < 4e-6
-        s1b, g1b = m.score_grad_raw(q, up)
-        assert torch.equal(s1, s1b) and torch.equal(g1, g1b)
 
 
 @pytest.mark.parametrize("name", ["cfg3_baxter_rq_c5", "cfg3_baxter_poly1_c5", "misc_baxterR_mq_c2"])
@@ -441,7 +304,6 @@ def test_one_sweep_jacobian_equals_one_sweep_per_class(ops, name, nw, knob):
     knob("ys", 1)
     knob("min_rows", 1)
     knob("xf", 0)
-    knob("mfma", 0)
     for B in (700, 64, 5):
         knob("jac_one_sweep", 0)
         knob("jac_per_class", 1)

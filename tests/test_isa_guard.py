@@ -17,10 +17,10 @@ CSRC = os.path.join(ROOT, "diffco_amd", "csrc")
 
 SRC = """#include "dcx_internal.h"
 namespace dcx {
-template __global__ void score_kernel<12, KF_POLY1, 1, MODE_GRAD_ROW, 1024, false, true>(const ScoreArgs);
-template __global__ void score_kernel<12, KF_POLY1, 1, MODE_GRAD_ROW, 1024, false, false>(const ScoreArgs);
-template __global__ void score_kernel<12, KF_RQ2, 5, MODE_GRAD_UP, 1024, false, false>(const ScoreArgs);
-template __global__ void score_kernel<6, KF_RQ2, 1, MODE_GRAD_ROW, 1024, false, false>(const ScoreArgs);
+template __global__ void score_kernel<12, KF_POLY1, 1, MODE_GRAD_ROW, 1024, true>(const ScoreArgs);
+template __global__ void score_kernel<12, KF_POLY1, 1, MODE_GRAD_ROW, 1024, false>(const ScoreArgs);
+template __global__ void score_kernel<12, KF_RQ2, 5, MODE_GRAD_UP, 1024, false>(const ScoreArgs);
+template __global__ void score_kernel<6, KF_RQ2, 1, MODE_GRAD_ROW, 1024, false>(const ScoreArgs);
 }
 """
 
@@ -38,7 +38,7 @@ def isa(tmp_path_factory):
 
 
 def _kernels(txt):
-    for m in re.finditer(r"^(_ZN3dcx12score_kernelILi(\d+)ELi(\d+)ELi(\d+)ELi(\d+)ELi1024ELb0ELb(\d)ELb0ELb0EEEvNS_9ScoreArgsE):", txt, re.M):
+    for m in re.finditer(r"^(_ZN3dcx12score_kernelILi(\d+)ELi(\d+)ELi(\d+)ELi(\d+)ELi1024ELb(\d)ELb0EEEvNS_9ScoreArgsE):", txt, re.M):
         body = txt[m.end():txt.index(".Lfunc_end", m.end())].split("\n")
         meta = txt[txt.index(".name:           " + m.group(1)):]
         yield dict(D=int(m.group(2)), KF=int(m.group(3)), C=int(m.group(4)), MODE=int(m.group(5)), XF=int(m.group(6)), body=body,
@@ -62,7 +62,7 @@ def _sweep_loop(body):
     return Counter(x.split()[0] for x in (y.strip() for y in best) if x and not x.startswith((".", ";")))
 
 
-def test_sweep_loops_have_no_lane_parking_and_no_scratch(isa):
+def test_score_kernel_sweep_loops_have_no_lane_parking_and_no_scratch(isa):
     seen = 0
     for k in _kernels(isa):
         c = _sweep_loop(k["body"])
@@ -75,7 +75,7 @@ def test_sweep_loops_have_no_lane_parking_and_no_scratch(isa):
     assert seen == 4
 
 
-def test_expanded_form_instruction_count(isa):
+def test_expanded_form_instruction_count_per_pair(isa):
     """four rows per loop iteration: 12 v_pk_fma per row in the expanded form and no packed add on the hot path; the
     direct form carries 6 v_pk_add + 12 v_pk_fma per row"""
     ks = {k["XF"]: _sweep_loop(k["body"]) for k in _kernels(isa) if k["D"] == 12 and k["C"] == 1}
@@ -87,15 +87,15 @@ def test_expanded_form_instruction_count(isa):
 
 SRC_R4 = """#include "dcx_internal.h"
 namespace dcx {
-template __global__ void score_kernel<12, KF_RQ2, 5, MODE_GRAD_ROW, 1024, false, true>(const ScoreArgs);
-template __global__ void score_kernel<12, KF_RQ2, 5, MODE_GRAD_ROW, 1024, false, false>(const ScoreArgs);
-template __global__ void score_kernel<12, KF_RQ2, 1, MODE_GRAD_ROW, 1024, false, true>(const ScoreArgs);
-template __global__ void score_kernel<6, KF_RQ2, 1, MODE_GRAD_ROW, 1024, false, false>(const ScoreArgs);
+template __global__ void score_kernel<12, KF_RQ2, 5, MODE_GRAD_ROW, 1024, true>(const ScoreArgs);
+template __global__ void score_kernel<12, KF_RQ2, 5, MODE_GRAD_ROW, 1024, false>(const ScoreArgs);
+template __global__ void score_kernel<12, KF_RQ2, 1, MODE_GRAD_ROW, 1024, true>(const ScoreArgs);
+template __global__ void score_kernel<6, KF_RQ2, 1, MODE_GRAD_ROW, 1024, false>(const ScoreArgs);
 }
 """
 
 
-def test_round4_sweeps_rq_folded_expanded_and_the_two_buffer_pipeline(tmp_path):
+def test_rq_folded_expanded_sweep_and_the_two_buffer_pipeline(tmp_path):
     """Round 4 (score_kernel.h, "the two-buffer pipeline", sweep_eval): what the counter passes of config #3 / #4 led to,
     held in the generated code.  (a) RQKernel(p = 2) with its constants folded: 15 VALU instructions per pair at D = 6
     (config #4; 17 before; 12 since round 5's pair2), no multiply by gamma left in the loop; (b) config #3's loop (D = 12, C = 5) in the expanded
@@ -153,7 +153,7 @@ def test_round4_sweeps_rq_folded_expanded_and_the_two_buffer_pipeline(tmp_path):
         assert ks[key]["vgpr"] <= 64 and ks[key]["scratch_bytes"] <= 44
 
 
-def test_handover_publishes_write_through_and_drains_before_the_counter(isa):
+def test_split_handover_publishes_write_through_and_drains_before_the_counter(isa):
     """The in-launch hand-over of a split launch (score_kernel.h) orders the partial-row stores before the arrival
     counter WITHOUT a release fence: it relies on gfx942 / gfx950 lowering agent-scope atomic stores to `global_store sc1`
     (write-through) and on those stores being counted by vmcnt.  Hold the generated code to exactly that: every store of
@@ -260,19 +260,19 @@ def test_dense_solve_keeps_its_panel_in_registers(tmp_path):
         assert ops["v_fma_f64"] + ops["v_fmac_f64_e32"] > 2500                    # the unrolled panel columns and updates
 
 
-def test_tile_of_16_configurations_sweeps_from_lds_without_scratch(tmp_path):
+def test_quarter_tile_sweeps_from_lds_without_scratch(tmp_path):
     """score_kernel<..., QT> (round 4): the rows come from LDS as whole float4s (three ds_read_b128 + the weight per pair at
     D = 12), two row buffers in registers, no scratch and no lane parking inside the sweep loop."""
     if shutil.which("hipcc") is None:
         pytest.skip("hipcc not available")
     src, out = tmp_path / "q.hip", tmp_path / "q.s"
     src.write_text('#include "dcx_internal.h"\nnamespace dcx {\n'
-                   "template __global__ void score_kernel<12, KF_POLY1, 1, MODE_GRAD_ROW, 1024, false, false, false, true>(const ScoreArgs);\n"
-                   "template __global__ void score_kernel<12, KF_RQ2, 1, MODE_GRAD_ROW, 1024, false, false, false, true>(const ScoreArgs);\n}\n")
+                   "template __global__ void score_kernel<12, KF_POLY1, 1, MODE_GRAD_ROW, 1024, false, true>(const ScoreArgs);\n"
+                   "template __global__ void score_kernel<12, KF_RQ2, 1, MODE_GRAD_ROW, 1024, false, true>(const ScoreArgs);\n}\n")
     subprocess.run(["hipcc", "-O3", "-std=c++17", "-fPIC", "--offload-arch=gfx950", "-I", CSRC, "-S", "--cuda-device-only",
                     str(src), "-o", str(out)], check=True, stderr=subprocess.DEVNULL)
     txt = out.read_text()
-    names = re.findall(r"^(_ZN3dcx12score_kernelILi12ELi\dELi1ELi1ELi1024ELb0ELb0ELb0ELb1EEEvNS_9ScoreArgsE):", txt, re.M)
+    names = re.findall(r"^(_ZN3dcx12score_kernelILi12ELi\dELi1ELi1ELi1024ELb0ELb1EEEvNS_9ScoreArgsE):", txt, re.M)
     assert len(names) == 2
     for name in names:
         start = txt.index(name + ":")

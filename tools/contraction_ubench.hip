@@ -5,7 +5,7 @@
 //
 //   fold   gx[b][k]  = sum_j coef[b][j] * s[j][k]            D = 12, C = 1 (the headline's gradient fold)
 //            valu    : 6 v_pk_fma_f32 per row                                       (what ships)
-//            mfma32  : v_mfma_f32_16x16x4_f32, 4 per 4 rows + the 4x4 lane transpose (DCX_MFMA=1, bitwise equal)
+//            mfma32  : v_mfma_f32_16x16x4_f32, 4 per 4 rows + the 4x4 lane transpose (bitwise equal)
 //            bf16x3  : coef and s split into three bf16 planes, six plane products on v_mfma_f32_16x16x32_bf16
 //                      (24 per 32 rows), coefficient split + pack + transposes on the VALU  (relative error ~1e-6)
 //   kw     sc[b][c]  = sum_j K[b][j] * W[j][c]               C = 5, 8 (MultiDiffCo score)

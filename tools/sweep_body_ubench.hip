@@ -166,12 +166,6 @@ void run(const char* name, int cus) {
         if (CC > 1) rows[(size_t)j * L::RS + L::WSUM_OFF] = 0.01f;
         rows[(size_t)j * L::RS + L::SS_OFF] = ss + (KF == KF_RQ2 ? 0.2f : 0.f);
     }
-    if (x2_applies(D, CC, KF)) {   // (a -DDCX_XF2=1 build: the product's expanded sweep of this shape reads pair-interleaved rows)
-        std::vector<float> il(rows.size(), 0.f);
-        for (int j = 0; j < rows_n + 16; ++j)
-            for (int e = 0; e < L::RS; ++e) il[(size_t)(j >> 1) * 2 * L::RS + 2 * e + (j & 1)] = rows[(size_t)j * L::RS + e];
-        rows.swap(il);
-    }
     float *d_rows, *d_out;
     unsigned long long* d_ts;
     const int blocks = cus * WPS;   // 256 threads = one wave per SIMD per block
