@@ -58,6 +58,9 @@ SYMBOLS = {
     "dcx_euler_frames_vjp": (C.c_int, [C.c_int, _c_fp, _c_fp, C.c_int64, _c_fp, C.c_void_p]),
     "dcx_kernel_matrix": (C.c_int, [C.c_int, C.c_int, C.POINTER(C.c_float), _c_fp, C.c_int64, _c_fp, C.c_int64,
                                     C.c_int32, _c_fp, C.c_void_p]),
+    "dcx_motion_work_bytes": (C.c_size_t, [C.c_void_p, C.c_int64]),
+    "dcx_check_motions": (C.c_int, [C.c_void_p, _c_fp, _c_fp, C.c_int64, C.c_void_p, _c_fp, _c_fp, _c_fp, C.c_void_p, C.c_size_t,
+                                    C.c_void_p]),
     "dcx_solve_work_bytes": (C.c_size_t, [C.c_int64, C.c_int64]),
     "dcx_solve": (C.c_int, [C.c_int, _c_fp, _c_fp, C.c_int64, C.c_int64, _c_fp, C.c_void_p, C.c_size_t, C.c_void_p, C.c_int32,
                             C.c_void_p]),
@@ -82,6 +85,11 @@ class EscapeOpts(C.Structure):
     """ctypes mirror of dcx_escape_opts (include/dcx.h)"""
     _fields_ = [(n, C.c_float) for n in ("lr", "beta1", "beta2", "eps")] + [
         (n, C.c_int32) for n in ("n_steps", "record_freq", "joint", "compact_every")] + [("wrap_mask", C.c_uint64)]
+
+
+class MotionOpts(C.Structure):
+    """ctypes mirror of dcx_motion_opts (include/dcx.h)"""
+    _fields_ = [("res", C.c_int32), ("max_step", C.c_float), ("max_samples", C.c_int32), ("reserved", C.c_int32)]
 
 
 _lib = None

@@ -6,6 +6,7 @@ moved back to the caller's device and dtype, so reference scripts written for CP
 unchanged on a GPU box.  Without a GPU every function raises (no CPU fallback).
 """
 import ctypes as C
+import math
 
 import torch
 from torch.autograd.function import once_differentiable
@@ -224,6 +225,21 @@ def train_perceptron_device(kind, p0, p1, beta, feats, y, gains, hypo, K, max_it
 
 
 # ----------------------------------------------------------------------------- fused score model
+MOTION_MAX_SAMPLES = 10000   # the default limit on one edge's samples (max_step rule): longer edges answer -2
+
+
+def motion_bound(qa32, qb32, max_step, limit=MOTION_MAX_SAMPLES):
+    """max_samples for a max_step call: the longest edge's sample count (+ 1 against a rounding of its length that differs
+    from the kernel's), at most `limit`.  One small reduction read back: dcx_check_motions sizes its grid from E * max_samples,
+    and a loose bound launches a block per tile it could have had (measured: profiles/r07_motion_checks.txt)."""
+    if len(qa32) == 0:
+        return 1
+    L = float((qb32 - qa32).norm(dim=1).max())
+    if not L == L or L == float("inf"):
+        return limit
+    return int(min(limit, math.ceil(L * (1.0 / float(max_step))) + 2))
+
+
 class ScoreModel:
     """Owns one ``dcx_model`` (device copy of support rows + FK parameters).  `update()` refills it in place with new
     supports / weights (same transform, kernel and class count): no reallocation while they fit `capacity`."""
@@ -371,6 +387,40 @@ class ScoreModel:
             _lib.check(self._lib.dcx_score_hinge_grad_mc(self._h, _ptr(q32), B, self.margins(margin), float(weight), _ptr(out),
                                                          _ptr(grad), self._st()))
         return out, grad
+
+    def check_motions(self, qa, qb, res=None, max_step=None, margin=0., max_samples=None):
+        """batched motion checks (dcx_check_motions): for E straight joint-space motions qa[e] -> qb[e] ([E, dof] each),
+        (first_hit, n_samples), int32 device tensors [E]: the first sample index with score_c - margin_c > 0 for some class
+        (-1: free; -2: the edge needs more than `max_samples` samples and was not checked) and the edge's sample count.
+        Exactly one rule: `res` (the points of Perceptron.line_predict) or `max_step` (the points of utils.dense_path).
+        `margin`: a number or one per class (a device tensor stays on the device).  Three launches on torch's current
+        stream.  The launch grid is sized from E * max_samples, so the bound should be tight: max_samples=None under the
+        max_step rule derives it from the longest edge (one read-back of a reduction; edges beyond MOTION_MAX_SAMPLES
+        still answer -2).  A given max_samples reads nothing back (capturable)."""
+        if (res is None) == (max_step is None):
+            raise ValueError("check_motions takes exactly one of res and max_step")
+        qa32 = _f32(torch.as_tensor(qa).reshape(-1, self.dof), self.dev)
+        qb32 = _f32(torch.as_tensor(qb).reshape(-1, self.dof), self.dev)
+        if qa32.shape != qb32.shape:
+            raise ValueError(f"{len(qa32)} start and {len(qb32)} target configurations")
+        E = len(qa32)
+        if max_samples is None:
+            max_samples = int(res) if res is not None else motion_bound(qa32, qb32, max_step)
+        opt = _lib.MotionOpts(int(res) if res is not None else 0, float(max_step) if max_step is not None else 0.0, int(max_samples), 0)
+        mg = None
+        if torch.is_tensor(margin) and margin.device == self.dev:
+            # a device tensor stays on the device (no copy through the host: the call can be captured in a graph)
+            mg = margin.detach().to(torch.float32).reshape(-1).expand(self.C).contiguous()
+        elif torch.is_tensor(margin) or not (isinstance(margin, (int, float)) and float(margin) == 0.0):
+            mg = torch.tensor(list(self.margins(margin)), dtype=torch.float32).to(self.dev)
+        first = torch.empty(E, device=self.dev, dtype=torch.int32)
+        n = torch.empty(E, device=self.dev, dtype=torch.int32)
+        nbytes = self._lib.dcx_motion_work_bytes(self._h, E)
+        work = torch.empty(max(int(nbytes), 1), device=self.dev, dtype=torch.uint8)
+        with _on_device(self.dev):
+            _lib.check(self._lib.dcx_check_motions(self._h, _ptr(qa32), _ptr(qb32), E, C.byref(opt), _ptr(mg), _ptr(first),
+                                                   _ptr(n), _ptr(work), int(nbytes), self._st()))
+        return first, n
 
     # autograd-aware ------------------------------------------------------------------------
     def score(self, q: torch.Tensor) -> torch.Tensor:

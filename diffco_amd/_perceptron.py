@@ -247,3 +247,74 @@ class FusedScorer:
         if self._model is not None:
             self._retired = self._model
         self._key, self._model, self._sup, self._w, self._fast = None, None, None, None, None
+
+
+# ---- batched motion checks ---------------------------------------------------------------------------------------------------
+def host_motions(score_fn, qa, qb, res=None, max_step=None, margin=0., max_samples=None):
+    """the composition a caller would write without dcx_check_motions: every edge's points (line_predict's / dense_path's
+    arithmetic) materialised, ONE score launch over all of them, the first hit per edge.  Same answers, (first_hit, n_samples)."""
+    import torch
+    qa, qb = qa.reshape(len(qa), -1), qb.reshape(len(qb), -1)
+    E, dev = len(qa), qa.device
+    d = qb - qa
+    if res is not None:
+        n = torch.full((E,), int(res), dtype=torch.int64, device=dev)
+        frac = None
+    else:
+        L = d.norm(dim=-1)
+        n = torch.ceil(L / max_step).to(torch.int64) + 1
+        frac = max_step / L
+    limit = int(res) if (max_samples is None and res is not None) else (
+        _ops.MOTION_MAX_SAMPLES if max_samples is None else int(max_samples))
+    ok = n <= limit
+    n_ok = torch.where(ok, n, torch.zeros_like(n))
+    edge = torch.repeat_interleave(torch.arange(E, device=dev), n_ok)
+    offs = torch.cumsum(n_ok, 0) - n_ok
+    k = torch.arange(len(edge), device=dev) - offs[edge]
+    if res is not None:
+        pts = qa[edge] + d[edge] * (k.to(qa.dtype) / int(res))[:, None]
+    else:
+        pts = qa[edge] + k.to(qa.dtype)[:, None] * (d[edge] * frac[edge][:, None])
+        last = k == n[edge] - 1
+        pts = torch.where(last[:, None], qb[edge], pts)
+    first = torch.full((E,), -1, dtype=torch.int64, device=dev)
+    if len(pts):
+        s = score_fn(pts).reshape(len(pts), -1)
+        mg = torch.as_tensor(margin, dtype=s.dtype, device=s.device).reshape(-1)
+        hit = (s - mg > 0).any(dim=-1)
+        big = torch.iinfo(torch.int64).max
+        cand = torch.where(hit, k, torch.full_like(k, big))
+        first = torch.full((E,), big, dtype=torch.int64, device=dev).scatter_reduce(0, edge, cand, reduce="amin")
+        first = torch.where(first == big, torch.full_like(first, -1), first)
+    first = torch.where(ok, first, torch.full_like(first, -2))
+    return first.to(torch.int32), n.clamp(max=2 ** 31 - 1).to(torch.int32)
+
+
+def check_motions(owner, fused, transform, kernel_func, support_feat, weights, qa, qb, res=None, max_step=None, margin=0.,
+                  max_samples=None, score_fn=None):
+    """(first_hit, n_samples) of the motions qa[e] -> qb[e] on the model `fused` holds: one dcx_check_motions call where the
+    transform fuses (none, or a diffco_amd robot's fkine), else the host composition (a foreign callable: its points through
+    `score_fn` in one launch).  owner.last_route says which ran: "fused" or "host"."""
+    import torch
+    if (res is None) == (max_step is None):
+        raise ValueError("check_motions takes exactly one of res and max_step")
+    qa, qb = torch.as_tensor(qa), torch.as_tensor(qb)
+    dev = qa.device if qa.device.type == "cuda" else (support_feat.device if support_feat.device.type == "cuda" else None)
+    m = fused.model(transform, kernel_func, support_feat, weights, dev)
+    if m.desc.kind == 0 and transform is not None:
+        owner.last_route = "host"
+        qa32 = qa.to(device=m.dev, dtype=torch.float32)
+        qb32 = qb.to(device=m.dev, dtype=torch.float32)
+        fn = score_fn or (lambda p: fused.score(transform, kernel_func, support_feat, weights, p))
+        return host_motions(lambda p: fn(p).detach(), qa32, qb32, res, max_step, margin, max_samples)
+    owner.last_route = "fused"
+    return m.check_motions(qa, qb, res=res, max_step=max_step, margin=margin, max_samples=max_samples)
+
+
+def motion_answer(first, return_first):
+    """the facades' answer: collides [E] bool (+ first_hit); raises for edges over max_samples (a read-back)"""
+    if bool((first == -2).any()):
+        bad = (first == -2).nonzero().reshape(-1)[:8].tolist()
+        raise ValueError(f"check_motions: edges {bad} need more than max_samples samples (pass a larger max_samples or max_step)")
+    hit = first >= 0
+    return (hit, first) if return_first else hit

@@ -203,6 +203,18 @@ class RBFDiffCo(CollisionChecker):
         raw = self.perceptron.poly_score(q.reshape(-1, shape_q[-1]))
         return raw.reshape(shape_q[:-1] + raw.shape[1:]) + bias
 
+    def check_motions(self, q_start, q_end, max_step=None, res=None, bias=None, return_first=False, max_samples=None):
+        """is the straight motion q_start[e] -> q_end[e] in collision, by `collision_score` (poly score + bias > 0; bias
+        defaults to safety_bias) at its samples?  Exactly one rule: `max_step` (utils.dense_path's points) or `res`
+        (line_predict's).  bool [E]; with return_first also the first colliding sample index (-1 = free)."""
+        from ._perceptron import check_motions, motion_answer
+        bias = self.safety_bias if bias is None else bias
+        margin = -bias if not torch.is_tensor(bias) else -bias.detach().reshape(-1)
+        p = self.perceptron
+        first, _ = check_motions(self, p._poly_fused, p.transform, p.rbf_kernel, p.support_transformed, p.rbf_nodes,
+                                 q_start, q_end, res=res, max_step=max_step, margin=margin, max_samples=max_samples)
+        return motion_answer(first, return_first)
+
     def _calculate_safety_bias(self, q_verify):
         """a third of the smaller of |min score| and |max score| over q_verify (collision_checkers.py:497-503; the
         reference defines it on the FK subclass only and its RBFDiffCo.fit calls it regardless)"""

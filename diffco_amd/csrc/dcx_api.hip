@@ -12,6 +12,7 @@
 #include <vector>
 
 #include "dcx_internal.h"
+#include "motion_kernel.h"
 #include "pack_kernels.h"
 #include "solve_kernels.h"
 
@@ -271,7 +272,8 @@ int fk_device_copy(int device, const dcx_fk_desc& fk, FkProg** out) {
 struct Knobs {
     std::atomic<int64_t> ys{-1}, nw{-1}, min_rows{-1}, split_finish_kernel{-1}, inlaunch_tiles{-1}, jac_per_class{-1},
         traj_fused{-1}, xf{-1}, jac_one_sweep{-1}, train_grid{-1}, fkk{-1}, jt_waves{-1}, hess_ys{-1}, hess_form{-1},
-        traj_ys{-1}, traj_across{-1}, owner_poll{-1}, solve_threads{-1}, qt{-1}, giveup_inject{-1}, skew{-1}, skew8{-1};
+        traj_ys{-1}, traj_across{-1}, owner_poll{-1}, solve_threads{-1}, qt{-1}, giveup_inject{-1}, skew{-1}, skew8{-1},
+        motion_early_exit{-1};
     Knobs() {
         auto rd = [](const char* name, std::atomic<int64_t>& dst, bool flag) {
             if (const char* e = std::getenv(name)) dst = flag ? 1 : std::atoll(e);
@@ -792,7 +794,7 @@ int dcx_debug_set(const char* name, int64_t value) {
                          : DCX_OK;
     std::atomic<int64_t>* dst = n == "ys" ? &k.ys : n == "nw" ? &k.nw : n == "min_rows" ? &k.min_rows
         : n == "split_finish_kernel" ? &k.split_finish_kernel : n == "inlaunch_tiles" ? &k.inlaunch_tiles
-        : n == "jac_per_class" ? &k.jac_per_class : n == "traj_fused" ? &k.traj_fused : n == "xf" ? &k.xf : n == "jac_one_sweep" ? &k.jac_one_sweep : n == "train_grid" ? &k.train_grid : n == "fkk" ? &k.fkk : n == "jt_waves" ? &k.jt_waves : n == "hess_ys" ? &k.hess_ys : n == "hess_form" ? &k.hess_form : n == "traj_ys" ? &k.traj_ys : n == "traj_across" ? &k.traj_across : n == "owner_poll" ? &k.owner_poll : n == "solve_threads" ? &k.solve_threads : n == "qt" ? &k.qt : n == "giveup_inject" ? &k.giveup_inject : n == "skew" ? &k.skew : n == "skew8" ? &k.skew8 : nullptr;
+        : n == "jac_per_class" ? &k.jac_per_class : n == "traj_fused" ? &k.traj_fused : n == "xf" ? &k.xf : n == "jac_one_sweep" ? &k.jac_one_sweep : n == "train_grid" ? &k.train_grid : n == "fkk" ? &k.fkk : n == "jt_waves" ? &k.jt_waves : n == "hess_ys" ? &k.hess_ys : n == "hess_form" ? &k.hess_form : n == "traj_ys" ? &k.traj_ys : n == "traj_across" ? &k.traj_across : n == "owner_poll" ? &k.owner_poll : n == "solve_threads" ? &k.solve_threads : n == "qt" ? &k.qt : n == "giveup_inject" ? &k.giveup_inject : n == "skew" ? &k.skew : n == "skew8" ? &k.skew8 : n == "motion_early_exit" ? &k.motion_early_exit : nullptr;
     if (!dst) return fail(DCX_ERR_INVALID, "unknown knob: " + n);
     *dst = value;
     return DCX_OK;
@@ -1599,6 +1601,147 @@ int dcx_escape_adam(const dcx_model* m, float* q, int64_t B, const float* margin
         }
     }
     return DCX_OK;   // (every loop wrote its final record where it stopped, or behind the last step)
+}
+
+// ---- batched motion checks (motion_kernel.h) ----------------------------------------------------------------------------------
+namespace {
+// A split launch (small batches: support super-chunks over gridDim.y, the tile finished by the last of its blocks to arrive) keeps
+// its arrival counters and partial rows in the caller's work buffer, so the buffer reserves room for the largest split the call
+// takes: at most kMotionSplitTiles tiles and kMotionSplitRows (tile, y) rows of DCX_MAX_C classes.  Bigger upper bounds run unsplit.
+constexpr int64_t kMotionSplitTiles = 256;
+constexpr int64_t kMotionSplitRows = 512;
+struct MotionWork {
+    size_t offs, frac, counters, partial, total;
+};
+MotionWork motion_work(int64_t E) {
+    auto up = [](size_t x) { return (x + 255) / 256 * 256; };
+    MotionWork w;
+    w.offs = 0;
+    w.frac = up((size_t)(E + 1) * sizeof(int64_t));
+    w.counters = w.frac + up((size_t)E * sizeof(float));
+    w.partial = w.counters + (size_t)kMotionSplitTiles * kCounterStride * sizeof(unsigned int);
+    w.total = w.partial + (size_t)kMotionSplitRows * DCX_MAX_C * 64 * sizeof(float);
+    return w;
+}
+motion_fn motion_for(int Dt) {
+    switch (Dt) {
+#define DCX_CASE(D) case D: return launch_motion_D##D;
+        DCX_CASE(2) DCX_CASE(4) DCX_CASE(6) DCX_CASE(8) DCX_CASE(12) DCX_CASE(16) DCX_CASE(18) DCX_CASE(21)
+        DCX_CASE(24) DCX_CASE(27) DCX_CASE(30) DCX_CASE(32) DCX_CASE(36) DCX_CASE(42) DCX_CASE(48) DCX_CASE(54)
+        DCX_CASE(60) DCX_CASE(64) DCX_CASE(72) DCX_CASE(84) DCX_CASE(96)
+#undef DCX_CASE
+    default: return nullptr;
+    }
+}
+}  // namespace
+
+size_t dcx_motion_work_bytes(const dcx_model* m, int64_t E) {
+    if (!m || E < 0) return 0;
+    return motion_work(E).total;
+}
+
+int dcx_check_motions(const dcx_model* m, const float* qa, const float* qb, int64_t E, const dcx_motion_opts* opt,
+                      const float* margin, int32_t* first_hit, int32_t* n_samples, void* work, size_t work_bytes, void* stream) {
+    // every argument is checked before anything touches the model or the device
+    if (!m) return fail(DCX_ERR_INVALID, "model is NULL");
+    if (!opt) return fail(DCX_ERR_INVALID, "motion options are NULL");
+    if (E < 0) return fail(DCX_ERR_INVALID, "E < 0");
+    if (E > 0 && (!qa || !qb || !first_hit || !work)) return fail(DCX_ERR_INVALID, "qa / qb / first_hit / work is NULL");
+    const bool by_res = opt->res > 0, by_step = opt->max_step > 0.f;
+    if (opt->res < 0 || !(opt->max_step >= 0.f) || by_res == by_step)
+        return fail(DCX_ERR_INVALID, "motion check needs exactly one sampling rule: res > 0 or max_step > 0 (the other 0)");
+    if (opt->max_samples < 1) return fail(DCX_ERR_INVALID, "motion check needs max_samples >= 1");
+    const MotionWork w = motion_work(E);
+    if (E > 0 && work_bytes < w.total) return fail(DCX_ERR_INVALID, "motion workspace is smaller than dcx_motion_work_bytes");
+    if (E > INT32_MAX) return fail(DCX_ERR_UNSUPPORTED, "motion check: more than 2^31 - 1 edges");
+    if (E == 0) return DCX_OK;
+    const int64_t tiles_max = (E * (int64_t)opt->max_samples + 63) / 64;
+    if (tiles_max > 0x7fffffffLL) return fail(DCX_ERR_UNSUPPORTED, "motion check: E * max_samples too large for one launch");
+    if (int rc = set_device(m->device)) return rc;
+    hipStream_t st = (hipStream_t)stream;
+    char* base = (char*)work;
+    const int d_fk = m->fk.n_points * m->fk.point_dim;
+    const int acc = m->Cc;
+    // grid: the sample count is on the device only; its upper bound E * max_samples sizes the grid and decides whether the
+    // launch splits the supports
+    Geometry g = pick_geometry(m, std::min<int64_t>(tiles_max, (int64_t)1 << 30) * 64, acc, true);
+    if (g.ys > 1 && (tiles_max > kMotionSplitTiles || tiles_max * g.ys > kMotionSplitRows))
+        g = pick_geometry(m, std::min<int64_t>(tiles_max, (int64_t)1 << 30) * 64, acc, false);
+    MotionPrepArgs p{};
+    p.qa = qa;
+    p.qb = qb;
+    p.E = E;
+    p.dof = m->fk.dof;
+    p.res = opt->res;
+    p.max_samples = opt->max_samples;
+    p.max_step = opt->max_step;
+    p.offs = (int64_t*)(base + w.offs);
+    p.frac = (float*)(base + w.frac);
+    p.first_hit = first_hit;
+    p.n_samples = n_samples;
+    p.counters = g.ys > 1 ? (unsigned int*)(base + w.counters) : nullptr;
+    p.n_counters = g.ys > 1 ? (int32_t)tiles_max : 0;
+    hipError_t e = launch_motion_prep(p, st);
+    if (e != hipSuccess) return fail_hip(e, "motion prep launch");
+
+    MotionArgs a{};
+    ScoreArgs& sa = a.sc;
+    sa.rows = m->rows_dev;
+    set_fk_walk(m, sa);
+    sa.B = 0;
+    sa.S = m->S_active;
+    sa.ys = g.ys;
+    sa.s_super = (m->S_active + g.ys - 1) / g.ys;
+    sa.s_chunk = (sa.s_super + g.nw - 1) / g.nw;
+    // the rows and slices exactly as run_score picks them for a score-only launch
+    const bool xf_able = knobs().xf != 0 && xf_applies(m->Dt, m->Cc, m->kf) && m->rows_xf_dev != nullptr &&
+                         (m->kf != KF_RQ2 || m->xf_rq_ok || knobs().xf >= 2);
+    if (!xf_able && m->rows_p2_dev != nullptr && p2_applies(m->Dt, m->Cc, m->kf)) {
+        sa.rows = m->rows_p2_dev;
+        sa.s_super = (sa.s_super + 1) & ~1;
+        sa.s_chunk = ((sa.s_super + g.nw - 1) / g.nw + 1) & ~1;
+    }
+    sa.s_skew = (g.nw == 16 && (sa.s_chunk >= 24 || knobs().skew > 0)) ? skew_rule(m->Cc, true)
+              : (g.nw == 8 && (sa.s_chunk >= 24 || knobs().skew8 > 0)) ? skew8_rule(true) : 0;
+    sa.red_slots = g.red_slots;
+    sa.dof = m->fk.dof;
+    sa.d_fk = d_fk;
+    sa.frame_floats = m->frame_floats;
+    sa.kind = m->kind;
+    sa.c_out = m->C;
+    sa.one_hot = -1;
+    sa.nz = 1;
+    sa.kp0 = m->kp0_sweep;
+    sa.kp1 = m->kp1;
+    sa.xf = xf_able ? 1 : 0;
+    if (sa.xf) {
+        sa.rows = m->rows_xf_dev;
+        sa.centre = m->centre_dev;
+    }
+    // a DH arm's chain split by rows over two waves, where run_score splits it
+    sa.jt_rows = (sa.fkk == 2 && g.nw >= 2 * m->dh.n_chains && m->dh.n_chains <= 2 && m->dh.end0 <= kDhUnroll &&
+                  m->dh.n_steps - m->dh.end0 <= kDhUnroll && knobs().jt_waves != 0) ? 1 : 0;
+    if (g.ys > 1) {
+        sa.partial = (float*)(base + w.partial);
+        sa.tile_done = (unsigned int*)(base + w.counters);
+    }
+    a.qa = qa;
+    a.qb = qb;
+    a.offs = p.offs;
+    a.frac = p.frac;
+    a.first_hit = reinterpret_cast<unsigned int*>(first_hit);
+    a.margin = margin;
+    a.E = E;
+    a.res = opt->res;
+    a.early_exit = knobs().motion_early_exit != 0 ? 1 : 0;
+    const int64_t nblk = tiles_max;   // one tile per block; blocks past the work list's end leave (motion_kernel.h)
+    const size_t lds = sizeof(float) * (((size_t)lds_plan(sa.dof, d_fk, m->frame_floats, g.nw > 1 ? g.red_slots : 0, acc, true).total +
+                                         m->prog_floats + 3) & ~(size_t)3) + sizeof(float) * kMotionLdsFloats;
+    motion_fn launch = motion_for(m->Dt);
+    if (!launch) return fail(DCX_ERR_UNSUPPORTED, "motion check: no kernel for this feature width");
+    e = launch(m->kf, m->Cc, g.nw, lds, nblk, a, st);
+    if (e != hipSuccess) return fail_hip(e, "motion kernel launch");
+    return DCX_OK;
 }
 
 int dcx_train_perceptron(int device, int kernel_kind, const float* kparams, float beta, const float* feats, int64_t N,

@@ -202,6 +202,17 @@ class DiffCo(CollisionChecker):
             s = s.reshape(-1)
         return s
 
+    def check_motions(self, starts, targets, res=None, max_step=None, margin=0., return_first=False, max_samples=None):
+        """motions starts[e] -> targets[e] under the `rbf_score` state: a sample collides iff rbf_score_c - margin_c > 0 for
+        some class (`margin`: a number or one per class).  Exactly one of `res` / `max_step`.  bool [E] (+ first index)."""
+        from ._perceptron import check_motions, motion_answer
+        if self.fkine is not None:
+            args = (self._rbf_fused, self.fkine, self.rbf_kernel, self.support_fkine, self.rbf_nodes)
+        else:
+            args = (self._rbf_fused, None, self.rbf_kernel, self.support_points, self.rbf_nodes)
+        first, _ = check_motions(self, *args, starts, targets, res=res, max_step=max_step, margin=margin, max_samples=max_samples)
+        return motion_answer(first, return_first)
+
     def poly_score(self, point):
         if point.ndim == 1:
             point = point[None, :]

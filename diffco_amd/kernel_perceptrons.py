@@ -299,6 +299,15 @@ class DiffCo(Perceptron):
             s = s.reshape(())
         return s
 
+    def check_motions(self, starts, targets, res=None, max_step=None, return_first=False, max_samples=None):
+        """is the straight motion starts[e] -> targets[e] in collision (`is_collision`: score > 0 at one of its samples)?
+        Exactly one rule: `res` (the points of `line_predict`) or `max_step` (those of utils.dense_path).  bool [E]; with
+        return_first also the first colliding sample index (-1 = free).  One fused launch (plus a small one) for all edges."""
+        from ._perceptron import check_motions, motion_answer
+        first, _ = check_motions(self, self._score_fused, self.transform, self.kernel_func, self.support_transformed, self.gains,
+                                 starts, targets, res=res, max_step=max_step, max_samples=max_samples)
+        return motion_answer(first, return_first)
+
     def poly_score(self, point=None, transformed_point=None):
         """sum_j K_rbf(T(q), support_j) rbf_nodes_j  ->  [N, 1]; `transformed_point` skips the FK."""
         if transformed_point is None:

@@ -163,6 +163,7 @@ int dcx_device_count(void);
  * never split the supports), "hess_form" (dcx_score_hess: 0 = one lane per (configuration, direction) sweeps the supports, 1 = the
  * moments form - one lane per configuration sweeps gradient, coefficient sum and the symmetric D x D matrix, the direction lanes
  * read M dx - wherever it is compiled (D <= 16); rule = from B = 1024; same Hessian to fp32 round-off),
+ * "motion_early_exit" (0 = dcx_check_motions sweeps every tile, none skipped behind a first hit: a measurement; same answers),
  * "solve_threads" (dcx_solve's workgroup size: 256 or 512; rule = 256 up to 736 unknowns; same pivots, same arithmetic),
  * "qt" (small batches of a one-class D = 12 / 24 model as tiles of 16 configurations that sweep all the rows from an LDS copy
  * instead of the split launch: 0 = never, 1 = wherever it is compiled and fits with >= 4 waves; rule = at most 16
@@ -353,6 +354,34 @@ typedef struct dcx_escape_opts {
 size_t dcx_escape_work_bytes(const dcx_model* m, int64_t B);
 int dcx_escape_adam(const dcx_model* m, float* q, int64_t B, const float* margin, const dcx_escape_opts* opt, void* work,
                     size_t work_bytes, float* history, int32_t* steps, void* stream);
+
+/* ---- batched motion checks (added under DCX_VERSION 109) ------------------------------------------------ */
+/* Is the straight joint-space motion qa[e] -> qb[e] free, and if not, which sample is the first to collide?  E edges
+ * (qa, qb: [E, dof] device floats), linear interpolation, exactly one sampling rule per call:
+ *   res > 0 (max_step = 0):      samples qa + (i / res)(qb - qa), i = 0 .. res - 1 (the target excluded): the point set of
+ *                                Perceptron.line_predict(qa, qb, res)
+ *   max_step > 0 (res = 0):      with L = |qb - qa|_2 and n = ceil(L / max_step): qa + k (max_step / L)(qb - qa) for
+ *                                k = 0 .. n - 1, then qb - the point set of utils.dense_path([qa, qb], max_step).  L = 0: qb.
+ * A sample collides iff score_c(q) - margin_c > 0 for some class c (margin: [C] device floats, NULL = 0).
+ * first_hit [E] (int32, device, out): the smallest colliding sample index, -1 for a free edge, -2 for an edge that needs more
+ *   than max_samples samples (not checked).  n_samples [E] (int32, device, out, may be NULL): the edge's sample count (the
+ *   count it would need, saturated at INT32_MAX, for an edge over max_samples).
+ * Samples behind an edge's first hit may be left unscored.  Three launches on the caller's stream (two small ones for the
+ * sample counts and their scan, then one fused interpolate -> FK -> score-only sweep -> compare launch); no allocation,
+ * no synchronisation, nothing read back: the call can be captured.
+ * work: dcx_motion_work_bytes(model, E) bytes of device memory, the caller's; initialised by the call itself.
+ * Argument errors (DCX_ERR_INVALID, before any device work): NULL model / opt / qa / qb / first_hit / work (E > 0), E < 0,
+ *   both or neither of res and max_step, max_samples < 1, work_bytes below dcx_motion_work_bytes.                         */
+typedef struct dcx_motion_opts {
+    int32_t res;          /* > 0: the res rule;  0: the max_step rule                                                  */
+    float max_step;       /* > 0: the max_step rule;  0: the res rule                                                  */
+    int32_t max_samples;  /* >= 1: edges needing more samples are answered -2.  It also sizes the launch (E *
+                             max_samples / 64 blocks, the surplus leaving at once): keep it close to the longest edge      */
+    int32_t reserved;     /* 0                                                                                         */
+} dcx_motion_opts;
+size_t dcx_motion_work_bytes(const dcx_model* m, int64_t E);
+int dcx_check_motions(const dcx_model* m, const float* qa, const float* qb, int64_t E, const dcx_motion_opts* opt,
+                      const float* margin, int32_t* first_hit, int32_t* n_samples, void* work, size_t work_bytes, void* stream);
 
 /* ---- kernel-perceptron trainer (producer of the path's state) ----------------------- */
 /* DiffCo.train_perceptron kernel_perceptrons.py:98-137 and MultiDiffCo.train_perceptron

@@ -1,0 +1,100 @@
+"""Batched motion checks on the headline model (Baxter DH-7, Polyharmonic(1,1), S = 2000): ScoreModel.check_motions against
+dcx_score on the same points already materialised (the bound without early exit) and against the host composition
+(the points built in torch, one score launch, the first hit per edge).  Edges of 8 - 64 samples (max_step rule), two sets:
+all free (a margin above every score) and cluttered (a margin at the 20th percentile of the sample scores: most edges hit
+within their first quarter).  check_motions runs with max_samples = 64 (the edges' own bound), with the default bound
+(max_samples=None: the longest edge's count, one read-back) and with a loose bound (10000), and with the early exit switched
+off (knob motion_early_exit = 0).
+
+    python tools/motion_bench.py [--edges 4096 65536] [--iters 50]
+
+One JSON line per (E, set) on stdout: median microseconds per call (CUDA events around each call on an idle stream).
+"""
+import argparse
+import json
+import os
+import sys
+
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+
+def timed(fn, iters, warmup=5):
+    for _ in range(warmup):
+        fn()
+    torch.cuda.synchronize()
+    ts = []
+    for _ in range(iters):
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        a.record()
+        fn()
+        b.record()
+        b.synchronize()
+        ts.append(a.elapsed_time(b) * 1e3)
+    ts.sort()
+    return ts[len(ts) // 2]
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--edges", type=int, nargs="+", default=[4096, 65536])
+    ap.add_argument("--iters", type=int, default=50)
+    args = ap.parse_args()
+    import bench
+    from diffco_amd import _lib
+    from diffco_amd._perceptron import host_motions
+    lib = _lib.require_gpu()
+    dev = torch.device("cuda", 0)
+    w = bench.make_workload("headline", 1024, dev)
+    m, lo, hi = w["model"], w["lo"].to(dev), w["hi"].to(dev)
+    step = 0.05
+    for E in args.edges:
+        g = torch.Generator(device=dev).manual_seed(E)
+        qa = torch.rand((E, 7), generator=g, device=dev) * (hi - lo) + lo
+        dirn = torch.randn((E, 7), generator=g, device=dev)
+        dirn = dirn / dirn.norm(dim=1, keepdim=True)
+        n_want = torch.randint(8, 65, (E, 1), generator=g, device=dev).float()
+        qb = qa + dirn * step * (n_want - 1.5)        # ceil(L / step) + 1 = n_want samples
+        first, n = m.check_motions(qa, qb, max_step=step, max_samples=64)
+        assert int((first == -2).sum()) == 0
+        # the materialised points (built once, outside the timing of the bound)
+        d = qb - qa
+        L = d.norm(dim=1)
+        nn = torch.ceil(L * (1.0 / step)).long() + 1
+        edge = torch.repeat_interleave(torch.arange(E, device=dev), nn)
+        k = torch.arange(len(edge), device=dev) - (torch.cumsum(nn, 0) - nn)[edge]
+        pts = (qa[edge] + k.float()[:, None] * (d[edge] * (step / L)[edge, None])).contiguous()
+        scores = m.score_raw(pts)[:, 0]
+        total = int(nn.sum())
+        for label, margin in (("free", float(scores.max()) + 1.0), ("cluttered", float(torch.quantile(scores[:1 << 20], 0.2)))):
+            f, _ = m.check_motions(qa, qb, max_step=step, margin=margin, max_samples=64)
+            hit = f >= 0
+            swept_hint = float(((f.float() + 1) / n.float()).where(hit, torch.ones_like(f, dtype=torch.float32)).mean())
+            res = dict(E=E, set=label, samples=total, hit_edges=int(hit.sum()), mean_first_frac=round(swept_hint, 3))
+            call = lambda ms: (lambda: m.check_motions(qa, qb, max_step=step, margin=margin, max_samples=ms))  # noqa: E731
+            # early exit on / off, interleaved three times (median of the three medians each)
+            on, off = [], []
+            for _ in range(3):
+                on.append(timed(call(64), args.iters))
+                lib.dcx_debug_set(b"motion_early_exit", 0)
+                off.append(timed(call(64), args.iters))
+                lib.dcx_debug_set(b"motion_early_exit", -1)
+            res["check_motions_us"] = sorted(on)[1]
+            res["check_motions_no_early_exit_us"] = sorted(off)[1]
+            # the default bound (max_samples=None: derived from the longest edge, one read-back) and a loose one (10000)
+            res["check_motions_default_bound_us"] = timed(call(None), args.iters)
+            res["check_motions_bound_10000_us"] = timed(call(10000), max(3, args.iters // 5))
+            res["dcx_score_materialised_us"] = timed(lambda: m.score_raw(pts), args.iters)
+            res["host_composition_us"] = timed(lambda: host_motions(lambda p: m.score_raw(p), qa, qb, max_step=step,
+                                                                    margin=margin, max_samples=64), max(5, args.iters // 5))
+            hf, _ = host_motions(lambda p: m.score_raw(p), qa, qb, max_step=step, margin=margin, max_samples=64)
+            res["host_agrees"] = float((hf == f).float().mean())
+            res["ratio_vs_score"] = round(res["check_motions_us"] / res["dcx_score_materialised_us"], 3)
+            res["speedup_vs_host"] = round(res["host_composition_us"] / res["check_motions_us"], 1)
+            print(json.dumps(res), flush=True)
+
+
+if __name__ == "__main__":
+    main()
