@@ -61,6 +61,9 @@ SYMBOLS = {
     "dcx_motion_work_bytes": (C.c_size_t, [C.c_void_p, C.c_int64]),
     "dcx_check_motions": (C.c_int, [C.c_void_p, _c_fp, _c_fp, C.c_int64, C.c_void_p, _c_fp, _c_fp, _c_fp, C.c_void_p, C.c_size_t,
                                     C.c_void_p]),
+    "dcx_motion_cost_work_bytes": (C.c_size_t, [C.c_void_p, C.c_int64, C.c_int32]),
+    "dcx_motion_cost": (C.c_int, [C.c_void_p, _c_fp, _c_fp, C.c_int64, C.c_void_p, _c_fp, C.c_float, _c_fp, _c_fp, _c_fp, _c_fp,
+                                  C.c_void_p, C.c_size_t, C.c_void_p]),
     "dcx_solve_work_bytes": (C.c_size_t, [C.c_int64, C.c_int64]),
     "dcx_solve": (C.c_int, [C.c_int, _c_fp, _c_fp, C.c_int64, C.c_int64, _c_fp, C.c_void_p, C.c_size_t, C.c_void_p, C.c_int32,
                             C.c_void_p]),
@@ -90,6 +93,12 @@ class EscapeOpts(C.Structure):
 class MotionOpts(C.Structure):
     """ctypes mirror of dcx_motion_opts (include/dcx.h)"""
     _fields_ = [("res", C.c_int32), ("max_step", C.c_float), ("max_samples", C.c_int32), ("reserved", C.c_int32)]
+
+
+class MotionCostOpts(C.Structure):
+    """ctypes mirror of dcx_motion_cost_opts (include/dcx.h)"""
+    _fields_ = [("res", C.c_int32), ("max_step", C.c_float), ("max_samples", C.c_int32), ("open_end", C.c_int32),
+                ("reserved", C.c_int32 * 4)]
 
 
 _lib = None

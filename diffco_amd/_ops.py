@@ -240,6 +240,22 @@ def motion_bound(qa32, qb32, max_step, limit=MOTION_MAX_SAMPLES):
     return int(min(limit, math.ceil(L * (1.0 / float(max_step))) + 2))
 
 
+def compose_path_cost(edge_cost, paths, dof):
+    """[T] costs of paths [T, W, dof] from an edge-cost callable edge_cost(qa, qb, open_end) under the max_step rule: the
+    open-ended edges p[i] -> p[i + 1] plus the zero-length edge p[-1] -> p[-1] (its one sample is p[-1]) cover the points of
+    utils.dense_path(p, max_step) once each"""
+    paths = torch.as_tensor(paths)
+    T, W = paths.shape[0], paths.shape[1]
+    if T == 0 or W == 0:
+        return paths.new_zeros(T)
+    p = paths.reshape(T, W, dof)
+    cost = edge_cost(p[:, -1], p[:, -1], False).reshape(T)
+    if W > 1:
+        seg = edge_cost(p[:, :-1].reshape(-1, dof), p[:, 1:].reshape(-1, dof), True)
+        cost = seg.reshape(T, W - 1).sum(dim=1) + cost
+    return cost
+
+
 class ScoreModel:
     """Owns one ``dcx_model`` (device copy of support rows + FK parameters).  `update()` refills it in place with new
     supports / weights (same transform, kernel and class count): no reallocation while they fit `capacity`."""
@@ -422,6 +438,61 @@ class ScoreModel:
                                                    _ptr(n), _ptr(work), int(nbytes), self._st()))
         return first, n
 
+    def _motion_margin(self, margin):
+        """the motion calls' margin argument: None (all zero), or [C] device floats (a device tensor stays on the device)"""
+        if torch.is_tensor(margin) and margin.device == self.dev:
+            return margin.detach().to(torch.float32).reshape(-1).expand(self.C).contiguous()
+        if torch.is_tensor(margin) or not (isinstance(margin, (int, float)) and float(margin) == 0.0):
+            return torch.tensor(list(self.margins(margin)), dtype=torch.float32).to(self.dev)
+        return None
+
+    def motion_cost_raw(self, qa, qb, res=None, max_step=None, margin=0., weight=1., open_end=False, max_samples=None):
+        """differentiable motion costs (dcx_motion_cost): for E straight joint-space motions qa[e] -> qb[e] ([E, dof] each),
+        (cost [E], grad_a [E, dof], grad_b [E, dof], n_samples [E] int32), fp32 device tensors:
+        cost[e] = weight * sum over the edge's samples of sum_c max(0, score_c - margin_c), and its gradients with respect to
+        qa[e] and qb[e] through the interpolation.  Exactly one rule, as check_motions: `res` or `max_step`; `open_end` drops
+        the target sample under max_step (the edges of a path plus its last waypoint then cover utils.dense_path once).
+        Edges over `max_samples` answer NaN.  max_samples=None under max_step derives the bound from the longest edge (one
+        read-back); a given bound reads nothing back (capturable).  Four launches (C > 1: five) on torch's current stream."""
+        if (res is None) == (max_step is None):
+            raise ValueError("motion_cost takes exactly one of res and max_step")
+        qa32 = _f32(torch.as_tensor(qa).reshape(-1, self.dof), self.dev)
+        qb32 = _f32(torch.as_tensor(qb).reshape(-1, self.dof), self.dev)
+        if qa32.shape != qb32.shape:
+            raise ValueError(f"{len(qa32)} start and {len(qb32)} target configurations")
+        E = len(qa32)
+        if max_samples is None:
+            max_samples = int(res) if res is not None else motion_bound(qa32, qb32, max_step)
+        opt = _lib.MotionCostOpts(int(res) if res is not None else 0, float(max_step) if max_step is not None else 0.0,
+                                  int(max_samples), 1 if open_end else 0)
+        mg = self._motion_margin(margin)
+        cost = torch.empty(E, device=self.dev, dtype=torch.float32)
+        ga = torch.empty((E, self.dof), device=self.dev, dtype=torch.float32)
+        gb = torch.empty((E, self.dof), device=self.dev, dtype=torch.float32)
+        n = torch.empty(E, device=self.dev, dtype=torch.int32)
+        nbytes = self._lib.dcx_motion_cost_work_bytes(self._h, E, int(max_samples))
+        work = torch.empty(max(int(nbytes), 1), device=self.dev, dtype=torch.uint8)
+        with _on_device(self.dev):
+            _lib.check(self._lib.dcx_motion_cost(self._h, _ptr(qa32), _ptr(qb32), E, C.byref(opt), _ptr(mg), float(weight),
+                                                 _ptr(cost), _ptr(ga), _ptr(gb), _ptr(n), _ptr(work), int(nbytes), self._st()))
+        return cost, ga, gb, n
+
+    def motion_cost(self, qa, qb, res=None, max_step=None, margin=0., weight=1., open_end=False, max_samples=None):
+        """[E] motion costs (motion_cost_raw), differentiable with respect to qa and qb (backward: upstream[e] * grad_*[e]; no
+        second derivatives).  Returned on qa's device and dtype."""
+        qa, qb = torch.as_tensor(qa), torch.as_tensor(qb)
+        kw = dict(res=res, max_step=max_step, margin=margin, weight=weight, open_end=open_end, max_samples=max_samples)
+        if not ((qa.requires_grad or qb.requires_grad) and torch.is_grad_enabled()):
+            cost = self.motion_cost_raw(qa, qb, **kw)[0]
+            return cost.to(device=qa.device, dtype=qa.dtype)
+        return _MotionCostFn.apply(qa, qb, self, kw)
+
+    def path_cost(self, paths, max_step, margin=0., weight=1., max_samples=None):
+        """[T] collision costs of T piecewise-straight paths [T, W, dof]: weight * sum over utils.dense_path(p, max_step)'s
+        points of sum_c max(0, score_c - margin_c), differentiable with respect to every waypoint (compose_path_cost)."""
+        kw = dict(max_step=max_step, margin=margin, weight=weight, max_samples=max_samples)
+        return compose_path_cost(lambda a, b, open_end: self.motion_cost(a, b, open_end=open_end, **kw), paths, self.dof)
+
     # autograd-aware ------------------------------------------------------------------------
     def score(self, q: torch.Tensor) -> torch.Tensor:
         """[B, C] scores for q [B, dof]; differentiable w.r.t. q (gradient from the fused HIP pass)."""
@@ -491,3 +562,22 @@ class _ScoreFn(torch.autograd.Function):
             return (gs.unsqueeze(-1) * jac).sum(dim=-2).reshape(ctx.in_shape), None
         _, g = model.score_grad_raw(q32, _f32(gs.reshape(-1, model.C), model.dev), want_score=False)
         return g.to(device=ctx.in_device, dtype=ctx.in_dtype).reshape(ctx.in_shape), None
+
+
+class _MotionCostFn(torch.autograd.Function):
+    """cost = motion_cost(qa, qb) [E]: ONE dcx_motion_cost call forms the cost and both endpoint gradients; backward scales
+    them by the upstream (no second derivatives)."""
+
+    @staticmethod
+    def forward(ctx, qa, qb, model, kw):
+        cost, ga, gb, _ = model.motion_cost_raw(qa, qb, **kw)
+        ctx.save_for_backward(ga.to(device=qa.device, dtype=qa.dtype).reshape(qa.shape),
+                              gb.to(device=qb.device, dtype=qb.dtype).reshape(qb.shape))
+        return cost.to(device=qa.device, dtype=qa.dtype)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, gc):
+        ga, gb = ctx.saved_tensors
+        up = gc.reshape((-1,) + (1,) * (ga.dim() - 1))
+        return (up * ga if ctx.needs_input_grad[0] else None), (up * gb if ctx.needs_input_grad[1] else None), None, None

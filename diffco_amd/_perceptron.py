@@ -318,3 +318,83 @@ def motion_answer(first, return_first):
         raise ValueError(f"check_motions: edges {bad} need more than max_samples samples (pass a larger max_samples or max_step)")
     hit = first >= 0
     return (hit, first) if return_first else hit
+
+
+# ---- differentiable motion costs ---------------------------------------------------------------------------------------------
+def host_motion_cost(score_fn, qa, qb, res=None, max_step=None, margin=0., weight=1., open_end=False, max_samples=None):
+    """the composition a caller would write without dcx_motion_cost: every edge's points materialised differentiably
+    (check_motions' arithmetic), scored through autograd, the hinge reduced per edge with index_add.  [E] costs,
+    differentiable with respect to qa and qb; NaN for an edge over max_samples."""
+    import torch
+    qa, qb = qa.reshape(len(qa), -1), qb.reshape(len(qb), -1)
+    E, dev = len(qa), qa.device
+    d = qb - qa
+    if res is not None:
+        n = torch.full((E,), int(res), dtype=torch.int64, device=dev)
+    else:
+        L = d.detach().norm(dim=-1)
+        steps = torch.ceil(L / max_step).to(torch.int64)
+        n = steps if open_end else steps + 1
+    limit = int(res) if (max_samples is None and res is not None) else (
+        _ops.MOTION_MAX_SAMPLES if max_samples is None else int(max_samples))
+    ok = n <= limit
+    n_ok = torch.where(ok, n, torch.zeros_like(n))
+    edge = torch.repeat_interleave(torch.arange(E, device=dev), n_ok)
+    offs = torch.cumsum(n_ok, 0) - n_ok
+    k = torch.arange(len(edge), device=dev) - offs[edge]
+    if res is not None:
+        pts = qa[edge] + d[edge] * (k.to(qa.dtype) / int(res))[:, None]
+    else:
+        # u = d / L differentiably (the sample counts are constants); L = 0 edges have only the target sample
+        Ld = d.norm(dim=-1, keepdim=True)
+        u = d / torch.where(Ld > 0, Ld, torch.ones_like(Ld))
+        pts = qa[edge] + (k.to(qa.dtype) * max_step)[:, None] * u[edge]
+        if not open_end:
+            last = k == n[edge] - 1
+            pts = torch.where(last[:, None], qb[edge], pts)
+    cost = torch.zeros(E, dtype=qa.dtype, device=dev)
+    if len(pts):
+        s = score_fn(pts).reshape(len(pts), -1)
+        mg = torch.as_tensor(margin, dtype=s.dtype, device=s.device).reshape(-1)
+        h = (s - mg).clamp(min=0).sum(dim=-1)
+        cost = cost.index_add(0, edge, h.to(cost.dtype))
+    cost = weight * cost
+    return torch.where(ok, cost, torch.full_like(cost, float("nan")))
+
+
+def motion_cost(owner, fused, transform, kernel_func, support_feat, weights, qa, qb, res=None, max_step=None, margin=0., weight=1.,
+                open_end=False, max_samples=None, score_fn=None):
+    """[E] differentiable motion costs on the model `fused` holds: one dcx_motion_cost call where the transform fuses (none, or
+    a diffco_amd robot's fkine), else the host composition (a foreign callable through `score_fn`).  owner.last_route says
+    which ran: "fused" or "host".  Raises ValueError for edges over max_samples (a read-back)."""
+    import torch
+    if (res is None) == (max_step is None):
+        raise ValueError("motion_cost takes exactly one of res and max_step")
+    qa, qb = torch.as_tensor(qa), torch.as_tensor(qb)
+    dev = qa.device if qa.device.type == "cuda" else (support_feat.device if support_feat.device.type == "cuda" else None)
+    m = fused.model(transform, kernel_func, support_feat, weights, dev)
+    kw = dict(res=res, max_step=max_step, margin=margin, weight=weight, open_end=open_end, max_samples=max_samples)
+    if m.desc.kind == 0 and transform is not None:
+        owner.last_route = "host"
+        fn = score_fn or (lambda p: fused.score(transform, kernel_func, support_feat, weights, p))
+        qa_d, qb_d = qa.to(device=m.dev, dtype=torch.float32), qb.to(device=m.dev, dtype=torch.float32)
+        cost = host_motion_cost(fn, qa_d, qb_d, **kw).to(device=qa.device, dtype=qa.dtype)
+    else:
+        owner.last_route = "fused"
+        cost = m.motion_cost(qa, qb, **kw)
+    if bool(torch.isnan(cost).any()):
+        bad = torch.isnan(cost).nonzero().reshape(-1)[:8].tolist()
+        raise ValueError(f"motion_cost: edges {bad} need more than max_samples samples (or hold non-finite values)")
+    return cost
+
+
+
+def path_cost(owner, fused, transform, kernel_func, support_feat, weights, paths, max_step, margin=0., weight=1., max_samples=None,
+              score_fn=None):
+    """[T] differentiable collision costs of paths [T, W, dof] (ScoreModel.path_cost's composition over either route)"""
+    import torch
+    paths = torch.as_tensor(paths)
+    dof = paths.shape[-1]
+    kw = dict(max_step=max_step, margin=margin, weight=weight, max_samples=max_samples, score_fn=score_fn)
+    return _ops.compose_path_cost(lambda a, b, open_end: motion_cost(owner, fused, transform, kernel_func, support_feat, weights, a,
+                                                                     b, open_end=open_end, **kw), paths, dof)

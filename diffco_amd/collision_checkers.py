@@ -215,6 +215,27 @@ class RBFDiffCo(CollisionChecker):
                                  q_start, q_end, res=res, max_step=max_step, margin=margin, max_samples=max_samples)
         return motion_answer(first, return_first)
 
+    def motion_cost(self, q_start, q_end, max_step=None, res=None, bias=None, weight=1., open_end=False, max_samples=None):
+        """[E] collision costs of the motions q_start[e] -> q_end[e] by `collision_score`: weight * sum over the samples of
+        max(0, poly score + bias) (bias defaults to safety_bias), differentiable with respect to both endpoints.  Exactly one
+        rule, as check_motions (open_end drops the target sample under max_step)."""
+        from ._perceptron import motion_cost
+        bias = self.safety_bias if bias is None else bias
+        margin = -bias if not torch.is_tensor(bias) else -bias.detach().reshape(-1)
+        p = self.perceptron
+        return motion_cost(self, p._poly_fused, p.transform, p.rbf_kernel, p.support_transformed, p.rbf_nodes, q_start, q_end,
+                           res=res, max_step=max_step, margin=margin, weight=weight, open_end=open_end, max_samples=max_samples)
+
+    def path_cost(self, paths, max_step, bias=None, weight=1., max_samples=None):
+        """[T] collision costs of paths [T, W, dof] by `collision_score` over utils.dense_path(p, max_step)'s points,
+        differentiable with respect to every waypoint"""
+        from ._perceptron import path_cost
+        bias = self.safety_bias if bias is None else bias
+        margin = -bias if not torch.is_tensor(bias) else -bias.detach().reshape(-1)
+        p = self.perceptron
+        return path_cost(self, p._poly_fused, p.transform, p.rbf_kernel, p.support_transformed, p.rbf_nodes, paths, max_step,
+                         margin=margin, weight=weight, max_samples=max_samples)
+
     def _calculate_safety_bias(self, q_verify):
         """a third of the smaller of |min score| and |max score| over q_verify (collision_checkers.py:497-503; the
         reference defines it on the FK subclass only and its RBFDiffCo.fit calls it regardless)"""

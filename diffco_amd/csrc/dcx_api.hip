@@ -12,6 +12,7 @@
 #include <vector>
 
 #include "dcx_internal.h"
+#include "motion_cost_kernel.h"
 #include "motion_kernel.h"
 #include "pack_kernels.h"
 #include "solve_kernels.h"
@@ -1741,6 +1742,194 @@ int dcx_check_motions(const dcx_model* m, const float* qa, const float* qb, int6
     if (!launch) return fail(DCX_ERR_UNSUPPORTED, "motion check: no kernel for this feature width");
     e = launch(m->kf, m->Cc, g.nw, lds, nblk, a, st);
     if (e != hipSuccess) return fail_hip(e, "motion kernel launch");
+    return DCX_OK;
+}
+
+// ---- differentiable motion costs (motion_cost_kernel.h, motion_cost_reduce.hip) --------------------------------------------
+namespace {
+// the workspace: dcx_check_motions' work list and split-launch room (partial rows of Dt + C accumulators), then per possible
+// sample (E * max_samples) its hinge value, its gradient row and - several classes - its class scores, and per tile the mark
+struct MotionCostWork {
+    size_t offs, frac, status, counters, partial, h, dq, scores, tile_on, total;
+};
+MotionCostWork motion_cost_work(const dcx_model* m, int64_t E, int32_t max_samples) {
+    auto up = [](size_t x) { return (x + 255) / 256 * 256; };
+    const size_t n = (size_t)E * (size_t)(max_samples > 0 ? max_samples : 0);
+    const size_t tiles = (n + 63) / 64;
+    const size_t acc = (size_t)m->Dt + (size_t)m->Cc;
+    MotionCostWork w;
+    w.offs = 0;
+    w.frac = up((size_t)(E + 1) * sizeof(int64_t));
+    w.status = w.frac + up((size_t)E * sizeof(float));
+    w.counters = w.status + up((size_t)E * sizeof(int32_t));
+    w.partial = w.counters + (size_t)kMotionSplitTiles * kCounterStride * sizeof(unsigned int);
+    w.h = w.partial + up((size_t)kMotionSplitRows * acc * 64 * sizeof(float));
+    w.dq = w.h + up(n * sizeof(float));
+    w.scores = w.dq + up(n * (size_t)m->fk.dof * sizeof(float));
+    w.tile_on = w.scores + (m->C > 1 ? up(n * (size_t)m->C * sizeof(float)) : 0);
+    w.total = w.tile_on + (m->C > 1 ? up(tiles * sizeof(int32_t)) : 0);
+    return w;
+}
+motion_cost_fn motion_cost_for(int Dt) {
+    switch (Dt) {
+#define DCX_CASE(D) case D: return launch_motion_cost_D##D;
+        DCX_CASE(2) DCX_CASE(4) DCX_CASE(6) DCX_CASE(8) DCX_CASE(12) DCX_CASE(16) DCX_CASE(18) DCX_CASE(21)
+        DCX_CASE(24) DCX_CASE(27) DCX_CASE(30) DCX_CASE(32) DCX_CASE(36) DCX_CASE(42) DCX_CASE(48) DCX_CASE(54)
+        DCX_CASE(60) DCX_CASE(64) DCX_CASE(72) DCX_CASE(84) DCX_CASE(96)
+#undef DCX_CASE
+    default: return nullptr;
+    }
+}
+}  // namespace
+
+size_t dcx_motion_cost_work_bytes(const dcx_model* m, int64_t E, int32_t max_samples) {
+    if (!m || E < 0 || max_samples < 1) return 0;
+    return motion_cost_work(m, E, max_samples).total;
+}
+
+int dcx_motion_cost(const dcx_model* m, const float* qa, const float* qb, int64_t E, const dcx_motion_cost_opts* opt,
+                    const float* margin, float weight, float* cost, float* grad_a, float* grad_b, int32_t* n_samples, void* work,
+                    size_t work_bytes, void* stream) {
+    // every argument is checked before anything touches the device
+    if (!m) return fail(DCX_ERR_INVALID, "model is NULL");
+    if (!opt) return fail(DCX_ERR_INVALID, "motion cost options are NULL");
+    if (E < 0) return fail(DCX_ERR_INVALID, "E < 0");
+    if (E > 0 && (!qa || !qb || !cost || !grad_a || !grad_b || !work))
+        return fail(DCX_ERR_INVALID, "qa / qb / cost / grad_a / grad_b / work is NULL");
+    const bool by_res = opt->res > 0, by_step = opt->max_step > 0.f;
+    if (opt->res < 0 || !(opt->max_step >= 0.f) || by_res == by_step)
+        return fail(DCX_ERR_INVALID, "motion cost needs exactly one sampling rule: res > 0 or max_step > 0 (the other 0)");
+    if (opt->max_samples < 1) return fail(DCX_ERR_INVALID, "motion cost needs max_samples >= 1");
+    if (opt->open_end != 0 && opt->open_end != 1) return fail(DCX_ERR_INVALID, "motion cost: open_end must be 0 or 1");
+    if (opt->reserved[0] || opt->reserved[1] || opt->reserved[2] || opt->reserved[3])
+        return fail(DCX_ERR_INVALID, "motion cost: reserved fields must be 0");
+    if (E > 0 && work_bytes < motion_cost_work(m, E, opt->max_samples).total)
+        return fail(DCX_ERR_INVALID, "motion cost workspace is smaller than dcx_motion_cost_work_bytes");
+    if (E > INT32_MAX) return fail(DCX_ERR_UNSUPPORTED, "motion cost: more than 2^31 - 1 edges");
+    if (E == 0) return DCX_OK;
+    const int64_t tiles_max = (E * (int64_t)opt->max_samples + 63) / 64;
+    if (tiles_max > 0x7fffffffLL) return fail(DCX_ERR_UNSUPPORTED, "motion cost: E * max_samples too large for one launch");
+    motion_cost_fn launch = motion_cost_for(m->Dt);
+    if (!launch) return fail(DCX_ERR_UNSUPPORTED, "motion cost: no kernel for this feature width");
+    if (int rc = set_device(m->device)) return rc;
+    hipStream_t st = (hipStream_t)stream;
+    const MotionCostWork w = motion_cost_work(m, E, opt->max_samples);
+    char* base = (char*)work;
+    const int d_fk = m->fk.n_points * m->fk.point_dim;
+    // geometry as dcx_score_grad picks it for the upper bound of the samples (the count itself is on the device only); a split
+    // launch keeps its counters and partial rows in the caller's work, so it is bounded like dcx_check_motions'
+    const int acc = m->Dt + m->Cc;
+    const int64_t b_max = std::min<int64_t>(tiles_max, (int64_t)1 << 30) * 64;
+    Geometry g = pick_geometry(m, b_max, acc, true);
+    if (g.ys > 1 && (tiles_max > kMotionSplitTiles || tiles_max * g.ys > kMotionSplitRows)) g = pick_geometry(m, b_max, acc, false);
+    MotionPrepArgs p{};
+    p.qa = qa;
+    p.qb = qb;
+    p.E = E;
+    p.dof = m->fk.dof;
+    p.res = opt->res;
+    p.max_samples = opt->max_samples;
+    p.max_step = opt->max_step;
+    p.offs = (int64_t*)(base + w.offs);
+    p.frac = (float*)(base + w.frac);
+    p.first_hit = (int32_t*)(base + w.status);
+    p.n_samples = n_samples;
+    p.counters = g.ys > 1 ? (unsigned int*)(base + w.counters) : nullptr;
+    p.n_counters = g.ys > 1 ? (int32_t)tiles_max : 0;
+    p.open_end = opt->max_step > 0.f ? opt->open_end : 0;
+    hipError_t e = launch_motion_prep(p, st);
+    if (e != hipSuccess) return fail_hip(e, "motion cost prep launch");
+
+    MotionCostArgs a{};
+    ScoreArgs& sa = a.sc;
+    sa.rows = m->rows_dev;
+    set_fk_walk(m, sa);
+    sa.B = 0;
+    sa.S = m->S_active;
+    sa.ys = g.ys;
+    sa.s_super = (m->S_active + g.ys - 1) / g.ys;
+    sa.s_chunk = (sa.s_super + g.nw - 1) / g.nw;
+    // the rows and slices as run_score picks them (per pass: the score pass and the gradient sweeps differ in their shares)
+    const bool xf_able = knobs().xf != 0 && xf_applies(m->Dt, m->Cc, m->kf) && m->rows_xf_dev != nullptr &&
+                         (m->kf != KF_RQ2 || m->xf_rq_ok || knobs().xf >= 2);
+    if (!xf_able && m->rows_p2_dev != nullptr && p2_applies(m->Dt, m->Cc, m->kf)) {
+        sa.rows = m->rows_p2_dev;
+        sa.s_super = (sa.s_super + 1) & ~1;
+        sa.s_chunk = ((sa.s_super + g.nw - 1) / g.nw + 1) & ~1;
+    }
+    sa.red_slots = g.red_slots;
+    sa.dof = m->fk.dof;
+    sa.d_fk = d_fk;
+    sa.frame_floats = m->frame_floats;
+    sa.kind = m->kind;
+    sa.c_out = m->C;
+    sa.one_hot = -1;
+    sa.nz = 1;
+    sa.kp0 = m->kp0_sweep;
+    sa.kp1 = m->kp1;
+    sa.xf = xf_able ? 1 : 0;
+    if (sa.xf) {
+        sa.rows = m->rows_xf_dev;
+        sa.centre = m->centre_dev;
+    }
+    sa.jt_rows = (sa.fkk == 2 && g.nw >= 2 * m->dh.n_chains && m->dh.n_chains <= 2 && m->dh.end0 <= kDhUnroll &&
+                  m->dh.n_steps - m->dh.end0 <= kDhUnroll && knobs().jt_waves != 0) ? 1 : 0;
+    sa.jt_waves = 0;   // J^T on wave 0 (fk_vjp_sel)
+    if (g.ys > 1) {
+        sa.partial = (float*)(base + w.partial);
+        sa.tile_done = (unsigned int*)(base + w.counters);
+    }
+    a.qa = qa;
+    a.qb = qb;
+    a.offs = p.offs;
+    a.frac = p.frac;
+    a.margin = margin;
+    a.h = (float*)(base + w.h);
+    a.dq = (float*)(base + w.dq);
+    a.scores = m->C > 1 ? (float*)(base + w.scores) : nullptr;
+    a.tile_on = m->C > 1 ? (int32_t*)(base + w.tile_on) : nullptr;
+    a.E = E;
+    a.weight = weight;
+    a.res = opt->res;
+    a.open_end = p.open_end;
+    auto skew_for = [&](bool score_only) {
+        return (g.nw == 16 && (sa.s_chunk >= 24 || knobs().skew > 0)) ? skew_rule(m->Cc, score_only)
+             : (g.nw == 8 && (sa.s_chunk >= 24 || knobs().skew8 > 0)) ? skew8_rule(score_only) : 0;
+    };
+    auto lds_for = [&](int acc_floats) {
+        return sizeof(float) * (((size_t)lds_plan(sa.dof, d_fk, m->frame_floats, g.nw > 1 ? g.red_slots : 0, acc_floats, true).total +
+                                 m->prog_floats + 3) & ~(size_t)3) + sizeof(float) * kMotionCostLdsFloats;
+    };
+    if (m->C == 1) {
+        sa.s_skew = skew_for(false);
+        e = launch(m->kf, m->Cc, MODE_GRAD_ROW, g.nw, lds_for(acc), tiles_max, a, st);
+    } else {
+        sa.s_skew = skew_for(true);
+        e = launch(m->kf, m->Cc, MODE_SCORE, g.nw, lds_for(m->Cc), tiles_max, a, st);
+        if (e == hipSuccess) {
+            sa.s_skew = skew_for(false);
+            e = launch(m->kf, m->Cc, MODE_GRAD_UP, g.nw, lds_for(acc), tiles_max, a, st);
+        }
+    }
+    if (e != hipSuccess) return fail_hip(e, "motion cost kernel launch");
+    MotionReduceArgs r{};
+    r.qa = qa;
+    r.qb = qb;
+    r.offs = p.offs;
+    r.frac = p.frac;
+    r.status = p.first_hit;
+    r.h = a.h;
+    r.dq = a.dq;
+    r.cost = cost;
+    r.grad_a = grad_a;
+    r.grad_b = grad_b;
+    r.E = E;
+    r.dof = m->fk.dof;
+    r.res = opt->res;
+    r.open_end = p.open_end;
+    r.weight = weight;
+    e = launch_motion_cost_reduce(r, st);
+    if (e != hipSuccess) return fail_hip(e, "motion cost reduction launch");
     return DCX_OK;
 }
 

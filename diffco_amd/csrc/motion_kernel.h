@@ -52,6 +52,7 @@ struct MotionPrepArgs {
     int32_t* n_samples;       // or null
     unsigned int* counters;   // split-launch arrival counters zeroed here (n_counters * kCounterStride words), or null
     int32_t n_counters;
+    int32_t open_end;         // max_step rule: 1 drops the target qb from the samples (dcx_motion_cost; dcx_check_motions: 0)
 };
 hipError_t launch_motion_prep(const MotionPrepArgs& p, hipStream_t stream);
 

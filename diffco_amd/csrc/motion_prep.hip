@@ -1,4 +1,4 @@
-// motion_prep.hip — the first launches of dcx_check_motions (motion_kernel.h): per edge its sample count under the call's rule,
+// motion_prep.hip — the first launches of dcx_check_motions and dcx_motion_cost (motion_kernel.h): per edge its sample count under the call's rule,
 // the step fraction of the max_step rule, first_hit set to -1 (or -2 for an edge over max_samples), n_samples (one thread per
 // edge over the whole chip), then the exclusive scan of the counts into the work list's offsets (one workgroup: chunks of 1024
 // counts, each scanned by wave shuffles and one pass over the 16 wave totals) and the split launch's arrival counters zeroed.
@@ -27,7 +27,8 @@ __global__ __launch_bounds__(kCountThreads) void motion_count_kernel(const Motio
         const float L = __fsqrt_rn(l2);
         const float steps = ceilf(__fmul_rn(L, __frcp_rn(p.max_step)));
         p.frac[e] = __fmul_rn(__frcp_rn(L), p.max_step);
-        n = (steps + 1.0f <= 2147483647.0f) ? (int64_t)steps + 1 : INT64_MAX;   // (NaN and inf land here too)
+        if (p.open_end) n = (steps <= 2147483647.0f) ? (int64_t)steps : INT64_MAX;   // without the target (L = 0: none)
+        else n = (steps + 1.0f <= 2147483647.0f) ? (int64_t)steps + 1 : INT64_MAX;   // (NaN and inf land here too)
     }
     const bool ok = n <= p.max_samples;
     if (p.n_samples) p.n_samples[e] = (int32_t)(n < INT32_MAX ? n : INT32_MAX);

@@ -213,6 +213,24 @@ class DiffCo(CollisionChecker):
         first, _ = check_motions(self, *args, starts, targets, res=res, max_step=max_step, margin=margin, max_samples=max_samples)
         return motion_answer(first, return_first)
 
+    def _rbf_args(self):
+        if self.fkine is not None:
+            return (self._rbf_fused, self.fkine, self.rbf_kernel, self.support_fkine, self.rbf_nodes)
+        return (self._rbf_fused, None, self.rbf_kernel, self.support_points, self.rbf_nodes)
+
+    def motion_cost(self, starts, targets, res=None, max_step=None, margin=0., weight=1., open_end=False, max_samples=None):
+        """[E] collision costs of the motions starts[e] -> targets[e] under the `rbf_score` state: weight * sum over the
+        samples of sum_c max(0, rbf_score_c - margin_c) (`margin`: a number or one per class), differentiable with respect to
+        starts and targets.  Exactly one of `res` / `max_step` (check_motions' samples; open_end drops the target)."""
+        from ._perceptron import motion_cost
+        return motion_cost(self, *self._rbf_args(), starts, targets, res=res, max_step=max_step, margin=margin, weight=weight,
+                           open_end=open_end, max_samples=max_samples)
+
+    def path_cost(self, paths, max_step, margin=0., weight=1., max_samples=None):
+        """[T] collision costs of paths [T, W, dof] over utils.dense_path(p, max_step)'s points, differentiable w.r.t. every waypoint"""
+        from ._perceptron import path_cost
+        return path_cost(self, *self._rbf_args(), paths, max_step, margin=margin, weight=weight, max_samples=max_samples)
+
     def poly_score(self, point):
         if point.ndim == 1:
             point = point[None, :]

@@ -308,6 +308,21 @@ class DiffCo(Perceptron):
                                  starts, targets, res=res, max_step=max_step, max_samples=max_samples)
         return motion_answer(first, return_first)
 
+    def motion_cost(self, starts, targets, res=None, max_step=None, margin=0., weight=1., open_end=False, max_samples=None):
+        """[E] collision costs of the motions starts[e] -> targets[e]: weight * sum over the samples of max(0, score - margin),
+        differentiable with respect to starts and targets.  Exactly one rule, as check_motions (open_end drops the target
+        sample under max_step).  One fused call (dcx_motion_cost) for all edges."""
+        from ._perceptron import motion_cost
+        return motion_cost(self, self._score_fused, self.transform, self.kernel_func, self.support_transformed, self.gains,
+                           starts, targets, res=res, max_step=max_step, margin=margin, weight=weight, open_end=open_end,
+                           max_samples=max_samples)
+
+    def path_cost(self, paths, max_step, margin=0., weight=1., max_samples=None):
+        """[T] collision costs of paths [T, W, dof] over utils.dense_path(p, max_step)'s points, differentiable w.r.t. every waypoint"""
+        from ._perceptron import path_cost
+        return path_cost(self, self._score_fused, self.transform, self.kernel_func, self.support_transformed, self.gains, paths,
+                         max_step, margin=margin, weight=weight, max_samples=max_samples)
+
     def poly_score(self, point=None, transformed_point=None):
         """sum_j K_rbf(T(q), support_j) rbf_nodes_j  ->  [N, 1]; `transformed_point` skips the FK."""
         if transformed_point is None:

@@ -383,6 +383,43 @@ size_t dcx_motion_work_bytes(const dcx_model* m, int64_t E);
 int dcx_check_motions(const dcx_model* m, const float* qa, const float* qb, int64_t E, const dcx_motion_opts* opt,
                       const float* margin, int32_t* first_hit, int32_t* n_samples, void* work, size_t work_bytes, void* stream);
 
+/* ---- differentiable motion costs (added under DCX_VERSION 109) ------------------------------------------ */
+/* The collision cost of the straight motion qa[e] -> qb[e] and its gradients with respect to both endpoints, E edges per call,
+ * on dcx_check_motions' sample set (exactly one rule per call, see above):
+ *   cost[e] = weight * sum over the edge's samples x_k of sum_c max(0, score_c(x_k) - margin_c)
+ * the optimisers' collision term (reference optim.py:88-89; ScoreModel.score_hinge_grad_raw) summed over an edge: the dense-check
+ * term of Weighted.step (optim.py:708-711), the per-segment con_collision_free of the SLSQP / trust-constr drivers
+ * (optim.py:190-207, :350-367), on the points of utils.dense_path (utils.py:87-).
+ * grad_a[e] = d cost[e] / d qa[e], grad_b[e] = d cost[e] / d qb[e] [E, dof], chained through the interpolation with the sample
+ * counts held constant (as autograd through utils.dense_path holds them):
+ *   res rule:      d x_k / d qb = (k / res) I
+ *   max_step rule: x_k = qa + k max_step u, u = (qb - qa) / L:  d x_k / d qb = (k max_step / L)(I - u u^T),
+ *                  d x_k / d qa = I - d x_k / d qb;  the target sample qb carries identity to grad_b.
+ * open_end (max_step rule only; the res rule never samples qb): the target is not a sample, so the edges of a path plus its last
+ *   waypoint cover utils.dense_path(p) once.  L = 0: the one sample is qb; with open_end there is none and the cost is 0.
+ * An edge over max_samples: cost, grad_a and grad_b NaN; n_samples (may be NULL) holds the count it would need.
+ * margin: [C] device floats, NULL = 0 (any C <= DCX_MAX_C, each class its own margin, as dcx_score_hinge_grad_mc).
+ * Launches on the caller's stream: the sample counts and their scan, one fused interpolate -> FK -> score + gradient sweep
+ * -> hinge -> J^T launch (C == 1; C > 1: a score pass, then the gradient sweep on the tiles that hold a sample above its
+ * margin), and a per-edge reduction in sample order (no atomics: repeated calls give the same bits).  No allocation, no
+ * synchronisation, nothing read back: the call can be captured.
+ * work: dcx_motion_cost_work_bytes(model, E, max_samples) bytes of device memory, the caller's; initialised by the call itself
+ *   (it holds per-sample values: about (dof + C + 1) * 4 bytes per possible sample).
+ * Argument errors (DCX_ERR_INVALID, before any device work): NULL model / opt / qa / qb / cost / grad_a / grad_b / work
+ *   (E > 0), E < 0, both or neither of res and max_step, max_samples < 1, open_end not 0 / 1, reserved not 0, work_bytes below
+ *   dcx_motion_cost_work_bytes.                                                                                           */
+typedef struct dcx_motion_cost_opts {
+    int32_t res;          /* > 0: the res rule;  0: the max_step rule                                                  */
+    float max_step;       /* > 0: the max_step rule;  0: the res rule                                                  */
+    int32_t max_samples;  /* >= 1: edges needing more samples answer NaN.  It sizes the launch and the workspace          */
+    int32_t open_end;     /* 1: the max_step rule without the target sample;  0: with it (dcx_check_motions' set)       */
+    int32_t reserved[4];  /* 0                                                                                         */
+} dcx_motion_cost_opts;
+size_t dcx_motion_cost_work_bytes(const dcx_model* m, int64_t E, int32_t max_samples);
+int dcx_motion_cost(const dcx_model* m, const float* qa, const float* qb, int64_t E, const dcx_motion_cost_opts* opt,
+                    const float* margin, float weight, float* cost, float* grad_a, float* grad_b, int32_t* n_samples, void* work,
+                    size_t work_bytes, void* stream);
+
 /* ---- kernel-perceptron trainer (producer of the path's state) ----------------------- */
 /* DiffCo.train_perceptron kernel_perceptrons.py:98-137 and MultiDiffCo.train_perceptron
  * deprecated/MultiDiffCo.py:50-83 as one persistent launch: worst-margin search, lazily filled kernel rows,
