@@ -7,20 +7,27 @@ A "step" = one pass of the hot path (ONE `dcx_score_grad` launch; config #5: one
 of synthetic configurations already resident in HBM.
 
     python bench.py                      # 1 GPU, headline workload
+    python bench.py --full               # the same, and every side measurement (below)
     python bench.py --gpus N --steps K --warmup W    # N > 1 without a launcher: becomes its own (self_launch) ...
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W [--scaling weak|strong] [--gather per-call|overlapped|bucketed|none]   # ... or under one
+
+A plain run does what its line's `value` needs and nothing else: it builds the workload, settles the clocks, runs the W
+warm-up and the K timed steps, writes --dump-outputs if asked, and prints the line.  `--full` adds the side measurements:
+the CPU baselines (`cpu_baseline`, None in a plain run, and `cpu_baseline_torch`), the shader clock beside the loop
+(`roofline.clock`), and with the headline workload on one GPU the short runs of the other BASELINE configurations
+(`configs`, `strong_bound`) and of the callers beside the path (`callers`).
 
 N > 1: one process per GPU, the model replicated, the configuration batch sharded, no data-path collective; the scores
 of EVERY call are all-gathered over RCCL/xGMI (`--gather per-call`, the default: in order on the launch stream, what a
 consumer that needs the scores before its next call sees; `overlapped`: the gather of call i runs beside the
 sweep of call i+1 on the process group's stream; `graph`: the same inside a captured HIP graph).  `--scaling weak` (default) keeps the per-GPU batch fixed as N grows,
 `--scaling strong` divides the workload's fixed global batch (65536 for headline / config #3, 256 restarts for
-config #5) by N.  With N > 1 the line also carries short measurements of the other variants (`variants`): the
-other scaling mode, the overlapped gather, the gather bucketed every 4 calls, and no gather.  The per-call form is measured and
-parked first (`multi.primary`); of the forms that deliver every call's scores (per-call, overlapped, graph), each timed over
-exactly K steps, the fastest that completed is the line's `value` (`multi.gather`).  Side measurements that hang end after
-DCX_BENCH_SIDE_BUDGET_S (240 s) with the line measured so far.
+config #5) by N.  The per-call form is measured and parked first (`multi.primary`); of the forms that deliver every call's
+scores (per-call, overlapped, graph), each timed over exactly K steps, the fastest that completed is the line's `value`
+(`multi.gather`), and the others are listed under `variants`.  With `--full` the line also carries short measurements of
+the other variants: the other scaling mode, the gather bucketed every 4 calls, and no gather.  Side measurements that hang
+end after DCX_BENCH_SIDE_BUDGET_S (240 s) with the line measured so far.
 
 Prints ONE JSON line on rank 0 (contract in the task statement) carrying `roofline` and `cpu_baseline`.  The line cannot
 be lost to a side measurement: rank 0 hands the PRIMARY line (timed region + CPU baseline) to a keeper process as soon as
@@ -1075,10 +1082,13 @@ def main():
                          "overlapped = eager, beside the next sweep; bucketed = every 4 calls; none = sharded consumer.  The other "
                          "forms are measured briefly as `variants` AFTER the primary line is safe, graph last")
     ap.add_argument("--no-gather", action="store_true", help="same as --gather none")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the side measurements: CPU baselines, the clock probe, the other BASELINE configurations and "
+                         "the callers (headline, N=1), the N>1 variants that cannot become `value`")
     ap.add_argument("--no-variants", action="store_true", help="N>1: skip the short runs of the other variants")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baselines")
     ap.add_argument("--no-configs", action="store_true",
-                    help="headline, N=1: skip the short measurements of the other BASELINE configurations (`configs` in the line)")
+                    help="--full, headline, N=1: skip the short measurements of the other BASELINE configurations (`configs` in the line)")
     ap.add_argument("--force-dist", action="store_true",
                     help="exercise the N>1 code path (process group + all-gather) even with one rank")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
@@ -1115,7 +1125,7 @@ def main():
     # The CPU baseline (rank 0's host cores) runs FIRST, before the process group exists: the other ranks wait in the TCP
     # rendezvous, not inside a collective kernel, and the primary line below is complete the moment the timed region ends.
     cpu_base, cpu_torch = None, None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:   # (N = 1 only: a launcher gives its ranks OMP_NUM_THREADS = 1)
+    if rank == 0 and world == 1 and args.full and not args.no_cpu_baseline:   # (N = 1 only: a launcher gives its ranks OMP_NUM_THREADS = 1)
         w0 = make_workload(args.workload, args.batch or min(WORKLOADS[args.workload][4], 65536), dev, seed=rank)
         cpu_base = cpu_baseline(w0)
         cpu_torch = torch_cpu_baseline(w0)
@@ -1172,7 +1182,7 @@ def main():
         # samples anything while the K steps are timed), the fraction against the peak at that clock, the driver's sensors beside it
         try:
             # (N = 1 only: the probe's busy loop would issue this rank's collectives without its peers)
-            ck = clock_under_load(loop, dev) if not (SAME_GPU or multi) else None
+            ck = clock_under_load(loop, dev) if args.full and not (SAME_GPU or multi) else None
         except Exception as exc:  # noqa: BLE001  (a side measurement)
             ck = {"error": f"{type(exc).__name__}: {exc}"[:160]}
         if ck is not None:
@@ -1215,11 +1225,14 @@ def main():
             # thread (see ScoreLoop._capture); by then every other variant is measured and the primary line is with the keeper
             others += [(f"gather_{g}", args.scaling, g) for g in ("per-call", "none", "bucketed", "overlapped", "graph") if g != args.gather]
         for key, sc, ga in others:
+            promotable = sc == args.scaling and ga in PROMOTABLE and args.gather in PROMOTABLE and not is_traj
+            if not (promotable or args.full):
+                continue   # (a form that cannot become `value`: --full)
             # A variant is a side measurement: if one fails (the same way on every rank: an allocation, an argument), it
             # is recorded as failed and the primary line above still goes out.
             try:
                 w2, l2 = build(sc, ga)
-                if sc == args.scaling and ga in PROMOTABLE and args.gather in PROMOTABLE and not is_traj:
+                if promotable:
                     # A form that hands the consumer the gathered scores of EVERY call, like the primary one: measured exactly
                     # as the primary line was - W warm-up steps, ONE timed region of exactly K steps, max over ranks - because
                     # the fastest of these that completes becomes the line's `value` (promotion, below)
@@ -1242,10 +1255,10 @@ def main():
             except Exception as exc:  # noqa: BLE001
                 variants[key] = {"scaling": sc, "gather": ga, "error": f"{type(exc).__name__}: {exc}"[:200]}
 
-    # The other BASELINE configurations, measured briefly in the same job on the same box (N = 1, headline run only): the
-    # driver's bench line then carries a number for every entry of BASELINE.json.configs that runs on a GPU.
+    # The other BASELINE configurations, measured briefly in the same job on the same box (--full, N = 1, headline run only):
+    # the line then carries a number for every entry of BASELINE.json.configs that runs on a GPU.
     configs = None
-    if world == 1 and not multi and name == "headline" and not args.batch and not args.no_configs:
+    if args.full and world == 1 and not multi and name == "headline" and not args.batch and not args.no_configs:
         configs = {}
         for cname, csteps in (("cfg2", 200), ("cfg2_panda", 200), ("cfg3", 200), ("cfg3_b65536", 200), ("cfg3_poly", 200), ("cfg4", 12),
                               ("cfg5", 200), ("cfg5_shard32", 200), ("cfg5_c5", 200), ("headline_rq", 100)):

@@ -5,6 +5,7 @@ import json
 import os
 import subprocess
 import sys
+import time
 
 import pytest
 
@@ -50,7 +51,7 @@ def test_one_json_line_per_baseline_workload(extra):
                                    ["--gather", "overlapped"], ["--gather", "bucketed", "--no-variants"], ["--no-gather", "--no-variants"]],
                          ids=["headline", "cfg3-strong", "cfg5-strong", "overlapped", "bucketed", "none"])
 def test_distributed_code_path_on_one_rank(extra):
-    d = _run(["--no-cpu-baseline", "--force-dist"] + extra, steps=24, warmup=4)
+    d = _run(["--full", "--no-cpu-baseline", "--force-dist"] + extra, steps=24, warmup=4)
     assert d["n_gpus"] == 1 and d["value"] > 0
     m = d["multi"]
     assert m["ranks"] == 1 and "nccl" in m["backend"]
@@ -84,9 +85,9 @@ def test_distributed_code_path_on_one_rank(extra):
 
 
 def test_headline_line_carries_every_baseline_config():
-    """the driver runs `python bench.py` only: its one line must hold a short measurement of every BASELINE.json config
-    that runs on a GPU"""
-    d = _run(["--no-cpu-baseline"], steps=10, warmup=3, timeout=900)
+    """`python bench.py --full`: its one line holds a short measurement of every BASELINE.json config that runs on a GPU
+    """
+    d = _run(["--full", "--no-cpu-baseline"], steps=10, warmup=3, timeout=900)
     cf = d["configs"]
     assert set(cf) == {"cfg2", "cfg2_panda", "cfg3", "cfg3_b65536", "cfg3_poly", "cfg4", "cfg5", "cfg5_shard32", "cfg5_c5", "headline_rq"}
     assert all("error" not in v for v in cf.values()), cf
@@ -111,7 +112,7 @@ def test_headline_line_carries_every_baseline_config():
     # (12.0 against 28.3 us).  The cluster form is a COOPERATIVE launch: it waits for the whole GPU, so once - 1 of 5 suite runs -
     # it read 67 us behind a previous test's processes that were still winding down; such a reading is taken again, once
     if not cf["cfg5_shard32"]["ms_per_step"] < 0.7 * cf["cfg5"]["ms_per_step"]:
-        d = _run(["--no-cpu-baseline"], steps=10, warmup=3, timeout=900)
+        d = _run(["--full", "--no-cpu-baseline"], steps=10, warmup=3, timeout=900)
         cf = d["configs"]
     assert cf["cfg5_shard32"]["ms_per_step"] < 0.7 * cf["cfg5"]["ms_per_step"]
     assert d["settle_steps"] > 0
@@ -144,8 +145,20 @@ def test_headline_line_carries_every_baseline_config():
         assert c["value"] > 0 and 0 < c["frac"] < 1 and c["kernel_ms"] <= c["ms_per_step"] * 1.05, (name, c)
 
 
+def test_plain_run_measures_the_headline_alone():
+    """a plain run does what `value` needs and nothing else - no CPU baseline, clock probe, configs or callers (`--full`) -
+    and spends at most 30 s of its whole run outside the warm-up and timed steps"""
+    t0 = time.perf_counter()
+    d = _run(["--gpus", "1"], steps=20, warmup=5)
+    outside = time.perf_counter() - t0 - (20 + 5) * d["ms_per_step"] * 1e-3
+    assert KEYS <= set(d) and d["steps"] == 20 and d["warmup"] == 5 and d["value"] > 0 and d["settle_steps"] > 0
+    assert d["cpu_baseline"] is None and not {"cpu_baseline_torch", "configs", "strong_bound", "callers"} & set(d)
+    assert "clock" not in d["roofline"] and "frac_at_measured_clock" not in d["roofline"]
+    assert outside < 30.0, outside
+
+
 def test_cpu_baseline_leg():
-    d = _run(["--batch", "4096"], steps=5, warmup=2)
+    d = _run(["--full", "--batch", "4096"], steps=5, warmup=2)
     cb = d["cpu_baseline"]
     assert {"value", "unit", "cores", "kind", "sample"} <= set(cb) and cb["kind"] == "port" and cb["value"] > 0
 
@@ -162,7 +175,7 @@ def test_two_rank_rehearsal_on_one_gpu(extra):
     port = str(29600 + (abs(hash(tuple(extra))) % 200))
     r = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr",
                         "127.0.0.1", "--master-port", port, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "12",
-                        "--warmup", "2"] + extra, capture_output=True, text=True, timeout=900, env=env, cwd=ROOT)
+                        "--warmup", "2", "--full"] + extra, capture_output=True, text=True, timeout=900, env=env, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [ln for ln in r.stdout.split("\n") if ln.strip().startswith("{")]
     assert len(lines) == 1, r.stdout
@@ -205,7 +218,8 @@ def test_the_line_survives_an_abort_after_the_timed_region():
     """fault injection: the process is aborted - as a library thread would, no Python clean-up - right
     after the timed region, before any variant: the keeper process still prints the primary line, exactly once"""
     env = dict(os.environ, MASTER_PORT="29549", DCX_BENCH_FAULT="after_primary")
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "12", "--warmup", "3", "--force-dist", "--batch", "4096"],
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "12", "--warmup", "3", "--force-dist", "--batch", "4096",
+                        "--full"],
                        capture_output=True, text=True, timeout=600, env=env, cwd=ROOT)
     assert r.returncode != 0
     d = _one_line(r.stdout)
