@@ -48,12 +48,13 @@ __global__ __launch_bounds__(kReduceThreads) void motion_cost_reduce_kernel(cons
             }
         }
         if (r.res <= 0 && n_in > 0) {   // u = (qb - qa) / L with L as motion_prep computed it (L > 0: there are interior samples)
+#pragma clang fp contract(off)
             float l2 = 0.0f;
             for (int i = 0; i < dof; ++i) {
                 const float d = __fsub_rn(r.qb[e * dof + i], r.qa[e * dof + i]);
-                l2 = __fadd_rn(l2, __fmul_rn(d, d));
+                l2 = l2 + d * d;
             }
-            uj = __fsub_rn(r.qb[e * dof + j], r.qa[e * dof + j]) / __fsqrt_rn(l2);
+            uj = __fsub_rn(r.qb[e * dof + j], r.qa[e * dof + j]) / sqrtf(l2);   // (correctly rounded, as motion_prep's L)
         }
     }
     if (r.res <= 0) {   // (kernel-uniform) P T = T - u (u . T): u . T summed over the edge's joints in order

@@ -18,13 +18,19 @@ __global__ __launch_bounds__(kCountThreads) void motion_count_kernel(const Motio
     if (p.res > 0) {
         n = p.res;
     } else {
-        // dense_path's arithmetic (utils.py): L = |qb - qa|, n = ceil(L * (1 / max_step)) + 1 points, step fraction (1 / L) * max_step
+#pragma clang fp contract(off)
+        // dense_path's arithmetic (utils.py): L = |qb - qa|, n = ceil(L * (1 / max_step)) + 1 points, step fraction (1 / L) * max_step.
+        // Each operation rounded on its own, with contraction off: -ffp-contract=fast fuses d * d + l2 into one FMA per joint
+        // (__fmul_rn / __fadd_rn included: they are plain * and + in the HIP headers) - a different l2, and a count off by one
+        // where L / max_step lies near an integer.
         float l2 = 0.0f;
         for (int j = 0; j < p.dof; ++j) {
             const float d = __fsub_rn(p.qb[e * p.dof + j], p.qa[e * p.dof + j]);
-            l2 = __fadd_rn(l2, __fmul_rn(d, d));
+            l2 = l2 + d * d;
         }
-        const float L = __fsqrt_rn(l2);
+        // sqrtf, not __fsqrt_rn: without OCML_BASIC_ROUNDED_OPERATIONS the latter is the native v_sqrt_f32 (1 ulp); sqrtf is
+        // correctly rounded (the compiler's default -fhip-fp32-correctly-rounded-divide-sqrt)
+        const float L = sqrtf(l2);
         const float steps = ceilf(__fmul_rn(L, __frcp_rn(p.max_step)));
         p.frac[e] = __fmul_rn(__frcp_rn(L), p.max_step);
         if (p.open_end) n = (steps <= 2147483647.0f) ? (int64_t)steps : INT64_MAX;   // without the target (L = 0: none)

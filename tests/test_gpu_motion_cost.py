@@ -7,6 +7,9 @@ import pytest
 import torch
 
 from helpers import CASE_ROBOT, case_kernel, desc_for, load, make_robot
+from helpers import motion_chain as _chain
+from helpers import motion_oracle_cost as _oracle
+from helpers import motion_samples as _samples
 
 pytestmark = pytest.mark.gpu
 
@@ -33,75 +36,6 @@ def _case(ops, name, weights=None):
     W = np.asarray(d["weights"] if weights is None else weights, F)
     m = ops.ScoreModel(desc, kind, p0, p1, _t(sup), _t(W))
     return d, m, desc, (kind, p0, p1), sup, W
-
-
-def _samples(qa, qb, res=None, max_step=None, open_end=False):
-    """per edge: (fp32 samples formed operation by operation as the kernel forms them, d x_k / d qb as (t_k, projected),
-    target flags) - the samples of check_motions' rules, open_end dropping the target under max_step"""
-    out = []
-    for a, b in zip(np.asarray(qa, F), np.asarray(qb, F)):
-        d = (b - a).astype(F)
-        if res is not None:
-            k = np.arange(res, dtype=F)
-            p = (a[None] + d[None] * (k / F(res))[:, None]).astype(F)
-            out.append((p, k.astype(np.float64) / res, None, np.zeros(res, bool)))
-            continue
-        l2 = F(0)
-        for v in d:
-            l2 = F(l2 + F(v * v))
-        L = F(np.sqrt(l2))
-        steps = int(np.ceil(F(L * F(F(1) / F(max_step)))))
-        frac = F(F(F(1) / L) * F(max_step)) if L > 0 else F(0)   # (L = 0: no interior sample)
-        k = np.arange(steps, dtype=F)
-        p = (a[None] + k[:, None] * (d * frac)[None]).astype(F)
-        t = k.astype(np.float64) * max_step / float(L) if L > 0 else np.zeros(0)
-        u = d.astype(np.float64) / float(L) if L > 0 else np.zeros(len(d))
-        tgt = np.zeros(steps, bool)
-        if not open_end:
-            p = np.concatenate([p, b[None]]).astype(F)
-            t = np.concatenate([t, [1.0]])
-            tgt = np.concatenate([tgt, [True]])
-        out.append((p.reshape(-1, len(a)), t, u, tgt))
-    return out
-
-
-def _chain(samples, s, g, weight):
-    """fp64 cost and endpoint gradients from per-sample hinge values s [N] and gradients g [N, dof] (already d(w h)/dx)"""
-    cost, ga, gb, i = [], [], [], 0
-    for p, t, u, tgt in samples:
-        n = len(p)
-        se, ge = s[i:i + n], g[i:i + n]
-        i += n
-        cost.append(weight * se.sum())
-        if u is None:   # res rule
-            gb.append((t[:, None] * ge).sum(0))
-            ga.append(((1 - t)[:, None] * ge).sum(0))
-            continue
-        P = np.eye(len(u)) - np.outer(u, u)
-        inner = ~tgt
-        T = P @ (t[inner][:, None] * ge[inner]).sum(0)
-        gb.append(T + ge[tgt].sum(0))
-        ga.append(ge[inner].sum(0) - T)
-    return np.array(cost), np.array(ga), np.array(gb)
-
-
-def _oracle(desc, kern, sup, W, samples, margin, weight):
-    """(cost, grad_a, grad_b, tie flags) in fp64: scores and per-class hinge gradients by the oracle, the chain on the host"""
-    from oracle import oracle
-    flat = np.concatenate([p for p, *_ in samples]) if samples else np.zeros((0, desc.dof), F)
-    C = W.reshape(len(sup), -1).shape[1]
-    mg = np.broadcast_to(np.asarray(margin, np.float64).reshape(-1), (C,))
-    s, _, _ = oracle.score_grad(desc, kern[0], kern[1], kern[2], sup, W, flat, dtype=np.float64)
-    up = (s - mg > 0).astype(np.float64) * weight
-    _, g, _ = oracle.score_grad(desc, kern[0], kern[1], kern[2], sup, W, flat, upstream=up, dtype=np.float64)
-    h = np.clip(s - mg, 0, None).sum(1)
-    cost, ga, gb = _chain(samples, h, g, weight)
-    band = 1e-4 * np.abs(s).max()
-    tie, i = [], 0
-    for p, *_ in samples:
-        tie.append(bool((np.abs(s[i:i + len(p)] - mg) <= band).any()))
-        i += len(p)
-    return cost, ga, gb, np.array(tie, bool)
 
 
 def _edges(q, E, seed, scale=1.0):

@@ -7,6 +7,8 @@ import pytest
 import torch
 
 from helpers import CASE_ROBOT, case_kernel, desc_for, load, make_robot
+from helpers import motion_oracle_first as _oracle_first
+from helpers import motion_points as _points
 
 pytestmark = pytest.mark.gpu
 
@@ -40,44 +42,6 @@ def _case(ops, name):
     sup = np.asarray(sup, dtype=F).reshape(len(sup), -1)
     m = ops.ScoreModel(desc, kind, p0, p1, _t(sup), _t(d["weights"]))
     return d, m, desc, (kind, p0, p1), sup
-
-
-def _points(qa, qb, res=None, max_step=None):
-    """every edge's samples in fp32, operation by operation as the kernel forms them (line_predict / dense_path arithmetic)"""
-    out = []
-    for a, b in zip(np.asarray(qa, F), np.asarray(qb, F)):
-        d = (b - a).astype(F)
-        if res is not None:
-            k = np.arange(res, dtype=F)
-            out.append((a[None] + d[None] * (k / F(res))[:, None]).astype(F))
-        else:
-            l2 = F(0)
-            for v in d:
-                l2 = F(l2 + F(v * v))
-            L = F(np.sqrt(l2))
-            n = int(np.ceil(F(L * F(F(1) / F(max_step))))) + 1
-            frac = F(F(F(1) / L) * F(max_step)) if L > 0 else F(np.inf)
-            k = np.arange(n - 1, dtype=F)
-            p = (a[None] + k[:, None] * (d * frac)[None]).astype(F)
-            out.append(np.concatenate([p, b[None]]).astype(F))
-    return out
-
-
-def _oracle_first(desc, kern, sup, W, pts, margin):
-    """(first colliding index per edge by the fp64 oracle, edges inside the tie band)"""
-    from oracle import oracle
-    flat = np.concatenate(pts)
-    s, _, _ = oracle.score_grad(desc, kern[0], kern[1], kern[2], sup, W, flat, dtype=np.float64)
-    s = s - np.asarray(margin, np.float64).reshape(1, -1)
-    band = 1e-4 * np.abs(s + np.asarray(margin, np.float64).reshape(1, -1)).max()
-    first, tie, i = [], [], 0
-    for p in pts:
-        se = s[i:i + len(p)]
-        i += len(p)
-        hit = (se > 0).any(axis=1)
-        first.append(int(np.argmax(hit)) if hit.any() else -1)
-        tie.append(bool((np.abs(se) <= band).any()))
-    return np.array(first), np.array(tie)
 
 
 def _edges(q, E, seed, scale=1.0):
