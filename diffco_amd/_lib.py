@@ -64,6 +64,11 @@ SYMBOLS = {
     "dcx_motion_cost_work_bytes": (C.c_size_t, [C.c_void_p, C.c_int64, C.c_int32]),
     "dcx_motion_cost": (C.c_int, [C.c_void_p, _c_fp, _c_fp, C.c_int64, C.c_void_p, _c_fp, C.c_float, _c_fp, _c_fp, _c_fp, _c_fp,
                                   C.c_void_p, C.c_size_t, C.c_void_p]),
+    # the two motion calls with a per-coordinate wrap mask (uint64 before the stream)
+    "dcx_check_motions_ex": (C.c_int, [C.c_void_p, _c_fp, _c_fp, C.c_int64, C.c_void_p, _c_fp, _c_fp, _c_fp, C.c_void_p, C.c_size_t,
+                                       C.c_uint64, C.c_void_p]),
+    "dcx_motion_cost_ex": (C.c_int, [C.c_void_p, _c_fp, _c_fp, C.c_int64, C.c_void_p, _c_fp, C.c_float, _c_fp, _c_fp, _c_fp, _c_fp,
+                                     C.c_void_p, C.c_size_t, C.c_uint64, C.c_void_p]),
     "dcx_solve_work_bytes": (C.c_size_t, [C.c_int64, C.c_int64]),
     "dcx_solve": (C.c_int, [C.c_int, _c_fp, _c_fp, C.c_int64, C.c_int64, _c_fp, C.c_void_p, C.c_size_t, C.c_void_p, C.c_int32,
                             C.c_void_p]),

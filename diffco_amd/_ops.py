@@ -7,6 +7,7 @@ unchanged on a GPU box.  Without a GPU every function raises (no CPU fallback).
 """
 import ctypes as C
 import math
+import numbers
 
 import torch
 from torch.autograd.function import once_differentiable
@@ -228,13 +229,48 @@ def train_perceptron_device(kind, p0, p1, beta, feats, y, gains, hypo, K, max_it
 MOTION_MAX_SAMPLES = 10000   # the default limit on one edge's samples (max_step rule): longer edges answer -2
 
 
-def motion_bound(qa32, qb32, max_step, limit=MOTION_MAX_SAMPLES):
+def wrap_mask(wrap, dof, transform=None):
+    """the motion calls' `wrap` argument as dcx_check_motions_ex's bitmask (bit j: coordinate j is an angle on the circle, the
+    edge runs along its shortest arc).  None / False: 0, the straight edge.  An int: the mask itself.  A sequence of dof
+    bools: one per coordinate.  True: the `wrap_mask` of the robot whose bound `fkine` is `transform` (model.py, urdf.py)."""
+    if wrap is None or wrap is False:
+        return 0
+    if wrap is True:
+        mask = getattr(getattr(transform, "__self__", None), "wrap_mask", None)
+        if mask is None:
+            raise ValueError("wrap=True needs a transform that is the fkine of a robot with a wrap_mask (diffco_amd.model / urdf): "
+                             "pass the mask itself, or one bool per coordinate")
+        wrap = mask
+    if isinstance(wrap, numbers.Integral):
+        mask = int(wrap)
+    else:
+        flags = torch.as_tensor(wrap).reshape(-1).tolist()
+        if len(flags) != dof or any(f not in (0, 1, False, True) for f in flags):
+            raise ValueError(f"wrap: expected one bool per coordinate ({dof}), got {len(flags)} values")
+        mask = sum(1 << j for j, f in enumerate(flags) if f)
+    if mask < 0 or mask >> dof:
+        raise ValueError(f"wrap mask {mask:#x} has a bit at or above dof = {dof}")
+    return mask
+
+
+def wrapped_delta(qa, qb, mask):
+    """qb - qa [E, dof] with the masked coordinates along the shortest arc (utils.wrap2pi of the difference; differentiable)"""
+    d = qb - qa
+    if mask:
+        from .utils import wrap2pi
+        on = torch.tensor([bool((mask >> j) & 1) for j in range(d.shape[-1])], device=d.device)
+        d = torch.where(on, wrap2pi(d), d)
+    return d
+
+
+def motion_bound(qa32, qb32, max_step, limit=MOTION_MAX_SAMPLES, wrap=None):
     """max_samples for a max_step call: the longest edge's sample count (+ 1 against a rounding of its length that differs
     from the kernel's), at most `limit`.  One small reduction read back: dcx_check_motions sizes its grid from E * max_samples,
-    and a loose bound launches a block per tile it could have had (measured: profiles/r07_motion_checks.txt)."""
+    and a loose bound launches a block per tile it could have had (measured: profiles/r07_motion_checks.txt).  `wrap`
+    (wrap_mask's values but True): the lengths are those of the wrapped edges."""
     if len(qa32) == 0:
         return 1
-    L = float((qb32 - qa32).norm(dim=1).max())
+    L = float(wrapped_delta(qa32, qb32, wrap_mask(wrap, qa32.shape[-1])).norm(dim=1).max())
     if not L == L or L == float("inf"):
         return limit
     return int(min(limit, math.ceil(L * (1.0 / float(max_step))) + 2))
@@ -404,7 +440,7 @@ class ScoreModel:
                                                          _ptr(grad), self._st()))
         return out, grad
 
-    def check_motions(self, qa, qb, res=None, max_step=None, margin=0., max_samples=None):
+    def check_motions(self, qa, qb, res=None, max_step=None, margin=0., max_samples=None, wrap=None):
         """batched motion checks (dcx_check_motions): for E straight joint-space motions qa[e] -> qb[e] ([E, dof] each),
         (first_hit, n_samples), int32 device tensors [E]: the first sample index with score_c - margin_c > 0 for some class
         (-1: free; -2: the edge needs more than `max_samples` samples and was not checked) and the edge's sample count.
@@ -412,16 +448,19 @@ class ScoreModel:
         `margin`: a number or one per class (a device tensor stays on the device).  Three launches on torch's current
         stream.  The launch grid is sized from E * max_samples, so the bound should be tight: max_samples=None under the
         max_step rule derives it from the longest edge (one read-back of a reduction; edges beyond MOTION_MAX_SAMPLES
-        still answer -2).  A given max_samples reads nothing back (capturable)."""
+        still answer -2).  A given max_samples reads nothing back (capturable).
+        `wrap` (wrap_mask: an int bitmask or one bool per coordinate): those coordinates are angles on the circle and the
+        edge runs along their shortest arc (dcx_check_motions_ex; the res rule's points are utils.anglin's)."""
         if (res is None) == (max_step is None):
             raise ValueError("check_motions takes exactly one of res and max_step")
+        mask = wrap_mask(wrap, self.dof)
         qa32 = _f32(torch.as_tensor(qa).reshape(-1, self.dof), self.dev)
         qb32 = _f32(torch.as_tensor(qb).reshape(-1, self.dof), self.dev)
         if qa32.shape != qb32.shape:
             raise ValueError(f"{len(qa32)} start and {len(qb32)} target configurations")
         E = len(qa32)
         if max_samples is None:
-            max_samples = int(res) if res is not None else motion_bound(qa32, qb32, max_step)
+            max_samples = int(res) if res is not None else motion_bound(qa32, qb32, max_step, wrap=mask)
         opt = _lib.MotionOpts(int(res) if res is not None else 0, float(max_step) if max_step is not None else 0.0, int(max_samples), 0)
         mg = None
         if torch.is_tensor(margin) and margin.device == self.dev:
@@ -434,8 +473,8 @@ class ScoreModel:
         nbytes = self._lib.dcx_motion_work_bytes(self._h, E)
         work = torch.empty(max(int(nbytes), 1), device=self.dev, dtype=torch.uint8)
         with _on_device(self.dev):
-            _lib.check(self._lib.dcx_check_motions(self._h, _ptr(qa32), _ptr(qb32), E, C.byref(opt), _ptr(mg), _ptr(first),
-                                                   _ptr(n), _ptr(work), int(nbytes), self._st()))
+            _lib.check(self._lib.dcx_check_motions_ex(self._h, _ptr(qa32), _ptr(qb32), E, C.byref(opt), _ptr(mg), _ptr(first),
+                                                      _ptr(n), _ptr(work), int(nbytes), mask, self._st()))
         return first, n
 
     def _motion_margin(self, margin):
@@ -446,23 +485,26 @@ class ScoreModel:
             return torch.tensor(list(self.margins(margin)), dtype=torch.float32).to(self.dev)
         return None
 
-    def motion_cost_raw(self, qa, qb, res=None, max_step=None, margin=0., weight=1., open_end=False, max_samples=None):
+    def motion_cost_raw(self, qa, qb, res=None, max_step=None, margin=0., weight=1., open_end=False, max_samples=None,
+                        wrap=None):
         """differentiable motion costs (dcx_motion_cost): for E straight joint-space motions qa[e] -> qb[e] ([E, dof] each),
         (cost [E], grad_a [E, dof], grad_b [E, dof], n_samples [E] int32), fp32 device tensors:
         cost[e] = weight * sum over the edge's samples of sum_c max(0, score_c - margin_c), and its gradients with respect to
         qa[e] and qb[e] through the interpolation.  Exactly one rule, as check_motions: `res` or `max_step`; `open_end` drops
         the target sample under max_step (the edges of a path plus its last waypoint then cover utils.dense_path once).
         Edges over `max_samples` answer NaN.  max_samples=None under max_step derives the bound from the longest edge (one
-        read-back); a given bound reads nothing back (capturable).  Four launches (C > 1: five) on torch's current stream."""
+        read-back); a given bound reads nothing back (capturable).  Four launches (C > 1: five) on torch's current stream.
+        `wrap`: as check_motions (dcx_motion_cost_ex); the gradients' unit direction is that of the wrapped edge."""
         if (res is None) == (max_step is None):
             raise ValueError("motion_cost takes exactly one of res and max_step")
+        mask = wrap_mask(wrap, self.dof)
         qa32 = _f32(torch.as_tensor(qa).reshape(-1, self.dof), self.dev)
         qb32 = _f32(torch.as_tensor(qb).reshape(-1, self.dof), self.dev)
         if qa32.shape != qb32.shape:
             raise ValueError(f"{len(qa32)} start and {len(qb32)} target configurations")
         E = len(qa32)
         if max_samples is None:
-            max_samples = int(res) if res is not None else motion_bound(qa32, qb32, max_step)
+            max_samples = int(res) if res is not None else motion_bound(qa32, qb32, max_step, wrap=mask)
         opt = _lib.MotionCostOpts(int(res) if res is not None else 0, float(max_step) if max_step is not None else 0.0,
                                   int(max_samples), 1 if open_end else 0)
         mg = self._motion_margin(margin)
@@ -473,24 +515,26 @@ class ScoreModel:
         nbytes = self._lib.dcx_motion_cost_work_bytes(self._h, E, int(max_samples))
         work = torch.empty(max(int(nbytes), 1), device=self.dev, dtype=torch.uint8)
         with _on_device(self.dev):
-            _lib.check(self._lib.dcx_motion_cost(self._h, _ptr(qa32), _ptr(qb32), E, C.byref(opt), _ptr(mg), float(weight),
-                                                 _ptr(cost), _ptr(ga), _ptr(gb), _ptr(n), _ptr(work), int(nbytes), self._st()))
+            _lib.check(self._lib.dcx_motion_cost_ex(self._h, _ptr(qa32), _ptr(qb32), E, C.byref(opt), _ptr(mg), float(weight),
+                                                    _ptr(cost), _ptr(ga), _ptr(gb), _ptr(n), _ptr(work), int(nbytes), mask,
+                                                    self._st()))
         return cost, ga, gb, n
 
-    def motion_cost(self, qa, qb, res=None, max_step=None, margin=0., weight=1., open_end=False, max_samples=None):
+    def motion_cost(self, qa, qb, res=None, max_step=None, margin=0., weight=1., open_end=False, max_samples=None, wrap=None):
         """[E] motion costs (motion_cost_raw), differentiable with respect to qa and qb (backward: upstream[e] * grad_*[e]; no
         second derivatives).  Returned on qa's device and dtype."""
         qa, qb = torch.as_tensor(qa), torch.as_tensor(qb)
-        kw = dict(res=res, max_step=max_step, margin=margin, weight=weight, open_end=open_end, max_samples=max_samples)
+        kw = dict(res=res, max_step=max_step, margin=margin, weight=weight, open_end=open_end, max_samples=max_samples, wrap=wrap)
         if not ((qa.requires_grad or qb.requires_grad) and torch.is_grad_enabled()):
             cost = self.motion_cost_raw(qa, qb, **kw)[0]
             return cost.to(device=qa.device, dtype=qa.dtype)
         return _MotionCostFn.apply(qa, qb, self, kw)
 
-    def path_cost(self, paths, max_step, margin=0., weight=1., max_samples=None):
+    def path_cost(self, paths, max_step, margin=0., weight=1., max_samples=None, wrap=None):
         """[T] collision costs of T piecewise-straight paths [T, W, dof]: weight * sum over utils.dense_path(p, max_step)'s
-        points of sum_c max(0, score_c - margin_c), differentiable with respect to every waypoint (compose_path_cost)."""
-        kw = dict(max_step=max_step, margin=margin, weight=weight, max_samples=max_samples)
+        points of sum_c max(0, score_c - margin_c), differentiable with respect to every waypoint (compose_path_cost).
+        `wrap`: every segment runs along the shortest arc of the masked coordinates (motion_cost's)."""
+        kw = dict(max_step=max_step, margin=margin, weight=weight, max_samples=max_samples, wrap=wrap)
         return compose_path_cost(lambda a, b, open_end: self.motion_cost(a, b, open_end=open_end, **kw), paths, self.dof)
 
     # autograd-aware ------------------------------------------------------------------------

@@ -250,13 +250,24 @@ class FusedScorer:
 
 
 # ---- batched motion checks ---------------------------------------------------------------------------------------------------
-def host_motions(score_fn, qa, qb, res=None, max_step=None, margin=0., max_samples=None):
+def _wrap_points(pts, mask):
+    """the masked coordinates of the points brought back to [-pi, pi) (utils.wrap2pi; slope 1 under autograd)"""
+    import torch
+    from .utils import wrap2pi
+    if not mask:
+        return pts
+    on = torch.tensor([bool((mask >> j) & 1) for j in range(pts.shape[-1])], device=pts.device)
+    return torch.where(on, wrap2pi(pts), pts)
+
+
+def host_motions(score_fn, qa, qb, res=None, max_step=None, margin=0., max_samples=None, wrap=0):
     """the composition a caller would write without dcx_check_motions: every edge's points (line_predict's / dense_path's
-    arithmetic) materialised, ONE score launch over all of them, the first hit per edge.  Same answers, (first_hit, n_samples)."""
+    arithmetic; `wrap`, a bitmask: utils.anglin's on the masked coordinates) materialised, ONE score launch over all of them,
+    the first hit per edge.  Same answers, (first_hit, n_samples)."""
     import torch
     qa, qb = qa.reshape(len(qa), -1), qb.reshape(len(qb), -1)
     E, dev = len(qa), qa.device
-    d = qb - qa
+    d = _ops.wrapped_delta(qa, qb, wrap)
     if res is not None:
         n = torch.full((E,), int(res), dtype=torch.int64, device=dev)
         frac = None
@@ -272,9 +283,9 @@ def host_motions(score_fn, qa, qb, res=None, max_step=None, margin=0., max_sampl
     offs = torch.cumsum(n_ok, 0) - n_ok
     k = torch.arange(len(edge), device=dev) - offs[edge]
     if res is not None:
-        pts = qa[edge] + d[edge] * (k.to(qa.dtype) / int(res))[:, None]
+        pts = _wrap_points(qa[edge] + d[edge] * (k.to(qa.dtype) / int(res))[:, None], wrap)
     else:
-        pts = qa[edge] + k.to(qa.dtype)[:, None] * (d[edge] * frac[edge][:, None])
+        pts = _wrap_points(qa[edge] + k.to(qa.dtype)[:, None] * (d[edge] * frac[edge][:, None]), wrap)
         last = k == n[edge] - 1
         pts = torch.where(last[:, None], qb[edge], pts)
     first = torch.full((E,), -1, dtype=torch.int64, device=dev)
@@ -291,14 +302,16 @@ def host_motions(score_fn, qa, qb, res=None, max_step=None, margin=0., max_sampl
 
 
 def check_motions(owner, fused, transform, kernel_func, support_feat, weights, qa, qb, res=None, max_step=None, margin=0.,
-                  max_samples=None, score_fn=None):
+                  max_samples=None, score_fn=None, wrap=None):
     """(first_hit, n_samples) of the motions qa[e] -> qb[e] on the model `fused` holds: one dcx_check_motions call where the
     transform fuses (none, or a diffco_amd robot's fkine), else the host composition (a foreign callable: its points through
-    `score_fn` in one launch).  owner.last_route says which ran: "fused" or "host"."""
+    `score_fn` in one launch).  owner.last_route says which ran: "fused" or "host".  `wrap` (_ops.wrap_mask; True: the mask
+    of the robot that owns `transform`): those coordinates run along their shortest arc."""
     import torch
     if (res is None) == (max_step is None):
         raise ValueError("check_motions takes exactly one of res and max_step")
     qa, qb = torch.as_tensor(qa), torch.as_tensor(qb)
+    mask = _ops.wrap_mask(wrap, qa.shape[-1], transform)
     dev = qa.device if qa.device.type == "cuda" else (support_feat.device if support_feat.device.type == "cuda" else None)
     m = fused.model(transform, kernel_func, support_feat, weights, dev)
     if m.desc.kind == 0 and transform is not None:
@@ -306,9 +319,9 @@ def check_motions(owner, fused, transform, kernel_func, support_feat, weights, q
         qa32 = qa.to(device=m.dev, dtype=torch.float32)
         qb32 = qb.to(device=m.dev, dtype=torch.float32)
         fn = score_fn or (lambda p: fused.score(transform, kernel_func, support_feat, weights, p))
-        return host_motions(lambda p: fn(p).detach(), qa32, qb32, res, max_step, margin, max_samples)
+        return host_motions(lambda p: fn(p).detach(), qa32, qb32, res, max_step, margin, max_samples, mask)
     owner.last_route = "fused"
-    return m.check_motions(qa, qb, res=res, max_step=max_step, margin=margin, max_samples=max_samples)
+    return m.check_motions(qa, qb, res=res, max_step=max_step, margin=margin, max_samples=max_samples, wrap=mask)
 
 
 def motion_answer(first, return_first):
@@ -321,14 +334,15 @@ def motion_answer(first, return_first):
 
 
 # ---- differentiable motion costs ---------------------------------------------------------------------------------------------
-def host_motion_cost(score_fn, qa, qb, res=None, max_step=None, margin=0., weight=1., open_end=False, max_samples=None):
+def host_motion_cost(score_fn, qa, qb, res=None, max_step=None, margin=0., weight=1., open_end=False, max_samples=None, wrap=0):
     """the composition a caller would write without dcx_motion_cost: every edge's points materialised differentiably
-    (check_motions' arithmetic), scored through autograd, the hinge reduced per edge with index_add.  [E] costs,
-    differentiable with respect to qa and qb; NaN for an edge over max_samples."""
+    (check_motions' arithmetic; `wrap`, a bitmask: the wrapped delta and wrapped points, both of slope 1), scored through
+    autograd, the hinge reduced per edge with index_add.  [E] costs, differentiable with respect to qa and qb; NaN for an
+    edge over max_samples."""
     import torch
     qa, qb = qa.reshape(len(qa), -1), qb.reshape(len(qb), -1)
     E, dev = len(qa), qa.device
-    d = qb - qa
+    d = _ops.wrapped_delta(qa, qb, wrap)
     if res is not None:
         n = torch.full((E,), int(res), dtype=torch.int64, device=dev)
     else:
@@ -343,12 +357,12 @@ def host_motion_cost(score_fn, qa, qb, res=None, max_step=None, margin=0., weigh
     offs = torch.cumsum(n_ok, 0) - n_ok
     k = torch.arange(len(edge), device=dev) - offs[edge]
     if res is not None:
-        pts = qa[edge] + d[edge] * (k.to(qa.dtype) / int(res))[:, None]
+        pts = _wrap_points(qa[edge] + d[edge] * (k.to(qa.dtype) / int(res))[:, None], wrap)
     else:
         # u = d / L differentiably (the sample counts are constants); L = 0 edges have only the target sample
         Ld = d.norm(dim=-1, keepdim=True)
         u = d / torch.where(Ld > 0, Ld, torch.ones_like(Ld))
-        pts = qa[edge] + (k.to(qa.dtype) * max_step)[:, None] * u[edge]
+        pts = _wrap_points(qa[edge] + (k.to(qa.dtype) * max_step)[:, None] * u[edge], wrap)
         if not open_end:
             last = k == n[edge] - 1
             pts = torch.where(last[:, None], qb[edge], pts)
@@ -363,17 +377,18 @@ def host_motion_cost(score_fn, qa, qb, res=None, max_step=None, margin=0., weigh
 
 
 def motion_cost(owner, fused, transform, kernel_func, support_feat, weights, qa, qb, res=None, max_step=None, margin=0., weight=1.,
-                open_end=False, max_samples=None, score_fn=None):
+                open_end=False, max_samples=None, score_fn=None, wrap=None):
     """[E] differentiable motion costs on the model `fused` holds: one dcx_motion_cost call where the transform fuses (none, or
     a diffco_amd robot's fkine), else the host composition (a foreign callable through `score_fn`).  owner.last_route says
-    which ran: "fused" or "host".  Raises ValueError for edges over max_samples (a read-back)."""
+    which ran: "fused" or "host".  Raises ValueError for edges over max_samples (a read-back).  `wrap`: as check_motions."""
     import torch
     if (res is None) == (max_step is None):
         raise ValueError("motion_cost takes exactly one of res and max_step")
     qa, qb = torch.as_tensor(qa), torch.as_tensor(qb)
+    mask = _ops.wrap_mask(wrap, qa.shape[-1], transform)
     dev = qa.device if qa.device.type == "cuda" else (support_feat.device if support_feat.device.type == "cuda" else None)
     m = fused.model(transform, kernel_func, support_feat, weights, dev)
-    kw = dict(res=res, max_step=max_step, margin=margin, weight=weight, open_end=open_end, max_samples=max_samples)
+    kw = dict(res=res, max_step=max_step, margin=margin, weight=weight, open_end=open_end, max_samples=max_samples, wrap=mask)
     if m.desc.kind == 0 and transform is not None:
         owner.last_route = "host"
         fn = score_fn or (lambda p: fused.score(transform, kernel_func, support_feat, weights, p))
@@ -390,11 +405,12 @@ def motion_cost(owner, fused, transform, kernel_func, support_feat, weights, qa,
 
 
 def path_cost(owner, fused, transform, kernel_func, support_feat, weights, paths, max_step, margin=0., weight=1., max_samples=None,
-              score_fn=None):
+              score_fn=None, wrap=None):
     """[T] differentiable collision costs of paths [T, W, dof] (ScoreModel.path_cost's composition over either route)"""
     import torch
     paths = torch.as_tensor(paths)
     dof = paths.shape[-1]
-    kw = dict(max_step=max_step, margin=margin, weight=weight, max_samples=max_samples, score_fn=score_fn)
+    kw = dict(max_step=max_step, margin=margin, weight=weight, max_samples=max_samples, score_fn=score_fn,
+              wrap=_ops.wrap_mask(wrap, dof, transform))
     return _ops.compose_path_cost(lambda a, b, open_end: motion_cost(owner, fused, transform, kernel_func, support_feat, weights, a,
                                                                      b, open_end=open_end, **kw), paths, dof)

@@ -203,38 +203,42 @@ class RBFDiffCo(CollisionChecker):
         raw = self.perceptron.poly_score(q.reshape(-1, shape_q[-1]))
         return raw.reshape(shape_q[:-1] + raw.shape[1:]) + bias
 
-    def check_motions(self, q_start, q_end, max_step=None, res=None, bias=None, return_first=False, max_samples=None):
+    def check_motions(self, q_start, q_end, max_step=None, res=None, bias=None, return_first=False, max_samples=None, wrap=None):
         """is the straight motion q_start[e] -> q_end[e] in collision, by `collision_score` (poly score + bias > 0; bias
         defaults to safety_bias) at its samples?  Exactly one rule: `max_step` (utils.dense_path's points) or `res`
-        (line_predict's).  bool [E]; with return_first also the first colliding sample index (-1 = free)."""
+        (line_predict's).  bool [E]; with return_first also the first colliding sample index (-1 = free).
+        `wrap` (None, True: the robot's own circular coordinates, an int bitmask or one bool per coordinate): those
+        coordinates are angles and the edge runs along their shortest arc."""
         from ._perceptron import check_motions, motion_answer
         bias = self.safety_bias if bias is None else bias
         margin = -bias if not torch.is_tensor(bias) else -bias.detach().reshape(-1)
         p = self.perceptron
         first, _ = check_motions(self, p._poly_fused, p.transform, p.rbf_kernel, p.support_transformed, p.rbf_nodes,
-                                 q_start, q_end, res=res, max_step=max_step, margin=margin, max_samples=max_samples)
+                                 q_start, q_end, res=res, max_step=max_step, margin=margin, max_samples=max_samples, wrap=wrap)
         return motion_answer(first, return_first)
 
-    def motion_cost(self, q_start, q_end, max_step=None, res=None, bias=None, weight=1., open_end=False, max_samples=None):
+    def motion_cost(self, q_start, q_end, max_step=None, res=None, bias=None, weight=1., open_end=False, max_samples=None,
+                    wrap=None):
         """[E] collision costs of the motions q_start[e] -> q_end[e] by `collision_score`: weight * sum over the samples of
         max(0, poly score + bias) (bias defaults to safety_bias), differentiable with respect to both endpoints.  Exactly one
-        rule, as check_motions (open_end drops the target sample under max_step)."""
+        rule, as check_motions (open_end drops the target sample under max_step; `wrap` as there)."""
         from ._perceptron import motion_cost
         bias = self.safety_bias if bias is None else bias
         margin = -bias if not torch.is_tensor(bias) else -bias.detach().reshape(-1)
         p = self.perceptron
         return motion_cost(self, p._poly_fused, p.transform, p.rbf_kernel, p.support_transformed, p.rbf_nodes, q_start, q_end,
-                           res=res, max_step=max_step, margin=margin, weight=weight, open_end=open_end, max_samples=max_samples)
+                           res=res, max_step=max_step, margin=margin, weight=weight, open_end=open_end, max_samples=max_samples,
+                           wrap=wrap)
 
-    def path_cost(self, paths, max_step, bias=None, weight=1., max_samples=None):
+    def path_cost(self, paths, max_step, bias=None, weight=1., max_samples=None, wrap=None):
         """[T] collision costs of paths [T, W, dof] by `collision_score` over utils.dense_path(p, max_step)'s points,
-        differentiable with respect to every waypoint"""
+        differentiable with respect to every waypoint (`wrap` as check_motions: per segment)"""
         from ._perceptron import path_cost
         bias = self.safety_bias if bias is None else bias
         margin = -bias if not torch.is_tensor(bias) else -bias.detach().reshape(-1)
         p = self.perceptron
         return path_cost(self, p._poly_fused, p.transform, p.rbf_kernel, p.support_transformed, p.rbf_nodes, paths, max_step,
-                         margin=margin, weight=weight, max_samples=max_samples)
+                         margin=margin, weight=weight, max_samples=max_samples, wrap=wrap)
 
     def _calculate_safety_bias(self, q_verify):
         """a third of the smaller of |min score| and |max score| over q_verify (collision_checkers.py:497-503; the

@@ -1643,6 +1643,12 @@ size_t dcx_motion_work_bytes(const dcx_model* m, int64_t E) {
 
 int dcx_check_motions(const dcx_model* m, const float* qa, const float* qb, int64_t E, const dcx_motion_opts* opt,
                       const float* margin, int32_t* first_hit, int32_t* n_samples, void* work, size_t work_bytes, void* stream) {
+    return dcx_check_motions_ex(m, qa, qb, E, opt, margin, first_hit, n_samples, work, work_bytes, 0, stream);
+}
+
+int dcx_check_motions_ex(const dcx_model* m, const float* qa, const float* qb, int64_t E, const dcx_motion_opts* opt,
+                         const float* margin, int32_t* first_hit, int32_t* n_samples, void* work, size_t work_bytes,
+                         uint64_t wrap_mask, void* stream) {
     // every argument is checked before anything touches the model or the device
     if (!m) return fail(DCX_ERR_INVALID, "model is NULL");
     if (!opt) return fail(DCX_ERR_INVALID, "motion options are NULL");
@@ -1652,6 +1658,8 @@ int dcx_check_motions(const dcx_model* m, const float* qa, const float* qb, int6
     if (opt->res < 0 || !(opt->max_step >= 0.f) || by_res == by_step)
         return fail(DCX_ERR_INVALID, "motion check needs exactly one sampling rule: res > 0 or max_step > 0 (the other 0)");
     if (opt->max_samples < 1) return fail(DCX_ERR_INVALID, "motion check needs max_samples >= 1");
+    if (wrap_mask != 0 && m->fk.dof < 64 && (wrap_mask >> m->fk.dof) != 0)   // (mask 0, the plain call: the model is not read here)
+        return fail(DCX_ERR_INVALID, "motion check: wrap_mask has a bit at or above dof");
     const MotionWork w = motion_work(E);
     if (E > 0 && work_bytes < w.total) return fail(DCX_ERR_INVALID, "motion workspace is smaller than dcx_motion_work_bytes");
     if (E > INT32_MAX) return fail(DCX_ERR_UNSUPPORTED, "motion check: more than 2^31 - 1 edges");
@@ -1682,6 +1690,7 @@ int dcx_check_motions(const dcx_model* m, const float* qa, const float* qb, int6
     p.n_samples = n_samples;
     p.counters = g.ys > 1 ? (unsigned int*)(base + w.counters) : nullptr;
     p.n_counters = g.ys > 1 ? (int32_t)tiles_max : 0;
+    p.wrap_mask = wrap_mask;
     hipError_t e = launch_motion_prep(p, st);
     if (e != hipSuccess) return fail_hip(e, "motion prep launch");
 
@@ -1735,6 +1744,7 @@ int dcx_check_motions(const dcx_model* m, const float* qa, const float* qb, int6
     a.E = E;
     a.res = opt->res;
     a.early_exit = knobs().motion_early_exit != 0 ? 1 : 0;
+    a.wrap_mask = wrap_mask;
     const int64_t nblk = tiles_max;   // one tile per block; blocks past the work list's end leave (motion_kernel.h)
     const size_t lds = sizeof(float) * (((size_t)lds_plan(sa.dof, d_fk, m->frame_floats, g.nw > 1 ? g.red_slots : 0, acc, true).total +
                                          m->prog_floats + 3) & ~(size_t)3) + sizeof(float) * kMotionLdsFloats;
@@ -1790,6 +1800,12 @@ size_t dcx_motion_cost_work_bytes(const dcx_model* m, int64_t E, int32_t max_sam
 int dcx_motion_cost(const dcx_model* m, const float* qa, const float* qb, int64_t E, const dcx_motion_cost_opts* opt,
                     const float* margin, float weight, float* cost, float* grad_a, float* grad_b, int32_t* n_samples, void* work,
                     size_t work_bytes, void* stream) {
+    return dcx_motion_cost_ex(m, qa, qb, E, opt, margin, weight, cost, grad_a, grad_b, n_samples, work, work_bytes, 0, stream);
+}
+
+int dcx_motion_cost_ex(const dcx_model* m, const float* qa, const float* qb, int64_t E, const dcx_motion_cost_opts* opt,
+                       const float* margin, float weight, float* cost, float* grad_a, float* grad_b, int32_t* n_samples, void* work,
+                       size_t work_bytes, uint64_t wrap_mask, void* stream) {
     // every argument is checked before anything touches the device
     if (!m) return fail(DCX_ERR_INVALID, "model is NULL");
     if (!opt) return fail(DCX_ERR_INVALID, "motion cost options are NULL");
@@ -1803,6 +1819,8 @@ int dcx_motion_cost(const dcx_model* m, const float* qa, const float* qb, int64_
     if (opt->open_end != 0 && opt->open_end != 1) return fail(DCX_ERR_INVALID, "motion cost: open_end must be 0 or 1");
     if (opt->reserved[0] || opt->reserved[1] || opt->reserved[2] || opt->reserved[3])
         return fail(DCX_ERR_INVALID, "motion cost: reserved fields must be 0");
+    if (wrap_mask != 0 && m->fk.dof < 64 && (wrap_mask >> m->fk.dof) != 0)   // (mask 0, the plain call: the model is not read here)
+        return fail(DCX_ERR_INVALID, "motion cost: wrap_mask has a bit at or above dof");
     if (E > 0 && work_bytes < motion_cost_work(m, E, opt->max_samples).total)
         return fail(DCX_ERR_INVALID, "motion cost workspace is smaller than dcx_motion_cost_work_bytes");
     if (E > INT32_MAX) return fail(DCX_ERR_UNSUPPORTED, "motion cost: more than 2^31 - 1 edges");
@@ -1837,6 +1855,7 @@ int dcx_motion_cost(const dcx_model* m, const float* qa, const float* qb, int64_
     p.counters = g.ys > 1 ? (unsigned int*)(base + w.counters) : nullptr;
     p.n_counters = g.ys > 1 ? (int32_t)tiles_max : 0;
     p.open_end = opt->max_step > 0.f ? opt->open_end : 0;
+    p.wrap_mask = wrap_mask;
     hipError_t e = launch_motion_prep(p, st);
     if (e != hipSuccess) return fail_hip(e, "motion cost prep launch");
 
@@ -1892,6 +1911,7 @@ int dcx_motion_cost(const dcx_model* m, const float* qa, const float* qb, int64_
     a.weight = weight;
     a.res = opt->res;
     a.open_end = p.open_end;
+    a.wrap_mask = wrap_mask;
     auto skew_for = [&](bool score_only) {
         return (g.nw == 16 && (sa.s_chunk >= 24 || knobs().skew > 0)) ? skew_rule(m->Cc, score_only)
              : (g.nw == 8 && (sa.s_chunk >= 24 || knobs().skew8 > 0)) ? skew8_rule(score_only) : 0;
@@ -1928,6 +1948,7 @@ int dcx_motion_cost(const dcx_model* m, const float* qa, const float* qb, int64_
     r.res = opt->res;
     r.open_end = p.open_end;
     r.weight = weight;
+    r.wrap_mask = wrap_mask;
     e = launch_motion_cost_reduce(r, st);
     if (e != hipSuccess) return fail_hip(e, "motion cost reduction launch");
     return DCX_OK;

@@ -37,6 +37,7 @@ struct MotionCostArgs {
     float weight;
     int32_t res;              // > 0: the res rule; 0: the max_step rule
     int32_t open_end;         // max_step rule: the target qb is not a sample
+    uint64_t wrap_mask;       // bit j: coordinate j is an angle, the edge runs along its shortest arc (motion_kernel.h motion_coord)
 };
 
 // one entry point per compiled width (motion_cost_inst.hip); mode: MODE_GRAD_ROW (C == 1), MODE_SCORE / MODE_GRAD_UP (C > 1)
@@ -67,6 +68,7 @@ struct MotionReduceArgs {
     int64_t E;
     int32_t dof, res, open_end;
     float weight;
+    uint64_t wrap_mask;       // u = delta / L from the wrapped delta of the masked coordinates (motion_prep's L)
 };
 hipError_t launch_motion_cost_reduce(const MotionReduceArgs& r, hipStream_t stream);
 
@@ -156,12 +158,7 @@ __global__ __launch_bounds__(MAXT, sweep_min_waves(D, CC, KF)) void motion_cost_
         const int64_t e = sEdge[l];
         const int k = sK[l];
         const float qa = m.qa[e * dof + j], qb = m.qb[e * dof + j];
-        const float d = __fsub_rn(qb, qa);
-        float v;
-        if (m.res > 0) v = __fadd_rn(qa, __fmul_rn(d, __fdiv_rn((float)k, (float)m.res)));
-        else if (!m.open_end && k == sN[l] - 1) v = qb;   // the target closes the max_step rule's point set
-        else v = __fadd_rn(qa, __fmul_rn((float)k, __fmul_rn(d, m.frac[e])));
-        sQ[i] = v;
+        sQ[i] = motion_coord(qa, qb, k, m.res, !m.open_end && k == sN[l] - 1, m.frac + e, (m.wrap_mask >> j) & 1ull);
     }
     __syncthreads();
     {

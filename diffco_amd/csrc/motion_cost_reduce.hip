@@ -5,10 +5,13 @@
 //   max_step rule:  x_k = qa + k max_step u, u = (qb - qa) / L, for the interior samples (d x_k / d qb = t_k (I - u u^T),
 //                   t_k = k max_step / L, d x_k / d qa = I - d x_k / d qb); the target sample x = qb carries identity to grad_b:
 //                   grad_b = P T + g_last,  grad_a = G - P T,  G = sum g_k, T = sum t_k g_k over the interior, P = I - u u^T
+// With a wrap mask (include/dcx.h) the masked coordinates of qb - qa are the wrapped deltas, in u and in L; wrap2pi has slope 1,
+// so nothing else of the chain changes.
 // Sample counts are constants (as autograd through utils.dense_path holds them).  An edge over max_samples answers NaN.
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include "motion_cost_kernel.h"
+#include "wrap_device.h"
 
 namespace dcx {
 namespace {
@@ -51,10 +54,10 @@ __global__ __launch_bounds__(kReduceThreads) void motion_cost_reduce_kernel(cons
 #pragma clang fp contract(off)
             float l2 = 0.0f;
             for (int i = 0; i < dof; ++i) {
-                const float d = __fsub_rn(r.qb[e * dof + i], r.qa[e * dof + i]);
+                const float d = motion_delta(r.qa[e * dof + i], r.qb[e * dof + i], r.wrap_mask, i);
                 l2 = l2 + d * d;
             }
-            uj = __fsub_rn(r.qb[e * dof + j], r.qa[e * dof + j]) / sqrtf(l2);   // (correctly rounded, as motion_prep's L)
+            uj = motion_delta(r.qa[e * dof + j], r.qb[e * dof + j], r.wrap_mask, j) / sqrtf(l2);   // (correctly rounded, as motion_prep's L)
         }
     }
     if (r.res <= 0) {   // (kernel-uniform) P T = T - u (u . T): u . T summed over the edge's joints in order

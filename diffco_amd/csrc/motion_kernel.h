@@ -19,6 +19,9 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "score_kernel.h"
+#ifdef __HIPCC__
+#include "wrap_device.h"
+#endif
 
 namespace dcx {
 
@@ -34,6 +37,7 @@ struct MotionArgs {
     int64_t E;
     int32_t res;              // > 0: the res rule (qa + (k / res)(qb - qa), k < res); 0: the max_step rule
     int32_t early_exit;       // 0: every tile sweeps (developer knob motion_early_exit; the bound the benchmark compares against)
+    uint64_t wrap_mask;       // bit j: coordinate j is an angle, the edge runs along its shortest arc (0: straight, every bit as before)
 };
 
 // LDS the motion kernel needs behind the sweep's plan and the FK program: per lane its edge, sample index, count, and the
@@ -53,6 +57,7 @@ struct MotionPrepArgs {
     unsigned int* counters;   // split-launch arrival counters zeroed here (n_counters * kCounterStride words), or null
     int32_t n_counters;
     int32_t open_end;         // max_step rule: 1 drops the target qb from the samples (dcx_motion_cost; dcx_check_motions: 0)
+    uint64_t wrap_mask;       // the edge's length is taken from the wrapped delta of the masked coordinates
 };
 hipError_t launch_motion_prep(const MotionPrepArgs& p, hipStream_t stream);
 
@@ -68,6 +73,30 @@ DCX_DECLARE_MOTION(96)
 #undef DCX_DECLARE_MOTION
 
 #ifdef __HIPCC__
+// Coordinate j of sample k of the edge qa -> qb (one joint's values): the sQ prologue of both motion kernels.
+//   res > 0:  qa + d (k / res);   res == 0:  qa + k (d frac), the target (`target`: the closed rule's last sample) qb itself.
+// Unmasked coordinates: d = qb - qa, the expression as it always stood (the compiler contracts its last product and sum).
+// Masked coordinates (include/dcx.h): d = wrap2pi(qb - qa), product and sum rounded one by one, then wrap2pi - a point one
+// ulp to the other side of the seam is 2 pi away in a raw feature, so this path leaves the compiler no choice.
+__device__ __forceinline__ float motion_coord(float qa, float qb, int k, int res, bool target, const float* frac_e, bool masked) {
+    if (masked) {
+#pragma clang fp contract(off)
+        const float d = wrap2pi_f32(__fsub_rn(qb, qa));
+        if (res > 0) {
+            const float p = d * __fdiv_rn((float)k, (float)res);
+            return wrap2pi_f32(qa + p);
+        }
+        if (target) return qb;
+        const float s = d * *frac_e;
+        const float p = (float)k * s;
+        return wrap2pi_f32(qa + p);
+    }
+    const float d = __fsub_rn(qb, qa);
+    if (res > 0) return __fadd_rn(qa, __fmul_rn(d, __fdiv_rn((float)k, (float)res)));
+    if (target) return qb;   // the target closes the max_step rule's point set
+    return __fadd_rn(qa, __fmul_rn((float)k, __fmul_rn(d, *frac_e)));
+}
+
 // one configuration per lane: the score-only sweep of score_kernel (its prologue, with the rows of sQ interpolated from the
 // edges instead of read from q), then the compare against the margins.  LDS: lds_plan(...).total + prog_floats (the FK
 // program) rounded to 4, then kMotionLdsFloats (mo_off below).
@@ -156,12 +185,7 @@ __global__ __launch_bounds__(MAXT, sweep_min_waves(D, CC, KF)) void motion_kerne
                 const int64_t e = sEdge[l];
                 const int k = sK[l];
                 const float qa = m.qa[e * dof + j], qb = m.qb[e * dof + j];
-                const float d = __fsub_rn(qb, qa);
-                float v;
-                if (m.res > 0) v = __fadd_rn(qa, __fmul_rn(d, __fdiv_rn((float)k, (float)m.res)));
-                else if (k == sN[l] - 1) v = qb;   // the target closes the max_step rule's point set
-                else v = __fadd_rn(qa, __fmul_rn((float)k, __fmul_rn(d, m.frac[e])));
-                sQ[i] = v;
+                sQ[i] = motion_coord(qa, qb, k, m.res, k == sN[l] - 1, m.frac + e, (m.wrap_mask >> j) & 1ull);
             }
             __syncthreads();
             const int lane = threadIdx.x & 63;

@@ -5,6 +5,7 @@
 // (The first form did both in ONE workgroup, each thread a contiguous run of edges: 420 us of a 2.9 ms call at E = 65536.)
 #include <hip/hip_runtime.h>
 #include "motion_kernel.h"
+#include "wrap_device.h"
 
 namespace dcx {
 namespace {
@@ -22,10 +23,10 @@ __global__ __launch_bounds__(kCountThreads) void motion_count_kernel(const Motio
         // dense_path's arithmetic (utils.py): L = |qb - qa|, n = ceil(L * (1 / max_step)) + 1 points, step fraction (1 / L) * max_step.
         // Each operation rounded on its own, with contraction off: -ffp-contract=fast fuses d * d + l2 into one FMA per joint
         // (__fmul_rn / __fadd_rn included: they are plain * and + in the HIP headers) - a different l2, and a count off by one
-        // where L / max_step lies near an integer.
+        // where L / max_step lies near an integer.  Masked coordinates enter with their wrapped delta (wrap_device.h).
         float l2 = 0.0f;
         for (int j = 0; j < p.dof; ++j) {
-            const float d = __fsub_rn(p.qb[e * p.dof + j], p.qa[e * p.dof + j]);
+            const float d = motion_delta(p.qa[e * p.dof + j], p.qb[e * p.dof + j], p.wrap_mask, j);
             l2 = l2 + d * d;
         }
         // sqrtf, not __fsqrt_rn: without OCML_BASIC_ROUNDED_OPERATIONS the latter is the native v_sqrt_f32 (1 ulp); sqrtf is

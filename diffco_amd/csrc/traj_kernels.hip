@@ -11,6 +11,7 @@
 #include <cmath>
 
 #include "dcx_internal.h"
+#include "wrap_device.h"
 
 namespace dcx {
 namespace {
@@ -221,13 +222,6 @@ hipError_t launch_traj_adam_step(const FkProg* fk_dev, const dcx_fk_desc& fk, co
 // (no pass afterwards): a three-step escape is six launches.
 namespace {
 
-__device__ __forceinline__ float escape_wrap2pi(float q) {  // utils.py:51-52 on fp32 tensors: (pi + q) % (2 pi) - pi, Python's %
-    const float pi = 3.14159265358979323846f, two_pi = 6.28318530717958647692f;
-    float r = fmodf(pi + q, two_pi);
-    if (r != 0.f && r < 0.f) r += two_pi;
-    return r - pi;
-}
-
 // joint form, before the update: ONE workgroup sums score - margin over the whole batch (escape.py:26) and takes the loop's
 // decision, so that the update launch only reads it
 // the whole batch's excess (escape.py:26), summed in double by one workgroup of 1024 lanes; every lane returns the sum
@@ -273,7 +267,7 @@ __device__ __forceinline__ void escape_row_step(const EscapeArgs& a, int64_t b, 
         v = fmaf(a.beta2, v, (1.f - a.beta2) * g * g);
         const float denom = sqrtf(v) / a.bias2_sqrt + a.eps;
         float qn = traj_adam_q(q[k], a.lr, a.bias1, m, denom);
-        if ((a.wrap_mask >> k) & 1ull) qn = escape_wrap2pi(qn);
+        if ((a.wrap_mask >> k) & 1ull) qn = wrap2pi_f32(qn);
         a.adam_m[b * dof + k] = m;
         a.adam_v[b * dof + k] = v;
         q[k] = qn;
@@ -350,7 +344,7 @@ __global__ __launch_bounds__(64) void escape_joint_wave_kernel(const EscapeArgs 
     v = fmaf(a.beta2, v, (1.f - a.beta2) * g * g);
     const float denom = sqrtf(v) / a.bias2_sqrt + a.eps;
     float qn = traj_adam_q(q, a.lr, a.bias1, m, denom);
-    if ((a.wrap_mask >> (l % a.dof)) & 1ull) qn = escape_wrap2pi(qn);
+    if ((a.wrap_mask >> (l % a.dof)) & 1ull) qn = wrap2pi_f32(qn);
     a.adam_m[l] = m;
     a.adam_v[l] = v;
     a.q[l] = qn;

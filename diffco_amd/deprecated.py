@@ -202,15 +202,18 @@ class DiffCo(CollisionChecker):
             s = s.reshape(-1)
         return s
 
-    def check_motions(self, starts, targets, res=None, max_step=None, margin=0., return_first=False, max_samples=None):
+    def check_motions(self, starts, targets, res=None, max_step=None, margin=0., return_first=False, max_samples=None, wrap=None):
         """motions starts[e] -> targets[e] under the `rbf_score` state: a sample collides iff rbf_score_c - margin_c > 0 for
-        some class (`margin`: a number or one per class).  Exactly one of `res` / `max_step`.  bool [E] (+ first index)."""
+        some class (`margin`: a number or one per class).  Exactly one of `res` / `max_step`.  bool [E] (+ first index).
+        `wrap` (None, True: the `fkine` owner's circular coordinates, an int bitmask or one bool per coordinate): those
+        coordinates are angles and the edge runs along their shortest arc."""
         from ._perceptron import check_motions, motion_answer
         if self.fkine is not None:
             args = (self._rbf_fused, self.fkine, self.rbf_kernel, self.support_fkine, self.rbf_nodes)
         else:
             args = (self._rbf_fused, None, self.rbf_kernel, self.support_points, self.rbf_nodes)
-        first, _ = check_motions(self, *args, starts, targets, res=res, max_step=max_step, margin=margin, max_samples=max_samples)
+        first, _ = check_motions(self, *args, starts, targets, res=res, max_step=max_step, margin=margin, max_samples=max_samples,
+                                 wrap=wrap)
         return motion_answer(first, return_first)
 
     def _rbf_args(self):
@@ -218,18 +221,19 @@ class DiffCo(CollisionChecker):
             return (self._rbf_fused, self.fkine, self.rbf_kernel, self.support_fkine, self.rbf_nodes)
         return (self._rbf_fused, None, self.rbf_kernel, self.support_points, self.rbf_nodes)
 
-    def motion_cost(self, starts, targets, res=None, max_step=None, margin=0., weight=1., open_end=False, max_samples=None):
+    def motion_cost(self, starts, targets, res=None, max_step=None, margin=0., weight=1., open_end=False, max_samples=None,
+                    wrap=None):
         """[E] collision costs of the motions starts[e] -> targets[e] under the `rbf_score` state: weight * sum over the
         samples of sum_c max(0, rbf_score_c - margin_c) (`margin`: a number or one per class), differentiable with respect to
-        starts and targets.  Exactly one of `res` / `max_step` (check_motions' samples; open_end drops the target)."""
+        starts and targets.  Exactly one of `res` / `max_step` (check_motions' samples and `wrap`; open_end drops the target)."""
         from ._perceptron import motion_cost
         return motion_cost(self, *self._rbf_args(), starts, targets, res=res, max_step=max_step, margin=margin, weight=weight,
-                           open_end=open_end, max_samples=max_samples)
+                           open_end=open_end, max_samples=max_samples, wrap=wrap)
 
-    def path_cost(self, paths, max_step, margin=0., weight=1., max_samples=None):
+    def path_cost(self, paths, max_step, margin=0., weight=1., max_samples=None, wrap=None):
         """[T] collision costs of paths [T, W, dof] over utils.dense_path(p, max_step)'s points, differentiable w.r.t. every waypoint"""
         from ._perceptron import path_cost
-        return path_cost(self, *self._rbf_args(), paths, max_step, margin=margin, weight=weight, max_samples=max_samples)
+        return path_cost(self, *self._rbf_args(), paths, max_step, margin=margin, weight=weight, max_samples=max_samples, wrap=wrap)
 
     def poly_score(self, point):
         if point.ndim == 1:

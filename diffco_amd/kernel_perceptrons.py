@@ -299,29 +299,32 @@ class DiffCo(Perceptron):
             s = s.reshape(())
         return s
 
-    def check_motions(self, starts, targets, res=None, max_step=None, return_first=False, max_samples=None):
+    def check_motions(self, starts, targets, res=None, max_step=None, return_first=False, max_samples=None, wrap=None):
         """is the straight motion starts[e] -> targets[e] in collision (`is_collision`: score > 0 at one of its samples)?
         Exactly one rule: `res` (the points of `line_predict`) or `max_step` (those of utils.dense_path).  bool [E]; with
-        return_first also the first colliding sample index (-1 = free).  One fused launch (plus a small one) for all edges."""
+        return_first also the first colliding sample index (-1 = free).  One fused launch (plus a small one) for all edges.
+        `wrap` (None, True: the robot's own circular coordinates, an int bitmask or one bool per coordinate): those
+        coordinates are angles and the edge runs along their shortest arc."""
         from ._perceptron import check_motions, motion_answer
         first, _ = check_motions(self, self._score_fused, self.transform, self.kernel_func, self.support_transformed, self.gains,
-                                 starts, targets, res=res, max_step=max_step, max_samples=max_samples)
+                                 starts, targets, res=res, max_step=max_step, max_samples=max_samples, wrap=wrap)
         return motion_answer(first, return_first)
 
-    def motion_cost(self, starts, targets, res=None, max_step=None, margin=0., weight=1., open_end=False, max_samples=None):
+    def motion_cost(self, starts, targets, res=None, max_step=None, margin=0., weight=1., open_end=False, max_samples=None,
+                    wrap=None):
         """[E] collision costs of the motions starts[e] -> targets[e]: weight * sum over the samples of max(0, score - margin),
         differentiable with respect to starts and targets.  Exactly one rule, as check_motions (open_end drops the target
-        sample under max_step).  One fused call (dcx_motion_cost) for all edges."""
+        sample under max_step; `wrap` as there).  One fused call (dcx_motion_cost) for all edges."""
         from ._perceptron import motion_cost
         return motion_cost(self, self._score_fused, self.transform, self.kernel_func, self.support_transformed, self.gains,
                            starts, targets, res=res, max_step=max_step, margin=margin, weight=weight, open_end=open_end,
-                           max_samples=max_samples)
+                           max_samples=max_samples, wrap=wrap)
 
-    def path_cost(self, paths, max_step, margin=0., weight=1., max_samples=None):
+    def path_cost(self, paths, max_step, margin=0., weight=1., max_samples=None, wrap=None):
         """[T] collision costs of paths [T, W, dof] over utils.dense_path(p, max_step)'s points, differentiable w.r.t. every waypoint"""
         from ._perceptron import path_cost
         return path_cost(self, self._score_fused, self.transform, self.kernel_func, self.support_transformed, self.gains, paths,
-                         max_step, margin=margin, weight=weight, max_samples=max_samples)
+                         max_step, margin=margin, weight=weight, max_samples=max_samples, wrap=wrap)
 
     def poly_score(self, point=None, transformed_point=None):
         """sum_j K_rbf(T(q), support_j) rbf_nodes_j  ->  [N, 1]; `transformed_point` skips the FK."""

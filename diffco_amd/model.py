@@ -25,6 +25,7 @@ class Model:
     dof = None
     limits = None
     _desc = None
+    wrap_mask = 0   # bit j: q_j is an angle on the circle (the motion calls' wrap=True); the DH arms' joints have limits: none
 
     def fk_desc(self):
         """plain-data description of this robot's transform (ctypes dcx_fk_desc)"""
@@ -68,6 +69,7 @@ class RevolutePlanarRobot(Model):
         self.link_length = torch.FloatTensor(lengths)
         self.limits = torch.FloatTensor(bounds)
         self.collision_objs = None
+        self.wrap_mask = (1 << n) - 1   # every joint, as wrap()
         self._desc = fd.planar_desc(lengths)
 
 
@@ -81,6 +83,7 @@ class RigidPlanarBody(Model):
             [[-10, 10], [-10, 10], [-pi, pi]])
         self.keypoints = torch.FloatTensor([p[1] for p in parts]).T  # 2 x M, as in the reference
         self.collision_objs = None
+        self.wrap_mask = 0b100   # theta, as wrap()
         self._desc = fd.keypoint_desc(self.keypoints.T.numpy(), 2)
 
     def wrap(self, q):
@@ -104,6 +107,7 @@ class RigidBody(Model):
             kp = kp.T
         self.keypoints = kp  # 3 x M
         self.collision_objs = []
+        self.wrap_mask = 0b111000   # roll, pitch, yaw, as wrap()
         self._desc = fd.keypoint_desc(self.keypoints.T.numpy(), 3)
 
     def wrap(self, q):

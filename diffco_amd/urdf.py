@@ -157,7 +157,8 @@ def compile_trees(trees, base_transforms=None, coord_major=True):
     info = dict(dof=q0, joint_names=[(i, n) for i, inf in enumerate(infos) for n in inf["joint_names"]],
                 joint_limits=np.concatenate([inf["joint_limits"] for inf in infos], axis=0),
                 feature_links=[(i, n) for i, inf in enumerate(infos) for n in inf["feature_links"]],
-                n_chains=len(chains), dofs=[inf["dof"] for inf in infos])
+                n_chains=len(chains), dofs=[inf["dof"] for inf in infos],
+                continuous=[c for inf in infos for c in inf["continuous"]])
     return fd.tree_desc(q0, chains, points, coord_major=coord_major), info
 
 
@@ -258,7 +259,7 @@ def plan_tree(tree: Tree, base_transform=None):
     assert all(p is not None for p in points)
     info = dict(dof=len(controlled), joint_names=[jt.name for jt in controlled],
                 controlled_links=[jt.child for jt in controlled], joint_limits=limits,
-                feature_links=feature_links, n_chains=len(chains))
+                feature_links=feature_links, n_chains=len(chains), continuous=[jt.type == "continuous" for jt in controlled])
     return chains, points, info
 
 
@@ -287,6 +288,8 @@ class URDFRobotFK:
         self.limits = self.joint_limits  # the name diffco_amd.model robots use
         self.unique_position_link_names = info["feature_links"]
         self.n_chains = info["n_chains"]
+        # bit j: controlled joint j is `continuous`, an angle on the circle (the motion calls' wrap=True)
+        self.wrap_mask = sum(1 << j for j, c in enumerate(info["continuous"]) if c)
         self.fkine_backup = None
 
     def fk_desc(self):

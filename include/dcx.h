@@ -420,6 +420,32 @@ int dcx_motion_cost(const dcx_model* m, const float* qa, const float* qb, int64_
                     const float* margin, float weight, float* cost, float* grad_a, float* grad_b, int32_t* n_samples, void* work,
                     size_t work_bytes, void* stream);
 
+/* ---- motions along the shortest arc of circular coordinates (added under DCX_VERSION 109) ---------------- */
+/* dcx_check_motions_ex / dcx_motion_cost_ex: the two calls above with a per-coordinate wrap mask.  Bit j of wrap_mask set:
+ * coordinate j is an angle on the circle and the edge runs along its shortest arc (a revolute planar arm's joints, the heading
+ * of an SE(2) body, the Euler angles of an SE(3) body, a URDF `continuous` joint).  wrap_mask = 0 is the plain call, bit for
+ * bit; dcx_check_motions / dcx_motion_cost forward with 0.  Everything else - the opts structs and their reserved rules, the
+ * workspace sizes, the launches, no allocation / synchronisation / read-back, capturable - is as above.
+ * All arithmetic fp32, each operation rounded on its own (no fused multiply-add on a masked coordinate):
+ *   wrap2pi(x) = fmodf(pi + x, 2 pi), + 2 pi if that is negative, - pi; pi = 3.14159265358979323846f, 2 pi =
+ *                6.28318530717958647692f (utils.wrap2pi, Python's %: the escape loop's wrap, one definition for both)
+ *   delta:       d_j = wrap2pi(qb_j - qa_j) for masked j (the subtraction rounded first), qb_j - qa_j otherwise.  Masked
+ *                deltas lie in [-pi, pi): a difference of exactly pi goes the negative way, as utils.anglin's
+ *   res rule:    x_k,j = wrap2pi(qa_j + d_j * (k / res)) for masked j, k = 0 .. res - 1: utils.anglin(qa, qb, res,
+ *                endpoint=False).  Unmasked j: the plain call's points
+ *   max_step:    L = |d|_2 accumulated over j = 0 .. dof - 1 as the plain call accumulates it; n and frac = (1 / L) * max_step
+ *                from L as above; x_k,j = wrap2pi(qa_j + k * (d_j * frac)) for masked j and the interior samples; the target
+ *                sample is qb as given, not wrapped again; open_end as above.  L = 0 after wrapping (qb = qa + 2 pi): the one
+ *                sample qb, or none with open_end and a cost of 0
+ *   gradients:   wrap2pi has slope 1: the chain above with u = d / L from the wrapped delta; sample counts stay constants
+ * Argument errors (DCX_ERR_INVALID, before any device work): those of the plain calls, and a wrap_mask bit at or above dof. */
+int dcx_check_motions_ex(const dcx_model* m, const float* qa, const float* qb, int64_t E, const dcx_motion_opts* opt,
+                         const float* margin, int32_t* first_hit, int32_t* n_samples, void* work, size_t work_bytes,
+                         uint64_t wrap_mask, void* stream);
+int dcx_motion_cost_ex(const dcx_model* m, const float* qa, const float* qb, int64_t E, const dcx_motion_cost_opts* opt,
+                       const float* margin, float weight, float* cost, float* grad_a, float* grad_b, int32_t* n_samples, void* work,
+                       size_t work_bytes, uint64_t wrap_mask, void* stream);
+
 /* ---- kernel-perceptron trainer (producer of the path's state) ----------------------- */
 /* DiffCo.train_perceptron kernel_perceptrons.py:98-137 and MultiDiffCo.train_perceptron
  * deprecated/MultiDiffCo.py:50-83 as one persistent launch: worst-margin search, lazily filled kernel rows,

@@ -4,9 +4,10 @@ dcx_score on the same points already materialised (the bound without early exit)
 all free (a margin above every score) and cluttered (a margin at the 20th percentile of the sample scores: most edges hit
 within their first quarter).  check_motions runs with max_samples = 64 (the edges' own bound), with the default bound
 (max_samples=None: the longest edge's count, one read-back) and with a loose bound (10000), and with the early exit switched
-off (knob motion_early_exit = 0).
+off (knob motion_early_exit = 0).  --wrap: every joint masked as an angle on the circle (the edges are shorter than pi, so the
+sample sets are the same and the difference to a plain run is the wrapped interpolation alone).
 
-    python tools/motion_bench.py [--edges 4096 65536] [--iters 50]
+    python tools/motion_bench.py [--edges 4096 65536] [--iters 50] [--wrap]
 
 One JSON line per (E, set) on stdout: median microseconds per call (CUDA events around each call on an idle stream).
 """
@@ -41,6 +42,7 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--edges", type=int, nargs="+", default=[4096, 65536])
     ap.add_argument("--iters", type=int, default=50)
+    ap.add_argument("--wrap", action="store_true", help="all joints masked: dcx_check_motions_ex along the shortest arc")
     args = ap.parse_args()
     import bench
     from diffco_amd import _lib
@@ -50,6 +52,8 @@ def main():
     w = bench.make_workload("headline", 1024, dev)
     m, lo, hi = w["model"], w["lo"].to(dev), w["hi"].to(dev)
     step = 0.05
+    wrap = (1 << 7) - 1 if args.wrap else None
+    kw = dict(wrap=wrap) if args.wrap else {}   # (a plain run passes nothing new: the call as it always was)
     for E in args.edges:
         g = torch.Generator(device=dev).manual_seed(E)
         qa = torch.rand((E, 7), generator=g, device=dev) * (hi - lo) + lo
@@ -57,7 +61,7 @@ def main():
         dirn = dirn / dirn.norm(dim=1, keepdim=True)
         n_want = torch.randint(8, 65, (E, 1), generator=g, device=dev).float()
         qb = qa + dirn * step * (n_want - 1.5)        # ceil(L / step) + 1 = n_want samples
-        first, n = m.check_motions(qa, qb, max_step=step, max_samples=64)
+        first, n = m.check_motions(qa, qb, max_step=step, max_samples=64, **kw)
         assert int((first == -2).sum()) == 0
         # the materialised points (built once, outside the timing of the bound)
         d = qb - qa
@@ -66,14 +70,18 @@ def main():
         edge = torch.repeat_interleave(torch.arange(E, device=dev), nn)
         k = torch.arange(len(edge), device=dev) - (torch.cumsum(nn, 0) - nn)[edge]
         pts = (qa[edge] + k.float()[:, None] * (d[edge] * (step / L)[edge, None])).contiguous()
+        if args.wrap:
+            from diffco_amd.utils import wrap2pi
+            pts = wrap2pi(pts).contiguous()
         scores = m.score_raw(pts)[:, 0]
         total = int(nn.sum())
         for label, margin in (("free", float(scores.max()) + 1.0), ("cluttered", float(torch.quantile(scores[:1 << 20], 0.2)))):
-            f, _ = m.check_motions(qa, qb, max_step=step, margin=margin, max_samples=64)
+            f, _ = m.check_motions(qa, qb, max_step=step, margin=margin, max_samples=64, **kw)
             hit = f >= 0
             swept_hint = float(((f.float() + 1) / n.float()).where(hit, torch.ones_like(f, dtype=torch.float32)).mean())
-            res = dict(E=E, set=label, samples=total, hit_edges=int(hit.sum()), mean_first_frac=round(swept_hint, 3))
-            call = lambda ms: (lambda: m.check_motions(qa, qb, max_step=step, margin=margin, max_samples=ms))  # noqa: E731
+            res = dict(E=E, set=label, wrap=bool(args.wrap), samples=total, hit_edges=int(hit.sum()),
+                       mean_first_frac=round(swept_hint, 3))
+            call = lambda ms: (lambda: m.check_motions(qa, qb, max_step=step, margin=margin, max_samples=ms, **kw))  # noqa: E731
             # early exit on / off, interleaved three times (median of the three medians each)
             on, off = [], []
             for _ in range(3):
@@ -88,8 +96,9 @@ def main():
             res["check_motions_bound_10000_us"] = timed(call(10000), max(3, args.iters // 5))
             res["dcx_score_materialised_us"] = timed(lambda: m.score_raw(pts), args.iters)
             res["host_composition_us"] = timed(lambda: host_motions(lambda p: m.score_raw(p), qa, qb, max_step=step,
-                                                                    margin=margin, max_samples=64), max(5, args.iters // 5))
-            hf, _ = host_motions(lambda p: m.score_raw(p), qa, qb, max_step=step, margin=margin, max_samples=64)
+                                                                    margin=margin, max_samples=64, wrap=wrap or 0),
+                                               max(5, args.iters // 5))
+            hf, _ = host_motions(lambda p: m.score_raw(p), qa, qb, max_step=step, margin=margin, max_samples=64, wrap=wrap or 0)
             res["host_agrees"] = float((hf == f).float().mean())
             res["ratio_vs_score"] = round(res["check_motions_us"] / res["dcx_score_materialised_us"], 3)
             res["speedup_vs_host"] = round(res["host_composition_us"] / res["check_motions_us"], 1)

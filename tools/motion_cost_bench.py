@@ -5,8 +5,10 @@ free (a margin above every score) or cluttered (a margin at the 20th percentile 
   (b) the host composition (points built differentiably in torch, scored through autograd, index_add per edge, backward),
   (c) check_motions on the same edges and margins.
 Every timing is the median of interleaved rounds (each a median over --iters calls, CUDA events on an idle stream).
+--wrap: every joint masked as an angle on the circle (the edges are shorter than pi: the same sample sets, so the difference to
+a plain run is the wrapped interpolation and the wrapped direction alone).
 
-    python tools/motion_cost_bench.py [--edges 4096 65536] [--iters 30] [--models headline cfg3]
+    python tools/motion_cost_bench.py [--edges 4096 65536] [--iters 30] [--models headline cfg3] [--wrap]
 
 One JSON line per (model, E, set) on stdout.
 """
@@ -43,6 +45,7 @@ def main():
     ap.add_argument("--iters", type=int, default=30)
     ap.add_argument("--rounds", type=int, default=3)
     ap.add_argument("--models", nargs="+", default=["headline", "cfg3"])
+    ap.add_argument("--wrap", action="store_true", help="all joints masked: dcx_motion_cost_ex along the shortest arc")
     args = ap.parse_args()
     import bench
     from diffco_amd import _lib
@@ -53,6 +56,8 @@ def main():
     for name in args.models:
         w = bench.make_workload(name, 1024, dev)
         m, lo, hi = w["model"], w["lo"].to(dev), w["hi"].to(dev)
+        wrap = (1 << m.dof) - 1 if args.wrap else None
+        kw = dict(wrap=wrap) if args.wrap else {}   # (a plain run passes nothing new: the call as it always was)
         for E in args.edges:
             g = torch.Generator(device=dev).manual_seed(E)
             qa = torch.rand((E, m.dof), generator=g, device=dev) * (hi - lo) + lo
@@ -67,26 +72,31 @@ def main():
             k = torch.arange(len(edge), device=dev) - (torch.cumsum(nn, 0) - nn)[edge]
             pts = (qa[edge] + k.float()[:, None] * (d[edge] * (step / L)[edge, None])).contiguous()
             last = k == nn[edge] - 1
+            if args.wrap:
+                from diffco_amd.utils import wrap2pi
+                pts = wrap2pi(pts)
             pts = torch.where(last[:, None], qb[edge], pts).contiguous()
             scores = m.score_raw(pts)
             total = int(nn.sum())
             free = (scores.max(dim=0).values + 1.0).tolist()
             clut = torch.quantile(scores[:1 << 20], 0.2, dim=0).tolist()
             for label, margin in (("free", free), ("cluttered", clut)):
-                cost, ga, gb, n = m.motion_cost_raw(qa, qb, max_step=step, margin=margin, max_samples=64)
+                cost, ga, gb, n = m.motion_cost_raw(qa, qb, max_step=step, margin=margin, max_samples=64, **kw)
                 assert int(torch.isnan(cost).sum()) == 0
-                res = dict(model=name, C=m.C, E=E, set=label, samples=total, costly_edges=int((cost > 0).sum()))
+                res = dict(model=name, C=m.C, E=E, set=label, wrap=bool(args.wrap), samples=total,
+                           costly_edges=int((cost > 0).sum()))
                 qa_g, qb_g = qa.clone().requires_grad_(True), qb.clone().requires_grad_(True)
                 mg_t = torch.tensor(margin, device=dev)
 
                 def host():
-                    c = host_motion_cost(lambda p: m.score(p), qa_g, qb_g, max_step=step, margin=mg_t, max_samples=64)
+                    c = host_motion_cost(lambda p: m.score(p), qa_g, qb_g, max_step=step, margin=mg_t, max_samples=64,
+                                         wrap=wrap or 0)
                     return torch.autograd.grad(c.sum(), (qa_g, qb_g))
 
                 calls = {
-                    "motion_cost_us": lambda: m.motion_cost_raw(qa, qb, max_step=step, margin=margin, max_samples=64),
+                    "motion_cost_us": lambda: m.motion_cost_raw(qa, qb, max_step=step, margin=margin, max_samples=64, **kw),
                     "hinge_grad_materialised_us": lambda: m.score_hinge_grad_raw(pts, margin, 1.0),
-                    "check_motions_us": lambda: m.check_motions(qa, qb, max_step=step, margin=margin, max_samples=64),
+                    "check_motions_us": lambda: m.check_motions(qa, qb, max_step=step, margin=margin, max_samples=64, **kw),
                 }
                 rounds = {k: [] for k in list(calls) + ["host_composition_us"]}
                 for _ in range(args.rounds):   # interleaved
@@ -95,7 +105,7 @@ def main():
                     rounds["host_composition_us"].append(timed(host, max(3, args.iters // 5)))
                 for k, v in rounds.items():
                     res[k] = round(sorted(v)[len(v) // 2], 1)
-                hc = host_motion_cost(lambda p: m.score(p), qa, qb, max_step=step, margin=mg_t, max_samples=64)
+                hc = host_motion_cost(lambda p: m.score(p), qa, qb, max_step=step, margin=mg_t, max_samples=64, wrap=wrap or 0)
                 res["host_cost_max_rel_diff"] = float((hc - cost).abs().max() / cost.abs().max().clamp(min=1e-30))
                 res["ratio_vs_hinge_grad"] = round(res["motion_cost_us"] / res["hinge_grad_materialised_us"], 3)
                 res["ratio_vs_check_motions"] = round(res["motion_cost_us"] / res["check_motions_us"], 3)
