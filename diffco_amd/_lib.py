@@ -69,6 +69,10 @@ SYMBOLS = {
                                        C.c_uint64, C.c_void_p]),
     "dcx_motion_cost_ex": (C.c_int, [C.c_void_p, _c_fp, _c_fp, C.c_int64, C.c_void_p, _c_fp, C.c_float, _c_fp, _c_fp, _c_fp, _c_fp,
                                      C.c_void_p, C.c_size_t, C.c_uint64, C.c_void_p]),
+    # worst-sample motion queries: peak score per edge, where, against which class, and its endpoint gradients
+    "dcx_motion_worst_work_bytes": (C.c_size_t, [C.c_void_p, C.c_int64]),
+    "dcx_motion_worst": (C.c_int, [C.c_void_p, _c_fp, _c_fp, C.c_int64, C.c_void_p, _c_fp, _c_fp, _c_fp, _c_fp, _c_fp, _c_fp, _c_fp,
+                                   C.c_void_p, C.c_size_t, C.c_uint64, C.c_void_p]),
     "dcx_solve_work_bytes": (C.c_size_t, [C.c_int64, C.c_int64]),
     "dcx_solve": (C.c_int, [C.c_int, _c_fp, _c_fp, C.c_int64, C.c_int64, _c_fp, C.c_void_p, C.c_size_t, C.c_void_p, C.c_int32,
                             C.c_void_p]),

@@ -292,6 +292,30 @@ def compose_path_cost(edge_cost, paths, dof):
     return cost
 
 
+def compose_path_worst(edge_worst, paths, dof):
+    """(worst [T], segment [T], sample [T]) of paths [T, W, dof] from an edge callable edge_worst(qa, qb) -> (worst, idx, cls)
+    [T * (W - 1)] under the closed max_step rule: the maximum over the path's segments, the first one in (segment, sample)
+    order.  worst is a gather of the edge values, so it is differentiable wherever they are.  W == 1: the zero-length edge
+    p[0] -> p[0] (its one sample is p[0])."""
+    paths = torch.as_tensor(paths)
+    T, W = paths.shape[0], paths.shape[1]
+    p = paths.reshape(T, W, dof)
+    if W == 1:
+        a, b = p[:, 0], p[:, 0]
+    else:
+        a, b = p[:, :-1].reshape(-1, dof), p[:, 1:].reshape(-1, dof)
+    worst, idx, _ = edge_worst(a, b)
+    S = max(W - 1, 1)
+    worst, idx = worst.reshape(T, S), idx.reshape(T, S)
+    if T == 0:
+        return worst.new_zeros(0), idx.new_zeros(0, dtype=torch.int64), idx.new_zeros(0, dtype=torch.int64)
+    # the first maximum: torch.max's index on ties is unspecified, so take the smallest segment that attains the value
+    top = worst.detach().max(dim=1, keepdim=True).values
+    at = (worst.detach() == top) | (torch.isnan(worst.detach()) & torch.isnan(top))
+    seg = at.int().argmax(dim=1)
+    return worst.gather(1, seg[:, None])[:, 0], seg, idx.gather(1, seg[:, None])[:, 0].long()
+
+
 class ScoreModel:
     """Owns one ``dcx_model`` (device copy of support rows + FK parameters).  `update()` refills it in place with new
     supports / weights (same transform, kernel and class count): no reallocation while they fit `capacity`."""
@@ -537,6 +561,57 @@ class ScoreModel:
         kw = dict(max_step=max_step, margin=margin, weight=weight, max_samples=max_samples, wrap=wrap)
         return compose_path_cost(lambda a, b, open_end: self.motion_cost(a, b, open_end=open_end, **kw), paths, self.dof)
 
+    def motion_worst_raw(self, qa, qb, res=None, max_step=None, margin=0., max_samples=None, wrap=None, grad=False):
+        """worst-sample motion queries (dcx_motion_worst): for E straight joint-space motions qa[e] -> qb[e] ([E, dof] each) on
+        check_motions' sample set, (worst [E] fp32, idx [E] int32, cls [E] int32, n_samples [E] int32[, grad_a, grad_b
+        [E, dof] fp32]) device tensors: worst[e] = max over the edge's samples of max_c (score_c - margin_c), the smallest
+        sample index that attains it, the smallest class that attains it there, and with grad=True the gradient of worst[e]
+        with respect to qa[e] and qb[e] through that sample.  Edges over `max_samples`: NaN / -2 / -1, NaN gradient rows.
+        `res`, `max_step`, `margin`, `max_samples` (None: the bound of motion_bound; a given bound reads nothing back and
+        the call can be captured) and `wrap` as check_motions."""
+        if (res is None) == (max_step is None):
+            raise ValueError("motion_worst takes exactly one of res and max_step")
+        mask = wrap_mask(wrap, self.dof)
+        qa32 = _f32(torch.as_tensor(qa).reshape(-1, self.dof), self.dev)
+        qb32 = _f32(torch.as_tensor(qb).reshape(-1, self.dof), self.dev)
+        if qa32.shape != qb32.shape:
+            raise ValueError(f"{len(qa32)} start and {len(qb32)} target configurations")
+        E = len(qa32)
+        if max_samples is None:
+            max_samples = int(res) if res is not None else motion_bound(qa32, qb32, max_step, wrap=mask)
+        opt = _lib.MotionOpts(int(res) if res is not None else 0, float(max_step) if max_step is not None else 0.0, int(max_samples), 0)
+        mg = self._motion_margin(margin)
+        worst = torch.empty(E, device=self.dev, dtype=torch.float32)
+        idx = torch.empty(E, device=self.dev, dtype=torch.int32)
+        cls = torch.empty(E, device=self.dev, dtype=torch.int32)
+        n = torch.empty(E, device=self.dev, dtype=torch.int32)
+        ga = torch.empty((E, self.dof), device=self.dev, dtype=torch.float32) if grad else None
+        gb = torch.empty((E, self.dof), device=self.dev, dtype=torch.float32) if grad else None
+        nbytes = self._lib.dcx_motion_worst_work_bytes(self._h, E)
+        work = torch.empty(max(int(nbytes), 1), device=self.dev, dtype=torch.uint8)
+        with _on_device(self.dev):
+            _lib.check(self._lib.dcx_motion_worst(self._h, _ptr(qa32), _ptr(qb32), E, C.byref(opt), _ptr(mg), _ptr(worst), _ptr(idx),
+                                                  _ptr(cls), _ptr(n), _ptr(ga), _ptr(gb), _ptr(work), int(nbytes), mask, self._st()))
+        return (worst, idx, cls, n, ga, gb) if grad else (worst, idx, cls, n)
+
+    def motion_worst(self, qa, qb, res=None, max_step=None, margin=0., max_samples=None, wrap=None):
+        """(worst [E], idx [E], cls [E]) of motion_worst_raw; worst is differentiable with respect to qa and qb (backward:
+        upstream[e] * grad_*[e], the sub-gradient through the worst sample; no second derivatives) and is returned on qa's
+        device and dtype."""
+        qa, qb = torch.as_tensor(qa), torch.as_tensor(qb)
+        kw = dict(res=res, max_step=max_step, margin=margin, max_samples=max_samples, wrap=wrap)
+        if not ((qa.requires_grad or qb.requires_grad) and torch.is_grad_enabled()):
+            worst, idx, cls, _ = self.motion_worst_raw(qa, qb, **kw)
+            return worst.to(device=qa.device, dtype=qa.dtype), idx, cls
+        return _MotionWorstFn.apply(qa, qb, self, kw)
+
+    def path_worst(self, paths, max_step, margin=0., max_samples=None, wrap=None):
+        """(worst [T], segment [T], sample [T]) of T piecewise-straight paths [T, W, dof]: the peak of max_c (score_c -
+        margin_c) over every segment's closed max_step sample set, the first maximum in (segment, sample) order; worst is
+        differentiable with respect to every waypoint (compose_path_worst over motion_worst)."""
+        kw = dict(max_step=max_step, margin=margin, max_samples=max_samples, wrap=wrap)
+        return compose_path_worst(lambda a, b: self.motion_worst(a, b, **kw), paths, self.dof)
+
     # autograd-aware ------------------------------------------------------------------------
     def score(self, q: torch.Tensor) -> torch.Tensor:
         """[B, C] scores for q [B, dof]; differentiable w.r.t. q (gradient from the fused HIP pass)."""
@@ -624,4 +699,24 @@ class _MotionCostFn(torch.autograd.Function):
     def backward(ctx, gc):
         ga, gb = ctx.saved_tensors
         up = gc.reshape((-1,) + (1,) * (ga.dim() - 1))
+        return (up * ga if ctx.needs_input_grad[0] else None), (up * gb if ctx.needs_input_grad[1] else None), None, None
+
+
+class _MotionWorstFn(torch.autograd.Function):
+    """(worst, idx, cls) = motion_worst(qa, qb): ONE dcx_motion_worst call forms the peak and both endpoint gradients; backward
+    scales them by the upstream (no second derivatives)."""
+
+    @staticmethod
+    def forward(ctx, qa, qb, model, kw):
+        worst, idx, cls, _, ga, gb = model.motion_worst_raw(qa, qb, grad=True, **kw)
+        ctx.save_for_backward(ga.to(device=qa.device, dtype=qa.dtype).reshape(qa.shape),
+                              gb.to(device=qb.device, dtype=qb.dtype).reshape(qb.shape))
+        ctx.mark_non_differentiable(idx, cls)
+        return worst.to(device=qa.device, dtype=qa.dtype), idx, cls
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, gw, _gi, _gc):
+        ga, gb = ctx.saved_tensors
+        up = gw.reshape((-1,) + (1,) * (ga.dim() - 1))
         return (up * ga if ctx.needs_input_grad[0] else None), (up * gb if ctx.needs_input_grad[1] else None), None, None

@@ -414,3 +414,110 @@ def path_cost(owner, fused, transform, kernel_func, support_feat, weights, paths
               wrap=_ops.wrap_mask(wrap, dof, transform))
     return _ops.compose_path_cost(lambda a, b, open_end: motion_cost(owner, fused, transform, kernel_func, support_feat, weights, a,
                                                                      b, open_end=open_end, **kw), paths, dof)
+
+
+# ---- worst-sample motion queries ---------------------------------------------------------------------------------------------
+def _first_where(at, dim):
+    """the smallest index along `dim` where `at` holds (argmax of a tie is unspecified in torch: a min over masked indices)"""
+    import torch
+    n = at.shape[dim]
+    shape = [1] * at.dim()
+    shape[dim] = n
+    ar = torch.arange(n, device=at.device).reshape(shape)
+    return torch.where(at, ar, torch.full_like(ar, n)).amin(dim=dim)
+
+
+def host_motion_worst(score_fn, qa, qb, res=None, max_step=None, margin=0., max_samples=None, wrap=0):
+    """the composition a caller would write without dcx_motion_worst: every edge's points materialised differentiably
+    (check_motions' closed sample set; `wrap`, a bitmask: the wrapped delta and wrapped points), scored through autograd, and a
+    segment arg-max: (worst [E], idx [E] int32, cls [E] int32, n_samples [E] int32).  worst[e] = max over the edge's samples
+    of max_c (score_c - margin_c) (a NaN score counts as -inf), the smallest sample that attains it, the smallest class that
+    attains it there; differentiable with respect to qa and qb through that sample.  An edge over max_samples: NaN / -2 / -1."""
+    import torch
+    qa, qb = qa.reshape(len(qa), -1), qb.reshape(len(qb), -1)
+    E, dev = len(qa), qa.device
+    d = _ops.wrapped_delta(qa, qb, wrap)
+    if res is not None:
+        n = torch.full((E,), int(res), dtype=torch.int64, device=dev)
+    else:
+        L = d.detach().norm(dim=-1)
+        n = torch.ceil(L / max_step).to(torch.int64) + 1
+    limit = int(res) if (max_samples is None and res is not None) else (
+        _ops.MOTION_MAX_SAMPLES if max_samples is None else int(max_samples))
+    ok = n <= limit
+    n_ok = torch.where(ok, n, torch.zeros_like(n))
+    edge = torch.repeat_interleave(torch.arange(E, device=dev), n_ok)
+    offs = torch.cumsum(n_ok, 0) - n_ok
+    k = torch.arange(len(edge), device=dev) - offs[edge]
+    if res is not None:
+        pts = _wrap_points(qa[edge] + d[edge] * (k.to(qa.dtype) / int(res))[:, None], wrap)
+    else:
+        # u = d / L differentiably (the sample counts are constants); L = 0 edges have only the target sample
+        Ld = d.norm(dim=-1, keepdim=True)
+        u = d / torch.where(Ld > 0, Ld, torch.ones_like(Ld))
+        pts = _wrap_points(qa[edge] + (k.to(qa.dtype) * max_step)[:, None] * u[edge], wrap)
+        pts = torch.where((k == n[edge] - 1)[:, None], qb[edge], pts)
+    nan = float("nan")
+    worst = torch.full((E,), nan, dtype=qa.dtype, device=dev)
+    idx = torch.full((E,), -2, dtype=torch.int64, device=dev)
+    cls = torch.full((E,), -1, dtype=torch.int64, device=dev)
+    if len(pts):
+        s = score_fn(pts).reshape(len(pts), -1)
+        mg = torch.as_tensor(margin, dtype=s.dtype, device=s.device).reshape(-1)
+        v = s - mg
+        vd = torch.nan_to_num(v.detach(), nan=-float("inf"), posinf=float("inf"), neginf=-float("inf"))
+        vk, _ = vd.max(dim=-1)
+        ck = _first_where(vd == vk[:, None], 1)
+        top = torch.full((E,), -float("inf"), dtype=vk.dtype, device=dev).scatter_reduce(0, edge, vk, reduce="amax", include_self=True)
+        big = torch.iinfo(torch.int64).max
+        first = torch.full((E,), big, dtype=torch.int64, device=dev).scatter_reduce(
+            0, edge, torch.where(vk == top[edge], k, torch.full_like(k, big)), reduce="amin", include_self=True)
+        has = ok & (n_ok > 0)
+        flat = (offs + torch.where(has, first, torch.zeros_like(first))).clamp(max=len(pts) - 1)
+        cbest = ck[flat]
+        picked = v[flat, cbest]                      # differentiable: the worst sample's winning class score
+        picked = torch.where(torch.isnan(picked.detach()), torch.full_like(picked, -float("inf")), picked)
+        worst = torch.where(has, picked.to(qa.dtype), worst)
+        idx = torch.where(has, first, idx)
+        cls = torch.where(has, cbest, cls)
+    return worst, idx.to(torch.int32), cls.to(torch.int32), n.clamp(max=2 ** 31 - 1).to(torch.int32)
+
+
+def motion_worst(owner, fused, transform, kernel_func, support_feat, weights, qa, qb, res=None, max_step=None, margin=0.,
+                 max_samples=None, score_fn=None, wrap=None):
+    """(worst [E], idx [E], cls [E]) of the motions qa[e] -> qb[e] on the model `fused` holds: one dcx_motion_worst call where
+    the transform fuses (none, or a diffco_amd robot's fkine), else the host composition (a foreign callable through
+    `score_fn`).  worst is differentiable with respect to qa and qb.  owner.last_route says which ran: "fused" or "host".
+    Raises ValueError for edges over max_samples (a read-back).  `wrap`: as check_motions."""
+    import torch
+    if (res is None) == (max_step is None):
+        raise ValueError("motion_worst takes exactly one of res and max_step")
+    qa, qb = torch.as_tensor(qa), torch.as_tensor(qb)
+    mask = _ops.wrap_mask(wrap, qa.shape[-1], transform)
+    dev = qa.device if qa.device.type == "cuda" else (support_feat.device if support_feat.device.type == "cuda" else None)
+    m = fused.model(transform, kernel_func, support_feat, weights, dev)
+    kw = dict(res=res, max_step=max_step, margin=margin, max_samples=max_samples, wrap=mask)
+    if m.desc.kind == 0 and transform is not None:
+        owner.last_route = "host"
+        fn = score_fn or (lambda p: fused.score(transform, kernel_func, support_feat, weights, p))
+        qa_d, qb_d = qa.to(device=m.dev, dtype=torch.float32), qb.to(device=m.dev, dtype=torch.float32)
+        worst, idx, cls, _ = host_motion_worst(fn, qa_d, qb_d, **kw)
+        worst = worst.to(device=qa.device, dtype=qa.dtype)
+    else:
+        owner.last_route = "fused"
+        worst, idx, cls = m.motion_worst(qa, qb, **kw)
+    if bool((idx == -2).any()):
+        bad = (idx == -2).nonzero().reshape(-1)[:8].tolist()
+        raise ValueError(f"motion_worst: edges {bad} need more than max_samples samples (pass a larger max_samples or max_step)")
+    return worst, idx, cls
+
+
+def path_worst(owner, fused, transform, kernel_func, support_feat, weights, paths, max_step, margin=0., max_samples=None,
+               score_fn=None, wrap=None):
+    """(worst [T], segment [T], sample [T]) of paths [T, W, dof] (ScoreModel.path_worst's composition over either route)"""
+    import torch
+    paths = torch.as_tensor(paths)
+    dof = paths.shape[-1]
+    kw = dict(max_step=max_step, margin=margin, max_samples=max_samples, score_fn=score_fn, wrap=_ops.wrap_mask(wrap, dof, transform))
+    return _ops.compose_path_worst(lambda a, b: motion_worst(owner, fused, transform, kernel_func, support_feat, weights, a, b, **kw),
+                                   paths, dof)

@@ -240,6 +240,35 @@ class RBFDiffCo(CollisionChecker):
         return path_cost(self, p._poly_fused, p.transform, p.rbf_kernel, p.support_transformed, p.rbf_nodes, paths, max_step,
                          margin=margin, weight=weight, max_samples=max_samples, wrap=wrap)
 
+    def motion_worst(self, q_start, q_end, max_step=None, res=None, bias=None, max_samples=None, wrap=None):
+        """(worst [E], sample [E], class [E]) of the motions q_start[e] -> q_end[e]: the peak of `collision_score` (poly score
+        + bias; bias defaults to safety_bias) over check_motions' samples and the first sample that attains it.  worst is
+        differentiable with respect to both endpoints.  Exactly one rule and `wrap` as check_motions."""
+        from ._perceptron import motion_worst
+        bias = self.safety_bias if bias is None else bias
+        margin = -bias if not torch.is_tensor(bias) else -bias.detach().reshape(-1)
+        p = self.perceptron
+        return motion_worst(self, p._poly_fused, p.transform, p.rbf_kernel, p.support_transformed, p.rbf_nodes, q_start, q_end,
+                            res=res, max_step=max_step, margin=margin, max_samples=max_samples, wrap=wrap)
+
+    def path_worst(self, paths, max_step, bias=None, max_samples=None, wrap=None):
+        """(worst [T], segment [T], sample [T]) of paths [T, W, dof] by `collision_score` (the closed max_step rule per segment,
+        the first maximum in (segment, sample) order); worst is differentiable with respect to every waypoint"""
+        from ._perceptron import path_worst
+        bias = self.safety_bias if bias is None else bias
+        margin = -bias if not torch.is_tensor(bias) else -bias.detach().reshape(-1)
+        p = self.perceptron
+        return path_worst(self, p._poly_fused, p.transform, p.rbf_kernel, p.support_transformed, p.rbf_nodes, paths, max_step,
+                          margin=margin, max_samples=max_samples, wrap=wrap)
+
+    def motion_bias_sweep(self, q_start, q_end, biases, max_step=None, res=None, max_samples=None, wrap=None):
+        """bool [len(biases), E]: would the motion q_start[e] -> q_end[e] collide under each candidate bias?  ONE worst-sample
+        call at bias 0 answers every bias: row b is worst_at_zero_bias + biases[b] > 0, what check_motions(bias=biases[b])
+        returns (up to the rounding of the sum at a tie)."""
+        worst, _, _ = self.motion_worst(q_start, q_end, max_step=max_step, res=res, bias=0.0, max_samples=max_samples, wrap=wrap)
+        b = torch.as_tensor(biases, dtype=worst.dtype, device=worst.device).reshape(-1)
+        return worst.detach()[None, :] + b[:, None] > 0
+
     def _calculate_safety_bias(self, q_verify):
         """a third of the smaller of |min score| and |max score| over q_verify (collision_checkers.py:497-503; the
         reference defines it on the FK subclass only and its RBFDiffCo.fit calls it regardless)"""

@@ -14,6 +14,7 @@
 #include "dcx_internal.h"
 #include "motion_cost_kernel.h"
 #include "motion_kernel.h"
+#include "motion_worst_kernel.h"
 #include "pack_kernels.h"
 #include "solve_kernels.h"
 
@@ -1634,41 +1635,14 @@ motion_fn motion_for(int Dt) {
     default: return nullptr;
     }
 }
-}  // namespace
-
-size_t dcx_motion_work_bytes(const dcx_model* m, int64_t E) {
-    if (!m || E < 0) return 0;
-    return motion_work(E).total;
-}
-
-int dcx_check_motions(const dcx_model* m, const float* qa, const float* qb, int64_t E, const dcx_motion_opts* opt,
-                      const float* margin, int32_t* first_hit, int32_t* n_samples, void* work, size_t work_bytes, void* stream) {
-    return dcx_check_motions_ex(m, qa, qb, E, opt, margin, first_hit, n_samples, work, work_bytes, 0, stream);
-}
-
-int dcx_check_motions_ex(const dcx_model* m, const float* qa, const float* qb, int64_t E, const dcx_motion_opts* opt,
-                         const float* margin, int32_t* first_hit, int32_t* n_samples, void* work, size_t work_bytes,
-                         uint64_t wrap_mask, void* stream) {
-    // every argument is checked before anything touches the model or the device
-    if (!m) return fail(DCX_ERR_INVALID, "model is NULL");
-    if (!opt) return fail(DCX_ERR_INVALID, "motion options are NULL");
-    if (E < 0) return fail(DCX_ERR_INVALID, "E < 0");
-    if (E > 0 && (!qa || !qb || !first_hit || !work)) return fail(DCX_ERR_INVALID, "qa / qb / first_hit / work is NULL");
-    const bool by_res = opt->res > 0, by_step = opt->max_step > 0.f;
-    if (opt->res < 0 || !(opt->max_step >= 0.f) || by_res == by_step)
-        return fail(DCX_ERR_INVALID, "motion check needs exactly one sampling rule: res > 0 or max_step > 0 (the other 0)");
-    if (opt->max_samples < 1) return fail(DCX_ERR_INVALID, "motion check needs max_samples >= 1");
-    if (wrap_mask != 0 && m->fk.dof < 64 && (wrap_mask >> m->fk.dof) != 0)   // (mask 0, the plain call: the model is not read here)
-        return fail(DCX_ERR_INVALID, "motion check: wrap_mask has a bit at or above dof");
-    const MotionWork w = motion_work(E);
-    if (E > 0 && work_bytes < w.total) return fail(DCX_ERR_INVALID, "motion workspace is smaller than dcx_motion_work_bytes");
-    if (E > INT32_MAX) return fail(DCX_ERR_UNSUPPORTED, "motion check: more than 2^31 - 1 edges");
-    if (E == 0) return DCX_OK;
-    const int64_t tiles_max = (E * (int64_t)opt->max_samples + 63) / 64;
-    if (tiles_max > 0x7fffffffLL) return fail(DCX_ERR_UNSUPPORTED, "motion check: E * max_samples too large for one launch");
-    if (int rc = set_device(m->device)) return rc;
-    hipStream_t st = (hipStream_t)stream;
-    char* base = (char*)work;
+// What dcx_check_motions and dcx_motion_worst share: the launch geometry for the upper bound of the samples and the sweep's
+// arguments - the rows, slices, wave-group shares and the split decision of a score-only launch, so that both calls score a
+// sample to the same bits for the same (model, E, max_samples).
+struct MotionSweepPlan {
+    Geometry g;
+    size_t lds;
+};
+MotionSweepPlan motion_sweep_plan(const dcx_model* m, int64_t tiles_max, char* base, const MotionWork& w, ScoreArgs& sa) {
     const int d_fk = m->fk.n_points * m->fk.point_dim;
     const int acc = m->Cc;
     // grid: the sample count is on the device only; its upper bound E * max_samples sizes the grid and decides whether the
@@ -1676,26 +1650,6 @@ int dcx_check_motions_ex(const dcx_model* m, const float* qa, const float* qb, i
     Geometry g = pick_geometry(m, std::min<int64_t>(tiles_max, (int64_t)1 << 30) * 64, acc, true);
     if (g.ys > 1 && (tiles_max > kMotionSplitTiles || tiles_max * g.ys > kMotionSplitRows))
         g = pick_geometry(m, std::min<int64_t>(tiles_max, (int64_t)1 << 30) * 64, acc, false);
-    MotionPrepArgs p{};
-    p.qa = qa;
-    p.qb = qb;
-    p.E = E;
-    p.dof = m->fk.dof;
-    p.res = opt->res;
-    p.max_samples = opt->max_samples;
-    p.max_step = opt->max_step;
-    p.offs = (int64_t*)(base + w.offs);
-    p.frac = (float*)(base + w.frac);
-    p.first_hit = first_hit;
-    p.n_samples = n_samples;
-    p.counters = g.ys > 1 ? (unsigned int*)(base + w.counters) : nullptr;
-    p.n_counters = g.ys > 1 ? (int32_t)tiles_max : 0;
-    p.wrap_mask = wrap_mask;
-    hipError_t e = launch_motion_prep(p, st);
-    if (e != hipSuccess) return fail_hip(e, "motion prep launch");
-
-    MotionArgs a{};
-    ScoreArgs& sa = a.sc;
     sa.rows = m->rows_dev;
     set_fk_walk(m, sa);
     sa.B = 0;
@@ -1735,6 +1689,66 @@ int dcx_check_motions_ex(const dcx_model* m, const float* qa, const float* qb, i
         sa.partial = (float*)(base + w.partial);
         sa.tile_done = (unsigned int*)(base + w.counters);
     }
+    const size_t lds = sizeof(float) * (((size_t)lds_plan(sa.dof, d_fk, m->frame_floats, g.nw > 1 ? g.red_slots : 0, acc, true).total +
+                                         m->prog_floats + 3) & ~(size_t)3) + sizeof(float) * kMotionLdsFloats;
+    return MotionSweepPlan{g, lds};
+}
+}  // namespace
+
+size_t dcx_motion_work_bytes(const dcx_model* m, int64_t E) {
+    if (!m || E < 0) return 0;
+    return motion_work(E).total;
+}
+
+int dcx_check_motions(const dcx_model* m, const float* qa, const float* qb, int64_t E, const dcx_motion_opts* opt,
+                      const float* margin, int32_t* first_hit, int32_t* n_samples, void* work, size_t work_bytes, void* stream) {
+    return dcx_check_motions_ex(m, qa, qb, E, opt, margin, first_hit, n_samples, work, work_bytes, 0, stream);
+}
+
+int dcx_check_motions_ex(const dcx_model* m, const float* qa, const float* qb, int64_t E, const dcx_motion_opts* opt,
+                         const float* margin, int32_t* first_hit, int32_t* n_samples, void* work, size_t work_bytes,
+                         uint64_t wrap_mask, void* stream) {
+    // every argument is checked before anything touches the model or the device
+    if (!m) return fail(DCX_ERR_INVALID, "model is NULL");
+    if (!opt) return fail(DCX_ERR_INVALID, "motion options are NULL");
+    if (E < 0) return fail(DCX_ERR_INVALID, "E < 0");
+    if (E > 0 && (!qa || !qb || !first_hit || !work)) return fail(DCX_ERR_INVALID, "qa / qb / first_hit / work is NULL");
+    const bool by_res = opt->res > 0, by_step = opt->max_step > 0.f;
+    if (opt->res < 0 || !(opt->max_step >= 0.f) || by_res == by_step)
+        return fail(DCX_ERR_INVALID, "motion check needs exactly one sampling rule: res > 0 or max_step > 0 (the other 0)");
+    if (opt->max_samples < 1) return fail(DCX_ERR_INVALID, "motion check needs max_samples >= 1");
+    if (wrap_mask != 0 && m->fk.dof < 64 && (wrap_mask >> m->fk.dof) != 0)   // (mask 0, the plain call: the model is not read here)
+        return fail(DCX_ERR_INVALID, "motion check: wrap_mask has a bit at or above dof");
+    const MotionWork w = motion_work(E);
+    if (E > 0 && work_bytes < w.total) return fail(DCX_ERR_INVALID, "motion workspace is smaller than dcx_motion_work_bytes");
+    if (E > INT32_MAX) return fail(DCX_ERR_UNSUPPORTED, "motion check: more than 2^31 - 1 edges");
+    if (E == 0) return DCX_OK;
+    const int64_t tiles_max = (E * (int64_t)opt->max_samples + 63) / 64;
+    if (tiles_max > 0x7fffffffLL) return fail(DCX_ERR_UNSUPPORTED, "motion check: E * max_samples too large for one launch");
+    if (int rc = set_device(m->device)) return rc;
+    hipStream_t st = (hipStream_t)stream;
+    char* base = (char*)work;
+    MotionArgs a{};
+    const MotionSweepPlan plan = motion_sweep_plan(m, tiles_max, base, w, a.sc);
+    const Geometry& g = plan.g;
+    MotionPrepArgs p{};
+    p.qa = qa;
+    p.qb = qb;
+    p.E = E;
+    p.dof = m->fk.dof;
+    p.res = opt->res;
+    p.max_samples = opt->max_samples;
+    p.max_step = opt->max_step;
+    p.offs = (int64_t*)(base + w.offs);
+    p.frac = (float*)(base + w.frac);
+    p.first_hit = first_hit;
+    p.n_samples = n_samples;
+    p.counters = g.ys > 1 ? (unsigned int*)(base + w.counters) : nullptr;
+    p.n_counters = g.ys > 1 ? (int32_t)tiles_max : 0;
+    p.wrap_mask = wrap_mask;
+    hipError_t e = launch_motion_prep(p, st);
+    if (e != hipSuccess) return fail_hip(e, "motion prep launch");
+
     a.qa = qa;
     a.qb = qb;
     a.offs = p.offs;
@@ -1746,12 +1760,143 @@ int dcx_check_motions_ex(const dcx_model* m, const float* qa, const float* qb, i
     a.early_exit = knobs().motion_early_exit != 0 ? 1 : 0;
     a.wrap_mask = wrap_mask;
     const int64_t nblk = tiles_max;   // one tile per block; blocks past the work list's end leave (motion_kernel.h)
-    const size_t lds = sizeof(float) * (((size_t)lds_plan(sa.dof, d_fk, m->frame_floats, g.nw > 1 ? g.red_slots : 0, acc, true).total +
-                                         m->prog_floats + 3) & ~(size_t)3) + sizeof(float) * kMotionLdsFloats;
+    const size_t lds = plan.lds;
     motion_fn launch = motion_for(m->Dt);
     if (!launch) return fail(DCX_ERR_UNSUPPORTED, "motion check: no kernel for this feature width");
     e = launch(m->kf, m->Cc, g.nw, lds, nblk, a, st);
     if (e != hipSuccess) return fail_hip(e, "motion kernel launch");
+    return DCX_OK;
+}
+
+// ---- worst-sample motion queries (motion_worst_kernel.h, motion_worst_finish.hip) ------------------------------------------
+namespace {
+// the workspace: dcx_check_motions' (work list, split-launch room), then per edge its status, its packed key, and for the
+// gradients the worst sample, its one-hot upstream row, the score+gradient launch's score row and its gradient row
+struct MotionWorstWork {
+    MotionWork mw;
+    size_t status, keys, xstar, up, score, g, total;
+};
+MotionWorstWork motion_worst_work(const dcx_model* m, int64_t E) {
+    auto up = [](size_t x) { return (x + 255) / 256 * 256; };
+    MotionWorstWork w;
+    w.mw = motion_work(E);
+    w.status = w.mw.total;
+    w.keys = w.status + up((size_t)E * sizeof(int32_t));
+    w.xstar = w.keys + up((size_t)E * sizeof(unsigned long long));
+    w.up = w.xstar + up((size_t)E * m->fk.dof * sizeof(float));
+    w.score = w.up + up((size_t)E * m->C * sizeof(float));
+    w.g = w.score + up((size_t)E * m->C * sizeof(float));
+    w.total = w.g + up((size_t)E * m->fk.dof * sizeof(float));
+    return w;
+}
+motion_worst_fn motion_worst_for(int Dt) {
+    switch (Dt) {
+#define DCX_CASE(D) case D: return launch_motion_worst_D##D;
+        DCX_CASE(2) DCX_CASE(4) DCX_CASE(6) DCX_CASE(8) DCX_CASE(12) DCX_CASE(16) DCX_CASE(18) DCX_CASE(21)
+        DCX_CASE(24) DCX_CASE(27) DCX_CASE(30) DCX_CASE(32) DCX_CASE(36) DCX_CASE(42) DCX_CASE(48) DCX_CASE(54)
+        DCX_CASE(60) DCX_CASE(64) DCX_CASE(72) DCX_CASE(84) DCX_CASE(96)
+#undef DCX_CASE
+    default: return nullptr;
+    }
+}
+}  // namespace
+
+size_t dcx_motion_worst_work_bytes(const dcx_model* m, int64_t E) {
+    if (!m || E < 0) return 0;
+    return motion_worst_work(m, E).total;
+}
+
+int dcx_motion_worst(const dcx_model* m, const float* qa, const float* qb, int64_t E, const dcx_motion_opts* opt,
+                     const float* margin, float* worst, int32_t* worst_idx, int32_t* worst_class, int32_t* n_samples,
+                     float* grad_a, float* grad_b, void* work, size_t work_bytes, uint64_t wrap_mask, void* stream) {
+    // every argument is checked before anything touches the device
+    if (!m) return fail(DCX_ERR_INVALID, "model is NULL");
+    if (!opt) return fail(DCX_ERR_INVALID, "motion options are NULL");
+    if (E < 0) return fail(DCX_ERR_INVALID, "E < 0");
+    if (E > 0 && (!qa || !qb || !worst || !worst_idx || !work)) return fail(DCX_ERR_INVALID, "qa / qb / worst / worst_idx / work is NULL");
+    if ((grad_a == nullptr) != (grad_b == nullptr)) return fail(DCX_ERR_INVALID, "motion worst: pass both grad_a and grad_b or neither");
+    const bool by_res = opt->res > 0, by_step = opt->max_step > 0.f;
+    if (opt->res < 0 || !(opt->max_step >= 0.f) || by_res == by_step)
+        return fail(DCX_ERR_INVALID, "motion worst needs exactly one sampling rule: res > 0 or max_step > 0 (the other 0)");
+    if (opt->max_samples < 1) return fail(DCX_ERR_INVALID, "motion worst needs max_samples >= 1");
+    if (opt->reserved != 0) return fail(DCX_ERR_INVALID, "motion worst: reserved must be 0");
+    if (wrap_mask != 0 && m->fk.dof < 64 && (wrap_mask >> m->fk.dof) != 0)
+        return fail(DCX_ERR_INVALID, "motion worst: wrap_mask has a bit at or above dof");
+    const MotionWorstWork w = motion_worst_work(m, E);
+    if (E > 0 && work_bytes < w.total) return fail(DCX_ERR_INVALID, "motion workspace is smaller than dcx_motion_worst_work_bytes");
+    if (E > INT32_MAX) return fail(DCX_ERR_UNSUPPORTED, "motion worst: more than 2^31 - 1 edges");
+    if (opt->max_samples > kMotionWorstSampleLimit) return fail(DCX_ERR_UNSUPPORTED, "motion worst: max_samples above 2^24 - 1");
+    if (E == 0) return DCX_OK;
+    const int64_t tiles_max = (E * (int64_t)opt->max_samples + 63) / 64;
+    if (tiles_max > 0x7fffffffLL) return fail(DCX_ERR_UNSUPPORTED, "motion worst: E * max_samples too large for one launch");
+    motion_worst_fn launch = motion_worst_for(m->Dt);
+    if (!launch) return fail(DCX_ERR_UNSUPPORTED, "motion worst: no kernel for this feature width");
+    if (int rc = set_device(m->device)) return rc;
+    hipStream_t st = (hipStream_t)stream;
+    char* base = (char*)work;
+    MotionWorstArgs a{};
+    const MotionSweepPlan plan = motion_sweep_plan(m, tiles_max, base, w.mw, a.sc);   // the check's geometry and sweep arguments
+    const Geometry& g = plan.g;
+    MotionPrepArgs p{};
+    p.qa = qa;
+    p.qb = qb;
+    p.E = E;
+    p.dof = m->fk.dof;
+    p.res = opt->res;
+    p.max_samples = opt->max_samples;
+    p.max_step = opt->max_step;
+    p.offs = (int64_t*)(base + w.mw.offs);
+    p.frac = (float*)(base + w.mw.frac);
+    p.first_hit = (int32_t*)(base + w.status);
+    p.n_samples = n_samples;
+    p.counters = g.ys > 1 ? (unsigned int*)(base + w.mw.counters) : nullptr;
+    p.n_counters = g.ys > 1 ? (int32_t)tiles_max : 0;
+    p.wrap_mask = wrap_mask;
+    hipError_t e = launch_motion_prep(p, st);
+    if (e != hipSuccess) return fail_hip(e, "motion worst prep launch");
+    a.keys = (unsigned long long*)(base + w.keys);
+    e = hipMemsetAsync(a.keys, 0, (size_t)E * sizeof(unsigned long long), st);   // key 0: no sample yet
+    if (e != hipSuccess) return fail_hip(e, "motion worst key reset");
+    a.qa = qa;
+    a.qb = qb;
+    a.offs = p.offs;
+    a.frac = p.frac;
+    a.margin = margin;
+    a.E = E;
+    a.res = opt->res;
+    a.wrap_mask = wrap_mask;
+    e = launch(m->kf, m->Cc, g.nw, plan.lds, tiles_max, a, st);
+    if (e != hipSuccess) return fail_hip(e, "motion worst kernel launch");
+    const bool grads = grad_a != nullptr;
+    MotionWorstFinishArgs f{};
+    f.qa = qa;
+    f.qb = qb;
+    f.offs = p.offs;
+    f.frac = p.frac;
+    f.status = p.first_hit;
+    f.keys = a.keys;
+    f.worst = worst;
+    f.worst_idx = worst_idx;
+    f.worst_class = worst_class;
+    f.xstar = grads ? (float*)(base + w.xstar) : nullptr;
+    f.up = grads && m->C > 1 ? (float*)(base + w.up) : nullptr;
+    f.E = E;
+    f.dof = m->fk.dof;
+    f.res = opt->res;
+    f.C = m->C;
+    f.wrap_mask = wrap_mask;
+    e = launch_motion_worst_finish(f, st);
+    if (e != hipSuccess) return fail_hip(e, "motion worst finish launch");
+    if (!grads) return DCX_OK;
+    // the gradient of the winning class at the worst samples: the library's own score+gradient launch on E points
+    float* gbuf = (float*)(base + w.g);
+    const int mode = m->C > 1 ? MODE_GRAD_UP : MODE_GRAD_ROW;
+    if (int rc = run_score(m, f.xstar, E, f.up, (float*)(base + w.score), gbuf, mode, -1, m->fk.dof, st)) return rc;
+    f.g = gbuf;
+    f.grad_a = grad_a;
+    f.grad_b = grad_b;
+    e = launch_motion_worst_chain(f, st);
+    if (e != hipSuccess) return fail_hip(e, "motion worst chain launch");
     return DCX_OK;
 }
 

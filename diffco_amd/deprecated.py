@@ -235,6 +235,20 @@ class DiffCo(CollisionChecker):
         from ._perceptron import path_cost
         return path_cost(self, *self._rbf_args(), paths, max_step, margin=margin, weight=weight, max_samples=max_samples, wrap=wrap)
 
+    def motion_worst(self, starts, targets, res=None, max_step=None, margin=0., max_samples=None, wrap=None):
+        """(worst [E], sample [E], class [E]) of the motions starts[e] -> targets[e] under the `rbf_score` state: the peak of
+        max_c (rbf_score_c - margin_c) over check_motions' samples, the first sample that attains it and the first class that
+        attains it there (MultiDiffCo: the binding obstacle).  worst is differentiable with respect to starts and targets."""
+        from ._perceptron import motion_worst
+        return motion_worst(self, *self._rbf_args(), starts, targets, res=res, max_step=max_step, margin=margin,
+                            max_samples=max_samples, wrap=wrap)
+
+    def path_worst(self, paths, max_step, margin=0., max_samples=None, wrap=None):
+        """(worst [T], segment [T], sample [T]) of paths [T, W, dof] under the `rbf_score` state (the closed max_step rule per
+        segment, the first maximum in (segment, sample) order); worst is differentiable w.r.t. every waypoint"""
+        from ._perceptron import path_worst
+        return path_worst(self, *self._rbf_args(), paths, max_step, margin=margin, max_samples=max_samples, wrap=wrap)
+
     def poly_score(self, point):
         if point.ndim == 1:
             point = point[None, :]

@@ -326,6 +326,21 @@ class DiffCo(Perceptron):
         return path_cost(self, self._score_fused, self.transform, self.kernel_func, self.support_transformed, self.gains, paths,
                          max_step, margin=margin, weight=weight, max_samples=max_samples, wrap=wrap)
 
+    def motion_worst(self, starts, targets, res=None, max_step=None, margin=0., max_samples=None, wrap=None):
+        """how close do the motions starts[e] -> targets[e] come?  (worst [E], sample [E], class [E]): the peak of score - margin
+        over check_motions' samples (exactly one rule; `wrap` as there), the first sample that attains it and the class (0).
+        worst is differentiable with respect to starts and targets through that sample.  One fused call (dcx_motion_worst)."""
+        from ._perceptron import motion_worst
+        return motion_worst(self, self._score_fused, self.transform, self.kernel_func, self.support_transformed, self.gains,
+                            starts, targets, res=res, max_step=max_step, margin=margin, max_samples=max_samples, wrap=wrap)
+
+    def path_worst(self, paths, max_step, margin=0., max_samples=None, wrap=None):
+        """(worst [T], segment [T], sample [T]) of paths [T, W, dof]: the peak of score - margin over every segment's samples
+        (the closed max_step rule), the first maximum in (segment, sample) order; worst is differentiable w.r.t. every waypoint"""
+        from ._perceptron import path_worst
+        return path_worst(self, self._score_fused, self.transform, self.kernel_func, self.support_transformed, self.gains, paths,
+                          max_step, margin=margin, max_samples=max_samples, wrap=wrap)
+
     def poly_score(self, point=None, transformed_point=None):
         """sum_j K_rbf(T(q), support_j) rbf_nodes_j  ->  [N, 1]; `transformed_point` skips the FK."""
         if transformed_point is None:

@@ -446,6 +446,47 @@ int dcx_motion_cost_ex(const dcx_model* m, const float* qa, const float* qb, int
                        const float* margin, float weight, float* cost, float* grad_a, float* grad_b, int32_t* n_samples, void* work,
                        size_t work_bytes, uint64_t wrap_mask, void* stream);
 
+/* ---- worst-sample motion queries (added under DCX_VERSION 109) ------------------------------------------- */
+/* How close does the straight motion qa[e] -> qb[e] come, where along it, and against which class?  E edges per call on exactly
+ * dcx_check_motions_ex's sample set (one rule per call; res rule: samples k = 0 .. res - 1; the closed max_step rule: the
+ * interior samples, then qb; wrap_mask as in the _ex calls, the points the same bits).  There is no open_end: a peak does not
+ * mind a waypoint scored twice.  opt->reserved must be 0.
+ *   sample value   v_k = max over c < C of (score_c(x_k) - margin_c);  margin: [C] device floats, NULL = 0.  A NaN class score
+ *                  counts as -inf (dcx_check_motions never reports such a sample either); -0 counts as +0
+ *   worst [E]        (float, device, out)                max_k v_k
+ *   worst_idx [E]    (int32, device, out)                the smallest k that attains it
+ *   worst_class [E]  (int32, device, out, may be NULL)   the smallest c that attains v_k at that k
+ *   n_samples [E]    (int32, device, out, may be NULL)   as dcx_check_motions'
+ * For the same (model, E, max_samples) the sweep takes the rows, slices, wave-group shares and split decision of
+ * dcx_check_motions, so worst[e] > 0 exactly where that call reports a hit.  The results do not depend on the launch geometry's
+ * block arrival order; repeated calls return the same bits.
+ * An edge over max_samples: worst NaN, worst_idx -2, worst_class -1, its gradient rows NaN; n_samples holds the count it needs.
+ * grad_a, grad_b [E, dof] (device, out; both or neither): the gradient of worst[e] with respect to qa[e] and qb[e] through the
+ *   worst sample only - with g = d score_c / dq of the winning class at that sample, dcx_motion_cost's per-sample chain:
+ *   res rule, t = k / res:           grad_b = t g,  grad_a = (1 - t) g
+ *   max_step rule, interior sample:  grad_b = (k max_step / L)(I - u u^T) g,  grad_a = g - grad_b;  u = d / L from the wrapped
+ *                                    delta where coordinates are masked; the sample count is held constant
+ *   max_step rule, the target:       grad_b = g,  grad_a = 0
+ * Launches on the caller's stream only: the sample counts and their scan, the reset of the per-edge keys, one fused interpolate
+ * -> FK -> score-only sweep -> packed 64-bit maximum per edge, a per-edge finish; with gradients one score+gradient launch of
+ * the library on the E worst samples and a chain kernel.  No synchronisation, nothing read back: the call can be captured.
+ * Without gradients nothing is allocated.  The gradient launch is dcx_score_grad's, with that call's rule: a batch small enough
+ * to split its supports over several blocks keeps their partial rows in the model's per-stream scratch, which is allocated
+ * (hipMalloc) on the stream's first such launch outside a capture; while a stream without that scratch is being captured the
+ * launch runs unsplit.  So grad_a / grad_b are the same bits on every call in the same state of the stream, but a call
+ * captured on a stream that has never run a small dcx_score / dcx_score_grad / gradient call of this model may differ from the
+ * eager call in the rounding of the gradient sum (worst, worst_idx, worst_class and n_samples never do).  One eager call on
+ * the stream before the capture, as for dcx_score_grad, makes the two identical.
+ * work: dcx_motion_worst_work_bytes(model, E) bytes of device memory, the caller's; initialised by the call itself.
+ * Argument errors (DCX_ERR_INVALID, before any device work): those of dcx_check_motions_ex (NULL model / opt / qa / qb / work
+ *   (E > 0), E < 0, both or neither of res and max_step, max_samples < 1, a wrap_mask bit at or above dof), NULL worst or
+ *   worst_idx (E > 0), exactly one of grad_a / grad_b, reserved not 0, work_bytes below dcx_motion_worst_work_bytes.
+ *   max_samples above 2^24 - 1 is DCX_ERR_UNSUPPORTED.                                                                    */
+size_t dcx_motion_worst_work_bytes(const dcx_model* m, int64_t E);
+int dcx_motion_worst(const dcx_model* m, const float* qa, const float* qb, int64_t E, const dcx_motion_opts* opt,
+                     const float* margin, float* worst, int32_t* worst_idx, int32_t* worst_class, int32_t* n_samples,
+                     float* grad_a, float* grad_b, void* work, size_t work_bytes, uint64_t wrap_mask, void* stream);
+
 /* ---- kernel-perceptron trainer (producer of the path's state) ----------------------- */
 /* DiffCo.train_perceptron kernel_perceptrons.py:98-137 and MultiDiffCo.train_perceptron
  * deprecated/MultiDiffCo.py:50-83 as one persistent launch: worst-margin search, lazily filled kernel rows,
