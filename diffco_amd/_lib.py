@@ -73,6 +73,12 @@ SYMBOLS = {
     "dcx_motion_worst_work_bytes": (C.c_size_t, [C.c_void_p, C.c_int64]),
     "dcx_motion_worst": (C.c_int, [C.c_void_p, _c_fp, _c_fp, C.c_int64, C.c_void_p, _c_fp, _c_fp, _c_fp, _c_fp, _c_fp, _c_fp, _c_fp,
                                    C.c_void_p, C.c_size_t, C.c_uint64, C.c_void_p]),
+    # dense-check Adam trajectory loop: the collision hinge along the segments (dcx_motion_cost_ex per iteration)
+    "dcx_traj_dense_step": (C.c_int, [C.c_int, C.POINTER(FkDesc), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32,
+                                      C.c_void_p]),
+    "dcx_traj_dense_work_bytes": (C.c_size_t, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32]),
+    "dcx_traj_dense_run": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, _c_fp, C.c_int32, C.c_int32,
+                                     C.c_void_p, C.c_size_t, C.c_void_p]),
     "dcx_solve_work_bytes": (C.c_size_t, [C.c_int64, C.c_int64]),
     "dcx_solve": (C.c_int, [C.c_int, _c_fp, _c_fp, C.c_int64, C.c_int64, _c_fp, C.c_void_p, C.c_size_t, C.c_void_p, C.c_int32,
                             C.c_void_p]),
@@ -108,6 +114,17 @@ class MotionCostOpts(C.Structure):
     """ctypes mirror of dcx_motion_cost_opts (include/dcx.h)"""
     _fields_ = [("res", C.c_int32), ("max_step", C.c_float), ("max_samples", C.c_int32), ("open_end", C.c_int32),
                 ("reserved", C.c_int32 * 4)]
+
+
+class TrajDenseOpts(C.Structure):
+    """ctypes mirror of dcx_traj_dense_opts (include/dcx.h)"""
+    _fields_ = [("max_step", C.c_float), ("max_samples", C.c_int32), ("wrap_mask", C.c_uint64), ("rewrap_mask", C.c_uint64),
+                ("normalize", C.c_int32), ("stop_tol", C.c_float), ("reserved", C.c_int32 * 4)]
+
+
+class TrajDenseIO(C.Structure):
+    """ctypes mirror of dcx_traj_dense_io (include/dcx.h)"""
+    _fields_ = [(n, C.c_void_p) for n in ("move", "history", "n_checks", "edge_cost", "grad_a", "grad_b", "n_samples")]
 
 
 _lib = None

@@ -17,6 +17,7 @@
 #include "motion_worst_kernel.h"
 #include "pack_kernels.h"
 #include "solve_kernels.h"
+#include "traj_dense.h"
 
 using namespace dcx;
 
@@ -2096,6 +2097,156 @@ int dcx_motion_cost_ex(const dcx_model* m, const float* qa, const float* qb, int
     r.wrap_mask = wrap_mask;
     e = launch_motion_cost_reduce(r, st);
     if (e != hipSuccess) return fail_hip(e, "motion cost reduction launch");
+    return DCX_OK;
+}
+
+// ---- dense-check Adam trajectory loop (traj_dense.hip; the motion costs above per iteration) -------------------------------
+namespace {
+// the workspace: the shifted path and the last waypoints (the edge lists), the margins the caller left to opt->safety_margin, the
+// R closed edges' results, the per-edge arrays (used when the caller gives none), then dcx_motion_cost_ex's workspace for R * W edges
+struct TrajDenseWork {
+    size_t qb, q_last, margin, c_cost, c_ga, c_gb, c_n, e_cost, e_ga, e_gb, e_n, motion, total;
+};
+TrajDenseWork traj_dense_work(const dcx_model* m, int64_t R, int64_t W, int32_t max_samples) {
+    auto up = [](size_t x) { return (x + 255) / 256 * 256; };
+    const size_t E = (size_t)R * (size_t)W, dof = (size_t)m->fk.dof;
+    TrajDenseWork w;
+    w.qb = 0;
+    w.q_last = w.qb + up(E * dof * sizeof(float));
+    w.margin = w.q_last + up((size_t)R * dof * sizeof(float));
+    w.c_cost = w.margin + up(DCX_MAX_C * sizeof(float));
+    w.c_ga = w.c_cost + up((size_t)R * sizeof(float));
+    w.c_gb = w.c_ga + up((size_t)R * dof * sizeof(float));
+    w.c_n = w.c_gb + up((size_t)R * dof * sizeof(float));
+    w.e_cost = w.c_n + up((size_t)R * sizeof(int32_t));
+    w.e_ga = w.e_cost + up(E * sizeof(float));
+    w.e_gb = w.e_ga + up(E * dof * sizeof(float));
+    w.e_n = w.e_gb + up(E * dof * sizeof(float));
+    w.motion = w.e_n + up(E * sizeof(int32_t));
+    w.total = w.motion + motion_cost_work(m, (int64_t)E, max_samples).total;
+    return w;
+}
+// (check_traj without col_score / col_grad, which the dense step does not read, and with the dense structs)
+int check_traj_dense(const dcx_traj_state* st, const dcx_traj_opts* opt, const dcx_traj_dense_opts* dopt, const dcx_traj_dense_io* io,
+                     int dof, bool need_edges) {
+    if (!st || !opt || !dopt || !io) return fail(DCX_ERR_INVALID, "dense trajectory: state / opts / dense opts / io is NULL");
+    if (st->n_paths < 0 || st->n_waypoints < 2 || st->n_waypoints > 1024)
+        return fail(DCX_ERR_UNSUPPORTED, "trajectory step needs 2 <= n_waypoints <= 1024 and n_paths >= 0");
+    if (st->n_paths > 0 && (!st->path || !st->adam_m || !st->adam_v || !st->limits || !st->stats || !st->lowest_loss ||
+                            !st->lowest_obj || !st->lowest_path || !st->best_valid_obj || !st->best_valid_path || !st->done ||
+                            !st->steps))
+        return fail(DCX_ERR_INVALID, "a trajectory state pointer is NULL");
+    if (!(opt->lr >= 0.f) || !(opt->beta1 >= 0.f && opt->beta1 < 1.f) || !(opt->beta2 >= 0.f && opt->beta2 < 1.f))
+        return fail(DCX_ERR_INVALID, "Adam options out of range");
+    if (!(dopt->max_step > 0.f)) return fail(DCX_ERR_INVALID, "dense trajectory: max_step must be > 0");
+    if (dopt->max_samples < 1) return fail(DCX_ERR_INVALID, "dense trajectory: max_samples must be >= 1");
+    if (dopt->normalize != 0 && dopt->normalize != 1) return fail(DCX_ERR_INVALID, "dense trajectory: normalize must be 0 or 1");
+    if (!(dopt->stop_tol >= 0.f)) return fail(DCX_ERR_INVALID, "dense trajectory: stop_tol must be >= 0");
+    if (dopt->reserved[0] || dopt->reserved[1] || dopt->reserved[2] || dopt->reserved[3])
+        return fail(DCX_ERR_INVALID, "dense trajectory: reserved fields must be 0");
+    if (dof < 64 && ((dopt->wrap_mask >> dof) != 0 || (dopt->rewrap_mask >> dof) != 0))
+        return fail(DCX_ERR_INVALID, "dense trajectory: wrap_mask / rewrap_mask has a bit at or above dof");
+    const int n_edge = (io->edge_cost ? 1 : 0) + (io->grad_a ? 1 : 0) + (io->grad_b ? 1 : 0) + (io->n_samples ? 1 : 0);
+    if (n_edge != 0 && n_edge != 4) return fail(DCX_ERR_INVALID, "dense trajectory: give all four per-edge arrays or none");
+    if (st->n_paths > 0 && need_edges && n_edge != 4) return fail(DCX_ERR_INVALID, "dense trajectory step: a per-edge array is NULL");
+    if (st->n_paths > 0 && !io->n_checks) return fail(DCX_ERR_INVALID, "dense trajectory: n_checks is NULL");
+    return DCX_OK;
+}
+}  // namespace
+
+int dcx_traj_dense_step(int device, const dcx_fk_desc* fk, const dcx_traj_state* st, const dcx_traj_opts* opt,
+                        const dcx_traj_dense_opts* dopt, const dcx_traj_dense_io* io, int32_t C, int32_t step, void* stream) {
+    if (!fk) return fail(DCX_ERR_INVALID, "fk is NULL");
+    if (C < 1 || C > DCX_MAX_C) return fail(DCX_ERR_UNSUPPORTED, "trajectory step: 1 <= C <= DCX_MAX_C");
+    if (step < 1) return fail(DCX_ERR_INVALID, "step is 1-based");
+    if (int rc = check_fk(*fk)) return rc;
+    if (int rc = check_traj_dense(st, opt, dopt, io, fk->dof, true)) return rc;
+    if (int rc = set_device(device)) return rc;
+    FkProg* dev = nullptr;
+    if (int rc = fk_device_copy(device, *fk, &dev)) return rc;
+    hipError_t e = launch_traj_dense_step(dev, *fk, *st, *opt, *dopt, *io, C, step, (hipStream_t)stream);
+    if (e != hipSuccess) return fail_hip(e, "dense trajectory step launch");
+    return DCX_OK;
+}
+
+size_t dcx_traj_dense_work_bytes(const dcx_model* m, int32_t R, int32_t W, int32_t max_samples) {
+    if (!m || R < 0 || W < 2 || max_samples < 1) return 0;
+    return traj_dense_work(m, R, W, max_samples).total;
+}
+
+int dcx_traj_dense_run(const dcx_model* m, const dcx_traj_state* st, const dcx_traj_opts* opt, const dcx_traj_dense_opts* dopt,
+                       const dcx_traj_dense_io* io, const float* margin, int32_t first_step, int32_t n_iters, void* work,
+                       size_t work_bytes, void* stream) {
+    // every argument is checked before anything touches the device
+    if (!m) return fail(DCX_ERR_INVALID, "model is NULL");
+    if (first_step < 1 || n_iters < 0) return fail(DCX_ERR_INVALID, "first_step is 1-based, n_iters >= 0");
+    if (int rc = check_traj_dense(st, opt, dopt, io, m->fk.dof, false)) return rc;
+    const int R = st->n_paths, W = st->n_waypoints, dof = m->fk.dof;
+    if (R == 0 || n_iters == 0) return DCX_OK;   // nothing to do needs no buffers
+    if (!work) return fail(DCX_ERR_INVALID, "dense trajectory: work is NULL");
+    if (work_bytes < traj_dense_work(m, R, W, dopt->max_samples).total)
+        return fail(DCX_ERR_INVALID, "dense trajectory workspace is smaller than dcx_traj_dense_work_bytes");
+    // what dcx_motion_cost_ex could still refuse depends on (model, R, W, max_samples) alone: refused here, before the first launch
+    if (((int64_t)R * W * (int64_t)dopt->max_samples + 63) / 64 > 0x7fffffffLL)
+        return fail(DCX_ERR_UNSUPPORTED, "dense trajectory: R * W * max_samples too large for one launch");
+    if (!motion_cost_for(m->Dt)) return fail(DCX_ERR_UNSUPPORTED, "dense trajectory: no motion-cost kernel for this feature width");
+    if (int rc = set_device(m->device)) return rc;
+    hipStream_t s = (hipStream_t)stream;
+    const TrajDenseWork w = traj_dense_work(m, R, W, dopt->max_samples);
+    char* base = (char*)work;
+    dcx_traj_dense_io o = *io;
+    if (!o.edge_cost) {
+        o.edge_cost = (float*)(base + w.e_cost);
+        o.grad_a = (float*)(base + w.e_ga);
+        o.grad_b = (float*)(base + w.e_gb);
+        o.n_samples = (int32_t*)(base + w.e_n);
+    }
+    TrajDenseEdgeArgs ea{};
+    ea.path = st->path;
+    ea.qb = (float*)(base + w.qb);
+    ea.q_last = (float*)(base + w.q_last);
+    ea.margin_fill = margin ? nullptr : (float*)(base + w.margin);
+    ea.margin_value = opt->safety_margin;
+    ea.R = R;
+    ea.W = W;
+    ea.dof = dof;
+    ea.C = m->C;
+    const float* margin_dev = margin ? margin : ea.margin_fill;
+    TrajDenseCloseArgs ca{};
+    ca.cost = (float*)(base + w.c_cost);
+    ca.grad_a = (float*)(base + w.c_ga);
+    ca.grad_b = (float*)(base + w.c_gb);
+    ca.n_samples = (int32_t*)(base + w.c_n);
+    ca.io = o;
+    ca.R = R;
+    ca.W = W;
+    ca.dof = dof;
+    dcx_motion_cost_opts mo{};
+    mo.max_step = dopt->max_step;
+    mo.max_samples = dopt->max_samples;
+    void* mwork = base + w.motion;
+    const size_t mbytes = work_bytes - w.motion;
+    const int64_t E = (int64_t)R * W;
+    for (int it = 0; it < n_iters; ++it) {
+        hipError_t e = launch_traj_dense_edges(ea, s);
+        if (e != hipSuccess) return fail_hip(e, "dense trajectory edge-list launch");
+        // the open edges: all R * W slots, slot W - 1 of a path zero-length (no sample, cost and gradients 0) ...
+        mo.open_end = 1;
+        if (int rc = dcx_motion_cost_ex(m, st->path, ea.qb, E, &mo, margin_dev, 1.f, o.edge_cost, o.grad_a, o.grad_b, o.n_samples, mwork,
+                                        mbytes, dopt->wrap_mask, stream))
+            return rc;
+        // ... and the R closed ones on the last waypoints, into slot W - 1
+        mo.open_end = 0;
+        if (int rc = dcx_motion_cost_ex(m, ea.q_last, ea.q_last, R, &mo, margin_dev, 1.f, const_cast<float*>(ca.cost),
+                                        const_cast<float*>(ca.grad_a), const_cast<float*>(ca.grad_b),
+                                        const_cast<int32_t*>(ca.n_samples), mwork, mbytes, dopt->wrap_mask, stream))
+            return rc;
+        e = launch_traj_dense_close(ca, s);
+        if (e != hipSuccess) return fail_hip(e, "dense trajectory closed-edge launch");
+        e = launch_traj_dense_step(m->fk_dev, m->fk, *st, *opt, *dopt, o, m->C, first_step + it, s);
+        if (e != hipSuccess) return fail_hip(e, "dense trajectory step launch");
+        if (o.history) o.history += (size_t)R * W * dof;
+    }
     return DCX_OK;
 }
 

@@ -8,6 +8,8 @@
 //
 // Mapping: one block per path, one lane per waypoint (W <= 1024); a wave owns 64 consecutive waypoints and
 // keeps their control points in its own LDS slab, so a waypoint reads its neighbours' control points from LDS.
+// traj_dense.hip (traj_dense_step_kernel) restates this kernel's FK staging, path terms, Adam update and bookkeeping with the
+// collision term taken per edge: a change to that arithmetic here belongs there as well.
 #include <cmath>
 
 #include "dcx_internal.h"

@@ -18,7 +18,7 @@ Differences worth knowing:
     Hessian and SLSQP / trust-constr records (tests/golden/optim_scipy_baxter.npz, tools/make_golden.py gen_optim_scipy).
 """
 import time
-from typing import Dict
+from typing import Dict, NamedTuple
 
 import numpy as np
 import torch
@@ -463,3 +463,193 @@ def gradient_free_traj_optimize(robot, checker, start_cfg, target_cfg, options: 
     rec = _scipy_driver(robot, checker, start_cfg, target_cfg, options, run, dense_cap=cap)
     options['safety_margin'] = saved_margin
     return rec
+
+
+# ================================================================================ Weighted (dense-check penalty method)
+class OptimizerResult(NamedTuple):
+    """what a TrajOptimizer's step() returns: the path and misc = {'path_history': [...], 'time': seconds}"""
+    x: torch.Tensor
+    misc: dict
+
+
+class TrajOptimizer:
+    """A trajectory optimiser bound to a robot and a checker.  `unnormalizer` is applied to the path handed to step() before
+    anything else, `normalizer` to every path handed back (identity by default)."""
+
+    def __init__(self, robot, checker, options):
+        self.robot, self.checker, self.options = robot, checker, options
+        self.normalizer = lambda x: x
+        self.unnormalizer = lambda x: x
+
+    def step(self, x):
+        raise NotImplementedError
+
+    def set_unnormalizer(self, f):
+        self.unnormalizer = f
+
+    def set_normalizer(self, f):
+        self.normalizer = f
+
+    def set_checker(self, checker):
+        self.checker = checker
+
+    def set_robot(self, robot):
+        self.robot = robot
+
+
+def _wrap_bits(robot, dof):
+    """the coordinates `robot.wrap` takes to [-pi, pi) as a bit mask, or None when wrap is not `utils.wrap2pi` on a fixed set
+    of coordinates (probed on values inside and outside the interval)"""
+    probe = torch.tensor([[4.0] * dof, [-5.0] * dof, [0.5] * dof, [11.0] * dof], dtype=torch.float64)
+    out = robot.wrap(probe.clone())
+    if tuple(out.shape) != tuple(probe.shape):
+        return None
+    ref = utils.wrap2pi(probe)
+    mask = 0
+    for j in range(dof):
+        if torch.equal(out[:, j], ref[:, j]):
+            mask |= 1 << j
+        elif not torch.equal(out[:, j], probe[:, j]):
+            return None
+    return mask
+
+
+class Weighted(TrajOptimizer):
+    """Penalty-method optimiser of ONE path: per iteration
+        loss = |cp[1:] - cp[:-1]|^2  +  collision_weight * mean over the checked points of clamp(score + safety_bias, 0) * W
+             + max_move_weight * sum clamp(|cp[w+1] - cp[w]|^2 - max_speed^2, 0)  +  joint_limit_weight * (limit violation)
+    a step of options['optimizer'](**options['optimizer_params']) with the gradient of the waypoints where `mask` is False
+    zeroed, robot.wrap of the path, and a stop behind the step whose constraint part was <= 0.5.  options['dense_check']: the
+    checked points are utils.dense_path(p, max_speed) instead of the waypoints.
+
+    Two routes, `last_route` says which one step() took:
+      'fused'  options['optimizer'] is torch.optim.Adam with only lr / betas / eps set, dense_check is true, and the checker's
+               score fuses with this robot's fkine: the whole loop runs on the device (traj.DenseAdamRun, dcx_traj_dense_run)
+               with nothing read back until it ends
+      'host'   anything else: the same loop in torch on the checker's score
+    `wrap` (an extra keyword of step(), as on the motion calls; fused route only) samples the segments along the shortest arc of
+    the masked coordinates; None samples them linearly."""
+
+    def __init__(self, robot, checker, options):
+        super().__init__(robot, checker, options)
+        # the step rule and when it stops
+        self.optimizer, self.optimizer_params = options['optimizer'], options['optimizer_params']
+        self.maxiter, self.history = options['maxiter'], options['history']
+        # the loss: weights (the path-length term's is fixed), the hinge's bias, and where the hinge is charged
+        self.dif_weight = DIF_WEIGHT
+        self.collision_weight, self.safety_bias = options['collision_weight'], options['safety_bias']
+        self.max_move_weight, self.max_speed = options['max_move_weight'], options['max_speed']
+        self.joint_limit_weight = options['joint_limit_weight']
+        self.dense_check = options['dense_check']
+        self.n_waypoints = options['n_waypoints']
+        self.last_route = None
+        self._logger = None
+
+    def setup_logger(self, logger):
+        self._logger = logger
+
+    def _dist_est(self):
+        for name in ('rbf_score', 'poly_score', 'score'):
+            est = getattr(self.checker, name, None)
+            if est is not None:
+                return est
+        raise TypeError("Weighted needs a checker with rbf_score / poly_score / score")
+
+    def _fusable(self, dist_est, dof):
+        """(model, rewrap mask) when step() can take the fused route, else None"""
+        if self.optimizer is not torch.optim.Adam or not self.dense_check:
+            return None
+        if not set(self.optimizer_params) <= {'lr', 'betas', 'eps'}:
+            return None
+        from . import traj
+        try:
+            model = traj._resolve_model(dist_est)
+        except TypeError:
+            return None
+        fk = getattr(self.robot, 'fk_desc', None)
+        if not callable(fk) or fk().key() != model.desc.key():
+            return None
+        bits = _wrap_bits(self.robot, dof)
+        return None if bits is None else (model, bits)
+
+    @torch.inference_mode(False)
+    def step(self, p, maxiter=None, mask=None, write=True, verbose=False, wrap=None):
+        t0 = time.time()
+        if not isinstance(p, torch.Tensor):
+            p = torch.as_tensor(np.asarray(p), dtype=torch.float32)
+        p = self.unnormalizer(p)
+        maxiter = self.maxiter if maxiter is None else maxiter
+        dist_est = self._dist_est()
+        fuse = self._fusable(dist_est, p.shape[-1])
+        if verbose and self._logger is not None:
+            self._logger.info(f'Weighted.step: up to {maxiter} iterations')
+        if fuse is not None:
+            self.last_route = 'fused'
+            x, hist = self._step_fused(p, maxiter, mask, wrap, *fuse)
+        else:
+            if wrap is not None:
+                raise ValueError("Weighted.step(wrap=...) needs the fused route (Adam, dense_check, a fusable checker)")
+            self.last_route = 'host'
+            x, hist = self._step_host(p, maxiter, mask, dist_est, verbose)
+        return OptimizerResult(x=self.normalizer(x), misc={'path_history': hist, 'time': time.time() - t0})
+
+    def _step_fused(self, p, maxiter, mask, wrap, model, rewrap):
+        from . import _ops, traj
+        W, dof = p.shape
+        move = torch.ones(W, dtype=torch.bool) if mask is None else torch.as_tensor(mask).reshape(-1).bool().cpu()
+        kw = self.optimizer_params
+        run = traj.DenseAdamRun(model, self.robot.limits, p.detach()[None], kw.get('lr', 1e-3), -self.safety_bias, self.max_speed,
+                                max_samples=self.options.get('dense_max_samples'), wrap=_ops.wrap_mask(wrap, dof, self.robot.fkine),
+                                rewrap=rewrap, normalize=True, stop_tol=0.5, move=move, history=bool(self.history),
+                                weights=(self.dif_weight, self.collision_weight, self.max_move_weight, self.joint_limit_weight),
+                                betas=kw.get('betas', (0.9, 0.999)), eps=kw.get('eps', 1e-8), valid_tol=-1.0, grad_tol=0.0)
+        try:
+            run.run(int(maxiter))
+            if bool(run.over_bound().any()):
+                raise _lib.DcxError(f"Weighted: a segment needed more than {run.max_samples} samples of max_speed = {self.max_speed}; "
+                                    "set options['dense_max_samples']")
+            steps = int(run.t['steps'][0])
+            x = run.t['path'][0].cpu()
+            hist = [self.normalizer(h[0].cpu()) for hh in run.history for h in hh][:steps] if self.history else []
+            self.cnt_check = int(run.n_checks[0])
+        finally:
+            run.close()
+        return x, hist
+
+    def _step_host(self, p, maxiter, mask, dist_est, verbose):
+        dev = getattr(self.checker, 'device', None)
+        p = p.detach().clone().to(dev) if dev is not None else p.detach().clone()
+        p.requires_grad_(True)
+        opt = self.optimizer([p], **self.optimizer_params)
+        limits = self.robot.limits.to(p.device, p.dtype)
+        axis = _coord_axis(self.robot)
+        keep = None if mask is None else torch.as_tensor(mask).reshape(-1).bool().to(p.device)
+        hist = []
+        for it in range(maxiter):
+            opt.zero_grad()
+            collision = p.new_zeros(())
+            if self.collision_weight != 0:
+                check_p = utils.dense_path(p, max_step=self.max_speed) if self.dense_check else p
+                collision = torch.clamp(dist_est(check_p) + self.safety_bias, min=0).mean() * len(p)
+            cp = self.robot.fkine(p)
+            seg = cp[1:] - cp[:-1]
+            max_move = torch.clamp(seg.square().sum(dim=axis) - self.max_speed ** 2, min=0).sum() if self.max_move_weight != 0 \
+                else p.new_zeros(())
+            joint = (torch.clamp(limits[:, 0] - p, min=0) + torch.clamp(p - limits[:, 1], min=0)).sum() \
+                if self.joint_limit_weight != 0 else p.new_zeros(())
+            constraint = self.collision_weight * collision + self.max_move_weight * max_move + self.joint_limit_weight * joint
+            loss = self.dif_weight * seg.square().sum() + constraint
+            loss.backward()
+            if keep is not None:
+                p.grad[~keep] = 0.0
+            opt.step()
+            p.data = self.robot.wrap(p.data)
+            if verbose and self._logger is not None and (it % max(1, maxiter // 5) == 0 or it + 1 == maxiter):
+                self._logger.info(f"iteration {it + 1}: length {float(seg.square().sum()):.3f}, collision {float(collision):.3f} "
+                                  f"(weight {self.collision_weight}), max-move {float(max_move):.3f} (weight {self.max_move_weight}), "
+                                  f"joint limits {float(joint):.3f} (weight {self.joint_limit_weight})")
+            if self.history:
+                hist.append(self.normalizer(p.detach().cpu().clone()))
+            if float(constraint.detach()) <= 0.5:
+                break
+        return p.detach().cpu(), hist

@@ -158,10 +158,136 @@ class ShardedAdamRun:
         return summ.cpu(), bvp, lop
 
 
-def fused_adam_traj_optimize(robot, dist_est, start_cfg, target_cfg, options, group=None):
+class DenseAdamRun:
+    """R restarts of one trajectory problem advanced together by the dense-check Adam loop (`dcx_traj_dense_run`): the
+    collision hinge is charged on the points of utils.dense_path(p, max_step) - along the segments, not at the waypoints only -
+    so a path cannot pass through an obstacle thinner than a stride between two waypoints.  ShardedAdamRun's shape (buffers,
+    lease, run(n), all_done(), finish()) on one device; per iteration the library's motion-cost launches and one step launch,
+    nothing read back.
+
+    normalize: the collision term is the MEAN hinge times W (Weighted's) instead of the sum (path_cost's).  move: [W] bools, a
+    waypoint with False keeps its place (None: the endpoints are fixed).  wrap: the SAMPLING mask (the motion calls' `wrap`);
+    rewrap: the coordinates wrapped to [-pi, pi) after every step.  stop_tol > 0: a restart whose constraint value is <= stop_tol
+    takes that step and stops.  history=True: run(n) keeps the paths after each of its steps in self.history ([n, R, W, dof]
+    per call).  max_samples: the most samples one segment may need; a restart with a longer segment is frozen where it stands
+    (`over_bound()`); None: twice the longest initial segment's count plus 8."""
+
+    def __init__(self, model, limits, init_paths, lr, safety_margin, max_step, max_speed=None, max_samples=None, wrap=None,
+                 rewrap=None, normalize=False, stop_tol=0., move=None, history=False, weights=None, betas=(0.9, 0.999), eps=1e-8,
+                 valid_tol=None, grad_tol=None):
+        self.lib = _lib.require_gpu()
+        self.model = model.acquire()   # a lease: the checker's cache must not refill these rows under the run
+        dev = model.dev
+        f32 = dict(device=dev, dtype=torch.float32)
+        R, W, dof = init_paths.shape
+        self.R, self.W, self.dof = R, W, dof
+        path = init_paths.to(**f32).contiguous().clone()
+        inf = float('inf')
+        mask, remask = _ops.wrap_mask(wrap, dof), _ops.wrap_mask(rewrap, dof)
+        if max_samples is None:
+            bound = _ops.motion_bound(path[:, :-1].reshape(-1, dof), path[:, 1:].reshape(-1, dof), max_step, wrap=mask) if R else 1
+            max_samples = min(_ops.MOTION_MAX_SAMPLES, 2 * bound + 8)
+        self.max_samples = int(max_samples)
+        self.margin = torch.tensor(list(model.margins(safety_margin)), dtype=torch.float32).to(dev)   # [C] device floats
+        self.t = dict(path=path, adam_m=torch.zeros_like(path), adam_v=torch.zeros_like(path),
+                      limits=limits.to(**f32).contiguous(), stats=torch.zeros((R, 8), **f32),
+                      lowest_loss=torch.full((R,), inf, **f32), lowest_obj=torch.full((R,), inf, **f32),
+                      lowest_path=path.clone(), best_valid_obj=torch.full((R,), inf, **f32),
+                      best_valid_path=path.clone(), done=torch.zeros((R,), device=dev, dtype=torch.int32),
+                      steps=torch.zeros((R,), device=dev, dtype=torch.int32))
+        self.n_checks = torch.zeros((R,), device=dev, dtype=torch.int64)
+        self.move = None if move is None else torch.as_tensor(move).reshape(-1).to(device=dev, dtype=torch.bool).to(torch.uint8).contiguous()
+        if self.move is not None and len(self.move) != W:
+            raise ValueError(f"move: expected one flag per waypoint ({W}), got {len(self.move)}")
+        ptr = lambda v: C.c_void_p(v.data_ptr() if v is not None and v.numel() else 0)
+        t = self.t
+        self.st = _lib.TrajState(R, W, ptr(t['path']), ptr(t['adam_m']), ptr(t['adam_v']), ptr(t['limits']), None, None,
+                                 ptr(t['stats']), ptr(t['lowest_loss']), ptr(t['lowest_obj']), ptr(t['lowest_path']),
+                                 ptr(t['best_valid_obj']), ptr(t['best_valid_path']), ptr(t['done']), ptr(t['steps']))
+        w = (DIF_WEIGHT, COLLISION_WEIGHT, MAX_MOVE_WEIGHT, JOINT_LIMIT_WEIGHT) if weights is None else tuple(float(v) for v in weights)
+        self.opt = _lib.TrajOpts(float(lr), float(betas[0]), float(betas[1]), float(eps), *w, float(self.margin[0]) if R else 0.,
+                                 float(max_step if max_speed is None else max_speed),
+                                 VALID_CONSTRAINT_LOSS if valid_tol is None else float(valid_tol),
+                                 STATIONARY_GRAD_NORM if grad_tol is None else float(grad_tol))
+        self.dopt = _lib.TrajDenseOpts(float(max_step), self.max_samples, mask, remask, 1 if normalize else 0, float(stop_tol))
+        nbytes = int(self.lib.dcx_traj_dense_work_bytes(model._h, R, W, self.max_samples))
+        self.work = torch.empty(max(nbytes, 1), device=dev, dtype=torch.uint8)
+        self.work_bytes = nbytes
+        self.keep_history, self.history = bool(history), []
+        self.it = 0
+
+    close = ShardedAdamRun.close
+    __del__ = ShardedAdamRun.__del__
+
+    def run(self, n_iters):
+        """enqueue n_iters more iterations on torch's current stream (no host synchronisation)"""
+        if self.R and n_iters > 0:
+            dev = self.model.dev
+            hist = torch.empty((n_iters, self.R, self.W, self.dof), device=dev, dtype=torch.float32) if self.keep_history else None
+            io = _lib.TrajDenseIO(C.c_void_p(self.move.data_ptr()) if self.move is not None else None,
+                                  C.c_void_p(hist.data_ptr()) if hist is not None else None, C.c_void_p(self.n_checks.data_ptr()),
+                                  None, None, None, None)
+            with torch.cuda.device(dev):
+                _lib.check(self.lib.dcx_traj_dense_run(self.model._h, C.byref(self.st), C.byref(self.opt), C.byref(self.dopt),
+                                                       C.byref(io), C.c_void_p(self.margin.data_ptr()), self.it + 1, int(n_iters),
+                                                       C.c_void_p(self.work.data_ptr()), self.work_bytes, self.model._st()))
+            if hist is not None:
+                self.history.append(hist)
+        self.it += n_iters
+
+    def all_done(self):
+        return self.R == 0 or bool(self.t['done'].all())
+
+    def over_bound(self):
+        """bool [R] on the host: the restarts frozen because a segment needed more than max_samples samples"""
+        return (self.t['stats'][:, 7] == -2).cpu()
+
+    def finish(self):
+        """(summaries [R, 5] on the host: best_valid_obj, lowest_loss, lowest_obj, steps, n_checks; best_valid_path,
+        lowest_path [R, W, dof] on the device)"""
+        t = self.t
+        summ = torch.stack([t['best_valid_obj'].double(), t['lowest_loss'].double(), t['lowest_obj'].double(), t['steps'].double(),
+                            self.n_checks.double()], dim=1)
+        return summ.cpu(), t['best_valid_path'], t['lowest_path']
+
+
+def _dense_adam_traj_optimize(robot, model, prob, inits, options, lr, wrap, t0, start_cfg, target_cfg):
+    """fused_adam_traj_optimize under options['dense_check']: the same restarts, selection policy and record, on DenseAdamRun"""
+    max_iter, seed = options['MAXITER'], options['seed']
+    W = inits[0].shape[0]
+    run = DenseAdamRun(model, robot.limits, torch.stack(inits), lr, prob.safety_margin, prob.max_speed,
+                       max_samples=options.get('dense_max_samples'), wrap=wrap, grad_tol=options.get('stationary_grad_norm'))
+    chunk = int(options.get('fused_chunk', 50))
+    while run.it < max_iter:
+        run.run(min(chunk, max_iter - run.it))
+        if run.it < max_iter and run.all_done():
+            break
+    summ, best_valid_path, lowest_path = run.finish()
+    over = run.over_bound()
+    run.close()
+    bvo, lol, loo, nst, nck = (summ[:, i] for i in range(5))
+    t_win, found, cost, _ = select_trial(bvo.float(), lol.float(), loo.float(), nst, W)
+    cnt = int(nck[:t_win + 1].sum().item()) if found else int(nck.sum().item())
+    solution = (best_valid_path if found else lowest_path)[t_win]
+    return {'start_cfg': _np(start_cfg).tolist(), 'target_cfg': _np(target_cfg).tolist(), 'cnt_check': cnt,
+            'cost': cost, 'time': time.time() - t0, 'success': found, 'seed': seed,
+            'solution': solution.double().cpu().numpy().tolist(),
+            'trial': t_win, 'cnt_check_batched': int(nck.sum().item()), 'iterations_enqueued': run.it,
+            'dense_check': True, 'dense_max_samples': run.max_samples,
+            'dense_frozen_on_bound': [int(i) for i in torch.nonzero(over).reshape(-1)]}
+
+
+def fused_adam_traj_optimize(robot, dist_est, start_cfg, target_cfg, options, group=None, wrap=None):
     """Drop-in for `optim.adam_traj_optimize` with all restarts batched on the GPU.  With an initialised
     torch.distributed `group` (or the default group when options['distributed'] is true) the restarts are sharded
-    across ranks (`ShardedAdamRun`); every rank returns the same record."""
+    across ranks (`ShardedAdamRun`); every rank returns the same record.
+
+    options['dense_check'] true: the collision hinge is charged along the segments (`DenseAdamRun`, one device; the points of
+    utils.dense_path(p, max_speed)); options['dense_max_samples'] bounds one segment's samples (default: from the longest
+    initial segment, with headroom) and the record's 'dense_frozen_on_bound' lists the restarts that froze on it.  `wrap`, as on
+    the motion calls, samples along the shortest arc of the masked coordinates.  'cnt_check' then counts the samples scored."""
+    if wrap is not None and not options.get('dense_check'):
+        raise ValueError("fused_adam_traj_optimize(wrap=...) needs options['dense_check']: the waypoint-only loop samples no segment")
     n_trials, max_iter = options['NUM_RE_TRIALS'], options['MAXITER']
     lr = options.get('extra_optimizer_options', {}).get('lr', 5e-1)
     seed = options['seed']
@@ -182,6 +308,9 @@ def fused_adam_traj_optimize(robot, dist_est, start_cfg, target_cfg, options, gr
                 'solution': inits[0].numpy().tolist()}
     if any(p.shape != (W, dof) for p in inits):
         raise ValueError("all restarts must have the same number of waypoints (init_solution vs N_WAYPOINTS)")
+    if options.get('dense_check'):
+        return _dense_adam_traj_optimize(robot, model, prob, inits, options, lr, _ops.wrap_mask(wrap, dof, robot.fkine), t0,
+                                         start_cfg, target_cfg)
 
     run = ShardedAdamRun(model, robot.limits, torch.stack(inits), lr, prob.safety_margin, prob.max_speed,
                          grad_tol=options.get('stationary_grad_norm'), group=group,

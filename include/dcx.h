@@ -487,6 +487,78 @@ int dcx_motion_worst(const dcx_model* m, const float* qa, const float* qb, int64
                      const float* margin, float* worst, int32_t* worst_idx, int32_t* worst_class, int32_t* n_samples,
                      float* grad_a, float* grad_b, void* work, size_t work_bytes, uint64_t wrap_mask, void* stream);
 
+/* ---- dense-check Adam trajectory loop (added under DCX_VERSION 109) --------------------------------------- */
+/* dcx_traj_adam_run charges the collision hinge at the waypoints only; here it is charged along the segments: the dense-check
+ * form of Weighted.step (optim.py:706-752 with dense_check=True).  R independent paths p = path[r] [W, dof]; one iteration:
+ *   sample set   the points of utils.dense_path(p, max_step): for w < W - 1 the OPEN max_step edge p[w] -> p[w+1]
+ *                (dcx_motion_cost_ex's samples with open_end = 1), then the single sample p[W-1] (the closed zero-length edge
+ *                p[W-1] -> p[W-1]).  wrap_mask != 0: every edge along the shortest arc, exactly as in dcx_motion_cost_ex
+ *   collision    coll_sum = sum over the N_r samples x_k and the classes c of max(0, score_c(x_k) - margin_c)
+ *                normalize = 0: collision = coll_sum                    (ScoreModel.path_cost, the scipy drivers' sum)
+ *                normalize = 1: collision = coll_sum * W / (N_r * C)    (Weighted's .mean() * len(p))
+ *                gradients through the interpolation with the sample counts, and so N_r, held constant (dcx_motion_cost)
+ *   the rest     as dcx_traj_adam_step: path length in control-point space, max-move, joint limits, Adam with bias correction,
+ *                stats[r, 0..6] (stats[r, 4] = collision as defined above), lowest-loss / best-valid bookkeeping, steps, the
+ *                valid_tol / grad_tol stop
+ *   move [W]     bytes, device, may be NULL: a waypoint whose byte is 0 gets a zero gradient (Weighted's mask, shared by the R
+ *                paths).  NULL: the two endpoints are fixed, dcx_traj_adam_step's rule
+ *   rewrap_mask  after the Adam update coordinate j with bit j set becomes wrap2pi(q_j) (the escape loop's function, see
+ *                dcx_motion_cost_ex) - robot.wrap after opt.step().  Independent of the SAMPLING wrap_mask: the reference wraps
+ *                after the step but samples linearly
+ *   stop_tol > 0 a path whose constraint value of THIS iteration (stats[r, 2]) is <= stop_tol takes this step and is then
+ *                frozen (done[r] = 1): Weighted's `if constraint_loss <= 0.5: break` after opt.step().  0: no such stop
+ *   history      may be NULL: [n_iters, R, W, dof], the path after each step of this call; a frozen path's row repeats
+ *   n_checks [R] int64, device, in/out: samples scored so far (+= N_r per step taken)
+ *   an edge needing more than max_samples samples (dcx_motion_cost_ex answers NaN; so does a NaN cost): the path takes NO step
+ *                and is frozen - done[r] = 1, stats[r, 7] = -2, and path, moments, bookkeeping, steps, n_checks and
+ *                stats[r, 0..6] are untouched (its history row is the unchanged path)
+ * The per-edge arrays of dcx_traj_dense_io hold dcx_motion_cost_ex's outputs (weight = 1) in the layout e = r * W + w: slot
+ * w < W - 1 is the open edge leaving waypoint w, slot W - 1 the closed zero-length edge on the last waypoint (its grad_a 0, its
+ * grad_b the hinge gradient at p[W-1], its n_samples 1).  The collision gradient of waypoint w is grad_a[e(r, w)] +
+ * grad_b[e(r, w-1)] (no left neighbour at w = 0; at w = W - 1 the closed edge's grad_b as well), scaled by w_collision and,
+ * under normalize, by W / (N_r * C).  N_r and coll_sum are summed in waypoint order: repeated calls return the same bits.
+ *
+ * dcx_traj_dense_step: the step half alone, ONE launch on per-edge arrays that already hold this iteration's motion costs;
+ *   st->col_score / st->col_grad are not read and may be NULL; io->history, if given, is THIS step's row [R, W, dof]; C is
+ *   the class count of the normalisation.
+ * dcx_traj_dense_run: n_iters iterations on the caller's stream, starting at 1-based step first_step; per iteration
+ *   1. an edge-list launch (the shifted path qb[e] = p[min(w + 1, W - 1)] beside qa = path itself, and the R last waypoints)
+ *   2. dcx_motion_cost_ex's launches twice: the R * W open slots (slot W - 1 is zero-length: no sample, cost 0), then the R
+ *      closed edges, whose results a small launch copies into slot W - 1
+ *   3. the dense step
+ *   The per-edge results go into the io arrays, or into the workspace where the caller leaves all four NULL.  margin: [C]
+ *   DEVICE floats as in the motion calls; NULL = opt->safety_margin for every class (kept in the workspace).  No allocation,
+ *   no synchronisation, nothing read back: the call can be captured.  work: dcx_traj_dense_work_bytes(model, R, W,
+ *   max_samples) bytes of device memory, the caller's; initialised by the call itself.
+ * Argument errors (DCX_ERR_INVALID, before any device work): NULL model / st / opt / dopt / io / n_checks / work / a state
+ *   pointer (R > 0), the per-edge arrays partly NULL (dcx_traj_dense_step: any of them NULL), n_iters < 0, first_step or step
+ *   < 1, max_step <= 0, max_samples < 1, normalize not 0 / 1, stop_tol < 0, a wrap_mask or rewrap_mask bit at or above dof,
+ *   reserved not 0, work_bytes below dcx_traj_dense_work_bytes.  W outside 2 .. 1024: DCX_ERR_UNSUPPORTED.            */
+typedef struct dcx_traj_dense_opts {
+    float max_step;        /* > 0: the sampling stride (Weighted: max_speed)                                            */
+    int32_t max_samples;   /* >= 1: a path with an edge needing more is frozen (-2).  It sizes the launches and the work  */
+    uint64_t wrap_mask;    /* sampling: bit j = coordinate j runs along its shortest arc                                  */
+    uint64_t rewrap_mask;  /* after the update: bit j = coordinate j is wrapped to [-pi, pi)                              */
+    int32_t normalize;     /* 0: collision = coll_sum;  1: coll_sum * W / (N_r * C)                                       */
+    float stop_tol;        /* > 0: freeze after the step whose constraint is <= stop_tol;  0: off                         */
+    int32_t reserved[4];   /* 0                                                                                         */
+} dcx_traj_dense_opts;
+typedef struct dcx_traj_dense_io {
+    const uint8_t* move;   /* [W] or NULL                                                                                */
+    float* history;        /* run: [n_iters, R, W, dof];  step: [R, W, dof];  or NULL                                    */
+    int64_t* n_checks;     /* [R] in/out                                                                                 */
+    float* edge_cost;      /* [R * W]                                                                                    */
+    float* grad_a;         /* [R * W, dof]                                                                               */
+    float* grad_b;         /* [R * W, dof]                                                                               */
+    int32_t* n_samples;    /* [R * W]                                                                                    */
+} dcx_traj_dense_io;
+int dcx_traj_dense_step(int device, const dcx_fk_desc* fk, const dcx_traj_state* st, const dcx_traj_opts* opt,
+                        const dcx_traj_dense_opts* dopt, const dcx_traj_dense_io* io, int32_t C, int32_t step, void* stream);
+size_t dcx_traj_dense_work_bytes(const dcx_model* m, int32_t R, int32_t W, int32_t max_samples);
+int dcx_traj_dense_run(const dcx_model* m, const dcx_traj_state* st, const dcx_traj_opts* opt, const dcx_traj_dense_opts* dopt,
+                       const dcx_traj_dense_io* io, const float* margin, int32_t first_step, int32_t n_iters, void* work,
+                       size_t work_bytes, void* stream);
+
 /* ---- kernel-perceptron trainer (producer of the path's state) ----------------------- */
 /* DiffCo.train_perceptron kernel_perceptrons.py:98-137 and MultiDiffCo.train_perceptron
  * deprecated/MultiDiffCo.py:50-83 as one persistent launch: worst-margin search, lazily filled kernel rows,
