@@ -1323,6 +1323,17 @@ static int check_traj(const dcx_traj_state* st, const dcx_traj_opts* opt, int do
     return DCX_OK;
 }
 
+// The step kernel (traj_kernels.hip) keeps one LDS slab per 64 waypoints: rows, control points, their gradient and the FK frames
+// of every waypoint of a path.  Whether that fits a CU's LDS depends on (transform, W) alone - host arithmetic, so a path too
+// long for its transform is refused before anything touches the device (it used to surface as a HIP error of the step launch,
+// inside the loop, behind the first sweep).
+static int check_traj_step_lds(const dcx_fk_desc& fk, const dcx_traj_state* st) {
+    if (traj_lds_bytes(fk, (st->n_waypoints + 63) / 64) > kCuLdsBytes)   // (n_paths = 0 included: the shape decides)
+        return fail(DCX_ERR_UNSUPPORTED, "trajectory step: n_waypoints is too large for this transform (the step kernel's LDS slabs of "
+                                         "ceil(n_waypoints / 64) x 64 waypoints exceed the 160 KB of a CU)");
+    return DCX_OK;
+}
+
 static int traj_step(int device, const dcx_fk_desc* fk, const dcx_traj_state* st, const dcx_traj_opts* opt, const float* margin,
                      int32_t C, int32_t step, void* stream) {
     if (!fk) return fail(DCX_ERR_INVALID, "fk is NULL");
@@ -1330,6 +1341,7 @@ static int traj_step(int device, const dcx_fk_desc* fk, const dcx_traj_state* st
     if (step < 1) return fail(DCX_ERR_INVALID, "step is 1-based");
     if (int rc = check_fk(*fk)) return rc;
     if (int rc = check_traj(st, opt, fk->dof)) return rc;
+    if (int rc = check_traj_step_lds(*fk, st)) return rc;
     if (int rc = set_device(device)) return rc;
     FkProg* dev = nullptr;
     if (int rc = fk_device_copy(device, *fk, &dev)) return rc;
@@ -1375,6 +1387,8 @@ static int traj_run(const dcx_model* m, const dcx_traj_state* st, const dcx_traj
     opt = &opt1;
     if (first_step < 1 || n_iters < 0) return fail(DCX_ERR_INVALID, "first_step is 1-based, n_iters >= 0");
     if (int rc = check_traj(st, opt, m->fk.dof)) return rc;
+    // (the persistent kernel's carve below holds everything the step kernel's does and more: what fits there passes here)
+    if (int rc = check_traj_step_lds(m->fk, st)) return rc;
     if (int rc = set_device(m->device)) return rc;
     const int64_t B = (int64_t)st->n_paths * st->n_waypoints;
     if (st->n_paths == 0 || n_iters == 0) return DCX_OK;
@@ -1400,11 +1414,15 @@ static int traj_run(const dcx_model* m, const dcx_traj_state* st, const dcx_traj
             while (ys > 1 && (m->S_active / (ys * nw) < min_rows || (int64_t)ys * st->n_paths > m->n_cu)) ys /= 2;
         }
         while (nw > 1 && m->S_active / (ys * nw) < 15) nw /= 2;
-        // the step-table walks on several waves (fk_device.h): chains of <= kDhUnroll steps and >= 4 waves per block
+        // the step-table walks on several waves (fk_device.h): chains of <= kDhUnroll steps, and enough waves for what the kernel
+        // runs in front of the sweep - the path terms on waves 0 / 1 and phase R1 of J^T on TWO waves PER CHAIN from wave 2 on
+        // (dh2_vjp_r1_sel): 4 waves for one chain, 6 for two.  (A two-chain arm in a 4-wave block - few supports, or a carve that
+        // lds_of cut - used to take this route with the second chain's R1 never run: a wrong gradient for its joints.)
         const bool dh_ok = m->fk.kind == DCX_FK_DH && m->dh_dev && knobs().fkk != 0 && knobs().fkk != 1 && knobs().jt_waves != 0 &&
                            m->dh.n_chains <= 2 && m->dh.end0 <= kDhUnroll && m->dh.n_steps - m->dh.end0 <= kDhUnroll;
+        const int jt_min_waves = 2 + 2 * m->dh.n_chains;
         auto lds_of = [&](int w) {
-            return sizeof(float) * (size_t)(traj_fused_plan(m->fk.dof, d_fk, m->frame_floats, w, m->Dt, (dh_ok && w >= 4) ? m->dh.n_pt : 0, m->Cc).total + m->prog_floats);
+            return sizeof(float) * (size_t)(traj_fused_plan(m->fk.dof, d_fk, m->frame_floats, w, m->Dt, (dh_ok && w >= jt_min_waves) ? m->dh.n_pt : 0, m->Cc).total + m->prog_floats);
         };
         while (nw > 1 && lds_of(nw) > 150 * 1024) nw /= 2;
         traj_fused_fn fn = traj_fused_for(m->Dt);
@@ -1414,7 +1432,7 @@ static int traj_run(const dcx_model* m, const dcx_traj_state* st, const dcx_traj
             for (int c = 0; c < DCX_MAX_C; ++c) a.margin_c[c] = margin[c];
             a.sc.rows = m->rows_dev;
             set_fk_walk(m, a.sc);
-            a.sc.jt_rows = a.sc.jt_waves = (dh_ok && nw >= 4 && a.sc.fkk == 2) ? 1 : 0;
+            a.sc.jt_rows = a.sc.jt_waves = (dh_ok && nw >= jt_min_waves && a.sc.fkk == 2) ? 1 : 0;
 #ifdef DCX_TIMING
             if (!g_ts_dev && hipMalloc((void**)&g_ts_dev, sizeof(unsigned long long) * kTsWords) == hipSuccess)
                 (void)hipMemset(g_ts_dev, 0, sizeof(unsigned long long) * kTsWords);

@@ -124,6 +124,10 @@ constexpr int kTrainGridMaxN = 128 * 1024;  // 128 workgroups x 1024 samples (tr
 // (n_class, margin_c: col_score is [R*W, n_class] under per-class margins; margin_c == nullptr: opt.safety_margin for every class)
 hipError_t launch_traj_adam_step(const FkProg* fk_dev, const dcx_fk_desc& fk, const dcx_traj_state& st,
                                  const dcx_traj_opts& opt, int step, hipStream_t stream, int n_class = 1, const float* margin_c = nullptr);
+// LDS bytes of that launch with nw wave slabs (it takes ceil(n_waypoints / 64)): host arithmetic on the description alone
+size_t traj_lds_bytes(const dcx_fk_desc& fk, int nw);
+// a CU's LDS on gfx950, the only target: what one workgroup can be given at most
+constexpr size_t kCuLdsBytes = 160 * 1024;
 // the update half of dcx_escape_adam: pointers into the caller's workspace, one configuration per lane
 struct EscapeArgs {
     float* q;             // [B, dof] in/out

@@ -270,7 +270,8 @@ int dcx_score_hinge_grad_mc(const dcx_model* m, const float* q, int64_t B, const
  * per-path stop when constraint <= valid_tol and |grad| < grad_tol).  All pointers are device memory owned by
  * the caller; every array is dense fp32 unless noted.                                                    */
 typedef struct dcx_traj_state {
-    int32_t n_paths, n_waypoints;      /* R, W (W <= 1024)                                              */
+    int32_t n_paths, n_waypoints;      /* R, W (W <= 1024, and ceil(W / 64) x 64 waypoints' rows, features (twice) and FK
+                                        * frames within a CU's 160 KB of LDS: DCX_ERR_UNSUPPORTED otherwise, before any launch) */
     float* path;                       /* [R, W, dof]  in/out                                            */
     float* adam_m;                     /* [R, W, dof]  first moment  (zero before step 1)                */
     float* adam_v;                     /* [R, W, dof]  second moment (zero before step 1)                */
