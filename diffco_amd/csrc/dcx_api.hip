@@ -33,6 +33,8 @@ struct dcx_model {
                                    // p2_applies models only; padded to an even row count with a zero-weight row)
     float* rows_xf_dev = nullptr;  // what the expanded-form sweeps read (score_kernel.h): the rows shifted by `centre`,
                                    // |s - c|^2 in their last column
+    float* rows_sp_dev = nullptr;  // the SPARE-SLOT form of rows_xf_dev (score_kernel.h spare_applies shapes; valid while spare_col >= 0)
+    int32_t spare_col = -1;        // the feature column all kept supports agree on bit for bit (found at every fill), -1: none
     float* centre_dev = nullptr;   // [Dt]: the support centroid for features an FK transform produced, zero for raw inputs
     int64_t S_in = 0;
     int32_t S_active = 0;
@@ -276,7 +278,7 @@ struct Knobs {
     std::atomic<int64_t> ys{-1}, nw{-1}, min_rows{-1}, split_finish_kernel{-1}, inlaunch_tiles{-1}, jac_per_class{-1},
         traj_fused{-1}, xf{-1}, jac_one_sweep{-1}, train_grid{-1}, fkk{-1}, jt_waves{-1}, hess_ys{-1}, hess_form{-1},
         traj_ys{-1}, traj_across{-1}, owner_poll{-1}, solve_threads{-1}, qt{-1}, giveup_inject{-1}, skew{-1}, skew8{-1},
-        motion_early_exit{-1};
+        motion_early_exit{-1}, spare{-1};
     Knobs() {
         auto rd = [](const char* name, std::atomic<int64_t>& dst, bool flag) {
             if (const char* e = std::getenv(name)) dst = flag ? 1 : std::atoll(e);
@@ -289,6 +291,7 @@ struct Knobs {
         rd("DCX_JAC_PER_CLASS", jac_per_class, true);
         rd("DCX_TRAJ_FUSED", traj_fused, false);
         rd("DCX_XF", xf, false);
+        rd("DCX_SPARE", spare, false);
         rd("DCX_JAC_ONE_SWEEP", jac_one_sweep, false);
         rd("DCX_TRAIN_GRID", train_grid, false);
         rd("DCX_FKK", fkk, false);
@@ -307,6 +310,19 @@ struct Knobs {
 Knobs& knobs() {
     static Knobs k;
     return k;
+}
+
+// THE predicate of the spare-slot form (score_kernel.h sweep_rows SP): every dispatch that picks an expanded-form kernel for a
+// model goes through xf_rows below, so all of them read the same rows in the same form.  Knob spare: 0 = never, -1 = this rule.
+bool spare_on(const dcx_model* m) {
+    return knobs().spare != 0 && m->spare_col >= 0 && m->rows_sp_dev != nullptr && spare_applies(m->Dt, m->Cc, m->kf);
+}
+// an expanded-form launch's rows, centre and form
+void xf_rows(const dcx_model* m, ScoreArgs& a) {
+    const bool sp = spare_on(m);
+    a.rows = sp ? m->rows_sp_dev : m->rows_xf_dev;
+    a.centre = m->centre_dev;
+    a.spare = sp ? m->spare_col + 1 : 0;
 }
 
 // Launch geometry.  nw = waves per block (support slices inside a block), ys = support super-chunks across
@@ -705,10 +721,7 @@ int run_score(const dcx_model* m, const float* q, int64_t B, const float* upstre
         a.qt_front = (int32_t)((int64_t)QT_SLICES * g.nw * qt_per * (kq >= 100 ? std::min<int64_t>(kq - 100, 100) : 45) / 100);
         nblk = (B + 15) / 16;
     }
-    if (a.xf) {  // the XF kernel: the centred rows and the centroid
-        a.rows = m->rows_xf_dev;
-        a.centre = m->centre_dev;
-    }
+    if (a.xf) xf_rows(m, a);  // the XF kernel: the centred rows (plain or spare-slot) and the centroid
     // J^T on several waves (fk_device.h dh2_vjp_waves): the step table, a parallel fold (its scratch rows 1 .. nw-1 hold 12
     // columns per point step), and not the finish-kernel mode.  Knob jt_waves = 0: wave 0 alone (tests: identical bits).
     a.jt_rows = (a.fkk == 2 && g.nw >= 2 * m->dh.n_chains && m->dh.n_chains <= 2 && m->dh.end0 <= kDhUnroll &&
@@ -797,7 +810,7 @@ int dcx_debug_set(const char* name, int64_t value) {
                          : DCX_OK;
     std::atomic<int64_t>* dst = n == "ys" ? &k.ys : n == "nw" ? &k.nw : n == "min_rows" ? &k.min_rows
         : n == "split_finish_kernel" ? &k.split_finish_kernel : n == "inlaunch_tiles" ? &k.inlaunch_tiles
-        : n == "jac_per_class" ? &k.jac_per_class : n == "traj_fused" ? &k.traj_fused : n == "xf" ? &k.xf : n == "jac_one_sweep" ? &k.jac_one_sweep : n == "train_grid" ? &k.train_grid : n == "fkk" ? &k.fkk : n == "jt_waves" ? &k.jt_waves : n == "hess_ys" ? &k.hess_ys : n == "hess_form" ? &k.hess_form : n == "traj_ys" ? &k.traj_ys : n == "traj_across" ? &k.traj_across : n == "owner_poll" ? &k.owner_poll : n == "solve_threads" ? &k.solve_threads : n == "qt" ? &k.qt : n == "giveup_inject" ? &k.giveup_inject : n == "skew" ? &k.skew : n == "skew8" ? &k.skew8 : n == "motion_early_exit" ? &k.motion_early_exit : nullptr;
+        : n == "jac_per_class" ? &k.jac_per_class : n == "traj_fused" ? &k.traj_fused : n == "xf" ? &k.xf : n == "spare" ? &k.spare : n == "jac_one_sweep" ? &k.jac_one_sweep : n == "train_grid" ? &k.train_grid : n == "fkk" ? &k.fkk : n == "jt_waves" ? &k.jt_waves : n == "hess_ys" ? &k.hess_ys : n == "hess_form" ? &k.hess_form : n == "traj_ys" ? &k.traj_ys : n == "traj_across" ? &k.traj_across : n == "owner_poll" ? &k.owner_poll : n == "solve_threads" ? &k.solve_threads : n == "qt" ? &k.qt : n == "giveup_inject" ? &k.giveup_inject : n == "skew" ? &k.skew : n == "skew8" ? &k.skew8 : n == "motion_early_exit" ? &k.motion_early_exit : nullptr;
     if (!dst) return fail(DCX_ERR_INVALID, "unknown knob: " + n);
     *dst = value;
     return DCX_OK;
@@ -819,7 +832,9 @@ static void model_free_rows(dcx_model* m) {
     if (m->rows_dev) (void)hipFree(m->rows_dev);
     if (m->rows_xf_dev) (void)hipFree(m->rows_xf_dev);
     if (m->rows_p2_dev) (void)hipFree(m->rows_p2_dev);
-    m->rows_dev = m->rows_xf_dev = m->rows_p2_dev = nullptr;
+    if (m->rows_sp_dev) (void)hipFree(m->rows_sp_dev);
+    m->rows_dev = m->rows_xf_dev = m->rows_p2_dev = m->rows_sp_dev = nullptr;
+    m->spare_col = -1;
     m->cap = 0;
 }
 
@@ -830,9 +845,10 @@ static int model_alloc_rows(dcx_model* m, int64_t cap) {
     // the new buffers first, the old ones freed only when both exist: a failed growth leaves the model as it was (ADVICE r4:
     // freeing first left rows_dev null beside the old S_active, and the next launch read through it)
     const size_t floats = (size_t)cap * m->RS + rows_tail_floats(m);
-    float *rows = nullptr, *rows_xf = nullptr, *rows_p2 = nullptr;
+    float *rows = nullptr, *rows_xf = nullptr, *rows_p2 = nullptr, *rows_sp = nullptr;
     hipError_t e = hipMalloc((void**)&rows, floats * sizeof(float));
     if (e == hipSuccess) e = hipMalloc((void**)&rows_xf, floats * sizeof(float));
+    if (e == hipSuccess && spare_applies(m->Dt, m->Cc, m->kf)) e = hipMalloc((void**)&rows_sp, floats * sizeof(float));
     if (e == hipSuccess && p2_applies(m->Dt, m->Cc, m->kf)) e = hipMalloc((void**)&rows_p2, (floats + m->RS) * sizeof(float));
     if (e == hipSuccess && !m->centre_dev) e = hipMalloc((void**)&m->centre_dev, (size_t)m->Dt * sizeof(float));
     if (e == hipSuccess && !m->info_dev) e = hipMalloc((void**)&m->info_dev, 16);
@@ -848,12 +864,14 @@ static int model_alloc_rows(dcx_model* m, int64_t cap) {
         if (rows) (void)hipFree(rows);
         if (rows_xf) (void)hipFree(rows_xf);
         if (rows_p2) (void)hipFree(rows_p2);
+        if (rows_sp) (void)hipFree(rows_sp);
         return fail_hip(e, "device allocation of the model");
     }
     model_free_rows(m);
     m->rows_dev = rows;
     m->rows_xf_dev = rows_xf;
     m->rows_p2_dev = rows_p2;
+    m->rows_sp_dev = rows_sp;
     m->cap = cap;
     return DCX_OK;
 }
@@ -866,6 +884,7 @@ static int model_fill_device(dcx_model* m, const float* feat_dev, const float* w
     a.w = w_dev;
     a.rows = m->rows_dev;
     a.rows_xf = m->rows_xf_dev;
+    a.rows_sp = m->rows_sp_dev;
     a.centre = m->centre_dev;
     a.info = m->info_dev;
     a.S = S;
@@ -887,6 +906,7 @@ static int model_fill_device(dcx_model* m, const float* feat_dev, const float* w
     std::memcpy(&ss_max, reinterpret_cast<const char*>(m->info_host) + 8, sizeof(double));
     m->S_in = S;
     m->S_active = m->info_host[0];
+    m->spare_col = m->info_host[1] - 1;   // the spare-slot rule's verdict (pack_rows_kernel; model_fill_host decides the same)
     m->xf_rq_ok = (m->kf == KF_RQ2 && m->fk.kind != DCX_FK_NONE && (double)m->kp0 * ss_max <= kXfRqRule) ? 1 : 0;
     return DCX_OK;
 }
@@ -941,6 +961,26 @@ static int model_fill_host(dcx_model* m, const float* support_feat, const float*
             centre[k] = (float)(acc / (double)kept);
         }
     }
+    // The spare-slot rule (score_kernel.h spare_applies; pack_rows_kernel restates it): the LAST column on which all kept
+    // supports agree bit for bit - zero padding up to the compiled width, or a feature of a transform (raw inputs keep their
+    // zero centre) - is the spare one, and the centre's entry in such a column is that value exactly: the centred rows hold 0 there.
+    int sp = -1;
+    if (m->rows_sp_dev && kept > 0) {
+        for (int k = m->Dt - 1; k >= 0; --k) {
+            bool same = (k >= D || m->fk.kind != DCX_FK_NONE);
+            if (same && k < D) {
+                uint32_t first, v;
+                std::memcpy(&first, &rows[k], 4);
+                for (int32_t j = 0; j < kept && same; ++j) {
+                    std::memcpy(&v, &rows[(size_t)j * m->RS + k], 4);
+                    same = (v == first);
+                }
+                if (same) centre[k] = rows[k];
+            }
+            if (same && sp < 0) sp = k;
+        }
+    }
+    m->spare_col = sp;
     double ss_max = 0.0;
     for (int32_t j = 0; j < kept; ++j) {
         float* cen = &rows_xf[(size_t)j * m->RS];
@@ -962,6 +1002,20 @@ static int model_fill_host(dcx_model* m, const float* support_feat, const float*
     rows_xf.resize(rows.size(), 0.0f);
     hipError_t e = hipMemcpy(m->rows_dev, rows.data(), rows.size() * sizeof(float), hipMemcpyHostToDevice);
     if (e == hipSuccess) e = hipMemcpy(m->rows_xf_dev, rows_xf.data(), rows_xf.size() * sizeof(float), hipMemcpyHostToDevice);
+    if (e == hipSuccess && sp >= 0) {
+        // the spare-slot copy: the agreed column swapped with the last one, whose slot carries |s - c|^2 (+ 2/gamma); the
+        // gradient pass's last operand pair {s_{Dt-2}, 1} behind the weight
+        std::vector<float> rows_sp(rows_xf);
+        for (int32_t j = 0; j < kept; ++j) {
+            const float* x = &rows_xf[(size_t)j * m->RS];
+            float* y = &rows_sp[(size_t)j * m->RS];
+            y[sp] = x[m->Dt - 1];
+            y[m->Dt - 1] = x[ss_off];
+            y[m->Dt + 2] = y[m->Dt - 2];
+            y[m->Dt + 3] = 1.0f;
+        }
+        e = hipMemcpy(m->rows_sp_dev, rows_sp.data(), rows_sp.size() * sizeof(float), hipMemcpyHostToDevice);
+    }
     if (e == hipSuccess) e = hipMemcpy(m->centre_dev, centre.data(), centre.size() * sizeof(float), hipMemcpyHostToDevice);
     if (e != hipSuccess) return fail_hip(e, "upload of the model's rows");
     return DCX_OK;
@@ -1117,6 +1171,7 @@ void dcx_model_destroy(dcx_model* m) {
     if (m->rows_dev) (void)hipFree(m->rows_dev);
     if (m->rows_xf_dev) (void)hipFree(m->rows_xf_dev);
     if (m->rows_p2_dev) (void)hipFree(m->rows_p2_dev);
+    if (m->rows_sp_dev) (void)hipFree(m->rows_sp_dev);
     if (m->centre_dev) (void)hipFree(m->centre_dev);
     if (m->info_dev) (void)hipFree(m->info_dev);
     if (m->info_host) (void)hipHostFree(m->info_host);
@@ -1461,8 +1516,7 @@ static int traj_run(const dcx_model* m, const dcx_traj_state* st, const dcx_traj
             a.sc.kp1 = m->kp1;
             a.sc.xf = (knobs().xf != 0 && m->kf == KF_POLY1 && xf_applies(m->Dt, m->Cc, KF_POLY1) && m->rows_xf_dev) ? 1 : 0;
             if (a.sc.xf) {
-                a.sc.rows = m->rows_xf_dev;
-                a.sc.centre = m->centre_dev;
+                xf_rows(m, a.sc);
             } else if (m->rows_p2_dev && p2_applies(m->Dt, m->Cc, m->kf)) {
                 a.sc.rows = m->rows_p2_dev;
                 traj_p2 = true;
@@ -1697,10 +1751,7 @@ MotionSweepPlan motion_sweep_plan(const dcx_model* m, int64_t tiles_max, char* b
     sa.kp0 = m->kp0_sweep;
     sa.kp1 = m->kp1;
     sa.xf = xf_able ? 1 : 0;
-    if (sa.xf) {
-        sa.rows = m->rows_xf_dev;
-        sa.centre = m->centre_dev;
-    }
+    if (sa.xf) xf_rows(m, sa);
     // a DH arm's chain split by rows over two waves, where run_score splits it
     sa.jt_rows = (sa.fkk == 2 && g.nw >= 2 * m->dh.n_chains && m->dh.n_chains <= 2 && m->dh.end0 <= kDhUnroll &&
                   m->dh.n_steps - m->dh.end0 <= kDhUnroll && knobs().jt_waves != 0) ? 1 : 0;
@@ -2051,10 +2102,7 @@ int dcx_motion_cost_ex(const dcx_model* m, const float* qa, const float* qb, int
     sa.kp0 = m->kp0_sweep;
     sa.kp1 = m->kp1;
     sa.xf = xf_able ? 1 : 0;
-    if (sa.xf) {
-        sa.rows = m->rows_xf_dev;
-        sa.centre = m->centre_dev;
-    }
+    if (sa.xf) xf_rows(m, sa);
     sa.jt_rows = (sa.fkk == 2 && g.nw >= 2 * m->dh.n_chains && m->dh.n_chains <= 2 && m->dh.end0 <= kDhUnroll &&
                   m->dh.n_steps - m->dh.end0 <= kDhUnroll && knobs().jt_waves != 0) ? 1 : 0;
     sa.jt_waves = 0;   // J^T on wave 0 (fk_vjp_sel)

@@ -33,8 +33,11 @@ hipError_t go(int nw, size_t lds, int64_t nblk, const MotionCostArgs& a, hipStre
         kern<<<grid, dim3(64 * nw), lds, st>>>(a, mc_off);
         return hipGetLastError();
     };
+    if constexpr (spare_applies(kD, CC, KF)) {   // the spare-slot form of the expanded sweep (score_kernel.h)
+        if (a.sc.xf && a.sc.spare > 0) return launch(motion_cost_kernel<kD, KF, CC, MODE, kMaxT, 2>);
+    }
     if constexpr (xf_applies(kD, CC, KF)) {
-        if (a.sc.xf) return launch(motion_cost_kernel<kD, KF, CC, MODE, kMaxT, true>);
+        if (a.sc.xf) return launch(motion_cost_kernel<kD, KF, CC, MODE, kMaxT, 1>);
     }
     return launch(motion_cost_kernel<kD, KF, CC, MODE, kMaxT>);
 }

@@ -121,7 +121,7 @@ __device__ __forceinline__ void motion_tile_lookup(const int64_t* offs, int64_t 
 
 // One configuration per lane.  LDS: lds_plan(dof, d_fk, frame_floats, red_slots, ACC, true).total + prog_floats rounded to 4,
 // then kMotionCostLdsFloats (mc_off).
-template <int D, int KF, int CC, int MODE, int MAXT, bool XF = false>
+template <int D, int KF, int CC, int MODE, int MAXT, int XF = 0 /* 1: the expanded form, 2: its spare-slot form (score_kernel.h sweep_rows SP) */>
 __global__ __launch_bounds__(MAXT, sweep_min_waves(D, CC, KF)) void motion_cost_kernel(const MotionCostArgs m, int32_t mc_off) {
     static_assert((CC == 1) == (MODE == MODE_GRAD_ROW), "one class: the hinge sweep; several: the score and gradient passes");
     extern __shared__ __attribute__((aligned(16))) float smem[];
@@ -178,7 +178,7 @@ __global__ __launch_bounds__(MAXT, sweep_min_waves(D, CC, KF)) void motion_cost_
 #pragma unroll
         for (int k = 0; k < D; ++k) x[k] = (k < a.d_fk) ? sX[k * 64 + lane0] : 0.0f;
     }
-    if constexpr (XF) {
+    if constexpr (XF != 0) {
         cfloat_ptr cen = (cfloat_ptr)(uintptr_t)a.centre;
 #pragma unroll
         for (int k = 0; k < D; ++k) x[k] -= cen[k];
@@ -203,7 +203,7 @@ __global__ __launch_bounds__(MAXT, sweep_min_waves(D, CC, KF)) void motion_cost_
     const int yend = (ybase + a.s_super < a.S) ? (ybase + a.s_super) : a.S;
     int j0, j1;
     wave_slice(wave, nw, a.s_chunk, a.s_skew, ybase, yend, j0, j1);
-    sweep_rows<D, KF, CC, MODE, XF>(a, x, up, j0, j1, sc, gx);
+    sweep_rows<D, KF, CC, MODE, XF != 0, 0, false, XF == 2>(a, x, up, j0, j1, sc, gx);
 
     // ---- epilogue: arguments read afresh (score_kernel.h reload_args); the block's partial sums meet on wave 0 ----
     const auto& b = reload_kernargs<MotionCostArgs>();

@@ -31,8 +31,11 @@ hipError_t go(int nw, size_t lds, int64_t nblk, const MotionArgs& a, hipStream_t
         kern<<<grid, dim3(64 * nw), lds, st>>>(a, mo_off);
         return hipGetLastError();
     };
+    if constexpr (spare_applies(kD, CC, KF)) {   // the spare-slot form of the expanded sweep (score_kernel.h)
+        if (a.sc.xf && a.sc.spare > 0) return launch(motion_kernel<kD, KF, CC, kMaxT, 2>);
+    }
     if constexpr (xf_applies(kD, CC, KF)) {
-        if (a.sc.xf) return launch(motion_kernel<kD, KF, CC, kMaxT, true>);
+        if (a.sc.xf) return launch(motion_kernel<kD, KF, CC, kMaxT, 1>);
     }
     return launch(motion_kernel<kD, KF, CC, kMaxT>);
 }

@@ -100,7 +100,7 @@ __device__ __forceinline__ float motion_coord(float qa, float qb, int k, int res
 // one configuration per lane: the score-only sweep of score_kernel (its prologue, with the rows of sQ interpolated from the
 // edges instead of read from q), then the compare against the margins.  LDS: lds_plan(...).total + prog_floats (the FK
 // program) rounded to 4, then kMotionLdsFloats (mo_off below).
-template <int D, int KF, int CC, int MAXT, bool XF = false>
+template <int D, int KF, int CC, int MAXT, int XF = 0 /* 1: the expanded form, 2: its spare-slot form (score_kernel.h sweep_rows SP) */>
 __global__ __launch_bounds__(MAXT, sweep_min_waves(D, CC, KF)) void motion_kernel(const MotionArgs m, int32_t mo_off) {
     extern __shared__ __attribute__((aligned(16))) float smem[];
     const ScoreArgs& a = m.sc;
@@ -202,7 +202,7 @@ __global__ __launch_bounds__(MAXT, sweep_min_waves(D, CC, KF)) void motion_kerne
 #pragma unroll
                 for (int k = 0; k < D; ++k) x[k] = (k < a.d_fk) ? sX[k * 64 + lane] : 0.0f;
             }
-            if constexpr (XF) {   // the expanded form's centred features (score_kernel.h)
+            if constexpr (XF != 0) {   // the expanded form's centred features (score_kernel.h)
                 cfloat_ptr cen = (cfloat_ptr)(uintptr_t)a.centre;
 #pragma unroll
                 for (int k = 0; k < D; ++k) x[k] -= cen[k];
@@ -216,7 +216,7 @@ __global__ __launch_bounds__(MAXT, sweep_min_waves(D, CC, KF)) void motion_kerne
             float gx[D];
 #pragma unroll
             for (int c = 0; c < CC; ++c) up[c] = 0.0f;
-            sweep_rows<D, KF, CC, MODE_SCORE, XF>(a, x, up, j0, j1, sc, gx);
+            sweep_rows<D, KF, CC, MODE_SCORE, XF != 0, 0, false, XF == 2>(a, x, up, j0, j1, sc, gx);
         }
         // ---- epilogue: the block's partial sums meet on wave 0 (rows in wave order, as score_kernel folds them) ----
         const auto& b = reload_kernargs<MotionArgs>();

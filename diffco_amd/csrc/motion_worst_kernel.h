@@ -88,7 +88,7 @@ __host__ __device__ inline uint32_t motion_worst_unorder(uint32_t o) { return (o
 #ifdef __HIPCC__
 // one configuration per lane: motion_kernel without the early exit, then the packed maximum per edge segment.
 // LDS: lds_plan(...).total + prog_floats rounded to 4, then kMotionLdsFloats (mo_off), as motion_kernel.
-template <int D, int KF, int CC, int MAXT, bool XF = false>
+template <int D, int KF, int CC, int MAXT, int XF = 0 /* 1: the expanded form, 2: its spare-slot form (score_kernel.h sweep_rows SP) */>
 __global__ __launch_bounds__(MAXT, sweep_min_waves(D, CC, KF)) void motion_worst_kernel(const MotionWorstArgs m, int32_t mo_off) {
     extern __shared__ __attribute__((aligned(16))) float smem[];
     const ScoreArgs& a = m.sc;
@@ -143,7 +143,7 @@ __global__ __launch_bounds__(MAXT, sweep_min_waves(D, CC, KF)) void motion_worst
 #pragma unroll
             for (int k = 0; k < D; ++k) x[k] = (k < a.d_fk) ? sX[k * 64 + lane] : 0.0f;
         }
-        if constexpr (XF) {   // the expanded form's centred features (score_kernel.h)
+        if constexpr (XF != 0) {   // the expanded form's centred features (score_kernel.h)
             cfloat_ptr cen = (cfloat_ptr)(uintptr_t)a.centre;
 #pragma unroll
             for (int k = 0; k < D; ++k) x[k] -= cen[k];
@@ -157,7 +157,7 @@ __global__ __launch_bounds__(MAXT, sweep_min_waves(D, CC, KF)) void motion_worst
         float gx[D];
 #pragma unroll
         for (int c = 0; c < CC; ++c) up[c] = 0.0f;
-        sweep_rows<D, KF, CC, MODE_SCORE, XF>(a, x, up, j0, j1, sc, gx);
+        sweep_rows<D, KF, CC, MODE_SCORE, XF != 0, 0, false, XF == 2>(a, x, up, j0, j1, sc, gx);
     }
     // ---- epilogue: the block's partial sums meet on wave 0 in motion_kernel's order (the same bits as the check's scores) ----
     const auto& b = reload_kernargs<MotionWorstArgs>();

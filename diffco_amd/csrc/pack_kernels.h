@@ -10,8 +10,10 @@ struct PackArgs {
     const float* w;      // [S, C] device
     float* rows;         // [cap + tail] x RS: the direct-form rows
     float* rows_xf;      // the centred copy
+    float* rows_sp;      // its spare-slot form (score_kernel.h spare_applies), written when the supports agree on a column; null: the
+                         // model's shape has no spare form
     float* centre;       // [Dt]
-    int32_t* info;       // 16 bytes out: [0] kept rows, [1] 0, then a double: max |s - c|^2 over the kept rows
+    int32_t* info;       // 16 bytes out: [0] kept rows, [1] the spare column + 1 (0: none), then a double: max |s - c|^2 over the kept rows
     int64_t S;
     int32_t D, Dt, C, RS;
     int32_t Cl;          // class count of the ROW LAYOUT (>= C: the compiled count; columns C .. Cl-1 are zero weights)

@@ -29,6 +29,7 @@ __global__ __launch_bounds__(kPackThreads) void pack_rows_kernel(const PackArgs 
     __shared__ int s_wave_cnt[kPackThreads / 64];
     __shared__ int s_base;
     __shared__ double s_max[kPackThreads / 64];
+    __shared__ int s_same[128];   // per feature column: do all kept supports agree bit for bit?  (the spare-slot rule)
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int ss_off = a.Dt + a.Cl + (a.Cl > 1 ? 1 : 0);
     if (tid == 0) s_base = 0;
@@ -77,42 +78,82 @@ __global__ __launch_bounds__(kPackThreads) void pack_rows_kernel(const PackArgs 
     for (int i = tid; i < a.tail_floats; i += kPackThreads) {
         a.rows[(size_t)kept * a.RS + i] = 0.0f;
         a.rows_xf[(size_t)kept * a.RS + i] = 0.0f;
+        if (a.rows_sp) a.rows_sp[(size_t)kept * a.RS + i] = 0.0f;
     }
     __syncthreads();
     // ---- centroid: one lane per feature, the kept rows in order, double accumulation (dcx_model_create's loop) ------------
+    // ... and the spare-slot rule (dcx_api.hip model_fill_host restates it): a column on which all kept supports agree bit for
+    // bit - a padding column, or a feature of a transform - can be the spare one; the centre's entry there is that value exactly
     if (tid < a.Dt) {
         float c = 0.0f;
+        bool same = kept > 0 && (tid >= a.D || a.centred);
+        uint32_t differ = 0;   // (or-ed bit differences: no branch between the loads, which stay 32 in flight)
         if (a.centred && tid < a.D && kept > 0) {
             double acc = 0.0;
             const float* col = a.rows + tid;
+            const float first = col[0];
             int j = 0;
             for (; j + 32 <= kept; j += 32) {   // 32 loads in flight, the additions in row order
                 float v[32];
 #pragma unroll
                 for (int u = 0; u < 32; ++u) v[u] = col[(size_t)(j + u) * a.RS];
 #pragma unroll
-                for (int u = 0; u < 32; ++u) acc += (double)v[u];
+                for (int u = 0; u < 32; ++u) {
+                    acc += (double)v[u];
+                    differ |= __float_as_uint(v[u]) ^ __float_as_uint(first);
+                }
             }
-            for (; j < kept; ++j) acc += (double)col[(size_t)j * a.RS];
+            for (; j < kept; ++j) {
+                const float v = col[(size_t)j * a.RS];
+                acc += (double)v;
+                differ |= __float_as_uint(v) ^ __float_as_uint(first);
+            }
+            same = same && differ == 0;
             c = (float)(acc / (double)kept);
+            if (a.rows_sp && same) c = first;
         }
         a.centre[tid] = c;
+        if (tid < 128) s_same[tid] = same ? 1 : 0;
     }
     __syncthreads();
+    int sp = -1;   // the spare column: the last one the supports agree on
+    if (a.rows_sp)
+        for (int k = (a.Dt < 128 ? a.Dt : 128) - 1; k >= 0 && sp < 0; --k)
+            if (s_same[k]) sp = k;
     // ---- centred rows ---------------------------------------------------------------------------------------------------
     double mx = 0.0;
     for (int j = tid; j < kept; j += kPackThreads) {
         const float* r = a.rows + (size_t)j * a.RS;
         float* x = a.rows_xf + (size_t)j * a.RS;
+        // the spare-slot copy (score_kernel.h spare_applies: one class, RS >= Dt + 4) is written beside the centred row, from
+        // the same registers: the agreed column (0 in every centred row) swapped with the last one, whose slot carries
+        // |s - c|^2 (+ 2/gamma), and the gradient pass's last operand pair {s_{Dt-2}, 1} behind the weight
+        float* y = sp >= 0 ? a.rows_sp + (size_t)j * a.RS : nullptr;
+        float v_last = 0.0f, v_pen = 0.0f;   // the centred features Dt-1 and Dt-2 (zero padding past D)
         double ss = 0.0;
         for (int k = 0; k < a.D; ++k) {
             const float v = r[k] - a.centre[k];
             x[k] = v;
+            if (y) y[k] = v;
+            v_last = (k == a.Dt - 1) ? v : v_last;
+            v_pen = (k == a.Dt - 2) ? v : v_pen;
             ss += (double)v * (double)v;
         }
-        for (int k = a.D; k < a.RS; ++k) x[k] = r[k];
-        x[ss_off] = a.rq2 ? (float)(ss + (double)a.seed) : (float)ss;
+        for (int k = a.D; k < a.RS; ++k) {
+            const float v = r[k];
+            x[k] = v;
+            if (y) y[k] = v;
+        }
+        const float ssf = a.rq2 ? (float)(ss + (double)a.seed) : (float)ss;
+        x[ss_off] = ssf;
         mx = ss > mx ? ss : mx;
+        if (y) {
+            y[ss_off] = ssf;
+            y[sp] = v_last;
+            y[a.Dt - 1] = ssf;
+            y[a.Dt + 2] = (sp == a.Dt - 2) ? v_last : v_pen;
+            y[a.Dt + 3] = 1.0f;
+        }
     }
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) {
@@ -125,7 +166,7 @@ __global__ __launch_bounds__(kPackThreads) void pack_rows_kernel(const PackArgs 
         double t = 0.0;
         for (int w = 0; w < kPackThreads / 64; ++w) t = s_max[w] > t ? s_max[w] : t;
         a.info[0] = kept;
-        a.info[1] = 0;
+        a.info[1] = sp + 1;
         reinterpret_cast<double*>(a.info)[1] = t;
     }
 }

@@ -46,6 +46,9 @@ hipError_t go(int nw, size_t lds, int64_t nblk, const ScoreArgs& a, hipStream_t 
     if constexpr (qt_applies(kD, CC, KF, MODE)) {   // the quarter tile (16 configurations per block, rows from LDS): nblk counts ITS blocks
         if (a.qt) return launch(score_kernel<kD, KF, CC, MODE, kMaxT, false, true>);
     }
+    if constexpr (spare_applies(kD, CC, KF)) {   // the spare-slot form of the expanded sweep: a kernel symbol of its own
+        if (a.xf && a.spare > 0) return launch(score_kernel_sp<kD, KF, CC, MODE, kMaxT>);
+    }
     if constexpr (xf_applies(kD, CC, KF)) {
         if (a.xf) return launch(score_kernel<kD, KF, CC, MODE, kMaxT, true>);
     }
@@ -179,18 +182,24 @@ hipError_t DCX_CAT(launch_traj_fused_D, DCX_INST_D)(int kf, int cc, int nw, size
     }
     auto go_t = [&](auto kern) { return traj_go(kern, nw, lds, n_paths, a, st); };
     if (a.ys > 1) {
+        if constexpr (spare_applies(kD, 1, KF_POLY1)) {
+            if (kf == KF_POLY1 && a.sc.xf && a.sc.spare > 0) return go_t(traj_fused_kernel<kD, KF_POLY1, kMaxT, 2, true>);
+        }
         if constexpr (xf_applies(kD, 1, KF_POLY1)) {
-            if (kf == KF_POLY1 && a.sc.xf) return go_t(traj_fused_kernel<kD, KF_POLY1, kMaxT, true, true>);
+            if (kf == KF_POLY1 && a.sc.xf) return go_t(traj_fused_kernel<kD, KF_POLY1, kMaxT, 1, true>);
         }
         switch (kf) {
-        case KF_RQ2: return go_t(traj_fused_kernel<kD, KF_RQ2, kMaxT, false, true>);
-        case KF_POLY1: return go_t(traj_fused_kernel<kD, KF_POLY1, kMaxT, false, true>);
-        case KF_GEN: return go_t(traj_fused_kernel<kD, KF_GEN, kMaxT, false, true>);
+        case KF_RQ2: return go_t(traj_fused_kernel<kD, KF_RQ2, kMaxT, 0, true>);
+        case KF_POLY1: return go_t(traj_fused_kernel<kD, KF_POLY1, kMaxT, 0, true>);
+        case KF_GEN: return go_t(traj_fused_kernel<kD, KF_GEN, kMaxT, 0, true>);
         default: return hipErrorInvalidValue;
         }
     }
+    if constexpr (spare_applies(kD, 1, KF_POLY1)) {
+        if (kf == KF_POLY1 && a.sc.xf && a.sc.spare > 0) return go_t(traj_fused_kernel<kD, KF_POLY1, kMaxT, 2>);
+    }
     if constexpr (xf_applies(kD, 1, KF_POLY1)) {
-        if (kf == KF_POLY1 && a.sc.xf) return go_t(traj_fused_kernel<kD, KF_POLY1, kMaxT, true>);
+        if (kf == KF_POLY1 && a.sc.xf) return go_t(traj_fused_kernel<kD, KF_POLY1, kMaxT, 1>);
     }
     switch (kf) {
     case KF_RQ2: return go_t(traj_fused_kernel<kD, KF_RQ2, kMaxT>);
@@ -208,20 +217,20 @@ hipError_t traj_mc(int kf, int nw, size_t lds, int n_paths, const TrajFusedArgs&
     auto go_t = [&](auto kern) { return traj_go(kern, nw, lds, n_paths, a, st); };
     if (a.ys > 1) {
         if constexpr (xf_applies(kD, CC, KF_POLY1)) {
-            if (kf == KF_POLY1 && a.sc.xf) return go_t(traj_fused_kernel<kD, KF_POLY1, kMaxT, true, true, CC>);
+            if (kf == KF_POLY1 && a.sc.xf) return go_t(traj_fused_kernel<kD, KF_POLY1, kMaxT, 1, true, CC>);
         }
         switch (kf) {
-        case KF_RQ2: return go_t(traj_fused_kernel<kD, KF_RQ2, kMaxT, false, true, CC>);
-        case KF_POLY1: return go_t(traj_fused_kernel<kD, KF_POLY1, kMaxT, false, true, CC>);
+        case KF_RQ2: return go_t(traj_fused_kernel<kD, KF_RQ2, kMaxT, 0, true, CC>);
+        case KF_POLY1: return go_t(traj_fused_kernel<kD, KF_POLY1, kMaxT, 0, true, CC>);
         default: return hipErrorNotSupported;   // (any other kernel function: the three-launch loop)
         }
     }
     if constexpr (xf_applies(kD, CC, KF_POLY1)) {
-        if (kf == KF_POLY1 && a.sc.xf) return go_t(traj_fused_kernel<kD, KF_POLY1, kMaxT, true, false, CC>);
+        if (kf == KF_POLY1 && a.sc.xf) return go_t(traj_fused_kernel<kD, KF_POLY1, kMaxT, 1, false, CC>);
     }
     switch (kf) {
-    case KF_RQ2: return go_t(traj_fused_kernel<kD, KF_RQ2, kMaxT, false, false, CC>);
-    case KF_POLY1: return go_t(traj_fused_kernel<kD, KF_POLY1, kMaxT, false, false, CC>);
+    case KF_RQ2: return go_t(traj_fused_kernel<kD, KF_RQ2, kMaxT, 0, false, CC>);
+    case KF_POLY1: return go_t(traj_fused_kernel<kD, KF_POLY1, kMaxT, 0, false, CC>);
     default: return hipErrorNotSupported;
     }
 }

@@ -88,6 +88,8 @@ struct ScoreArgs {
 #endif
     float kp0, kp1;           // kernel parameters
     int32_t xf;               // 1: the launch uses the expanded form of the sweep (score_kernel<..., XF = true>)
+    int32_t spare;            // xf launches: c + 1 > 0 selects the SPARE form (score_kernel_sp, sweep_rows<..., SP = true>): `rows` is the
+                              // model's spare-slot copy and c the feature column every support agrees on; 0: the plain expanded form
     int32_t fkk;              // DCX_FK_DH only: 1 = the FK walks read the program with scalar loads (fk_*_dh_k), 2 = the step
                               // table (fk_device.h dh2_*; `dh` below); 0 = every kind: FkProg interpreted from its LDS copy
     int32_t fk_dwords;        // dwords of FkProg the transform uses (staged into LDS; the host knows it: no dependent load)
@@ -450,6 +452,19 @@ constexpr bool xf_applies(int D, int CC, int KF) {
     const int parts = (4 * used <= (CC > 1 ? DCX_P0_MAX_MULTI : DCX_P0_MAX_SINGLE)) ? 0 : (used + 37) / 38;
     return (KF == KF_POLY1 || KF == KF_RQ2) && used + 1 <= 38 && parts <= 1;
 }
+// The SPARE form of the expanded sweep (SP): a feature column on which all supports agree bit for bit - value v, the centre's
+// entry set to v exactly - is 0 in every centred row, so the two multiply slots it holds in the row's packed fmas do nothing.  The
+// sweep swaps that column with the last one and the model's spare-slot rows carry something useful in its place:
+//     floats 0 .. D-2   the centred features (the swapped order)
+//     float  D-1        |s - c|^2 (+ 2/gamma for RQ2)           distance pass: xm[D/2-1] = {-2 x_{D-2}, 1.0}, seed {|x|^2, 0}
+//     float  D          the weight
+//     floats D+2, D+3   {s_{D-2}, 1.0}                          gradient pass: ga[D/2-1] += coef {s_{D-2}, 1}, so .y = sum(c)
+// one v_add per pair less in each pass (the seed |x|^2 + |s|^2 and the run's sum of coefficients).  The query's own value in that
+// column need not be v: e = x - v joins |x|^2 as e^2, the near-pair block's differences as e, and the gradient as e sum(c).
+// One class, the four-row pipeline, a stride with two floats to spare behind the weight (D a multiple of four).
+constexpr bool spare_applies(int D, int CC, int KF) {
+    return CC == 1 && (D % 4) == 0 && D >= 4 && D <= 12 && (KF == KF_POLY1 || KF == KF_RQ2) && D + 4 <= (D + 2 + 3) / 4 * 4;
+}
 // Does a launch of this shape in the DIRECT form take two rows per packed instruction (sweep_rows, P2) - and therefore read the
 // pair-interleaved copy of the rows on even-aligned slices?  (the host's mirror of sweep_rows' own condition)
 constexpr bool p2_applies(int D, int CC, int KF) {
@@ -468,23 +483,50 @@ constexpr bool p2_applies(int D, int CC, int KF) {
 // at few waves per SIMD trade one packed add per row for a shorter dependent chain)
 // NS (several classes, MODE_GRAD_UP): no score accumulation - a caller that already holds this batch's class scores (the persistent
 // trajectory kernel's second sweep) saves the CC fma per pair; sc[] comes back untouched
-template <int D, int KF, int CC, int MODE, bool XF = false, int NACC = 0, bool NS = false>
-__device__ __forceinline__ void sweep_rows(const ScoreArgs& a, const float (&x)[D], const float (&up)[CC], int j0, int j1,
+template <int D, int KF, int CC, int MODE, bool XF = false, int NACC = 0, bool NS = false, bool SP = false>
+__device__ __forceinline__ void sweep_rows(const ScoreArgs& a, const float (&x_in)[D], const float (&up)[CC], int j0, int j1,
                                            float (&sc)[CC], float (&gx)[D]) {
     static_assert(!NS || (CC > 1 && MODE == MODE_GRAD_UP), "NS: the gradient sweep of a multi-class model");
+    static_assert(!SP || (XF && spare_applies(D, CC, KF) && xf_applies(D, CC, KF)), "the spare form: expanded, one class, D = 4, 8, 12");
+    // SP: the features in the sweep's own order - the agreed column swapped with the last one.  The column's index stays in
+    // a VGPR across the loop (its SGPRs all belong to the row pipeline) for the way back
+    float x[D];
+    float e_sp = 0.0f, tot_sp = 0.0f;   // x - v in the agreed column; the sweep's sum(c): the run totals taken at each flush
+    int col_sp = 0;
+    if constexpr (SP) {
+        const int c = a.spare - 1;
+        e_sp = x_in[D - 1];
+#pragma unroll
+        for (int k = 0; k + 1 < D; ++k) {
+            e_sp = (k == c) ? x_in[k] : e_sp;
+            x[k] = (k == c) ? x_in[D - 1] : x_in[k];
+        }
+        x[D - 1] = 0.0f;
+        col_sp = c;
+        asm volatile("" : "+v"(col_sp));
+    } else {
+#pragma unroll
+        for (int k = 0; k < D; ++k) x[k] = x_in[k];
+    }
     using L = RowLayout<D, CC>;
     constexpr bool GRAD = (MODE != MODE_SCORE);
     v2f gx2[D / 2 + 1];
 #pragma unroll
     for (int k = 0; k < D / 2 + 1; ++k) gx2[k] = v2f{0.0f, 0.0f};
     cfloat_ptr rows = (cfloat_ptr)(uintptr_t)a.rows;
+    if constexpr (SP) {   // a register pair of its own: left inside the eight-dword argument load, the whole tuple was parked
+        uint64_t rp = (uint64_t)(uintptr_t)a.rows;
+        asm volatile("" : "+s"(rp));
+        rows = (cfloat_ptr)(uintptr_t)rp;
+    }
     // only the floats a row really carries are loaded (the tail of the padded stride is never touched)
     constexpr int USED_DIRECT = D + CC + (CC > 1 ? 1 : 0);
     constexpr bool XFA = XF && xf_applies(D, CC, KF);
-    constexpr int USED = USED_DIRECT + (XFA ? 1 : 0);
+    constexpr int USED = SP ? D + 4 : USED_DIRECT + (XFA ? 1 : 0);   // (SP: the operand pair behind the weight)
     constexpr int RSTRIDE = L::RS;
     // (how a row travels through the SGPRs: 0 = four whole rows in flight, 1 = two whole rows, >= 2 = parts of a row; see below)
-    constexpr int PARTS = (4 * USED <= (CC > 1 ? DCX_P0_MAX_MULTI : DCX_P0_MAX_SINGLE)) ? 0 : (USED + 37) / 38;  // parts of <= 38 floats
+    // (SP: the same whole-stride loads as the plain expanded form of this width - four rows in flight)
+    constexpr int PARTS = SP ? 0 : (4 * USED <= (CC > 1 ? DCX_P0_MAX_MULTI : DCX_P0_MAX_SINGLE)) ? 0 : (USED + 37) / 38;  // parts of <= 38 floats
     // Two-buffer pipeline, several classes: the class scores accumulate as explicit packed pairs.  Left as CC scalar fmaf
     // chains the SLP vectoriser packs them itself - across BOTH rows of the loop body, which moves row A's score updates
     // behind row B's body and keeps A's weights alive in copies (see row_opaque).  Same sums, class by class.
@@ -517,6 +559,7 @@ __device__ __forceinline__ void sweep_rows(const ScoreArgs& a, const float (&x)[
     if constexpr (XFA) {
 #pragma unroll
         for (int k = 0; k < D; ++k) xx = fmaf(x[k], x[k], xx);
+        if constexpr (SP) xx = fmaf(e_sp, e_sp, xx);
         thr = fmaxf(DCX_XF_TAU * xx, 1e-30f);
 #pragma unroll
         for (int k = 0; k + 1 < D; k += 2) {
@@ -524,12 +567,14 @@ __device__ __forceinline__ void sweep_rows(const ScoreArgs& a, const float (&x)[
             ga[k / 2] = v2f{0.0f, 0.0f};
         }
         if constexpr (D & 1) xm_tail = -2.0f * x[D - 1];
+        if constexpr (SP) xm[D / 2 - 1].y = 1.0f;   // |s - c|^2 rides in the last packed fma of the distance
     }
     // squared distance of one support row in the expanded form, clamped at thr (== thr marks a near pair)
     auto d2_x = [&](const auto& r) __attribute__((always_inline)) -> float {
         constexpr int NA = NACC > 0 ? NACC : DCX_D2_ACCS(D);
         v2f acc[NA];
-        acc[0] = v2f{xx + r[L::SS_OFF], 0.0f};
+        if constexpr (SP) acc[0] = v2f{xx, 0.0f};   // loop-invariant
+        else acc[0] = v2f{xx + r[L::SS_OFF], 0.0f};
 #pragma unroll
         for (int i = 1; i < NA; ++i) acc[i] = v2f{0.0f, 0.0f};
 #pragma unroll
@@ -575,11 +620,15 @@ __device__ __forceinline__ void sweep_rows(const ScoreArgs& a, const float (&x)[
             const v2f c2 = {coef, coef};
 #pragma unroll
             for (int k = 0; k + 1 < D; k += 2) {
-                const v2f rv = {r[k], r[k + 1]};
+                // (SP, last pair: {s_{D-2}, 1.0} from behind the weight - the .y half accumulates the run's sum(c))
+                v2f rv = {r[k], r[k + 1]};
+                if constexpr (SP) {
+                    if (k == D - 2) rv = v2f{r[D + 2], r[D + 3]};
+                }
                 ga[k / 2] = __builtin_elementwise_fma(c2, rv, ga[k / 2]);
             }
             if constexpr (D & 1) ga_tail = fmaf(coef, r[D - 1], ga_tail);
-            asum += coef;
+            if constexpr (!SP) asum += coef;
         }
     };
     auto pair_x = [&](const auto& r) __attribute__((always_inline)) -> float {
@@ -600,7 +649,10 @@ __device__ __forceinline__ void sweep_rows(const ScoreArgs& a, const float (&x)[
 #pragma unroll
         for (int k = 0; k + 1 < D; k += 2) {
             const v2f rv = {r[k], r[k + 1]};
-            const v2f dk = xm[k / 2] * mh - rv;
+            v2f dk = xm[k / 2] * mh - rv;
+            if constexpr (SP) {
+                if (k == D - 2) dk.y = e_sp;   // the agreed column: x - v
+            }
             dacc = __builtin_elementwise_fma(dk, dk, dacc);
         }
         float d2d = dacc.x + dacc.y;
@@ -621,7 +673,14 @@ __device__ __forceinline__ void sweep_rows(const ScoreArgs& a, const float (&x)[
 #pragma unroll
             for (int k = 0; k + 1 < D; k += 2) {
                 const v2f rv = {r[k], r[k + 1]};
-                ga[k / 2] = __builtin_elementwise_fma(cd2, xm[k / 2] * mh - rv, ga[k / 2]);
+                if (SP && k == D - 2) {
+                    // the run's sum(c) in .y is the EXPANDED pairs' alone (it multiplies x at the flush); this pair's
+                    // coefficient goes to the sweep total, which only the agreed column's e sum(c) reads
+                    ga[k / 2].x = fmaf(cd, fmaf(xm[k / 2].x, -0.5f, -rv.x), ga[k / 2].x);
+                    tot_sp -= cd;
+                } else {
+                    ga[k / 2] = __builtin_elementwise_fma(cd2, xm[k / 2] * mh - rv, ga[k / 2]);
+                }
             }
             if constexpr (D & 1) ga_tail = fmaf(cd, -0.5f * xm_tail - r[D - 1], ga_tail);
         }
@@ -652,10 +711,15 @@ __device__ __forceinline__ void sweep_rows(const ScoreArgs& a, const float (&x)[
     // fold the run's x * sum(c) into H in place: H <- H - x A = H + (-2 x) (A / 2), bit for bit the same product
     auto flush_x = [&]() __attribute__((always_inline)) {
         if constexpr (XFA && GRAD) {
+            if constexpr (SP) asum = ga[D / 2 - 1].y;   // the run's sum(c), accumulated by the gradient pass
             const v2f ah = {0.5f * asum, 0.5f * asum};
 #pragma unroll
             for (int k = 0; k + 1 < D; k += 2) ga[k / 2] = __builtin_elementwise_fma(xm[k / 2], ah, ga[k / 2]);
             if constexpr (D & 1) ga_tail = fmaf(xm_tail, 0.5f * asum, ga_tail);
+            if constexpr (SP) {
+                tot_sp += asum;
+                ga[D / 2 - 1].y = 0.0f;
+            }
             asum = 0.0f;
         }
     };
@@ -776,7 +840,12 @@ __device__ __forceinline__ void sweep_rows(const ScoreArgs& a, const float (&x)[
         --exp_real_loads;
 #endif
 #pragma unroll
-        for (int e = 0; e < NLOAD; ++e) dst[e] = r[e];
+        for (int e = 0; e < NLOAD; ++e) {
+            // (SP: the float between the weight and the operand pair is not fetched - 15 SGPRs per row, and the four rows in
+            // flight fit the wave's budget like the plain form's 16 + 16 + 14 + 14)
+            if (SP && e == D + 1) continue;
+            dst[e] = r[e];
+        }
     };
 
     // How many SGPRs a pipeline may keep in flight: ~100 exist, the kernel needs a dozen for itself.  Four whole rows
@@ -1049,12 +1118,26 @@ __device__ __forceinline__ void sweep_rows(const ScoreArgs& a, const float (&x)[
 
     if constexpr (XFA && GRAD) {
         flush_x();
+        if constexpr (SP) {
+            // back to the caller's column order: the agreed column's gradient is e sum(c)
+            const int c = __builtin_amdgcn_readfirstlane(col_sp);
+            const float gl = e_sp * tot_sp;
+            float gsw = gl;            // what the sweep's column `c` holds belongs to the caller's last column
+#pragma unroll
+            for (int k = 0; k + 1 < D; ++k) {
+                const float h = (k & 1) ? ga[k / 2].y : ga[k / 2].x;
+                gsw = (k == c) ? -h : gsw;
+                gx[k] += (k == c) ? gl : -h;
+            }
+            gx[D - 1] += gsw;
+        } else {
 #pragma unroll
         for (int k = 0; k + 1 < D; k += 2) {
             gx[k] -= ga[k / 2].x;
             gx[k + 1] -= ga[k / 2].y;
         }
         if constexpr (D & 1) gx[D - 1] -= ga_tail;
+        }
     } else {
 #pragma unroll
         for (int k = 0; k + 1 < D; k += 2) {
@@ -1202,8 +1285,9 @@ __device__ __forceinline__ void fold_partial_rows(float* sRed, int wave, int lan
 }
 
 
-template <int D, int KF, int CC, int MODE, int MAXT, bool XF = false, bool QT = false>
-__global__ __launch_bounds__(MAXT, sweep_min_waves(D, CC, KF, QT)) void score_kernel(const ScoreArgs a) {
+// (the body of score_kernel and of score_kernel_sp, its spare-form twin - below)
+template <int D, int KF, int CC, int MODE, int MAXT, bool XF, bool QT, bool SP>
+__device__ __forceinline__ void score_body(const ScoreArgs& a) {
     extern __shared__ __attribute__((aligned(16))) float smem[];
     constexpr bool GRAD = (MODE != MODE_SCORE);
     constexpr int ACC = (GRAD ? D : 0) + CC;
@@ -1344,7 +1428,7 @@ __global__ __launch_bounds__(MAXT, sweep_min_waves(D, CC, KF, QT)) void score_ke
         const float* slice = smem + a.qt_off + base + ((wave & 3) * kQtSlices + (lane >> 4)) * (per * RSQ + 4);
         sweep_rows_lds<D, KF, GRAD>(a, x, slice, per, sc[0], gx);
     } else {
-        sweep_rows<D, KF, CC, MODE, XF>(a, x, up, j0, j1, sc, gx);
+        sweep_rows<D, KF, CC, MODE, XF, 0, false, SP>(a, x, up, j0, j1, sc, gx);
     }
     DCX_TS(3);
     {   // ---- epilogue: everything below reads the kernel arguments afresh (reload_args) and re-derives what it needs ----
@@ -1744,6 +1828,17 @@ __global__ __launch_bounds__(MAXT, sweep_min_waves(D, CC, KF, QT)) void score_ke
         DCX_TSB(3);
     }
     }  // epilogue
+}
+
+template <int D, int KF, int CC, int MODE, int MAXT, bool XF = false, bool QT = false>
+__global__ __launch_bounds__(MAXT, sweep_min_waves(D, CC, KF, QT)) void score_kernel(const ScoreArgs a) {
+    score_body<D, KF, CC, MODE, MAXT, XF, QT, false>(a);
+}
+// the expanded form with the spare slot (sweep_rows SP; ScoreArgs::spare > 0, rows = the model's spare-slot copy)
+template <int D, int KF, int CC, int MODE, int MAXT>
+__global__ __launch_bounds__(MAXT, sweep_min_waves(D, CC, KF, false)) void score_kernel_sp(const ScoreArgs a) {
+    static_assert(spare_applies(D, CC, KF), "no spare form for this shape");
+    score_body<D, KF, CC, MODE, MAXT, true, false, true>(a);
 }
 
 // Second half of a split launch: one wave per 64-configuration tile adds the ys partial rows, redoes the

@@ -309,7 +309,7 @@ __device__ __forceinline__ void traj_path_terms(const A& b, const TrajLds& L, in
 // three-launch loop, tests/test_gpu_multiclass_optim.py).  Exchange rows of the cluster form: CC + 2 D words per workgroup -
 // [0, CC + D) for the first exchange(s) of an iteration, [CC + D, CC + 2 D) for the gradient after a failed speculation, whose
 // peers may still be reading the first.
-template <int D, int KF, int MAXT, bool XF = false, bool CL = false, int CC = 1>
+template <int D, int KF, int MAXT, int XF = 0 /* 1: the expanded form, 2: its spare-slot form (score_kernel.h sweep_rows SP) */, bool CL = false, int CC = 1>
 __global__ __launch_bounds__(MAXT, (MAXT / 256 > 0 ? MAXT / 256 : 1)) void traj_fused_kernel(const TrajFusedArgs a) {
     extern __shared__ __attribute__((aligned(16))) float smem[];
     constexpr int ACC = D + CC;
@@ -401,12 +401,13 @@ __global__ __launch_bounds__(MAXT, (MAXT / 256 > 0 ? MAXT / 256 : 1)) void traj_
             } else {
                 wave_slice(wave, nw, b.sc.s_chunk, b.sc.s_skew, 0, b.sc.S, j0, j1);
             }
-            if constexpr (XF) {  // the expanded form works on centred data (score_kernel.h)
+            if constexpr (XF != 0) {  // the expanded form works on centred data (score_kernel.h)
                 cfloat_ptr cen = (cfloat_ptr)(uintptr_t)b.sc.centre;
 #pragma unroll
                 for (int k = 0; k < D; ++k) x[k] -= cen[k];
             }
             sa.rows = b.sc.rows;
+            sa.spare = b.sc.spare;
             sa.kind = b.sc.kind;
             sa.kp0 = b.sc.kp0;
             sa.kp1 = b.sc.kp1;
@@ -421,7 +422,7 @@ __global__ __launch_bounds__(MAXT, (MAXT / 256 > 0 ? MAXT / 256 : 1)) void traj_
         for (int c = 0; c < CC; ++c) sc[c] = 0.0f;
         if constexpr (CC == 1) {
             const float up[1] = {1.0f};
-            sweep_rows<D, KF, 1, MODE_GRAD_ROW, XF, DCX_TRAJ_NACC>(sa, x, up, j0, j1, sc, gx);
+            sweep_rows<D, KF, 1, MODE_GRAD_ROW, XF != 0, DCX_TRAJ_NACC, false, XF == 2>(sa, x, up, j0, j1, sc, gx);
         } else {
             float up[CC];
             bool resweep = true;   // does the gradient still need a sweep with the indicator of this iteration's scores?
@@ -443,7 +444,7 @@ __global__ __launch_bounds__(MAXT, (MAXT / 256 > 0 ? MAXT / 256 : 1)) void traj_
                 // ONE sweep with the last iteration's upstream: class scores and gradient together
 #pragma unroll
                 for (int c = 0; c < CC; ++c) up[c] = up_prev[c];
-                sweep_rows<D, KF, CC, MODE_GRAD_UP, XF, DCX_TRAJ_NACC>(sa, x, up, j0, j1, sc, gx);
+                sweep_rows<D, KF, CC, MODE_GRAD_UP, XF != 0, DCX_TRAJ_NACC>(sa, x, up, j0, j1, sc, gx);
                 const auto& b = reload_kernargs<TrajFusedArgs>();
                 const TrajLds L = traj_lds<D, CC>(smem, b, nw);
                 float* mine = L.sRed + (size_t)wave * ACC * 64 + lane;
@@ -471,7 +472,7 @@ __global__ __launch_bounds__(MAXT, (MAXT / 256 > 0 ? MAXT / 256 : 1)) void traj_
                 // the class scores first ...
 #pragma unroll
                 for (int c = 0; c < CC; ++c) up[c] = 0.0f;
-                sweep_rows<D, KF, CC, MODE_SCORE, XF, DCX_TRAJ_NACC>(sa, x, up, j0, j1, sc, gx);
+                sweep_rows<D, KF, CC, MODE_SCORE, XF != 0, DCX_TRAJ_NACC>(sa, x, up, j0, j1, sc, gx);
                 const auto& b = reload_kernargs<TrajFusedArgs>();
                 const TrajLds L = traj_lds<D, CC>(smem, b, nw);
                 float* mine = L.sRed + (size_t)wave * ACC * 64 + lane;
@@ -506,7 +507,7 @@ __global__ __launch_bounds__(MAXT, (MAXT / 256 > 0 ? MAXT / 256 : 1)) void traj_
                 for (int c = 0; c < CC; ++c) sc[c] = 0.0f;
 #pragma unroll
                 for (int k = 0; k < D; ++k) gx[k] = 0.0f;
-                sweep_rows<D, KF, CC, MODE_GRAD_UP, XF, DCX_TRAJ_NACC, true>(sa, x, up, j0, j1, sc, gx);   // (NS: the scores are known)
+                sweep_rows<D, KF, CC, MODE_GRAD_UP, XF != 0, DCX_TRAJ_NACC, true>(sa, x, up, j0, j1, sc, gx);   // (NS: the scores are known)
             }
             grad_folded = !resweep;             // a speculation that held (or no gradient at all): the totals are in row 0 already
             regrad = spec_full && resweep;      // a speculation that failed: its second gradient travels through words of its own
