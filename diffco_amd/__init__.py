@@ -17,7 +17,7 @@ from . import escape  # noqa: F401
 from . import urdf  # noqa: F401
 from .urdf import URDFRobotFK, MultiURDFRobotFK  # noqa: F401
 from . import collision_checkers  # noqa: F401
-from .collision_checkers import RBFDiffCo, ForwardKinematicsDiffCo  # noqa: F401
+from .collision_checkers import RBFDiffCo, ForwardKinematicsDiffCo, HybridForwardKinematicsDiffCo  # noqa: F401
 from .traj import fused_adam_traj_optimize  # noqa: F401
 
-__all__ = ["kernel", "model", "utils", "optim", "sharded", "traj", "escape", "fused_adam_traj_optimize", "urdf", "URDFRobotFK", "MultiURDFRobotFK", "collision_checkers", "RBFDiffCo", "ForwardKinematicsDiffCo", "deprecated", "DiffCo", "MultiDiffCo", "DiffCoBeta"]
+__all__ = ["kernel", "model", "utils", "optim", "sharded", "traj", "escape", "fused_adam_traj_optimize", "urdf", "URDFRobotFK", "MultiURDFRobotFK", "collision_checkers", "RBFDiffCo", "ForwardKinematicsDiffCo", "HybridForwardKinematicsDiffCo", "deprecated", "DiffCo", "MultiDiffCo", "DiffCoBeta"]

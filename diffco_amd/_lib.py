@@ -73,6 +73,10 @@ SYMBOLS = {
     "dcx_motion_worst_work_bytes": (C.c_size_t, [C.c_void_p, C.c_int64]),
     "dcx_motion_worst": (C.c_int, [C.c_void_p, _c_fp, _c_fp, C.c_int64, C.c_void_p, _c_fp, _c_fp, _c_fp, _c_fp, _c_fp, _c_fp, _c_fp,
                                    C.c_void_p, C.c_size_t, C.c_uint64, C.c_void_p]),
+    # hybrid motion checks: sure verdicts per edge and the ordered list of the samples that still need the ground truth
+    "dcx_motion_band_work_bytes": (C.c_size_t, [C.c_void_p, C.c_int64, C.c_int32]),
+    "dcx_motion_band": (C.c_int, [C.c_void_p, _c_fp, _c_fp, C.c_int64, C.c_void_p, _c_fp, _c_fp, C.c_void_p, C.c_void_p, C.c_size_t,
+                                  C.c_uint64, C.c_void_p]),
     # dense-check Adam trajectory loop: the collision hinge along the segments (dcx_motion_cost_ex per iteration)
     "dcx_traj_dense_step": (C.c_int, [C.c_int, C.POINTER(FkDesc), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32,
                                       C.c_void_p]),
@@ -108,6 +112,12 @@ class EscapeOpts(C.Structure):
 class MotionOpts(C.Structure):
     """ctypes mirror of dcx_motion_opts (include/dcx.h)"""
     _fields_ = [("res", C.c_int32), ("max_step", C.c_float), ("max_samples", C.c_int32), ("reserved", C.c_int32)]
+
+
+class MotionBandOut(C.Structure):
+    """ctypes mirror of dcx_motion_band_out (include/dcx.h)"""
+    _fields_ = [(n, C.c_void_p) for n in ("verdict", "first_hit", "n_samples", "n_uncertain", "unc_total", "unc_edge",
+                                          "unc_sample", "unc_q")] + [("unc_cap", C.c_int64), ("reserved", C.c_int64 * 2)]
 
 
 class MotionCostOpts(C.Structure):

@@ -612,6 +612,80 @@ class ScoreModel:
         kw = dict(max_step=max_step, margin=margin, max_samples=max_samples, wrap=wrap)
         return compose_path_worst(lambda a, b: self.motion_worst(a, b, **kw), paths, self.dof)
 
+    def motion_band_raw(self, qa, qb, lo, hi, res=None, max_step=None, max_samples=None, wrap=None, unc_cap=0, want_q=True):
+        """one dcx_motion_band call with a list capacity of `unc_cap` entries; nothing is read back (capturable when
+        max_samples is given and lo / hi are numbers or device tensors).  A dict of device tensors: verdict, first_hit,
+        n_samples, n_uncertain [E] int32, unc_total [1] int64, unc_edge, unc_sample [unc_cap] int32, unc_q [unc_cap, dof]
+        fp32 (None without want_q).  Only the first min(unc_total, unc_cap) list entries are written."""
+        if (res is None) == (max_step is None):
+            raise ValueError("motion_band takes exactly one of res and max_step")
+        mask = wrap_mask(wrap, self.dof)
+        qa32 = _f32(torch.as_tensor(qa).reshape(-1, self.dof), self.dev)
+        qb32 = _f32(torch.as_tensor(qb).reshape(-1, self.dof), self.dev)
+        if qa32.shape != qb32.shape:
+            raise ValueError(f"{len(qa32)} start and {len(qb32)} target configurations")
+        on_dev = lambda t: torch.is_tensor(t) and t.device == self.dev
+        if not (on_dev(lo) or on_dev(hi)):   # (device thresholds are not read back: there hit wins, as in the C call)
+            bad = [c for c, (l, h) in enumerate(zip(self.margins(lo), self.margins(hi))) if l > h]
+            if bad:
+                raise ValueError(f"motion_band: lo > hi for class {bad[0]}")
+        E = len(qa32)
+        cap = int(unc_cap)
+        if cap < 0:
+            raise ValueError("motion_band: a negative list capacity")
+        if max_samples is None:
+            max_samples = int(res) if res is not None else motion_bound(qa32, qb32, max_step, wrap=mask)
+        opt = _lib.MotionOpts(int(res) if res is not None else 0, float(max_step) if max_step is not None else 0.0, int(max_samples), 0)
+        lo_t, hi_t = self._motion_margin(lo), self._motion_margin(hi)
+        i32 = lambda *shape: torch.empty(shape, device=self.dev, dtype=torch.int32)
+        r = dict(verdict=i32(E), first_hit=i32(E), n_samples=i32(E), n_uncertain=i32(E),
+                 unc_total=torch.zeros(1, device=self.dev, dtype=torch.int64), unc_edge=i32(cap), unc_sample=i32(cap),
+                 unc_q=torch.empty((cap, self.dof), device=self.dev, dtype=torch.float32) if want_q else None)
+        out = _lib.MotionBandOut(*(_ptr(r[k]) for k in ("verdict", "first_hit", "n_samples", "n_uncertain", "unc_total",
+                                                        "unc_edge", "unc_sample", "unc_q")), cap)
+        nbytes = self._lib.dcx_motion_band_work_bytes(self._h, E, int(max_samples))
+        work = torch.empty(max(int(nbytes), 1), device=self.dev, dtype=torch.uint8)
+        with _on_device(self.dev):
+            _lib.check(self._lib.dcx_motion_band(self._h, _ptr(qa32), _ptr(qb32), E, C.byref(opt), _ptr(lo_t), _ptr(hi_t),
+                                                 C.byref(out), _ptr(work), int(nbytes), mask, self._st()))
+        return r
+
+    def motion_band(self, qa, qb, lo, hi, res=None, max_step=None, max_samples=None, wrap=None, max_uncertain=None, want_q=True):
+        """hybrid motion checks (dcx_motion_band): for E straight joint-space motions qa[e] -> qb[e] ([E, dof] each) on
+        check_motions' sample set and two thresholds lo <= hi (a number or one per class, as `margin`), a sample is a sure hit
+        where score_c - hi_c > 0 for some class, surely clear where score_c - lo_c <= 0 for every class, and uncertain
+        otherwise (a NaN score included).  Returns (verdict, first_hit, n_uncertain, unc_edge, unc_sample, unc_q), device tensors:
+          verdict [E] int32      1 a sure hit, else 2 an uncertain sample, else 0; -2: over `max_samples`, not checked
+          first_hit [E] int32    the first sure hit: check_motions(margin=hi)'s answer, bit for bit
+          n_uncertain [E] int32  the uncertain samples of a verdict-2 edge, 0 for every other edge
+          unc_edge, unc_sample [U] int32, unc_q [U, dof] fp32 (None without want_q): the uncertain samples of the verdict-2
+                                 edges in (edge, sample) order with their configurations - what a ground-truth checker still
+                                 has to look at
+        max_uncertain=None: U is the full count.  The call picks a capacity, reads the count back - this SYNCHRONISES - and
+        repeats once with the exact capacity if the list was cut.  max_uncertain given: the list arrays have that many rows,
+        of which the first min(unc_total, max_uncertain) are written; nothing is read back (with max_samples given the call
+        can be captured) and unc_total ([1] int64, device) is returned as a seventh value.
+        Raises ValueError where lo > hi for some class.  `res`, `max_step`, `max_samples` and `wrap` as check_motions."""
+        kw = dict(res=res, max_step=max_step, max_samples=max_samples, wrap=wrap, want_q=want_q)
+        keys = ("verdict", "first_hit", "n_uncertain", "unc_edge", "unc_sample", "unc_q")
+        if max_uncertain is not None:
+            r = self.motion_band_raw(qa, qb, lo, hi, unc_cap=max_uncertain, **kw)
+            return tuple(r[k] for k in keys) + (r["unc_total"],)
+        E = torch.as_tensor(qa).reshape(-1, self.dof).shape[0]
+        r = self.motion_band_raw(qa, qb, lo, hi, unc_cap=max(4096, 2 * E), **kw)
+        total = int(r["unc_total"])
+        if total > len(r["unc_edge"]):
+            r = self.motion_band_raw(qa, qb, lo, hi, unc_cap=total, **kw)
+        cut = lambda t: None if t is None else t[:total]
+        return r["verdict"], r["first_hit"], r["n_uncertain"], cut(r["unc_edge"]), cut(r["unc_sample"]), cut(r["unc_q"])
+
+    def score_band(self, q, lo, hi):
+        """(label [B] int32, unc_idx [U] int64) for configurations q [B, dof]: label 1 where score_c - hi_c > 0 for some class,
+        0 where score_c - lo_c <= 0 for every class, 2 otherwise, and the ascending indices of the label-2 configurations.
+        It is motion_band(q, q, res=1): one sample per "edge" (synchronises, as motion_band without max_uncertain)."""
+        verdict, _, _, unc_edge, _, _ = self.motion_band(q, q, lo, hi, res=1, want_q=False)
+        return verdict, unc_edge.to(torch.int64)
+
     # autograd-aware ------------------------------------------------------------------------
     def score(self, q: torch.Tensor) -> torch.Tensor:
         """[B, C] scores for q [B, dof]; differentiable w.r.t. q (gradient from the fused HIP pass)."""

@@ -260,12 +260,10 @@ def _wrap_points(pts, mask):
     return torch.where(on, wrap2pi(pts), pts)
 
 
-def host_motions(score_fn, qa, qb, res=None, max_step=None, margin=0., max_samples=None, wrap=0):
-    """the composition a caller would write without dcx_check_motions: every edge's points (line_predict's / dense_path's
-    arithmetic; `wrap`, a bitmask: utils.anglin's on the masked coordinates) materialised, ONE score launch over all of them,
-    the first hit per edge.  Same answers, (first_hit, n_samples)."""
+def _motion_samples(qa, qb, res, max_step, max_samples, wrap):
+    """every checked edge's points, materialised (line_predict's / dense_path's arithmetic; `wrap`, a bitmask: utils.anglin's
+    on the masked coordinates): (pts [N, dof], edge [N], k [N], n [E] the counts the edges need, ok [E] within the limit)"""
     import torch
-    qa, qb = qa.reshape(len(qa), -1), qb.reshape(len(qb), -1)
     E, dev = len(qa), qa.device
     d = _ops.wrapped_delta(qa, qb, wrap)
     if res is not None:
@@ -288,6 +286,17 @@ def host_motions(score_fn, qa, qb, res=None, max_step=None, margin=0., max_sampl
         pts = _wrap_points(qa[edge] + k.to(qa.dtype)[:, None] * (d[edge] * frac[edge][:, None]), wrap)
         last = k == n[edge] - 1
         pts = torch.where(last[:, None], qb[edge], pts)
+    return pts, edge, k, n, ok
+
+
+def host_motions(score_fn, qa, qb, res=None, max_step=None, margin=0., max_samples=None, wrap=0):
+    """the composition a caller would write without dcx_check_motions: every edge's points (line_predict's / dense_path's
+    arithmetic; `wrap`, a bitmask: utils.anglin's on the masked coordinates) materialised, ONE score launch over all of them,
+    the first hit per edge.  Same answers, (first_hit, n_samples)."""
+    import torch
+    qa, qb = qa.reshape(len(qa), -1), qb.reshape(len(qb), -1)
+    E, dev = len(qa), qa.device
+    pts, edge, k, n, ok = _motion_samples(qa, qb, res, max_step, max_samples, wrap)
     first = torch.full((E,), -1, dtype=torch.int64, device=dev)
     if len(pts):
         s = score_fn(pts).reshape(len(pts), -1)
@@ -331,6 +340,75 @@ def motion_answer(first, return_first):
         raise ValueError(f"check_motions: edges {bad} need more than max_samples samples (pass a larger max_samples or max_step)")
     hit = first >= 0
     return (hit, first) if return_first else hit
+
+
+# ---- hybrid motion checks ----------------------------------------------------------------------------------------------------
+def host_motion_band(score_fn, qa, qb, lo, hi, res=None, max_step=None, max_samples=None, wrap=0, want_q=True):
+    """the composition a caller would write without dcx_motion_band: host_motions' samples materialised, ONE score launch over
+    all of them, the two thresholds, a segment reduction per edge and a `nonzero` for the list.  ScoreModel.motion_band's
+    outputs in its order: (verdict, first_hit, n_uncertain, unc_edge, unc_sample, unc_q)."""
+    import torch
+    qa, qb = qa.reshape(len(qa), -1), qb.reshape(len(qb), -1)
+    E, dev = len(qa), qa.device
+    pts, edge, k, n, ok = _motion_samples(qa, qb, res, max_step, max_samples, wrap)
+    big = torch.iinfo(torch.int64).max
+    first = torch.full((E,), -1, dtype=torch.int64, device=dev)
+    n_unc = torch.zeros(E, dtype=torch.int64, device=dev)
+    listed = torch.zeros(len(pts), dtype=torch.bool, device=dev)
+    if len(pts):
+        s = score_fn(pts).reshape(len(pts), -1)
+        lo_t = torch.as_tensor(lo, dtype=s.dtype, device=s.device).reshape(-1)
+        hi_t = torch.as_tensor(hi, dtype=s.dtype, device=s.device).reshape(-1)
+        hit = (s - hi_t > 0).any(dim=-1)
+        clear = (s - lo_t <= 0).all(dim=-1)           # (a NaN score is neither: the sample is uncertain)
+        unc = ~hit & ~clear
+        cand = torch.where(hit, k, torch.full_like(k, big))
+        first = torch.full((E,), big, dtype=torch.int64, device=dev).scatter_reduce(0, edge, cand, reduce="amin")
+        first = torch.where(first == big, torch.full_like(first, -1), first)
+        n_unc = n_unc.index_add(0, edge, unc.to(torch.int64))
+        n_unc = torch.where(first >= 0, torch.zeros_like(n_unc), n_unc)   # an edge with a sure hit is decided
+        listed = unc & (first[edge] < 0)
+    verdict = torch.where(first >= 0, torch.ones_like(first), torch.where(n_unc > 0, torch.full_like(first, 2), torch.zeros_like(first)))
+    verdict = torch.where(ok, verdict, torch.full_like(verdict, -2))
+    first = torch.where(ok, first, torch.full_like(first, -2))
+    at = listed.nonzero().reshape(-1)                  # ascending flat index: (edge, sample) order
+    i32 = torch.int32
+    return (verdict.to(i32), first.to(i32), n_unc.to(i32), edge[at].to(i32), k[at].to(i32), pts[at] if want_q else None)
+
+
+def motion_band(owner, fused, transform, kernel_func, support_feat, weights, qa, qb, lo, hi, res=None, max_step=None,
+                max_samples=None, score_fn=None, wrap=None, want_q=True):
+    """(verdict, first_hit, n_uncertain, unc_edge, unc_sample, unc_q) of the motions qa[e] -> qb[e] on the model `fused` holds:
+    dcx_motion_band where the transform fuses (none, or a diffco_amd robot's fkine), else the host composition (a foreign
+    callable through `score_fn`).  owner.last_route says which ran: "fused" or "host".  Both read the list's length back.
+    Raises ValueError where lo > hi.  `wrap`: as check_motions."""
+    import torch
+    if (res is None) == (max_step is None):
+        raise ValueError("motion_band takes exactly one of res and max_step")
+    qa, qb = torch.as_tensor(qa), torch.as_tensor(qb)
+    mask = _ops.wrap_mask(wrap, qa.shape[-1], transform)
+    dev = qa.device if qa.device.type == "cuda" else (support_feat.device if support_feat.device.type == "cuda" else None)
+    m = fused.model(transform, kernel_func, support_feat, weights, dev)
+    kw = dict(res=res, max_step=max_step, max_samples=max_samples, wrap=mask, want_q=want_q)
+    if m.desc.kind == 0 and transform is not None:
+        owner.last_route = "host"
+        lo_c, hi_c = list(m.margins(lo)), list(m.margins(hi))
+        if any(l > h for l, h in zip(lo_c, hi_c)):
+            raise ValueError("motion_band: lo > hi")
+        fn = score_fn or (lambda p: fused.score(transform, kernel_func, support_feat, weights, p))
+        qa_d, qb_d = qa.to(device=m.dev, dtype=torch.float32), qb.to(device=m.dev, dtype=torch.float32)
+        return host_motion_band(lambda p: fn(p).detach(), qa_d, qb_d, lo_c, hi_c, **kw)
+    owner.last_route = "fused"
+    return m.motion_band(qa, qb, lo, hi, **kw)
+
+
+def score_band(owner, fused, transform, kernel_func, support_feat, weights, q, lo, hi, score_fn=None):
+    """(label [B] int32, unc_idx [U] int64) of the configurations q: motion_band(q, q, res=1), one sample per "edge", on
+    either route"""
+    import torch
+    verdict, _, _, unc_edge, _, _ = motion_band(owner, fused, transform, kernel_func, support_feat, weights, q, q, lo, hi, res=1,
+                                                score_fn=score_fn, want_q=False)
+    return verdict, unc_edge.to(torch.int64)
 
 
 # ---- differentiable motion costs ---------------------------------------------------------------------------------------------

@@ -358,3 +358,119 @@ class ForwardKinematicsDiffCo(RBFDiffCo):
         else:
             raise ValueError("collision_score needs q or q_link_pos")
         return raw + bias
+
+
+class HybridForwardKinematicsDiffCo(ForwardKinematicsDiffCo):
+    """ForwardKinematicsDiffCo used safely in a planner: the proxy's verdict counts where the unbiased poly score is clearly
+    above +band or at or below -band, and only the configurations inside the band go to `gt_check_func` (a callable
+    q [U, dof] -> bool [U]).  `band` defaults to safety_bias.  With lazy_line_check only the worst configuration of a line is
+    ground-truth checked.  `last_gt_checks` counts the configurations the last call handed to the ground truth.
+
+    The reference's class (collision_checkers.py:511-548) reads `self.safe_bias` in its non-lazy branch, an attribute nothing
+    defines, so that branch raises as written; the band it means is [-safety_bias, +safety_bias] on the unbiased score."""
+
+    def __init__(self, robot=None, robot_base_transform=None, environment=None, robot_topic=None,
+                 planning_scene_topic=None, gt_check_func=None, device='cpu', lazy_line_check=False, perceptron_class=DiffCo,
+                 **perceptron_kwargs):
+        super().__init__(robot=robot, robot_base_transform=robot_base_transform, environment=environment,
+                         robot_topic=robot_topic, planning_scene_topic=planning_scene_topic, gt_check_func=gt_check_func,
+                         device=device, perceptron_class=perceptron_class, **perceptron_kwargs)
+        self.lazy_line_check = lazy_line_check
+        self.last_gt_checks = 0
+
+    def _band(self, band):
+        band = self.safety_bias if band is None else band
+        band = float(band)
+        if not band >= 0:
+            raise ValueError(f"the uncertainty band must be >= 0, got {band}")
+        return band
+
+    def _poly_args(self):
+        p = self.perceptron
+        return p._poly_fused, p.transform, p.rbf_kernel, p.support_transformed, p.rbf_nodes
+
+    def _gt(self, q, device):
+        self.last_gt_checks += len(q)
+        return torch.as_tensor(self.gt_check_func(q)).reshape(-1).to(device=device, dtype=torch.bool)
+
+    def collision(self, q, band=None):
+        """bool labels q.shape[:-1] (the reference's lines 538-548 with the band it means).  Not lazy: a score above +band
+        collides, one at or below -band is free, and the configurations between go through `gt_check_func` in ONE call, in
+        order; their labels replace the proxy's.  Lazy (q: the points of one line): the labels are score + safety_bias > 0,
+        and the one configuration with the largest score is ground-truth checked."""
+        self.last_gt_checks = 0
+        shape = q.shape[:-1]
+        q2 = q.reshape(-1, q.shape[-1])
+        if self.lazy_line_check:
+            s = self.collision_score(q2, bias=0).reshape(len(q2), -1).amax(dim=-1)
+            labels = s + self.safety_bias > 0
+            if len(q2):
+                i = s.argmax()
+                labels[i] = self._gt(q2[i:i + 1], labels.device)[0]
+            return labels.reshape(shape)
+        from ._perceptron import score_band
+        band = self._band(band)
+        label, unc_idx = score_band(self, *self._poly_args(), q2, -band, band)
+        labels = (label == 1).to(q2.device)
+        if len(unc_idx):
+            unc_idx = unc_idx.to(q2.device)
+            labels[unc_idx] = self._gt(q2[unc_idx], q2.device)
+        return labels.reshape(shape)
+
+    def check_motions(self, q_start, q_end, max_step=None, res=None, band=None, return_first=False, max_samples=None, wrap=None):
+        """is the straight motion q_start[e] -> q_end[e] in collision?  bool [E]; with return_first also the first sample that
+        collided - sure, or confirmed by the ground truth - (-1 = free).  One dcx_motion_band call on the unbiased poly score
+        with lo = -band, hi = +band (`band` defaults to safety_bias); exactly one rule and `wrap` as
+        ForwardKinematicsDiffCo.check_motions.
+        Not lazy: `gt_check_func` is called once on the uncertain samples of the edges without a sure hit; such an edge
+        collides iff one of its listed samples does.  Lazy: one dcx_motion_worst call at bias 0; only the worst sample of each
+        edge whose peak lies in the band is ground-truth checked, and the edge takes its label (the sample returned with
+        return_first is then the edge's worst sample, not its first one above the band)."""
+        from ._perceptron import motion_band, motion_worst
+        band = self._band(band)
+        self.last_gt_checks = 0
+        q_start, q_end = torch.as_tensor(q_start), torch.as_tensor(q_end)
+        kw = dict(res=res, max_step=max_step, max_samples=max_samples, wrap=wrap)
+        if self.lazy_line_check:
+            worst, idx, _ = motion_worst(self, *self._poly_args(), q_start, q_end, margin=0., **kw)
+            worst, first = worst.detach(), idx.to(torch.int64)
+            hit = worst > band
+            unc = ~hit & ~(worst <= -band)
+            first = torch.where(hit | unc, first, torch.full_like(first, -1))
+            e = unc.nonzero().reshape(-1)
+            if len(e):
+                q = self._motion_points(q_start, q_end, e, first[e], res, max_step, wrap)
+                gt = self._gt(q, hit.device)
+                hit[e] = gt
+                first[e] = torch.where(gt, first[e], torch.full_like(first[e], -1))
+            return (hit, first.to(torch.int32)) if return_first else hit
+        verdict, first, _, unc_edge, unc_sample, unc_q = motion_band(self, *self._poly_args(), q_start, q_end, -band, band, **kw)
+        if bool((verdict == -2).any()):
+            bad = (verdict == -2).nonzero().reshape(-1)[:8].tolist()
+            raise ValueError(f"check_motions: edges {bad} need more than max_samples samples (pass a larger max_samples or max_step)")
+        hit = verdict == 1
+        first = first.clone()
+        if len(unc_edge):
+            gt = self._gt(unc_q.to(device=q_start.device, dtype=q_start.dtype), hit.device)
+            edges, samples = unc_edge.to(torch.int64)[gt], unc_sample[gt]
+            hit[edges] = True
+            big = torch.iinfo(torch.int32).max
+            confirmed = torch.full_like(first, big).scatter_reduce(0, edges, samples, reduce="amin")
+            first = torch.where(confirmed < big, confirmed, first)
+        return (hit, first) if return_first else hit
+
+    def _motion_points(self, q_start, q_end, edges, samples, res, max_step, wrap):
+        """sample samples[i] of the edge edges[i]: the points the host composition materialises (_perceptron._motion_samples)"""
+        from . import _ops
+        from ._perceptron import _wrap_points
+        qa = q_start.reshape(-1, q_start.shape[-1])[edges.to(q_start.device)]
+        qb = q_end.reshape(-1, q_end.shape[-1])[edges.to(q_end.device)]
+        mask = _ops.wrap_mask(wrap, qa.shape[-1], self.perceptron.transform)
+        d = _ops.wrapped_delta(qa, qb, mask)
+        k = samples.to(device=qa.device, dtype=qa.dtype)[:, None]
+        if res is not None:
+            return _wrap_points(qa + d * (k / int(res)), mask)
+        L = d.norm(dim=-1, keepdim=True)
+        n = torch.ceil(L / max_step) + 1
+        pts = _wrap_points(qa + k * (d * (max_step / L)), mask)
+        return torch.where(k == n - 1, qb, pts)

@@ -15,6 +15,7 @@
 #include "motion_cost_kernel.h"
 #include "motion_kernel.h"
 #include "motion_worst_kernel.h"
+#include "motion_band_kernel.h"
 #include "pack_kernels.h"
 #include "solve_kernels.h"
 #include "traj_dense.h"
@@ -1967,6 +1968,132 @@ int dcx_motion_worst(const dcx_model* m, const float* qa, const float* qb, int64
     f.grad_b = grad_b;
     e = launch_motion_worst_chain(f, st);
     if (e != hipSuccess) return fail_hip(e, "motion worst chain launch");
+    return DCX_OK;
+}
+
+// ---- hybrid motion checks (motion_band_kernel.h, motion_band_finish.hip) -----------------------------------------------------
+namespace {
+// the workspace: dcx_check_motions' (work list, split-launch room), then per edge its status, one code byte per possible sample
+// (E * max_samples rounded up to whole tiles; flat sample s below offs[E] at codes[s], as dcx_motion_cost's per-sample values)
+// and the int64 offsets of the list [E + 1]
+struct MotionBandWork {
+    MotionWork mw;
+    size_t status, codes, uoffs, total;
+};
+MotionBandWork motion_band_work(int64_t E, int32_t max_samples) {
+    auto up = [](size_t x) { return (x + 255) / 256 * 256; };
+    const size_t n = (size_t)E * (size_t)(max_samples > 0 ? max_samples : 0);
+    MotionBandWork w;
+    w.mw = motion_work(E);
+    w.status = w.mw.total;
+    w.codes = w.status + up((size_t)E * sizeof(int32_t));
+    w.uoffs = w.codes + up((n + 63) / 64 * 64);
+    w.total = w.uoffs + up((size_t)(E + 1) * sizeof(int64_t));
+    return w;
+}
+motion_band_fn motion_band_for(int Dt) {
+    switch (Dt) {
+#define DCX_CASE(D) case D: return launch_motion_band_D##D;
+        DCX_CASE(2) DCX_CASE(4) DCX_CASE(6) DCX_CASE(8) DCX_CASE(12) DCX_CASE(16) DCX_CASE(18) DCX_CASE(21)
+        DCX_CASE(24) DCX_CASE(27) DCX_CASE(30) DCX_CASE(32) DCX_CASE(36) DCX_CASE(42) DCX_CASE(48) DCX_CASE(54)
+        DCX_CASE(60) DCX_CASE(64) DCX_CASE(72) DCX_CASE(84) DCX_CASE(96)
+#undef DCX_CASE
+    default: return nullptr;
+    }
+}
+}  // namespace
+
+size_t dcx_motion_band_work_bytes(const dcx_model* m, int64_t E, int32_t max_samples) {
+    if (!m || E < 0 || max_samples < 1) return 0;
+    return motion_band_work(E, max_samples).total;
+}
+
+int dcx_motion_band(const dcx_model* m, const float* qa, const float* qb, int64_t E, const dcx_motion_opts* opt,
+                    const float* lo, const float* hi, const dcx_motion_band_out* out, void* work, size_t work_bytes,
+                    uint64_t wrap_mask, void* stream) {
+    // every argument is checked before anything touches the device
+    if (!m) return fail(DCX_ERR_INVALID, "model is NULL");
+    if (!opt) return fail(DCX_ERR_INVALID, "motion options are NULL");
+    if (!out) return fail(DCX_ERR_INVALID, "motion band: out is NULL");
+    if (E < 0) return fail(DCX_ERR_INVALID, "E < 0");
+    if (E > 0 && (!qa || !qb || !work)) return fail(DCX_ERR_INVALID, "qa / qb / work is NULL");
+    if (E > 0 && (!out->verdict || !out->unc_total)) return fail(DCX_ERR_INVALID, "motion band: verdict / unc_total is NULL");
+    if (out->unc_cap < 0) return fail(DCX_ERR_INVALID, "motion band: unc_cap < 0");
+    if (out->unc_cap > 0 && (!out->unc_edge || !out->unc_sample))
+        return fail(DCX_ERR_INVALID, "motion band: unc_edge / unc_sample is NULL with unc_cap > 0");
+    if (out->reserved[0] || out->reserved[1]) return fail(DCX_ERR_INVALID, "motion band: out's reserved fields must be 0");
+    const bool by_res = opt->res > 0, by_step = opt->max_step > 0.f;
+    if (opt->res < 0 || !(opt->max_step >= 0.f) || by_res == by_step)
+        return fail(DCX_ERR_INVALID, "motion band needs exactly one sampling rule: res > 0 or max_step > 0 (the other 0)");
+    if (opt->max_samples < 1) return fail(DCX_ERR_INVALID, "motion band needs max_samples >= 1");
+    if (opt->reserved != 0) return fail(DCX_ERR_INVALID, "motion band: reserved must be 0");
+    if (wrap_mask != 0 && m->fk.dof < 64 && (wrap_mask >> m->fk.dof) != 0)
+        return fail(DCX_ERR_INVALID, "motion band: wrap_mask has a bit at or above dof");
+    const MotionBandWork w = motion_band_work(E, opt->max_samples);
+    if (E > 0 && work_bytes < w.total) return fail(DCX_ERR_INVALID, "motion workspace is smaller than dcx_motion_band_work_bytes");
+    if (E > INT32_MAX) return fail(DCX_ERR_UNSUPPORTED, "motion band: more than 2^31 - 1 edges");
+    if (E == 0) return DCX_OK;
+    const int64_t tiles_max = (E * (int64_t)opt->max_samples + 63) / 64;
+    if (tiles_max > 0x7fffffffLL) return fail(DCX_ERR_UNSUPPORTED, "motion band: E * max_samples too large for one launch");
+    motion_band_fn launch = motion_band_for(m->Dt);
+    if (!launch) return fail(DCX_ERR_UNSUPPORTED, "motion band: no kernel for this feature width");
+    if (int rc = set_device(m->device)) return rc;
+    hipStream_t st = (hipStream_t)stream;
+    char* base = (char*)work;
+    MotionBandArgs a{};
+    const MotionSweepPlan plan = motion_sweep_plan(m, tiles_max, base, w.mw, a.sc);   // the check's geometry and sweep arguments
+    const Geometry& g = plan.g;
+    MotionPrepArgs p{};
+    p.qa = qa;
+    p.qb = qb;
+    p.E = E;
+    p.dof = m->fk.dof;
+    p.res = opt->res;
+    p.max_samples = opt->max_samples;
+    p.max_step = opt->max_step;
+    p.offs = (int64_t*)(base + w.mw.offs);
+    p.frac = (float*)(base + w.mw.frac);
+    p.first_hit = (int32_t*)(base + w.status);
+    p.n_samples = out->n_samples;
+    p.counters = g.ys > 1 ? (unsigned int*)(base + w.mw.counters) : nullptr;
+    p.n_counters = g.ys > 1 ? (int32_t)tiles_max : 0;
+    p.wrap_mask = wrap_mask;
+    hipError_t e = launch_motion_prep(p, st);
+    if (e != hipSuccess) return fail_hip(e, "motion band prep launch");
+    a.qa = qa;
+    a.qb = qb;
+    a.offs = p.offs;
+    a.frac = p.frac;
+    a.codes = (uint8_t*)(base + w.codes);
+    a.lo = lo;
+    a.hi = hi;
+    a.E = E;
+    a.res = opt->res;
+    a.wrap_mask = wrap_mask;
+    e = launch(m->kf, m->Cc, g.nw, plan.lds, tiles_max, a, st);
+    if (e != hipSuccess) return fail_hip(e, "motion band kernel launch");
+    MotionBandFinishArgs f{};
+    f.qa = qa;
+    f.qb = qb;
+    f.offs = p.offs;
+    f.frac = p.frac;
+    f.status = p.first_hit;
+    f.codes = a.codes;
+    f.verdict = out->verdict;
+    f.first_hit = out->first_hit;
+    f.n_uncertain = out->n_uncertain;
+    f.uoffs = (int64_t*)(base + w.uoffs);
+    f.unc_total = out->unc_total;
+    f.unc_edge = out->unc_edge;
+    f.unc_sample = out->unc_sample;
+    f.unc_q = out->unc_q;
+    f.unc_cap = out->unc_cap;
+    f.E = E;
+    f.dof = m->fk.dof;
+    f.res = opt->res;
+    f.wrap_mask = wrap_mask;
+    e = launch_motion_band_finish(f, st);
+    if (e != hipSuccess) return fail_hip(e, "motion band finish launch");
     return DCX_OK;
 }
 

@@ -341,6 +341,23 @@ class DiffCo(Perceptron):
         return path_worst(self, self._score_fused, self.transform, self.kernel_func, self.support_transformed, self.gains, paths,
                           max_step, margin=margin, max_samples=max_samples, wrap=wrap)
 
+    def motion_band(self, starts, targets, lo, hi, res=None, max_step=None, max_samples=None, wrap=None, want_q=True):
+        """hybrid motion checks on `score`: (verdict, first_hit, n_uncertain, unc_edge, unc_sample, unc_q) of the motions
+        starts[e] -> targets[e] on check_motions' samples - verdict 1 where a sample scores above hi, else 2 where one lies
+        above lo (or is NaN), else 0, and the (edge, sample)-ordered list of the uncertain samples of the verdict-2 edges with
+        their configurations, for a ground-truth checker.  One fused call (dcx_motion_band) where the transform fuses, the
+        host composition for a foreign callable (`last_route`).  Raises ValueError where lo > hi."""
+        from ._perceptron import motion_band
+        return motion_band(self, self._score_fused, self.transform, self.kernel_func, self.support_transformed, self.gains,
+                           starts, targets, lo, hi, res=res, max_step=max_step, max_samples=max_samples, wrap=wrap, want_q=want_q)
+
+    def score_band(self, point, lo, hi):
+        """(label [N] int32, unc_idx [U] int64): 1 where `score` lies above hi, 0 where it is at or below lo, 2 between (or NaN),
+        and the ascending indices of the label-2 configurations: motion_band with one sample per edge"""
+        from ._perceptron import score_band
+        return score_band(self, self._score_fused, self.transform, self.kernel_func, self.support_transformed, self.gains,
+                          point, lo, hi)
+
     def poly_score(self, point=None, transformed_point=None):
         """sum_j K_rbf(T(q), support_j) rbf_nodes_j  ->  [N, 1]; `transformed_point` skips the FK."""
         if transformed_point is None:

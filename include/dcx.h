@@ -488,6 +488,58 @@ int dcx_motion_worst(const dcx_model* m, const float* qa, const float* qb, int64
                      const float* margin, float* worst, int32_t* worst_idx, int32_t* worst_class, int32_t* n_samples,
                      float* grad_a, float* grad_b, void* work, size_t work_bytes, uint64_t wrap_mask, void* stream);
 
+/* ---- hybrid motion checks (added under DCX_VERSION 109) --------------------------------------------------- */
+/* A two-threshold motion check: the proxy's verdict where its score is clearly above hi or clearly at or below lo, and a compact,
+ * ordered list of exactly those samples that still need a ground-truth checker (the reference's HybridForwardKinematicsDiffCo,
+ * collision_checkers.py:511-548, for motions).  E edges per call on exactly dcx_check_motions_ex's sample set, bit for bit (one
+ * rule per call: the res rule or the closed max_step rule; wrap_mask as there).  opt->reserved must be 0.
+ *   lo, hi         [C] device floats, NULL = 0 for that side
+ *   sample code    from the class scores s_c of sample k:  hit_k = some c has s_c - hi_c > 0 (dcx_check_motions' comparison with
+ *                  margin = hi);  clear_k = every c has s_c - lo_c <= 0;  code 1 if hit_k, else 0 if clear_k, else 2.  A NaN
+ *                  class score is neither a hit nor clear: the sample is uncertain.  lo_c > hi_c is the caller's error: hit wins
+ *   verdict [E]      (int32, device, out)                1 if a sample has code 1, else 2 if one has code 2, else 0;
+ *                                                        -2 for an edge over max_samples (not checked)
+ *   first_hit [E]    (int32, device, out, may be NULL)   the smallest k with code 1, -1 none, -2 over max_samples
+ *   n_samples [E]    (int32, device, out, may be NULL)   as dcx_check_motions'
+ *   n_uncertain [E]  (int32, device, out, may be NULL)   the code-2 samples of an edge with verdict 2; 0 for every other edge
+ *                                                        (an edge with a sure hit is decided: its band samples do not count)
+ *   unc_total [1]    (int64, device, out)                the sum of n_uncertain; may exceed unc_cap
+ *   unc_edge, unc_sample [unc_cap] (int32, device, out)  the code-2 samples of the verdict-2 edges, ordered by (edge, sample)
+ *                                                        ascending: entry j at index j for j < unc_cap, nothing written at or
+ *                                                        beyond unc_cap
+ *   unc_q [unc_cap, dof] (float, device, out, may be NULL) the listed samples' configurations as the sweep evaluated them
+ * An edge over max_samples: verdict -2, first_hit -2, n_uncertain 0, nothing listed; n_samples holds the count it needs.
+ * For the same (model, E, max_samples) the sweep takes the rows, slices, wave-group shares and split decision of
+ * dcx_check_motions, so first_hit equals dcx_check_motions_ex(margin = hi)'s with no tolerance, and verdict == 0 exactly where
+ * dcx_motion_worst(margin = lo) reports worst <= 0 (NaN scores aside).
+ * Launches on the caller's stream only: the sample counts and their scan, one fused interpolate -> FK -> score-only sweep ->
+ * one code byte per sample, then a per-edge pass over the codes in sample order, a scan of the per-edge counts and the scatter
+ * of the list.  No allocation, no synchronisation, nothing read back: the call can be captured.  No atomics decide the order
+ * of anything; repeated calls return the same bits.
+ * work: dcx_motion_band_work_bytes(model, E, max_samples) bytes of device memory, the caller's; initialised by the call itself
+ *   (dcx_check_motions' workspace, then one byte per possible sample and 12 bytes per edge).
+ * Argument errors (DCX_ERR_INVALID, before any device work): those of dcx_check_motions_ex (NULL model / opt / qa / qb / work
+ *   (E > 0), E < 0, both or neither of res and max_step, max_samples < 1, a wrap_mask bit at or above dof), out NULL, verdict or
+ *   unc_total NULL (E > 0), unc_cap < 0, unc_edge or unc_sample NULL with unc_cap > 0, reserved not 0 (opt's or out's),
+ *   work_bytes below dcx_motion_band_work_bytes.  E above 2^31 - 1, E * max_samples too large for one launch and a feature
+ *   width without a kernel are DCX_ERR_UNSUPPORTED.  E = 0 launches nothing and writes nothing.                             */
+typedef struct dcx_motion_band_out {
+    int32_t* verdict;      /* [E] out: 0 free, 1 collides, 2 uncertain, -2 over max_samples (not checked)          */
+    int32_t* first_hit;    /* [E] out, may be NULL: smallest sample above hi, -1 none, -2 over max_samples          */
+    int32_t* n_samples;    /* [E] out, may be NULL: as dcx_check_motions'                                            */
+    int32_t* n_uncertain;  /* [E] out, may be NULL: band samples of an edge with verdict 2; 0 for every other edge   */
+    int64_t* unc_total;    /* [1] out: sum of n_uncertain; may exceed unc_cap                                        */
+    int32_t* unc_edge;     /* [unc_cap] out                                                                          */
+    int32_t* unc_sample;   /* [unc_cap] out                                                                          */
+    float*   unc_q;        /* [unc_cap, dof] out, may be NULL: the listed samples' configurations                    */
+    int64_t  unc_cap;      /* >= 0                                                                                   */
+    int64_t  reserved[2];  /* 0                                                                                      */
+} dcx_motion_band_out;
+size_t dcx_motion_band_work_bytes(const dcx_model* m, int64_t E, int32_t max_samples);
+int dcx_motion_band(const dcx_model* m, const float* qa, const float* qb, int64_t E, const dcx_motion_opts* opt,
+                    const float* lo, const float* hi, const dcx_motion_band_out* out, void* work, size_t work_bytes,
+                    uint64_t wrap_mask, void* stream);
+
 /* ---- dense-check Adam trajectory loop (added under DCX_VERSION 109) --------------------------------------- */
 /* dcx_traj_adam_run charges the collision hinge at the waypoints only; here it is charged along the segments: the dense-check
  * form of Weighted.step (optim.py:706-752 with dense_check=True).  R independent paths p = path[r] [W, dof]; one iteration:
