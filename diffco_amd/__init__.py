@@ -19,5 +19,7 @@ from .urdf import URDFRobotFK, MultiURDFRobotFK  # noqa: F401
 from . import collision_checkers  # noqa: F401
 from .collision_checkers import RBFDiffCo, ForwardKinematicsDiffCo, HybridForwardKinematicsDiffCo  # noqa: F401
 from .traj import fused_adam_traj_optimize  # noqa: F401
+from . import roadmap  # noqa: F401
+from .roadmap import Roadmap, knn, knn_edges  # noqa: F401
 
-__all__ = ["kernel", "model", "utils", "optim", "sharded", "traj", "escape", "fused_adam_traj_optimize", "urdf", "URDFRobotFK", "MultiURDFRobotFK", "collision_checkers", "RBFDiffCo", "ForwardKinematicsDiffCo", "HybridForwardKinematicsDiffCo", "deprecated", "DiffCo", "MultiDiffCo", "DiffCoBeta"]
+__all__ = ["kernel", "model", "utils", "optim", "sharded", "traj", "escape", "fused_adam_traj_optimize", "roadmap", "Roadmap", "knn", "knn_edges", "urdf", "URDFRobotFK", "MultiURDFRobotFK", "collision_checkers", "RBFDiffCo", "ForwardKinematicsDiffCo", "HybridForwardKinematicsDiffCo", "deprecated", "DiffCo", "MultiDiffCo", "DiffCoBeta"]

@@ -83,6 +83,10 @@ SYMBOLS = {
     "dcx_traj_dense_work_bytes": (C.c_size_t, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32]),
     "dcx_traj_dense_run": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, _c_fp, C.c_int32, C.c_int32,
                                      C.c_void_p, C.c_size_t, C.c_void_p]),
+    # k nearest neighbours under the motion calls' metric (no model)
+    "dcx_knn_work_bytes": (C.c_size_t, [C.c_int64, C.c_int64, C.c_int32, C.c_int32]),
+    "dcx_knn": (C.c_int, [C.c_int, _c_fp, C.c_int64, _c_fp, C.c_int64, C.c_int32, C.c_void_p, _c_fp, _c_fp, C.c_void_p, C.c_size_t,
+                          C.c_void_p]),
     "dcx_solve_work_bytes": (C.c_size_t, [C.c_int64, C.c_int64]),
     "dcx_solve": (C.c_int, [C.c_int, _c_fp, _c_fp, C.c_int64, C.c_int64, _c_fp, C.c_void_p, C.c_size_t, C.c_void_p, C.c_int32,
                             C.c_void_p]),
@@ -118,6 +122,15 @@ class MotionBandOut(C.Structure):
     """ctypes mirror of dcx_motion_band_out (include/dcx.h)"""
     _fields_ = [(n, C.c_void_p) for n in ("verdict", "first_hit", "n_samples", "n_uncertain", "unc_total", "unc_edge",
                                           "unc_sample", "unc_q")] + [("unc_cap", C.c_int64), ("reserved", C.c_int64 * 2)]
+
+
+KNN_MAX_K = 64   # DCX_KNN_MAX_K
+
+
+class KnnOpts(C.Structure):
+    """ctypes mirror of dcx_knn_opts (include/dcx.h)"""
+    _fields_ = [("k", C.c_int32), ("reserved0", C.c_int32), ("wrap_mask", C.c_uint64), ("max_dist2", C.c_float),
+                ("reserved1", C.c_int32), ("self_offset", C.c_int64), ("reserved", C.c_int64 * 2)]
 
 
 class MotionCostOpts(C.Structure):

@@ -276,6 +276,42 @@ def motion_bound(qa32, qb32, max_step, limit=MOTION_MAX_SAMPLES, wrap=None):
     return int(min(limit, math.ceil(L * (1.0 / float(max_step))) + 2))
 
 
+def knn(queries, points, k, wrap=None, max_dist=None, exclude_self=False, self_offset=None, transform=None):
+    """the k nearest of points [N, dof] for each of queries [Q, dof] under the motion calls' metric (dcx_knn): (idx int32 [Q, k],
+    dist2 float32 [Q, k]) on the points' device, ordered by (dist2, index) ascending; unfilled slots hold -1 / +inf.  dist2 is,
+    bit for bit, the squared edge length check_motions(queries[i], points[idx], wrap=wrap) walks.
+    `wrap` as wrap_mask (True: the mask of the robot whose fkine is `transform`).  `max_dist`: a radius (squared in float32).
+    `exclude_self`: queries are the points themselves (the same tensor or equal shapes), none its own neighbour;
+    `self_offset`: queries are points[self_offset : self_offset + Q]."""
+    lib = _lib.require_gpu()
+    points = torch.as_tensor(points)
+    queries = torch.as_tensor(queries)
+    dev = _device(points.device if points.device.type == "cuda" else queries.device)
+    if points.dim() != 2 or queries.dim() != 2 or queries.shape[1] != points.shape[1]:
+        raise ValueError(f"knn: queries {tuple(queries.shape)} and points {tuple(points.shape)} must be [Q, dof] and [N, dof]")
+    if exclude_self:
+        if self_offset not in (None, 0):
+            raise ValueError("knn: exclude_self means self_offset = 0")
+        if queries is not points and queries.shape != points.shape:
+            raise ValueError("knn: exclude_self needs the queries to be the points")
+        self_offset = 0
+    dof = points.shape[1]
+    p32 = _f32(points, dev)
+    q32 = p32 if queries is points else _f32(queries, dev)
+    Q, N = len(q32), len(p32)
+    d2 = float("inf") if max_dist is None else float(torch.tensor(float(max_dist), dtype=torch.float32).square())
+    opt = _lib.KnnOpts(int(k), 0, wrap_mask(wrap, dof, transform), d2, 0, -1 if self_offset is None else int(self_offset), (C.c_int64 * 2)(0, 0))
+    idx = torch.empty((Q, int(k)), device=dev, dtype=torch.int32)
+    dist2 = torch.empty((Q, int(k)), device=dev, dtype=torch.float32)
+    nbytes = int(lib.dcx_knn_work_bytes(Q, N, dof, int(k)))
+    # as the motion calls: torch's caching allocator is the per-device cache (a freed block is reused on its stream, no hipMalloc)
+    work = torch.empty(max(nbytes, 1), device=dev, dtype=torch.uint8)
+    with _on_device(dev):
+        _lib.check(lib.dcx_knn(dev.index, _ptr(q32), Q, _ptr(p32), N, dof, C.byref(opt), _ptr(idx), _ptr(dist2), _ptr(work),
+                               work.numel(), _stream(dev)))
+    return idx, dist2
+
+
 def compose_path_cost(edge_cost, paths, dof):
     """[T] costs of paths [T, W, dof] from an edge-cost callable edge_cost(qa, qb, open_end) under the max_step rule: the
     open-ended edges p[i] -> p[i + 1] plus the zero-length edge p[-1] -> p[-1] (its one sample is p[-1]) cover the points of

@@ -19,6 +19,7 @@
 #include "pack_kernels.h"
 #include "solve_kernels.h"
 #include "traj_dense.h"
+#include "knn_kernel.h"
 
 using namespace dcx;
 
@@ -279,7 +280,7 @@ struct Knobs {
     std::atomic<int64_t> ys{-1}, nw{-1}, min_rows{-1}, split_finish_kernel{-1}, inlaunch_tiles{-1}, jac_per_class{-1},
         traj_fused{-1}, xf{-1}, jac_one_sweep{-1}, train_grid{-1}, fkk{-1}, jt_waves{-1}, hess_ys{-1}, hess_form{-1},
         traj_ys{-1}, traj_across{-1}, owner_poll{-1}, solve_threads{-1}, qt{-1}, giveup_inject{-1}, skew{-1}, skew8{-1},
-        motion_early_exit{-1}, spare{-1};
+        motion_early_exit{-1}, spare{-1}, knn_split{-1};
     Knobs() {
         auto rd = [](const char* name, std::atomic<int64_t>& dst, bool flag) {
             if (const char* e = std::getenv(name)) dst = flag ? 1 : std::atoll(e);
@@ -811,7 +812,7 @@ int dcx_debug_set(const char* name, int64_t value) {
                          : DCX_OK;
     std::atomic<int64_t>* dst = n == "ys" ? &k.ys : n == "nw" ? &k.nw : n == "min_rows" ? &k.min_rows
         : n == "split_finish_kernel" ? &k.split_finish_kernel : n == "inlaunch_tiles" ? &k.inlaunch_tiles
-        : n == "jac_per_class" ? &k.jac_per_class : n == "traj_fused" ? &k.traj_fused : n == "xf" ? &k.xf : n == "spare" ? &k.spare : n == "jac_one_sweep" ? &k.jac_one_sweep : n == "train_grid" ? &k.train_grid : n == "fkk" ? &k.fkk : n == "jt_waves" ? &k.jt_waves : n == "hess_ys" ? &k.hess_ys : n == "hess_form" ? &k.hess_form : n == "traj_ys" ? &k.traj_ys : n == "traj_across" ? &k.traj_across : n == "owner_poll" ? &k.owner_poll : n == "solve_threads" ? &k.solve_threads : n == "qt" ? &k.qt : n == "giveup_inject" ? &k.giveup_inject : n == "skew" ? &k.skew : n == "skew8" ? &k.skew8 : n == "motion_early_exit" ? &k.motion_early_exit : nullptr;
+        : n == "jac_per_class" ? &k.jac_per_class : n == "traj_fused" ? &k.traj_fused : n == "xf" ? &k.xf : n == "spare" ? &k.spare : n == "jac_one_sweep" ? &k.jac_one_sweep : n == "train_grid" ? &k.train_grid : n == "fkk" ? &k.fkk : n == "jt_waves" ? &k.jt_waves : n == "hess_ys" ? &k.hess_ys : n == "hess_form" ? &k.hess_form : n == "traj_ys" ? &k.traj_ys : n == "traj_across" ? &k.traj_across : n == "owner_poll" ? &k.owner_poll : n == "solve_threads" ? &k.solve_threads : n == "qt" ? &k.qt : n == "giveup_inject" ? &k.giveup_inject : n == "skew" ? &k.skew : n == "skew8" ? &k.skew8 : n == "motion_early_exit" ? &k.motion_early_exit : n == "knn_split" ? &k.knn_split : nullptr;
     if (!dst) return fail(DCX_ERR_INVALID, "unknown knob: " + n);
     *dst = value;
     return DCX_OK;
@@ -2550,6 +2551,53 @@ int dcx_kernel_matrix(int device, int kernel_kind, const float* kparams, const f
                                             (hipStream_t)stream);
         if (e != hipSuccess) return fail_hip(e, "kernel_matrix launch");
     }
+    return DCX_OK;
+}
+
+// ---- k-nearest neighbours (knn_kernel.h): the same checks for the size query and the call, one plan for both ----------------
+static int knn_check_sizes(int64_t Q, int64_t N, int32_t dof, int32_t k) {
+    if (Q < 0 || N < 0) return fail(DCX_ERR_INVALID, "knn: Q < 0 or N < 0");
+    if (dof < 1 || dof > kKnnMaxDof) return fail(DCX_ERR_INVALID, "knn: dof must be in [1, 64]");
+    if (k < 1 || k > DCX_KNN_MAX_K) return fail(DCX_ERR_INVALID, "knn: k must be in [1, DCX_KNN_MAX_K]");
+    return DCX_OK;
+}
+
+size_t dcx_knn_work_bytes(int64_t Q, int64_t N, int32_t dof, int32_t k) {
+    if (knn_check_sizes(Q, N, dof, k)) return 0;
+    return knn_plan(Q, N, dof, k, knobs().knn_split).work_bytes;
+}
+
+int dcx_knn(int device, const float* queries, int64_t Q, const float* points, int64_t N, int32_t dof, const dcx_knn_opts* opt,
+            int32_t* idx, float* dist2, void* work, size_t work_bytes, void* stream) {
+    if (!opt) return fail(DCX_ERR_INVALID, "knn: options are NULL");
+    if (int rc = knn_check_sizes(Q, N, dof, opt->k)) return rc;
+    if (dof < 64 && (opt->wrap_mask >> dof)) return fail(DCX_ERR_INVALID, "knn: wrap_mask has a bit at or above dof");
+    if (!(opt->max_dist2 >= 0.0f)) return fail(DCX_ERR_INVALID, "knn: max_dist2 is NaN or negative");
+    if (opt->self_offset < -1) return fail(DCX_ERR_INVALID, "knn: self_offset < -1");
+    if (opt->reserved0 || opt->reserved1 || opt->reserved[0] || opt->reserved[1]) return fail(DCX_ERR_INVALID, "knn: reserved fields must be 0");
+    if (Q == 0) return DCX_OK;
+    if (!queries || !idx || !dist2 || !work) return fail(DCX_ERR_INVALID, "knn: queries / idx / dist2 / work is NULL");
+    if (N > 0 && !points) return fail(DCX_ERR_INVALID, "knn: points is NULL");
+    const KnnPlan plan = knn_plan(Q, N, dof, opt->k, knobs().knn_split);
+    if (!plan.ok) return fail(DCX_ERR_UNSUPPORTED, "knn: N above 2^31 - 1, or more query tiles x point splits than one launch takes");
+    if (work_bytes < plan.work_bytes) return fail(DCX_ERR_INVALID, "knn: the workspace is smaller than dcx_knn_work_bytes(Q, N, dof, k)");
+    if (int rc = set_device(device)) return rc;
+    KnnArgs a{};
+    a.queries = queries;
+    a.points = points;
+    a.Q = Q;
+    a.N = (int32_t)N;
+    a.dof = dof;
+    a.k = opt->k;
+    a.splits = plan.splits;
+    a.wrap_mask = opt->wrap_mask;
+    a.max_dist2 = opt->max_dist2;
+    a.self_offset = opt->self_offset;
+    a.idx = idx;
+    a.dist2 = dist2;
+    a.part = static_cast<unsigned long long*>(work);
+    const hipError_t e = launch_knn(a, plan, (hipStream_t)stream);
+    if (e != hipSuccess) return fail_hip(e, "knn launch");
     return DCX_OK;
 }
 

@@ -171,6 +171,8 @@ int dcx_device_count(void);
  * "skew" (how a 16-wave block's rows are dealt to its four wave groups: 0 = equal slices, w0 | w1 << 10 | w2 << 20 = the per-mille
  * shares of groups 0 - 2, rule = 480 / 320 / 150 / 50: a SIMD issues oldest-first and a block's last waves would finish alone; the tile of 16 configurations
  * deals its row slices the same way), "skew8" (the same for 8-wave blocks: the per-mille share of waves 0 - 3, rule = 600, 0 = equal).
+ * "knn_split" (dcx_knn's point splits: n > 0 = n blocks per query tile, at most 1024, 0 / rule = what the plan picks;
+ * dcx_knn_work_bytes follows the knob; bit-identical results).
  * value < 0 restores the rule.  The initial values come from the DCX_YS / DCX_NW / DCX_XF / ... environment variables,
  * read once at library load; no launch calls getenv.   */
 int dcx_debug_set(const char* name, int64_t value);
@@ -539,6 +541,41 @@ size_t dcx_motion_band_work_bytes(const dcx_model* m, int64_t E, int32_t max_sam
 int dcx_motion_band(const dcx_model* m, const float* qa, const float* qb, int64_t E, const dcx_motion_opts* opt,
                     const float* lo, const float* hi, const dcx_motion_band_out* out, void* work, size_t work_bytes,
                     uint64_t wrap_mask, void* stream);
+
+/* ---- k-nearest neighbours (added under DCX_VERSION 109) -------------------------------------------------- */
+/* The k nearest of N points for each of Q queries under the motion calls' metric: the producer of their (qa, qb).  No model.
+ * Distance: the squared length of the edge query -> point exactly as dcx_check_motions_ex(qa = query, qb = point, wrap_mask)
+ *   accumulates it: d_j = point_j - query_j (rounded), along the shortest arc (wrap2pi of it) where bit j of wrap_mask is set;
+ *   l2 = l2 + d_j * d_j for j = 0 .. dof - 1 from +0.0f, every operation fp32 and rounded on its own (no fused multiply-add).
+ *   dist2 holds the very bits whose square root is the motion call's edge length L.  Under a wrap mask the value depends on the
+ *   direction: wrap2pi(x) and -wrap2pi(-x) may differ in their last bits, so dist2(query -> point) need not equal
+ *   dist2(point -> query) bit for bit.
+ * Order: neighbours are totally ordered by (dist2, point index) ascending, the lower index winning a tie.  dist2 is never negative
+ *   or -0, so its bit pattern orders like its value: the key is bits(dist2) << 32 | index.
+ * Row i of idx / dist2 holds the first k of that order over the admissible points.  Not admissible: a point whose dist2 is NaN,
+ *   one whose dist2 is above max_dist2, and point self_offset + i (self_offset >= 0).  Unfilled slots: idx -1, dist2 +inf.
+ * The result is a function of the inputs alone: it does not depend on how the launch is split, and nothing is atomic.
+ * Launches on the caller's stream only (a search over (query tiles) x (point splits), then a merge of the splits' lists where
+ * there are several).  No allocation, no synchronisation, nothing read back: the call can be captured.
+ * work: dcx_knn_work_bytes(Q, N, dof, k) bytes of device memory, the caller's; initialised by the call itself.
+ * Q == 0 returns 0 and touches nothing; N == 0 fills -1 / +inf.
+ * Argument errors (DCX_ERR_INVALID, before any device work): opt NULL; queries / idx / dist2 / work NULL (Q > 0), points NULL
+ *   (Q > 0 and N > 0); Q < 0 or N < 0; dof outside 1 .. 64; k outside 1 .. DCX_KNN_MAX_K; a wrap_mask bit at or above dof; a NaN
+ *   or negative max_dist2; self_offset < -1; a reserved field not 0; work_bytes below dcx_knn_work_bytes.  N above 2^31 - 1 and
+ *   a grid beyond one launch are DCX_ERR_UNSUPPORTED.  dcx_knn_work_bytes is 0 for arguments dcx_knn refuses.               */
+#define DCX_KNN_MAX_K 64
+typedef struct dcx_knn_opts {
+    int32_t  k;            /* 1 .. DCX_KNN_MAX_K                                                        */
+    int32_t  reserved0;    /* 0                                                                          */
+    uint64_t wrap_mask;    /* bit j: coordinate j is an angle, measured along the shortest arc           */
+    float    max_dist2;    /* keep only neighbours with dist2 <= max_dist2; +inf: no radius              */
+    int32_t  reserved1;    /* 0                                                                          */
+    int64_t  self_offset;  /* >= 0: query i IS point self_offset + i and is not its own neighbour; -1: none */
+    int64_t  reserved[2];  /* 0                                                                          */
+} dcx_knn_opts;
+size_t dcx_knn_work_bytes(int64_t Q, int64_t N, int32_t dof, int32_t k);
+int dcx_knn(int device, const float* queries, int64_t Q, const float* points, int64_t N, int32_t dof, const dcx_knn_opts* opt,
+            int32_t* idx, float* dist2, void* work, size_t work_bytes, void* stream);
 
 /* ---- dense-check Adam trajectory loop (added under DCX_VERSION 109) --------------------------------------- */
 /* dcx_traj_adam_run charges the collision hinge at the waypoints only; here it is charged along the segments: the dense-check
