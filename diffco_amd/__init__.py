@@ -21,5 +21,7 @@ from .collision_checkers import RBFDiffCo, ForwardKinematicsDiffCo, HybridForwar
 from .traj import fused_adam_traj_optimize  # noqa: F401
 from . import roadmap  # noqa: F401
 from .roadmap import Roadmap, knn, knn_edges  # noqa: F401
+from . import rrt  # noqa: F401
+from .rrt import rrt_connect, host_rrt_connect, RRTResult  # noqa: F401
 
-__all__ = ["kernel", "model", "utils", "optim", "sharded", "traj", "escape", "fused_adam_traj_optimize", "roadmap", "Roadmap", "knn", "knn_edges", "urdf", "URDFRobotFK", "MultiURDFRobotFK", "collision_checkers", "RBFDiffCo", "ForwardKinematicsDiffCo", "HybridForwardKinematicsDiffCo", "deprecated", "DiffCo", "MultiDiffCo", "DiffCoBeta"]
+__all__ = ["rrt", "rrt_connect", "host_rrt_connect", "RRTResult","kernel", "model", "utils", "optim", "sharded", "traj", "escape", "fused_adam_traj_optimize", "roadmap", "Roadmap", "knn", "knn_edges", "urdf", "URDFRobotFK", "MultiURDFRobotFK", "collision_checkers", "RBFDiffCo", "ForwardKinematicsDiffCo", "HybridForwardKinematicsDiffCo", "deprecated", "DiffCo", "MultiDiffCo", "DiffCoBeta"]

@@ -87,6 +87,10 @@ SYMBOLS = {
     "dcx_knn_work_bytes": (C.c_size_t, [C.c_int64, C.c_int64, C.c_int32, C.c_int32]),
     "dcx_knn": (C.c_int, [C.c_int, _c_fp, C.c_int64, _c_fp, C.c_int64, C.c_int32, C.c_void_p, _c_fp, _c_fp, C.c_void_p, C.c_size_t,
                           C.c_void_p]),
+    # batched RRT-Connect: R trees grown in lockstep over the kNN metric and the motion checks
+    "dcx_rrt_work_bytes": (C.c_size_t, [C.c_void_p, C.c_int64, C.c_int32]),
+    "dcx_rrt_connect_run": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, _c_fp, C.c_int32, C.c_int64, C.c_void_p, _c_fp, C.c_void_p,
+                                      C.c_size_t, C.c_void_p]),
     "dcx_solve_work_bytes": (C.c_size_t, [C.c_int64, C.c_int64]),
     "dcx_solve": (C.c_int, [C.c_int, _c_fp, _c_fp, C.c_int64, C.c_int64, _c_fp, C.c_void_p, C.c_size_t, C.c_void_p, C.c_int32,
                             C.c_void_p]),
@@ -131,6 +135,21 @@ class KnnOpts(C.Structure):
     """ctypes mirror of dcx_knn_opts (include/dcx.h)"""
     _fields_ = [("k", C.c_int32), ("reserved0", C.c_int32), ("wrap_mask", C.c_uint64), ("max_dist2", C.c_float),
                 ("reserved1", C.c_int32), ("self_offset", C.c_int64), ("reserved", C.c_int64 * 2)]
+
+
+RRT_MAX_SLOTS = 16        # DCX_RRT_MAX_SLOTS
+RRT_MAX_CAP = 1 << 20     # DCX_RRT_MAX_CAP
+
+
+class RrtState(C.Structure):
+    """ctypes mirror of dcx_rrt_state (include/dcx.h)"""
+    _fields_ = [(n, C.c_void_p) for n in ("nodes", "parent", "count", "status", "link", "solved_round")]
+
+
+class RrtOpts(C.Structure):
+    """ctypes mirror of dcx_rrt_opts (include/dcx.h)"""
+    _fields_ = [("range", C.c_float), ("max_step", C.c_float), ("max_samples", C.c_int32), ("slots", C.c_int32), ("cap", C.c_int32),
+                ("reserved0", C.c_int32), ("wrap_mask", C.c_uint64), ("reserved", C.c_int64 * 2)]
 
 
 class MotionCostOpts(C.Structure):

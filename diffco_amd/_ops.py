@@ -537,6 +537,31 @@ class ScoreModel:
                                                       _ptr(n), _ptr(work), int(nbytes), mask, self._st()))
         return first, n
 
+    def rrt_connect_run(self, state, samples, round0, range, max_step, max_samples, cap, margin=0., wrap=None):
+        """T rounds of batched RRT-Connect (dcx_rrt_connect_run) on the caller's state, in place: `state` maps nodes
+        [R, 2, cap, dof] float32, parent [R, 2, cap], count [R, 2], status [R], link [R, 2], solved_round [R] (int32) to
+        contiguous tensors on the model's device; samples [T, R, P, dof] float32 there.  Rounds round0 .. round0 + T - 1 are
+        enqueued on torch's current stream; nothing is read back (capturable).  `margin` as check_motions."""
+        T, R, P = (int(v) for v in samples.shape[:3])
+        kinds = dict(nodes=torch.float32, parent=torch.int32, count=torch.int32, status=torch.int32, link=torch.int32,
+                     solved_round=torch.int32)
+        shapes = dict(nodes=(R, 2, cap, self.dof), parent=(R, 2, cap), count=(R, 2), status=(R,), link=(R, 2), solved_round=(R,))
+        for name, dt in kinds.items():
+            t = state[name]
+            if t.dtype != dt or t.device != self.dev or not t.is_contiguous() or tuple(t.shape) != shapes[name]:
+                raise ValueError(f"rrt_connect_run: state[{name!r}] must be a contiguous {dt} tensor {shapes[name]} on {self.dev}")
+        if samples.dtype != torch.float32 or samples.device != self.dev or not samples.is_contiguous() or samples.shape[3] != self.dof:
+            raise ValueError(f"rrt_connect_run: samples must be a contiguous float32 tensor [T, R, P, {self.dof}] on {self.dev}")
+        st = _lib.RrtState(*(state[n].data_ptr() for n in kinds))
+        opt = _lib.RrtOpts(float(range), float(max_step), int(max_samples), P, int(cap), 0, wrap_mask(wrap, self.dof),
+                           (C.c_int64 * 2)(0, 0))
+        mg = self._motion_margin(margin)
+        nbytes = int(self._lib.dcx_rrt_work_bytes(self._h, R, P))
+        work = torch.empty(max(nbytes, 1), device=self.dev, dtype=torch.uint8)
+        with _on_device(self.dev):
+            _lib.check(self._lib.dcx_rrt_connect_run(self._h, C.byref(st), R, _ptr(samples), T, int(round0), C.byref(opt), _ptr(mg),
+                                                     _ptr(work), nbytes, self._st()))
+
     def _motion_margin(self, margin):
         """the motion calls' margin argument: None (all zero), or [C] device floats (a device tensor stays on the device)"""
         if torch.is_tensor(margin) and margin.device == self.dev:

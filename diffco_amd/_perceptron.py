@@ -333,6 +333,16 @@ def check_motions(owner, fused, transform, kernel_func, support_feat, weights, q
     return m.check_motions(qa, qb, res=res, max_step=max_step, margin=margin, max_samples=max_samples, wrap=mask)
 
 
+def _motion_model(fused, transform, kernel_func, support_feat, weights, device=None, margin=0.):
+    """(ScoreModel, margin) where check_motions above takes the fused route on these arguments, else None (a foreign transform:
+    the host composition).  What a planner needs to enqueue the fused motion checks itself (rrt.rrt_connect)."""
+    dev = device if device is not None and device.type == "cuda" else (support_feat.device if support_feat.device.type == "cuda" else None)
+    m = fused.model(transform, kernel_func, support_feat, weights, dev)
+    if m.desc.kind == 0 and transform is not None:
+        return None
+    return m, margin
+
+
 def motion_answer(first, return_first):
     """the facades' answer: collides [E] bool (+ first_hit); raises for edges over max_samples (a read-back)"""
     if bool((first == -2).any()):

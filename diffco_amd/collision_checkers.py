@@ -217,6 +217,15 @@ class RBFDiffCo(CollisionChecker):
                                  q_start, q_end, res=res, max_step=max_step, margin=margin, max_samples=max_samples, wrap=wrap)
         return motion_answer(first, return_first)
 
+    def _rrt_model(self, device=None):
+        """(ScoreModel, margin) of check_motions' fused route - the safety bias becomes the margin - or None where it takes the
+        host route (rrt.rrt_connect)"""
+        from ._perceptron import _motion_model
+        bias = self.safety_bias
+        margin = -bias if not torch.is_tensor(bias) else -bias.detach().reshape(-1)
+        p = self.perceptron
+        return _motion_model(p._poly_fused, p.transform, p.rbf_kernel, p.support_transformed, p.rbf_nodes, device, margin)
+
     def motion_cost(self, q_start, q_end, max_step=None, res=None, bias=None, weight=1., open_end=False, max_samples=None,
                     wrap=None):
         """[E] collision costs of the motions q_start[e] -> q_end[e] by `collision_score`: weight * sum over the samples of
@@ -458,6 +467,10 @@ class HybridForwardKinematicsDiffCo(ForwardKinematicsDiffCo):
             confirmed = torch.full_like(first, big).scatter_reduce(0, edges, samples, reduce="amin")
             first = torch.where(confirmed < big, confirmed, first)
         return (hit, first) if return_first else hit
+
+    def _rrt_model(self, device=None):
+        """None: an edge's verdict may need the ground truth, so a planner goes through check_motions (rrt.host_rrt_connect)"""
+        return None
 
     def _motion_points(self, q_start, q_end, edges, samples, res, max_step, wrap):
         """sample samples[i] of the edge edges[i]: the points the host composition materialises (_perceptron._motion_samples)"""

@@ -20,6 +20,7 @@
 #include "solve_kernels.h"
 #include "traj_dense.h"
 #include "knn_kernel.h"
+#include "rrt_kernel.h"
 
 using namespace dcx;
 
@@ -2598,6 +2599,91 @@ int dcx_knn(int device, const float* queries, int64_t Q, const float* points, in
     a.part = static_cast<unsigned long long*>(work);
     const hipError_t e = launch_knn(a, plan, (hipStream_t)stream);
     if (e != hipSuccess) return fail_hip(e, "knn launch");
+    return DCX_OK;
+}
+
+// ---- batched RRT-Connect (rrt_kernel.h): the size query and the call share the checks and rrt_plan --------------------------
+static int rrt_check_sizes(const dcx_model* m, int64_t R, int32_t slots) {
+    if (!m) return fail(DCX_ERR_INVALID, "rrt: model is NULL");
+    if (R < 0) return fail(DCX_ERR_INVALID, "rrt: R < 0");
+    if (slots < 1 || slots > DCX_RRT_MAX_SLOTS) return fail(DCX_ERR_INVALID, "rrt: slots must be in [1, DCX_RRT_MAX_SLOTS]");
+    if (R > INT32_MAX / slots) return fail(DCX_ERR_UNSUPPORTED, "rrt: more than 2^31 - 1 edges per phase");
+    return DCX_OK;
+}
+
+size_t dcx_rrt_work_bytes(const dcx_model* m, int64_t R, int32_t slots) {
+    if (rrt_check_sizes(m, R, slots)) return 0;
+    return rrt_plan(R, slots, m->fk.dof, motion_work(R * slots).total).total;
+}
+
+int dcx_rrt_connect_run(const dcx_model* m, const dcx_rrt_state* state, int64_t R, const float* samples, int32_t T, int64_t round0,
+                        const dcx_rrt_opts* opt, const float* margin, void* work, size_t work_bytes, void* stream) {
+    // every argument is checked before anything touches the model's device
+    if (!opt) return fail(DCX_ERR_INVALID, "rrt: options are NULL");
+    if (T < 0) return fail(DCX_ERR_INVALID, "rrt: T < 0");
+    if (int rc = rrt_check_sizes(m, R, opt->slots)) return rc;
+    if (round0 < 0 || round0 > INT32_MAX - (int64_t)T) return fail(DCX_ERR_INVALID, "rrt: round0 < 0 or round0 + T above 2^31 - 1");
+    if (!(opt->range > 0.f)) return fail(DCX_ERR_INVALID, "rrt: range must be > 0");
+    if (!(opt->max_step > 0.f)) return fail(DCX_ERR_INVALID, "rrt: max_step must be > 0");
+    if (opt->max_samples < 1) return fail(DCX_ERR_INVALID, "rrt: max_samples must be >= 1");
+    if (opt->cap < 1 || opt->cap > DCX_RRT_MAX_CAP) return fail(DCX_ERR_INVALID, "rrt: cap must be in [1, DCX_RRT_MAX_CAP]");
+    if (opt->reserved0 || opt->reserved[0] || opt->reserved[1]) return fail(DCX_ERR_INVALID, "rrt: reserved fields must be 0");
+    if (opt->wrap_mask != 0 && m->fk.dof < 64 && (opt->wrap_mask >> m->fk.dof) != 0)
+        return fail(DCX_ERR_INVALID, "rrt: wrap_mask has a bit at or above dof");
+    if (R > 0 && (!state || !state->nodes || !state->parent || !state->count || !state->status || !state->link || !state->solved_round))
+        return fail(DCX_ERR_INVALID, "rrt: state or one of its pointers is NULL");
+    if (R > 0 && T > 0 && !samples) return fail(DCX_ERR_INVALID, "rrt: samples is NULL");
+    if (R > 0 && !work) return fail(DCX_ERR_INVALID, "rrt: work is NULL");
+    const int64_t E = R * opt->slots;
+    const MotionWork mw = motion_work(E);
+    const RrtPlan plan = rrt_plan(R, opt->slots, m->fk.dof, mw.total);
+    if (R > 0 && work_bytes < plan.total) return fail(DCX_ERR_INVALID, "rrt: the workspace is smaller than dcx_rrt_work_bytes");
+    if (R == 0 || T == 0) return DCX_OK;
+    // what dcx_check_motions_ex could still refuse depends on (model, E, max_samples) alone: refused here, before the first launch
+    if (m->fk.dof < 1 || m->fk.dof > DCX_MAX_DOF) return fail(DCX_ERR_UNSUPPORTED, "rrt: dof outside 1 .. DCX_MAX_DOF");
+    if ((E * (int64_t)opt->max_samples + 63) / 64 > 0x7fffffffLL)
+        return fail(DCX_ERR_UNSUPPORTED, "rrt: R * slots * max_samples too large for one launch");
+    if (!motion_for(m->Dt)) return fail(DCX_ERR_UNSUPPORTED, "rrt: no motion kernel for this feature width");
+    if (int rc = set_device(m->device)) return rc;
+    hipStream_t st = (hipStream_t)stream;
+    char* base = (char*)work;
+    RrtArgs a{};
+    a.nodes = state->nodes;
+    a.parent = state->parent;
+    a.count = state->count;
+    a.status = state->status;
+    a.link = state->link;
+    a.solved_round = state->solved_round;
+    a.qa = (float*)(base + plan.qa);
+    a.qb = (float*)(base + plan.qb);
+    a.near = (int32_t*)(base + plan.near);
+    a.added = (int32_t*)(base + plan.added);
+    a.first_hit = (int32_t*)(base + plan.first_hit);
+    a.full = (int32_t*)(base + plan.full);
+    a.frac = (const float*)(base + mw.frac);
+    a.R = (int32_t)R;
+    a.P = opt->slots;
+    a.cap = opt->cap;
+    a.dof = m->fk.dof;
+    a.range = opt->range;
+    a.wrap_mask = opt->wrap_mask;
+    dcx_motion_opts mo{};
+    mo.max_step = opt->max_step;
+    mo.max_samples = opt->max_samples;
+    for (int32_t t = 0; t < T; ++t) {
+        a.round = (int32_t)(round0 + t);
+        a.tree = a.round & 1;
+        a.samples = samples + (int64_t)t * E * a.dof;
+        for (a.phase = 1; a.phase <= 2; ++a.phase) {
+            hipError_t e = launch_rrt_nearest(a, st);
+            if (e != hipSuccess) return fail_hip(e, "rrt nearest launch");
+            if (int rc = dcx_check_motions_ex(m, a.qa, a.qb, E, &mo, margin, (int32_t*)(base + plan.first_hit), nullptr, work, mw.total,
+                                              opt->wrap_mask, stream))
+                return rc;
+            e = launch_rrt_commit(a, st);
+            if (e != hipSuccess) return fail_hip(e, "rrt commit launch");
+        }
+    }
     return DCX_OK;
 }
 

@@ -310,6 +310,11 @@ class DiffCo(Perceptron):
                                  starts, targets, res=res, max_step=max_step, max_samples=max_samples, wrap=wrap)
         return motion_answer(first, return_first)
 
+    def _rrt_model(self, device=None):
+        """(ScoreModel, margin) of check_motions' fused route, or None where it takes the host route (rrt.rrt_connect)"""
+        from ._perceptron import _motion_model
+        return _motion_model(self._score_fused, self.transform, self.kernel_func, self.support_transformed, self.gains, device)
+
     def motion_cost(self, starts, targets, res=None, max_step=None, margin=0., weight=1., open_end=False, max_samples=None,
                     wrap=None):
         """[E] collision costs of the motions starts[e] -> targets[e]: weight * sum over the samples of max(0, score - margin),

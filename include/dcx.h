@@ -649,6 +649,83 @@ int dcx_traj_dense_run(const dcx_model* m, const dcx_traj_state* st, const dcx_t
                        const dcx_traj_dense_io* io, const float* margin, int32_t first_step, int32_t n_iters, void* work,
                        size_t work_bytes, void* stream);
 
+/* ---- batched RRT-Connect (added under DCX_VERSION 109) ---------------------------------------------------- */
+/* R independent planning problems grown in lockstep, P = opts->slots extensions per problem and round: the tree planner over
+ * dcx_knn's metric and dcx_check_motions_ex's verdicts (the reference's scripts/motion_planner.py hands OMPL's RRTConnect a
+ * DiffCo validity checker; misc/rrt_star.py grows a tree over line_collision).  All tree logic runs on the device, the edge
+ * checks are dcx_check_motions_ex's own launches, and nothing is read back between rounds.
+ * State (dcx_rrt_state; caller-owned device memory, R problems, cap = opts->cap):
+ *   nodes [R, 2, cap, dof] float    tree 0 is rooted at the start (node 0, parent -1), tree 1 at the goal
+ *   parent [R, 2, cap] int32        count [R, 2] int32: the trees' sizes (>= 1)
+ *   status [R] int32                0 running, 1 solved, 2 a tree is full, 3 an endpoint collides (set by the caller when it
+ *                                   initialises the state, never by the kernels)
+ *   link [R, 2] int32               of a solved problem: (index in tree 0, index in tree 1) of the two nodes the free joining
+ *                                   motion connects
+ *   solved_round [R] int32          of a solved problem: the round g that solved it
+ * Round g = round0 + t, t = 0 .. T - 1: tree a = g & 1 extends, tree b = 1 - a connects.  Both phases see each tree as it stood
+ * at the start of the round.  A problem's status is read at the start of the round and written only at its end; a problem that
+ * is not running (status != 0) is left as it is.  Solved wins over full.
+ * Phase 1, extend - slot p < P of a running problem r:
+ *   1. target s = samples[t, r, p, :]
+ *   2. near = the nearest node of tree a under dcx_knn's contract (query = s, points = the tree's nodes, k = 1): the same dist2
+ *      bits (d = node - s, wrapped on masked coordinates, summed from +0 in coordinate order, every operation rounded alone),
+ *      the same key order bits(dist2) << 32 | index; a NaN distance is not admitted.  No admissible node: the slot is idle
+ *   3. steer, every operation fp32 and rounded alone: d_j = the motion calls' delta of the edge near -> s (wrap2pi of the
+ *      rounded difference on masked j), l2 = l2 + d_j * d_j from +0 in coordinate order, L = sqrtf(l2) (correctly rounded) as
+ *      dcx_check_motions_ex forms an edge's length.  !(L > 0): the slot is idle.  L <= range: qb = s as given.  Otherwise
+ *      f = range / L (one correctly rounded division) and qb_j = near_j + d_j * f, then wrap2pi on masked j
+ *   4. the edge near -> qb is checked by dcx_check_motions_ex (the closed max_step rule, opts->max_samples, margin, wrap_mask):
+ *      first_hit == -1 accepts the slot, anything else (-2 included) rejects it
+ *   5. commit: the accepted slots append qb to tree a in ascending slot order with parent = near while count < cap; a slot that
+ *      does not fit is dropped and marks the problem full
+ * Phase 2, connect - each slot whose node x was appended in phase 1:
+ *   1. nb = the nearest node of tree b under the same contract, query = x
+ *   2. the edge nb -> x is checked (the closed max_step rule; not capped at range)
+ *   3. first_hit == -1: the slot joins.  The joining slot with the lowest p sets status = 1, link and solved_round = g
+ *   4. first_hit = h >= 2: sample h - 1 of that edge - the last free one - is appended to tree b with parent = nb: bit for bit
+ *      the point dcx_check_motions_ex scored (x_k of the max_step rule above with the call's own frac), in the same slot order
+ *      and under the same cap rule as phase 1.  Every slot of a round appends what it has, also beside a joining slot
+ *   5. h in {0, 1, -2}: nothing is appended
+ * Fixed batch: every phase of every round submits exactly R * P edges in (r, p) order.  Idle, dropped and non-running slots
+ *   submit the edge nodes[r, 0, 0] -> nodes[r, 0, 0] (one sample, its verdict ignored), so the geometry of the motion sweep never
+ *   depends on the state: the call can be captured, and a referee that submits the same batch to dcx_check_motions_ex gets the
+ *   same verdicts.
+ * dcx_rrt_connect_run enqueues T rounds on the caller's stream: per round and phase one nearest (+ steer) launch, the launches
+ *   of dcx_check_motions_ex, one commit launch.  No allocation, no synchronisation, no atomic decides any order, nothing read
+ *   back; repeated calls give the same bits, and T rounds in one call equal T calls of one round each.
+ *   samples [T, R, P, dof] device floats;  margin [C] device floats, NULL = 0.
+ * work: dcx_rrt_work_bytes(model, R, slots) bytes of device memory, the caller's (dcx_check_motions' workspace for R * P edges,
+ *   then the per-slot scratch: the edge batch, its verdicts and append indices); initialised by the call itself.
+ * Argument errors (DCX_ERR_INVALID, before any device work): NULL model / opts; NULL state, state pointer, samples (T > 0) or
+ *   work with R > 0; R < 0 or T < 0; round0 < 0 or round0 + T above 2^31 - 1; range or max_step <= 0 or NaN; max_samples < 1;
+ *   slots outside 1 .. DCX_RRT_MAX_SLOTS; cap outside 1 .. DCX_RRT_MAX_CAP; a wrap_mask bit at or above dof; a reserved field
+ *   not 0; work_bytes below dcx_rrt_work_bytes.  R * slots above 2^31 - 1, R * slots * max_samples too large for one launch,
+ *   dof above DCX_MAX_DOF and a feature width without a motion kernel are DCX_ERR_UNSUPPORTED.  R = 0 or T = 0 launches nothing.
+ *   dcx_rrt_work_bytes is 0 for arguments the call refuses.                                                                  */
+#define DCX_RRT_MAX_SLOTS 16
+#define DCX_RRT_MAX_CAP 1048576
+typedef struct dcx_rrt_state {
+    float*   nodes;         /* [R, 2, cap, dof]                                                             */
+    int32_t* parent;        /* [R, 2, cap]                                                                  */
+    int32_t* count;         /* [R, 2]                                                                       */
+    int32_t* status;        /* [R]: 0 running, 1 solved, 2 full, 3 an endpoint collides                     */
+    int32_t* link;          /* [R, 2]                                                                       */
+    int32_t* solved_round;  /* [R]                                                                          */
+} dcx_rrt_state;
+typedef struct dcx_rrt_opts {
+    float    range;        /* > 0: the longest extension of phase 1                                         */
+    float    max_step;     /* > 0: the sampling stride of every edge check                                  */
+    int32_t  max_samples;  /* >= 1: an edge needing more samples is rejected; it sizes the sweep launches   */
+    int32_t  slots;        /* P, 1 .. DCX_RRT_MAX_SLOTS                                                     */
+    int32_t  cap;          /* nodes per tree, 1 .. DCX_RRT_MAX_CAP                                          */
+    int32_t  reserved0;    /* 0                                                                             */
+    uint64_t wrap_mask;    /* bit j: coordinate j is an angle, measured and walked along the shortest arc   */
+    int64_t  reserved[2];  /* 0                                                                             */
+} dcx_rrt_opts;
+size_t dcx_rrt_work_bytes(const dcx_model* m, int64_t R, int32_t slots);
+int dcx_rrt_connect_run(const dcx_model* m, const dcx_rrt_state* state, int64_t R, const float* samples, int32_t T, int64_t round0,
+                        const dcx_rrt_opts* opts, const float* margin, void* work, size_t work_bytes, void* stream);
+
 /* ---- kernel-perceptron trainer (producer of the path's state) ----------------------- */
 /* DiffCo.train_perceptron kernel_perceptrons.py:98-137 and MultiDiffCo.train_perceptron
  * deprecated/MultiDiffCo.py:50-83 as one persistent launch: worst-margin search, lazily filled kernel rows,
