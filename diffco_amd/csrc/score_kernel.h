@@ -662,6 +662,9 @@ __device__ __forceinline__ void sweep_rows(const ScoreArgs& a, const float (&x_i
         }
         float val, g;
         kernel_eval<KF>(d2d, a, val, g);
+        // (SP: a NaN configuration stays NaN in the score.  Its clamped expanded distance makes every pair a near pair, and
+        // kernel_eval's own clamp would turn the direct term into 1e-15 per support - a finite score beside a NaN gradient)
+        if constexpr (SP && KF == KF_POLY1) val = (d2d == d2d) ? val : d2d;
         val = nr ? val : 0.0f;
         if constexpr (!NS) {
 #pragma unroll
@@ -685,10 +688,102 @@ __device__ __forceinline__ void sweep_rows(const ScoreArgs& a, const float (&x_i
             if constexpr (D & 1) ga_tail = fmaf(cd, -0.5f * xm_tail - r[D - 1], ga_tail);
         }
     };
+    // ---- the lean stage of the spare form ----------------------------------------------------------------------------------
+    // The clamp does nothing where no lane is near: the gate goes in FRONT of the accumulation.  Raw distances of the stage's two
+    // rows, one ballot of !(d2 > thr) per row (the negated compare sends NaN the way fmaxf sent it: to the rare block) and one
+    // branch; a stage with a near lane runs the clamped sequence and the rare block exactly as below, every other stage a body
+    // without v_max in which the two rows' kernel values and coefficients are packed multiplies (the same IEEE multiplies; the
+    // gradient fmas take coef.x / coef.y by op_sel).  Per row the score fma and the gradient fmas keep their order, so no bit moves.
+    // d2_x's seed and fma order row by row, the two rows' chains interleaved (back to back, each dependent pair costs an s_nop)
+    auto d2_raw2 = [&](const auto& r0, const auto& r1) __attribute__((always_inline)) -> v2f {
+        constexpr int NA = NACC > 0 ? NACC : DCX_D2_ACCS(D);
+        v2f a0[NA], a1[NA];
+        a0[0] = a1[0] = v2f{xx, 0.0f};
+#pragma unroll
+        for (int i = 1; i < NA; ++i) a0[i] = a1[i] = v2f{0.0f, 0.0f};
+#pragma unroll
+        for (int k = 0; k + 1 < D; k += 2) {
+            a0[(k / 2) % NA] = __builtin_elementwise_fma(xm[k / 2], v2f{r0[k], r0[k + 1]}, a0[(k / 2) % NA]);
+            a1[(k / 2) % NA] = __builtin_elementwise_fma(xm[k / 2], v2f{r1[k], r1[k + 1]}, a1[(k / 2) % NA]);
+        }
+#pragma unroll
+        for (int i = 1; i < NA; ++i) {
+            a0[0] += a0[i];
+            a1[0] += a1[i];
+        }
+        return v2f{a0[0].x + a0[0].y, a1[0].x + a1[0].y};
+    };
+    // one row's score and gradient terms from its kernel value and coefficient: apply_x's accumulation, in its order
+    auto fold_x = [&](const auto& r, float d2, float val, float coef) __attribute__((always_inline)) {
+        constexpr bool SCORE_BY_COEF = (KF == KF_POLY1 && MODE == MODE_GRAD_ROW);
+        if constexpr (!SCORE_BY_COEF) sc[0] = fmaf(r[L::W_OFF], val, sc[0]);
+        if constexpr (GRAD) {
+            if constexpr (SCORE_BY_COEF) sc[0] = fmaf(coef, d2, sc[0]);
+            const v2f c2 = {coef, coef};
+#pragma unroll
+            for (int k = 0; k + 1 < D; k += 2) {
+                const v2f rv = (k == D - 2) ? v2f{r[D + 2], r[D + 3]} : v2f{r[k], r[k + 1]};
+                ga[k / 2] = __builtin_elementwise_fma(c2, rv, ga[k / 2]);
+            }
+        }
+    };
+    // the quarter-rate op of both rows: 1 / t (RQ2), 1 / sqrt(d2) (Polyharmonic(1))
+    auto quarter2 = [&](v2f d2) __attribute__((always_inline)) -> v2f {
+        if constexpr (KF == KF_RQ2) return v2f{__builtin_amdgcn_rcpf(d2.x), __builtin_amdgcn_rcpf(d2.y)};
+        else return v2f{__builtin_amdgcn_rsqf(d2.x), __builtin_amdgcn_rsqf(d2.y)};
+    };
+    auto lean_stage_x = [&](const auto& r0, const auto& r1, v2f d2, v2f q2) __attribute__((always_inline)) {
+        v2f val2, g2, coef2 = {0.0f, 0.0f};
+        if constexpr (KF == KF_RQ2) {   // sweep_eval<KF_RQ2> on both rows: u u and val u packed
+            val2 = q2 * q2;
+            g2 = val2 * q2;
+        } else {                        // kernel_eval<KF_POLY1, CLAMPED>
+            g2 = q2;
+            val2 = d2 * g2;
+        }
+        if constexpr (GRAD) {
+            v2f w2 = {r0[L::W_OFF], r1[L::W_OFF]};
+            // (coef_of's fmaf(up, w, 0) stays as it is: the zero signs)
+            if constexpr (MODE != MODE_GRAD_ROW) w2 = v2f{fmaf(up[0], w2.x, 0.0f), fmaf(up[0], w2.y, 0.0f)};
+            coef2 = g2 * w2;
+        }
+        fold_x(r0, d2.x, val2.x, coef2.x);
+        fold_x(r1, d2.y, val2.y, coef2.y);
+    };
     // two rows of a pipeline stage in the expanded form + the near check.  Each row's "any lane near?" goes to an SGPR
     // mask straight away (the distances are not kept: the rare block recomputes them, bit for bit), one scalar branch
     // per stage.
-    auto stage_x = [&](const auto& r0, const auto& r1) __attribute__((always_inline)) {
+    // (SP: the lean stage above.)  n0, n1: the rows whose loads were issued in front of this stage (in flight while it runs)
+    auto stage_x = [&](const auto& r0, const auto& r1, const auto& n0, const auto& n1) __attribute__((always_inline)) {
+        if constexpr (SP) {
+            const v2f d2 = d2_raw2(r0, r1);
+            if constexpr (KF == KF_POLY1) {
+                const auto m0 = __builtin_amdgcn_ballot_w64(!(d2.x > thr));
+                const auto m1 = __builtin_amdgcn_ballot_w64(!(d2.y > thr));
+                // two one-sided branches on the same mask, not if / else: each updates the accumulators in place.  As a diamond the
+                // join's phis met undefined values on the lean side, and every loop-carried scalar accumulator cost a v_mov per stage
+                auto near = m0 | m1;
+                // both v_rsq_f32 in front of the branch (a near stage does not read them): the compares and the branch cover
+                // the wait state between a transcendental op and its first use, which the lean block alone fills with an s_nop
+                v2f q2 = quarter2(d2);
+                asm volatile("" : "+v"(q2));
+                if (__builtin_expect(near != 0, 0)) {
+                    (void)pair_x(r0);
+                    (void)pair_x(r1);
+                    fix_near(r0, d2_x(r0));
+                    fix_near(r1, d2_x(r1));
+                    // the rows in flight count as read on this side too.  Their operand pairs behind the weight are first read by
+                    // the NEXT stage's gradient pass; with no reader here their s_load_dwordx2 were sunk below this branch, to
+                    // half the cover in front of the next wait (config #5, four waves per SIMD: 25.6 -> 28.5 us per iteration)
+                    asm volatile("" ::"s"(n0[D + 2]), "s"(n0[D + 3]), "s"(n1[D + 2]), "s"(n1[D + 3]));
+                }
+                asm volatile("" : "+s"(near));   // (keeps the two branches from being threaded back into one diamond)
+                if (__builtin_expect(near == 0, 1)) lean_stage_x(r0, r1, d2, q2);
+                return;
+            }
+            lean_stage_x(r0, r1, d2, quarter2(d2));
+            return;
+        }
         if constexpr (KF != KF_POLY1) {
             (void)pair_x(r0);
             (void)pair_x(r1);
@@ -704,6 +799,17 @@ __device__ __forceinline__ void sweep_rows(const ScoreArgs& a, const float (&x_i
     auto single_x = [&](const auto& r0) __attribute__((always_inline)) {
         if constexpr (KF != KF_POLY1) {
             (void)pair_x(r0);
+            return;
+        }
+        if constexpr (SP) {   // the same gate on one row's chain (the tail rows): raw distance, no clamp where no lane is near
+            const float d2 = d2_raw2(r0, r0).x;   // (the twin chain is the same value: one chain is emitted)
+            auto near = __builtin_amdgcn_ballot_w64(!(d2 > thr));
+            if (__builtin_expect(near != 0, 0)) {
+                (void)pair_x(r0);
+                fix_near(r0, d2_x(r0));
+            }
+            asm volatile("" : "+s"(near));
+            if (__builtin_expect(near == 0, 1)) apply_x(r0, d2, std::integral_constant<int, 1>{}, true);
             return;
         }
         if (__builtin_expect(__builtin_amdgcn_ballot_w64(pair_x(r0) <= thr) != 0, 0)) fix_near(r0, d2_x(r0));
@@ -913,7 +1019,7 @@ __device__ __forceinline__ void sweep_rows(const ScoreArgs& a, const float (&x_i
             load_row(rowD, j + 3);
             __builtin_amdgcn_sched_barrier(0);
             if constexpr (XFA) {
-                stage_x(rowA, rowB);
+                stage_x(rowA, rowB, rowC, rowD);
             } else {
                 pair(rowA);
                 pair(rowB);
@@ -925,7 +1031,7 @@ __device__ __forceinline__ void sweep_rows(const ScoreArgs& a, const float (&x_i
             load_row(rowB, (j + 5 < j1) ? j + 5 : jl);
             __builtin_amdgcn_sched_barrier(0);
             if constexpr (XFA) {
-                stage_x(rowC, rowD);
+                stage_x(rowC, rowD, rowA, rowB);
             } else {
                 pair(rowC);
                 pair(rowD);
