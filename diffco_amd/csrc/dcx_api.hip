@@ -1681,7 +1681,7 @@ int dcx_escape_adam(const dcx_model* m, float* q, int64_t B, const float* margin
     return DCX_OK;   // (every loop wrote its final record where it stopped, or behind the last step)
 }
 
-// ---- batched motion checks (motion_kernel.h) ----------------------------------------------------------------------------------
+// ---- the motion calls (motion_tile.h): what dcx_check_motions, dcx_motion_worst, dcx_motion_band and dcx_motion_cost share ------
 namespace {
 // A split launch (small batches: support super-chunks over gridDim.y, the tile finished by the last of its blocks to arrive) keeps
 // its arrival counters and partial rows in the caller's work buffer, so the buffer reserves room for the largest split the call
@@ -1701,26 +1701,95 @@ MotionWork motion_work(int64_t E) {
     w.total = w.partial + (size_t)kMotionSplitRows * DCX_MAX_C * 64 * sizeof(float);
     return w;
 }
-motion_fn motion_for(int Dt) {
-    switch (Dt) {
-#define DCX_CASE(D) case D: return launch_motion_D##D;
-        DCX_CASE(2) DCX_CASE(4) DCX_CASE(6) DCX_CASE(8) DCX_CASE(12) DCX_CASE(16) DCX_CASE(18) DCX_CASE(21)
-        DCX_CASE(24) DCX_CASE(27) DCX_CASE(30) DCX_CASE(32) DCX_CASE(36) DCX_CASE(42) DCX_CASE(48) DCX_CASE(54)
-        DCX_CASE(60) DCX_CASE(64) DCX_CASE(72) DCX_CASE(84) DCX_CASE(96)
-#undef DCX_CASE
-    default: return nullptr;
-    }
+// where a call's workspace keeps the work list and the split launch's room (dcx_motion_cost lays them out on its own)
+struct MotionSlots {
+    int64_t* offs;
+    float* frac;
+    unsigned int* counters;
+    float* partial;
+};
+MotionSlots motion_slots(char* base, const MotionWork& w) {
+    return MotionSlots{(int64_t*)(base + w.offs), (float*)(base + w.frac), (unsigned int*)(base + w.counters), (float*)(base + w.partial)};
 }
-// What dcx_check_motions and dcx_motion_worst share: the launch geometry for the upper bound of the samples and the sweep's
-// arguments - the rows, slices, wave-group shares and the split decision of a score-only launch, so that both calls score a
-// sample to the same bits for the same (model, E, max_samples).
+
+// the per-width entry points (motion_inst.hip, motion_worst_inst.hip, motion_band_inst.hip, motion_cost_inst.hip)
+#define DCX_CASE_(sym, D) case D: return sym##D;
+#define DCX_WIDTH_TABLE(fn, name, CASE)                \
+    fn name(int Dt) {                                  \
+        switch (Dt) {                                  \
+            DCX_FOREACH_WIDTH(CASE)                    \
+        default: return nullptr;                       \
+        }                                              \
+    }
+#define DCX_CASE_CHECK(D) DCX_CASE_(launch_motion_D, D)
+#define DCX_CASE_WORST(D) DCX_CASE_(launch_motion_worst_D, D)
+#define DCX_CASE_BAND(D) DCX_CASE_(launch_motion_band_D, D)
+#define DCX_CASE_COST(D) DCX_CASE_(launch_motion_cost_D, D)
+DCX_WIDTH_TABLE(motion_fn, motion_for, DCX_CASE_CHECK)
+DCX_WIDTH_TABLE(motion_worst_fn, motion_worst_for, DCX_CASE_WORST)
+DCX_WIDTH_TABLE(motion_band_fn, motion_band_for, DCX_CASE_BAND)
+DCX_WIDTH_TABLE(motion_cost_fn, motion_cost_for, DCX_CASE_COST)
+#undef DCX_WIDTH_TABLE
+#undef DCX_CASE_CHECK
+#undef DCX_CASE_WORST
+#undef DCX_CASE_BAND
+#undef DCX_CASE_COST
+#undef DCX_CASE_
+
+// The argument checks the four calls repeat, `what` ("motion check", "motion worst", ...) substituted into the messages.  A call's
+// own checks stand between them and the first failing check names the error, so the shared ones come as the runs they form.
+struct MotionSampling {   // the sampling rule of dcx_motion_opts / dcx_motion_cost_opts
+    int32_t res;
+    float max_step;
+    int32_t max_samples;
+};
+struct MotionCheck {
+    const char* what;
+    int nulls(const dcx_model* m, const void* opt, const char* opts) const {
+        if (!m) return fail(DCX_ERR_INVALID, "model is NULL");
+        if (!opt) return fail(DCX_ERR_INVALID, std::string(opts) + " options are NULL");
+        return DCX_OK;
+    }
+    int sampling(const MotionSampling& r) const {
+        const bool by_res = r.res > 0, by_step = r.max_step > 0.f;
+        if (r.res < 0 || !(r.max_step >= 0.f) || by_res == by_step)
+            return fail(DCX_ERR_INVALID, std::string(what) + " needs exactly one sampling rule: res > 0 or max_step > 0 (the other 0)");
+        if (r.max_samples < 1) return fail(DCX_ERR_INVALID, std::string(what) + " needs max_samples >= 1");
+        return DCX_OK;
+    }
+    int mask(const dcx_model* m, uint64_t wrap_mask) const {   // (mask 0, the plain call: the model is not read here)
+        if (wrap_mask != 0 && m->fk.dof < 64 && (wrap_mask >> m->fk.dof) != 0)
+            return fail(DCX_ERR_INVALID, std::string(what) + ": wrap_mask has a bit at or above dof");
+        return DCX_OK;
+    }
+    int edges(int64_t E) const {
+        if (E > INT32_MAX) return fail(DCX_ERR_UNSUPPORTED, std::string(what) + ": more than 2^31 - 1 edges");
+        return DCX_OK;
+    }
+    int tiles(int64_t E, int32_t max_samples, int64_t& tiles_max) const {   // the grid's upper bound: one tile per block
+        tiles_max = (E * (int64_t)max_samples + 63) / 64;
+        if (tiles_max > 0x7fffffffLL) return fail(DCX_ERR_UNSUPPORTED, std::string(what) + ": E * max_samples too large for one launch");
+        return DCX_OK;
+    }
+};
+
+// What the calls share: the launch geometry for the upper bound of the samples and the sweep's arguments - the rows, slices,
+// wave-group shares and the split decision of a launch with `acc` accumulators per lane (Cc: a score-only launch, so that the
+// three score-only calls score a sample to the same bits for the same (model, E, max_samples); Dt + Cc: dcx_motion_cost).
 struct MotionSweepPlan {
     Geometry g;
-    size_t lds;
+    size_t lds;   // for launches with `acc` accumulators per lane ONLY: a pass with another count takes motion_lds_bytes(m, g, count)
 };
-MotionSweepPlan motion_sweep_plan(const dcx_model* m, int64_t tiles_max, char* base, const MotionWork& w, ScoreArgs& sa) {
+int motion_skew(const dcx_model* m, const Geometry& g, const ScoreArgs& sa, bool score_only) {
+    return (g.nw == 16 && (sa.s_chunk >= 24 || knobs().skew > 0)) ? skew_rule(m->Cc, score_only)
+         : (g.nw == 8 && (sa.s_chunk >= 24 || knobs().skew8 > 0)) ? skew8_rule(score_only) : 0;
+}
+size_t motion_lds_bytes(const dcx_model* m, const Geometry& g, int acc) {
     const int d_fk = m->fk.n_points * m->fk.point_dim;
-    const int acc = m->Cc;
+    return sizeof(float) * (((size_t)lds_plan(m->fk.dof, d_fk, m->frame_floats, g.nw > 1 ? g.red_slots : 0, acc, true).total +
+                             m->prog_floats + 3) & ~(size_t)3) + sizeof(float) * kMotionLdsFloats;
+}
+MotionSweepPlan motion_sweep_plan(const dcx_model* m, int64_t tiles_max, int acc, const MotionSlots& s, ScoreArgs& sa) {
     // grid: the sample count is on the device only; its upper bound E * max_samples sizes the grid and decides whether the
     // launch splits the supports
     Geometry g = pick_geometry(m, std::min<int64_t>(tiles_max, (int64_t)1 << 30) * 64, acc, true);
@@ -1733,7 +1802,7 @@ MotionSweepPlan motion_sweep_plan(const dcx_model* m, int64_t tiles_max, char* b
     sa.ys = g.ys;
     sa.s_super = (m->S_active + g.ys - 1) / g.ys;
     sa.s_chunk = (sa.s_super + g.nw - 1) / g.nw;
-    // the rows and slices exactly as run_score picks them for a score-only launch
+    // the rows and slices exactly as run_score picks them
     const bool xf_able = knobs().xf != 0 && xf_applies(m->Dt, m->Cc, m->kf) && m->rows_xf_dev != nullptr &&
                          (m->kf != KF_RQ2 || m->xf_rq_ok || knobs().xf >= 2);
     if (!xf_able && m->rows_p2_dev != nullptr && p2_applies(m->Dt, m->Cc, m->kf)) {
@@ -1741,11 +1810,10 @@ MotionSweepPlan motion_sweep_plan(const dcx_model* m, int64_t tiles_max, char* b
         sa.s_super = (sa.s_super + 1) & ~1;
         sa.s_chunk = ((sa.s_super + g.nw - 1) / g.nw + 1) & ~1;
     }
-    sa.s_skew = (g.nw == 16 && (sa.s_chunk >= 24 || knobs().skew > 0)) ? skew_rule(m->Cc, true)
-              : (g.nw == 8 && (sa.s_chunk >= 24 || knobs().skew8 > 0)) ? skew8_rule(true) : 0;
+    sa.s_skew = motion_skew(m, g, sa, true);   // a score-only pass; dcx_motion_cost sets it per pass
     sa.red_slots = g.red_slots;
     sa.dof = m->fk.dof;
-    sa.d_fk = d_fk;
+    sa.d_fk = m->fk.n_points * m->fk.point_dim;
     sa.frame_floats = m->frame_floats;
     sa.kind = m->kind;
     sa.c_out = m->C;
@@ -1755,19 +1823,44 @@ MotionSweepPlan motion_sweep_plan(const dcx_model* m, int64_t tiles_max, char* b
     sa.kp1 = m->kp1;
     sa.xf = xf_able ? 1 : 0;
     if (sa.xf) xf_rows(m, sa);
-    // a DH arm's chain split by rows over two waves, where run_score splits it
+    // a DH arm's chain split by rows over two waves, where run_score splits it (J^T stays on wave 0: jt_waves = 0)
     sa.jt_rows = (sa.fkk == 2 && g.nw >= 2 * m->dh.n_chains && m->dh.n_chains <= 2 && m->dh.end0 <= kDhUnroll &&
                   m->dh.n_steps - m->dh.end0 <= kDhUnroll && knobs().jt_waves != 0) ? 1 : 0;
     if (g.ys > 1) {
-        sa.partial = (float*)(base + w.partial);
-        sa.tile_done = (unsigned int*)(base + w.counters);
+        sa.partial = s.partial;
+        sa.tile_done = s.counters;
     }
-    const size_t lds = sizeof(float) * (((size_t)lds_plan(sa.dof, d_fk, m->frame_floats, g.nw > 1 ? g.red_slots : 0, acc, true).total +
-                                         m->prog_floats + 3) & ~(size_t)3) + sizeof(float) * kMotionLdsFloats;
-    return MotionSweepPlan{g, lds};
+    return MotionSweepPlan{g, motion_lds_bytes(m, g, acc)};
+}
+
+// The prep launch of a call (motion_prep.hip) and the head of its kernel's arguments.  status: where first_hit's -1 / -2 go (the
+// caller's first_hit for dcx_check_motions, a workspace slot for the others).
+hipError_t motion_prep(const dcx_model* m, const float* qa, const float* qb, int64_t E, const MotionSampling& r, int32_t open_end,
+                       uint64_t wrap_mask, const MotionSlots& s, int32_t* status, int32_t* n_samples, int ys, int64_t tiles_max,
+                       MotionEdgeArgs& head, hipStream_t st) {
+    MotionPrepArgs p{};
+    p.qa = head.qa = qa;
+    p.qb = head.qb = qb;
+    p.E = head.E = E;
+    p.dof = m->fk.dof;
+    p.res = head.res = r.res;
+    p.max_samples = r.max_samples;
+    p.max_step = r.max_step;
+    p.offs = s.offs;
+    p.frac = s.frac;
+    head.offs = s.offs;
+    head.frac = s.frac;
+    p.first_hit = status;
+    p.n_samples = n_samples;
+    p.counters = ys > 1 ? s.counters : nullptr;
+    p.n_counters = ys > 1 ? (int32_t)tiles_max : 0;
+    p.open_end = open_end;
+    p.wrap_mask = head.wrap_mask = wrap_mask;
+    return launch_motion_prep(p, st);
 }
 }  // namespace
 
+// ---- batched motion checks (motion_kernel.h) ----------------------------------------------------------------------------------
 size_t dcx_motion_work_bytes(const dcx_model* m, int64_t E) {
     if (!m || E < 0) return 0;
     return motion_work(E).total;
@@ -1782,61 +1875,32 @@ int dcx_check_motions_ex(const dcx_model* m, const float* qa, const float* qb, i
                          const float* margin, int32_t* first_hit, int32_t* n_samples, void* work, size_t work_bytes,
                          uint64_t wrap_mask, void* stream) {
     // every argument is checked before anything touches the model or the device
-    if (!m) return fail(DCX_ERR_INVALID, "model is NULL");
-    if (!opt) return fail(DCX_ERR_INVALID, "motion options are NULL");
+    const MotionCheck chk{"motion check"};
+    if (int rc = chk.nulls(m, opt, "motion")) return rc;
     if (E < 0) return fail(DCX_ERR_INVALID, "E < 0");
     if (E > 0 && (!qa || !qb || !first_hit || !work)) return fail(DCX_ERR_INVALID, "qa / qb / first_hit / work is NULL");
-    const bool by_res = opt->res > 0, by_step = opt->max_step > 0.f;
-    if (opt->res < 0 || !(opt->max_step >= 0.f) || by_res == by_step)
-        return fail(DCX_ERR_INVALID, "motion check needs exactly one sampling rule: res > 0 or max_step > 0 (the other 0)");
-    if (opt->max_samples < 1) return fail(DCX_ERR_INVALID, "motion check needs max_samples >= 1");
-    if (wrap_mask != 0 && m->fk.dof < 64 && (wrap_mask >> m->fk.dof) != 0)   // (mask 0, the plain call: the model is not read here)
-        return fail(DCX_ERR_INVALID, "motion check: wrap_mask has a bit at or above dof");
+    const MotionSampling rule{opt->res, opt->max_step, opt->max_samples};
+    if (int rc = chk.sampling(rule)) return rc;
+    if (int rc = chk.mask(m, wrap_mask)) return rc;
     const MotionWork w = motion_work(E);
     if (E > 0 && work_bytes < w.total) return fail(DCX_ERR_INVALID, "motion workspace is smaller than dcx_motion_work_bytes");
-    if (E > INT32_MAX) return fail(DCX_ERR_UNSUPPORTED, "motion check: more than 2^31 - 1 edges");
+    if (int rc = chk.edges(E)) return rc;
     if (E == 0) return DCX_OK;
-    const int64_t tiles_max = (E * (int64_t)opt->max_samples + 63) / 64;
-    if (tiles_max > 0x7fffffffLL) return fail(DCX_ERR_UNSUPPORTED, "motion check: E * max_samples too large for one launch");
+    int64_t tiles_max;
+    if (int rc = chk.tiles(E, opt->max_samples, tiles_max)) return rc;
     if (int rc = set_device(m->device)) return rc;
     hipStream_t st = (hipStream_t)stream;
-    char* base = (char*)work;
+    const MotionSlots slots = motion_slots((char*)work, w);
     MotionArgs a{};
-    const MotionSweepPlan plan = motion_sweep_plan(m, tiles_max, base, w, a.sc);
-    const Geometry& g = plan.g;
-    MotionPrepArgs p{};
-    p.qa = qa;
-    p.qb = qb;
-    p.E = E;
-    p.dof = m->fk.dof;
-    p.res = opt->res;
-    p.max_samples = opt->max_samples;
-    p.max_step = opt->max_step;
-    p.offs = (int64_t*)(base + w.offs);
-    p.frac = (float*)(base + w.frac);
-    p.first_hit = first_hit;
-    p.n_samples = n_samples;
-    p.counters = g.ys > 1 ? (unsigned int*)(base + w.counters) : nullptr;
-    p.n_counters = g.ys > 1 ? (int32_t)tiles_max : 0;
-    p.wrap_mask = wrap_mask;
-    hipError_t e = launch_motion_prep(p, st);
+    const MotionSweepPlan plan = motion_sweep_plan(m, tiles_max, m->Cc, slots, a.sc);
+    hipError_t e = motion_prep(m, qa, qb, E, rule, 0, wrap_mask, slots, first_hit, n_samples, plan.g.ys, tiles_max, a, st);
     if (e != hipSuccess) return fail_hip(e, "motion prep launch");
-
-    a.qa = qa;
-    a.qb = qb;
-    a.offs = p.offs;
-    a.frac = p.frac;
     a.first_hit = reinterpret_cast<unsigned int*>(first_hit);
     a.margin = margin;
-    a.E = E;
-    a.res = opt->res;
     a.early_exit = knobs().motion_early_exit != 0 ? 1 : 0;
-    a.wrap_mask = wrap_mask;
-    const int64_t nblk = tiles_max;   // one tile per block; blocks past the work list's end leave (motion_kernel.h)
-    const size_t lds = plan.lds;
     motion_fn launch = motion_for(m->Dt);
     if (!launch) return fail(DCX_ERR_UNSUPPORTED, "motion check: no kernel for this feature width");
-    e = launch(m->kf, m->Cc, g.nw, lds, nblk, a, st);
+    e = launch(m->kf, m->Cc, plan.g.nw, plan.lds, tiles_max, a, st);   // one tile per block
     if (e != hipSuccess) return fail_hip(e, "motion kernel launch");
     return DCX_OK;
 }
@@ -1862,16 +1926,6 @@ MotionWorstWork motion_worst_work(const dcx_model* m, int64_t E) {
     w.total = w.g + up((size_t)E * m->fk.dof * sizeof(float));
     return w;
 }
-motion_worst_fn motion_worst_for(int Dt) {
-    switch (Dt) {
-#define DCX_CASE(D) case D: return launch_motion_worst_D##D;
-        DCX_CASE(2) DCX_CASE(4) DCX_CASE(6) DCX_CASE(8) DCX_CASE(12) DCX_CASE(16) DCX_CASE(18) DCX_CASE(21)
-        DCX_CASE(24) DCX_CASE(27) DCX_CASE(30) DCX_CASE(32) DCX_CASE(36) DCX_CASE(42) DCX_CASE(48) DCX_CASE(54)
-        DCX_CASE(60) DCX_CASE(64) DCX_CASE(72) DCX_CASE(84) DCX_CASE(96)
-#undef DCX_CASE
-    default: return nullptr;
-    }
-}
 }  // namespace
 
 size_t dcx_motion_worst_work_bytes(const dcx_model* m, int64_t E) {
@@ -1883,70 +1937,46 @@ int dcx_motion_worst(const dcx_model* m, const float* qa, const float* qb, int64
                      const float* margin, float* worst, int32_t* worst_idx, int32_t* worst_class, int32_t* n_samples,
                      float* grad_a, float* grad_b, void* work, size_t work_bytes, uint64_t wrap_mask, void* stream) {
     // every argument is checked before anything touches the device
-    if (!m) return fail(DCX_ERR_INVALID, "model is NULL");
-    if (!opt) return fail(DCX_ERR_INVALID, "motion options are NULL");
+    const MotionCheck chk{"motion worst"};
+    if (int rc = chk.nulls(m, opt, "motion")) return rc;
     if (E < 0) return fail(DCX_ERR_INVALID, "E < 0");
     if (E > 0 && (!qa || !qb || !worst || !worst_idx || !work)) return fail(DCX_ERR_INVALID, "qa / qb / worst / worst_idx / work is NULL");
     if ((grad_a == nullptr) != (grad_b == nullptr)) return fail(DCX_ERR_INVALID, "motion worst: pass both grad_a and grad_b or neither");
-    const bool by_res = opt->res > 0, by_step = opt->max_step > 0.f;
-    if (opt->res < 0 || !(opt->max_step >= 0.f) || by_res == by_step)
-        return fail(DCX_ERR_INVALID, "motion worst needs exactly one sampling rule: res > 0 or max_step > 0 (the other 0)");
-    if (opt->max_samples < 1) return fail(DCX_ERR_INVALID, "motion worst needs max_samples >= 1");
+    const MotionSampling rule{opt->res, opt->max_step, opt->max_samples};
+    if (int rc = chk.sampling(rule)) return rc;
     if (opt->reserved != 0) return fail(DCX_ERR_INVALID, "motion worst: reserved must be 0");
-    if (wrap_mask != 0 && m->fk.dof < 64 && (wrap_mask >> m->fk.dof) != 0)
-        return fail(DCX_ERR_INVALID, "motion worst: wrap_mask has a bit at or above dof");
+    if (int rc = chk.mask(m, wrap_mask)) return rc;
     const MotionWorstWork w = motion_worst_work(m, E);
     if (E > 0 && work_bytes < w.total) return fail(DCX_ERR_INVALID, "motion workspace is smaller than dcx_motion_worst_work_bytes");
-    if (E > INT32_MAX) return fail(DCX_ERR_UNSUPPORTED, "motion worst: more than 2^31 - 1 edges");
+    if (int rc = chk.edges(E)) return rc;
     if (opt->max_samples > kMotionWorstSampleLimit) return fail(DCX_ERR_UNSUPPORTED, "motion worst: max_samples above 2^24 - 1");
     if (E == 0) return DCX_OK;
-    const int64_t tiles_max = (E * (int64_t)opt->max_samples + 63) / 64;
-    if (tiles_max > 0x7fffffffLL) return fail(DCX_ERR_UNSUPPORTED, "motion worst: E * max_samples too large for one launch");
+    int64_t tiles_max;
+    if (int rc = chk.tiles(E, opt->max_samples, tiles_max)) return rc;
     motion_worst_fn launch = motion_worst_for(m->Dt);
     if (!launch) return fail(DCX_ERR_UNSUPPORTED, "motion worst: no kernel for this feature width");
     if (int rc = set_device(m->device)) return rc;
     hipStream_t st = (hipStream_t)stream;
     char* base = (char*)work;
+    const MotionSlots slots = motion_slots(base, w.mw);
+    int32_t* status = (int32_t*)(base + w.status);
     MotionWorstArgs a{};
-    const MotionSweepPlan plan = motion_sweep_plan(m, tiles_max, base, w.mw, a.sc);   // the check's geometry and sweep arguments
-    const Geometry& g = plan.g;
-    MotionPrepArgs p{};
-    p.qa = qa;
-    p.qb = qb;
-    p.E = E;
-    p.dof = m->fk.dof;
-    p.res = opt->res;
-    p.max_samples = opt->max_samples;
-    p.max_step = opt->max_step;
-    p.offs = (int64_t*)(base + w.mw.offs);
-    p.frac = (float*)(base + w.mw.frac);
-    p.first_hit = (int32_t*)(base + w.status);
-    p.n_samples = n_samples;
-    p.counters = g.ys > 1 ? (unsigned int*)(base + w.mw.counters) : nullptr;
-    p.n_counters = g.ys > 1 ? (int32_t)tiles_max : 0;
-    p.wrap_mask = wrap_mask;
-    hipError_t e = launch_motion_prep(p, st);
+    const MotionSweepPlan plan = motion_sweep_plan(m, tiles_max, m->Cc, slots, a.sc);   // the check's geometry and sweep arguments
+    hipError_t e = motion_prep(m, qa, qb, E, rule, 0, wrap_mask, slots, status, n_samples, plan.g.ys, tiles_max, a, st);
     if (e != hipSuccess) return fail_hip(e, "motion worst prep launch");
     a.keys = (unsigned long long*)(base + w.keys);
     e = hipMemsetAsync(a.keys, 0, (size_t)E * sizeof(unsigned long long), st);   // key 0: no sample yet
     if (e != hipSuccess) return fail_hip(e, "motion worst key reset");
-    a.qa = qa;
-    a.qb = qb;
-    a.offs = p.offs;
-    a.frac = p.frac;
     a.margin = margin;
-    a.E = E;
-    a.res = opt->res;
-    a.wrap_mask = wrap_mask;
-    e = launch(m->kf, m->Cc, g.nw, plan.lds, tiles_max, a, st);
+    e = launch(m->kf, m->Cc, plan.g.nw, plan.lds, tiles_max, a, st);
     if (e != hipSuccess) return fail_hip(e, "motion worst kernel launch");
     const bool grads = grad_a != nullptr;
     MotionWorstFinishArgs f{};
     f.qa = qa;
     f.qb = qb;
-    f.offs = p.offs;
-    f.frac = p.frac;
-    f.status = p.first_hit;
+    f.offs = slots.offs;
+    f.frac = slots.frac;
+    f.status = status;
     f.keys = a.keys;
     f.worst = worst;
     f.worst_idx = worst_idx;
@@ -1993,16 +2023,6 @@ MotionBandWork motion_band_work(int64_t E, int32_t max_samples) {
     w.total = w.uoffs + up((size_t)(E + 1) * sizeof(int64_t));
     return w;
 }
-motion_band_fn motion_band_for(int Dt) {
-    switch (Dt) {
-#define DCX_CASE(D) case D: return launch_motion_band_D##D;
-        DCX_CASE(2) DCX_CASE(4) DCX_CASE(6) DCX_CASE(8) DCX_CASE(12) DCX_CASE(16) DCX_CASE(18) DCX_CASE(21)
-        DCX_CASE(24) DCX_CASE(27) DCX_CASE(30) DCX_CASE(32) DCX_CASE(36) DCX_CASE(42) DCX_CASE(48) DCX_CASE(54)
-        DCX_CASE(60) DCX_CASE(64) DCX_CASE(72) DCX_CASE(84) DCX_CASE(96)
-#undef DCX_CASE
-    default: return nullptr;
-    }
-}
 }  // namespace
 
 size_t dcx_motion_band_work_bytes(const dcx_model* m, int64_t E, int32_t max_samples) {
@@ -2014,8 +2034,8 @@ int dcx_motion_band(const dcx_model* m, const float* qa, const float* qb, int64_
                     const float* lo, const float* hi, const dcx_motion_band_out* out, void* work, size_t work_bytes,
                     uint64_t wrap_mask, void* stream) {
     // every argument is checked before anything touches the device
-    if (!m) return fail(DCX_ERR_INVALID, "model is NULL");
-    if (!opt) return fail(DCX_ERR_INVALID, "motion options are NULL");
+    const MotionCheck chk{"motion band"};
+    if (int rc = chk.nulls(m, opt, "motion")) return rc;
     if (!out) return fail(DCX_ERR_INVALID, "motion band: out is NULL");
     if (E < 0) return fail(DCX_ERR_INVALID, "E < 0");
     if (E > 0 && (!qa || !qb || !work)) return fail(DCX_ERR_INVALID, "qa / qb / work is NULL");
@@ -2024,62 +2044,38 @@ int dcx_motion_band(const dcx_model* m, const float* qa, const float* qb, int64_
     if (out->unc_cap > 0 && (!out->unc_edge || !out->unc_sample))
         return fail(DCX_ERR_INVALID, "motion band: unc_edge / unc_sample is NULL with unc_cap > 0");
     if (out->reserved[0] || out->reserved[1]) return fail(DCX_ERR_INVALID, "motion band: out's reserved fields must be 0");
-    const bool by_res = opt->res > 0, by_step = opt->max_step > 0.f;
-    if (opt->res < 0 || !(opt->max_step >= 0.f) || by_res == by_step)
-        return fail(DCX_ERR_INVALID, "motion band needs exactly one sampling rule: res > 0 or max_step > 0 (the other 0)");
-    if (opt->max_samples < 1) return fail(DCX_ERR_INVALID, "motion band needs max_samples >= 1");
+    const MotionSampling rule{opt->res, opt->max_step, opt->max_samples};
+    if (int rc = chk.sampling(rule)) return rc;
     if (opt->reserved != 0) return fail(DCX_ERR_INVALID, "motion band: reserved must be 0");
-    if (wrap_mask != 0 && m->fk.dof < 64 && (wrap_mask >> m->fk.dof) != 0)
-        return fail(DCX_ERR_INVALID, "motion band: wrap_mask has a bit at or above dof");
+    if (int rc = chk.mask(m, wrap_mask)) return rc;
     const MotionBandWork w = motion_band_work(E, opt->max_samples);
     if (E > 0 && work_bytes < w.total) return fail(DCX_ERR_INVALID, "motion workspace is smaller than dcx_motion_band_work_bytes");
-    if (E > INT32_MAX) return fail(DCX_ERR_UNSUPPORTED, "motion band: more than 2^31 - 1 edges");
+    if (int rc = chk.edges(E)) return rc;
     if (E == 0) return DCX_OK;
-    const int64_t tiles_max = (E * (int64_t)opt->max_samples + 63) / 64;
-    if (tiles_max > 0x7fffffffLL) return fail(DCX_ERR_UNSUPPORTED, "motion band: E * max_samples too large for one launch");
+    int64_t tiles_max;
+    if (int rc = chk.tiles(E, opt->max_samples, tiles_max)) return rc;
     motion_band_fn launch = motion_band_for(m->Dt);
     if (!launch) return fail(DCX_ERR_UNSUPPORTED, "motion band: no kernel for this feature width");
     if (int rc = set_device(m->device)) return rc;
     hipStream_t st = (hipStream_t)stream;
     char* base = (char*)work;
+    const MotionSlots slots = motion_slots(base, w.mw);
+    int32_t* status = (int32_t*)(base + w.status);
     MotionBandArgs a{};
-    const MotionSweepPlan plan = motion_sweep_plan(m, tiles_max, base, w.mw, a.sc);   // the check's geometry and sweep arguments
-    const Geometry& g = plan.g;
-    MotionPrepArgs p{};
-    p.qa = qa;
-    p.qb = qb;
-    p.E = E;
-    p.dof = m->fk.dof;
-    p.res = opt->res;
-    p.max_samples = opt->max_samples;
-    p.max_step = opt->max_step;
-    p.offs = (int64_t*)(base + w.mw.offs);
-    p.frac = (float*)(base + w.mw.frac);
-    p.first_hit = (int32_t*)(base + w.status);
-    p.n_samples = out->n_samples;
-    p.counters = g.ys > 1 ? (unsigned int*)(base + w.mw.counters) : nullptr;
-    p.n_counters = g.ys > 1 ? (int32_t)tiles_max : 0;
-    p.wrap_mask = wrap_mask;
-    hipError_t e = launch_motion_prep(p, st);
+    const MotionSweepPlan plan = motion_sweep_plan(m, tiles_max, m->Cc, slots, a.sc);   // the check's geometry and sweep arguments
+    hipError_t e = motion_prep(m, qa, qb, E, rule, 0, wrap_mask, slots, status, out->n_samples, plan.g.ys, tiles_max, a, st);
     if (e != hipSuccess) return fail_hip(e, "motion band prep launch");
-    a.qa = qa;
-    a.qb = qb;
-    a.offs = p.offs;
-    a.frac = p.frac;
     a.codes = (uint8_t*)(base + w.codes);
     a.lo = lo;
     a.hi = hi;
-    a.E = E;
-    a.res = opt->res;
-    a.wrap_mask = wrap_mask;
-    e = launch(m->kf, m->Cc, g.nw, plan.lds, tiles_max, a, st);
+    e = launch(m->kf, m->Cc, plan.g.nw, plan.lds, tiles_max, a, st);
     if (e != hipSuccess) return fail_hip(e, "motion band kernel launch");
     MotionBandFinishArgs f{};
     f.qa = qa;
     f.qb = qb;
-    f.offs = p.offs;
-    f.frac = p.frac;
-    f.status = p.first_hit;
+    f.offs = slots.offs;
+    f.frac = slots.frac;
+    f.status = status;
     f.codes = a.codes;
     f.verdict = out->verdict;
     f.first_hit = out->first_hit;
@@ -2124,16 +2120,6 @@ MotionCostWork motion_cost_work(const dcx_model* m, int64_t E, int32_t max_sampl
     w.total = w.tile_on + (m->C > 1 ? up(tiles * sizeof(int32_t)) : 0);
     return w;
 }
-motion_cost_fn motion_cost_for(int Dt) {
-    switch (Dt) {
-#define DCX_CASE(D) case D: return launch_motion_cost_D##D;
-        DCX_CASE(2) DCX_CASE(4) DCX_CASE(6) DCX_CASE(8) DCX_CASE(12) DCX_CASE(16) DCX_CASE(18) DCX_CASE(21)
-        DCX_CASE(24) DCX_CASE(27) DCX_CASE(30) DCX_CASE(32) DCX_CASE(36) DCX_CASE(42) DCX_CASE(48) DCX_CASE(54)
-        DCX_CASE(60) DCX_CASE(64) DCX_CASE(72) DCX_CASE(84) DCX_CASE(96)
-#undef DCX_CASE
-    default: return nullptr;
-    }
-}
 }  // namespace
 
 size_t dcx_motion_cost_work_bytes(const dcx_model* m, int64_t E, int32_t max_samples) {
@@ -2151,134 +2137,66 @@ int dcx_motion_cost_ex(const dcx_model* m, const float* qa, const float* qb, int
                        const float* margin, float weight, float* cost, float* grad_a, float* grad_b, int32_t* n_samples, void* work,
                        size_t work_bytes, uint64_t wrap_mask, void* stream) {
     // every argument is checked before anything touches the device
-    if (!m) return fail(DCX_ERR_INVALID, "model is NULL");
-    if (!opt) return fail(DCX_ERR_INVALID, "motion cost options are NULL");
+    const MotionCheck chk{"motion cost"};
+    if (int rc = chk.nulls(m, opt, "motion cost")) return rc;
     if (E < 0) return fail(DCX_ERR_INVALID, "E < 0");
     if (E > 0 && (!qa || !qb || !cost || !grad_a || !grad_b || !work))
         return fail(DCX_ERR_INVALID, "qa / qb / cost / grad_a / grad_b / work is NULL");
-    const bool by_res = opt->res > 0, by_step = opt->max_step > 0.f;
-    if (opt->res < 0 || !(opt->max_step >= 0.f) || by_res == by_step)
-        return fail(DCX_ERR_INVALID, "motion cost needs exactly one sampling rule: res > 0 or max_step > 0 (the other 0)");
-    if (opt->max_samples < 1) return fail(DCX_ERR_INVALID, "motion cost needs max_samples >= 1");
+    const MotionSampling rule{opt->res, opt->max_step, opt->max_samples};
+    if (int rc = chk.sampling(rule)) return rc;
     if (opt->open_end != 0 && opt->open_end != 1) return fail(DCX_ERR_INVALID, "motion cost: open_end must be 0 or 1");
     if (opt->reserved[0] || opt->reserved[1] || opt->reserved[2] || opt->reserved[3])
         return fail(DCX_ERR_INVALID, "motion cost: reserved fields must be 0");
-    if (wrap_mask != 0 && m->fk.dof < 64 && (wrap_mask >> m->fk.dof) != 0)   // (mask 0, the plain call: the model is not read here)
-        return fail(DCX_ERR_INVALID, "motion cost: wrap_mask has a bit at or above dof");
+    if (int rc = chk.mask(m, wrap_mask)) return rc;
     if (E > 0 && work_bytes < motion_cost_work(m, E, opt->max_samples).total)
         return fail(DCX_ERR_INVALID, "motion cost workspace is smaller than dcx_motion_cost_work_bytes");
-    if (E > INT32_MAX) return fail(DCX_ERR_UNSUPPORTED, "motion cost: more than 2^31 - 1 edges");
+    if (int rc = chk.edges(E)) return rc;
     if (E == 0) return DCX_OK;
-    const int64_t tiles_max = (E * (int64_t)opt->max_samples + 63) / 64;
-    if (tiles_max > 0x7fffffffLL) return fail(DCX_ERR_UNSUPPORTED, "motion cost: E * max_samples too large for one launch");
+    int64_t tiles_max;
+    if (int rc = chk.tiles(E, opt->max_samples, tiles_max)) return rc;
     motion_cost_fn launch = motion_cost_for(m->Dt);
     if (!launch) return fail(DCX_ERR_UNSUPPORTED, "motion cost: no kernel for this feature width");
     if (int rc = set_device(m->device)) return rc;
     hipStream_t st = (hipStream_t)stream;
     const MotionCostWork w = motion_cost_work(m, E, opt->max_samples);
     char* base = (char*)work;
-    const int d_fk = m->fk.n_points * m->fk.point_dim;
-    // geometry as dcx_score_grad picks it for the upper bound of the samples (the count itself is on the device only); a split
-    // launch keeps its counters and partial rows in the caller's work, so it is bounded like dcx_check_motions'
+    const MotionSlots slots{(int64_t*)(base + w.offs), (float*)(base + w.frac), (unsigned int*)(base + w.counters), (float*)(base + w.partial)};
+    int32_t* status = (int32_t*)(base + w.status);
+    // geometry as dcx_score_grad picks it for the upper bound of the samples, Dt + Cc accumulators per lane; the split launch is
+    // bounded like dcx_check_motions'
     const int acc = m->Dt + m->Cc;
-    const int64_t b_max = std::min<int64_t>(tiles_max, (int64_t)1 << 30) * 64;
-    Geometry g = pick_geometry(m, b_max, acc, true);
-    if (g.ys > 1 && (tiles_max > kMotionSplitTiles || tiles_max * g.ys > kMotionSplitRows)) g = pick_geometry(m, b_max, acc, false);
-    MotionPrepArgs p{};
-    p.qa = qa;
-    p.qb = qb;
-    p.E = E;
-    p.dof = m->fk.dof;
-    p.res = opt->res;
-    p.max_samples = opt->max_samples;
-    p.max_step = opt->max_step;
-    p.offs = (int64_t*)(base + w.offs);
-    p.frac = (float*)(base + w.frac);
-    p.first_hit = (int32_t*)(base + w.status);
-    p.n_samples = n_samples;
-    p.counters = g.ys > 1 ? (unsigned int*)(base + w.counters) : nullptr;
-    p.n_counters = g.ys > 1 ? (int32_t)tiles_max : 0;
-    p.open_end = opt->max_step > 0.f ? opt->open_end : 0;
-    p.wrap_mask = wrap_mask;
-    hipError_t e = launch_motion_prep(p, st);
-    if (e != hipSuccess) return fail_hip(e, "motion cost prep launch");
-
     MotionCostArgs a{};
-    ScoreArgs& sa = a.sc;
-    sa.rows = m->rows_dev;
-    set_fk_walk(m, sa);
-    sa.B = 0;
-    sa.S = m->S_active;
-    sa.ys = g.ys;
-    sa.s_super = (m->S_active + g.ys - 1) / g.ys;
-    sa.s_chunk = (sa.s_super + g.nw - 1) / g.nw;
-    // the rows and slices as run_score picks them (per pass: the score pass and the gradient sweeps differ in their shares)
-    const bool xf_able = knobs().xf != 0 && xf_applies(m->Dt, m->Cc, m->kf) && m->rows_xf_dev != nullptr &&
-                         (m->kf != KF_RQ2 || m->xf_rq_ok || knobs().xf >= 2);
-    if (!xf_able && m->rows_p2_dev != nullptr && p2_applies(m->Dt, m->Cc, m->kf)) {
-        sa.rows = m->rows_p2_dev;
-        sa.s_super = (sa.s_super + 1) & ~1;
-        sa.s_chunk = ((sa.s_super + g.nw - 1) / g.nw + 1) & ~1;
-    }
-    sa.red_slots = g.red_slots;
-    sa.dof = m->fk.dof;
-    sa.d_fk = d_fk;
-    sa.frame_floats = m->frame_floats;
-    sa.kind = m->kind;
-    sa.c_out = m->C;
-    sa.one_hot = -1;
-    sa.nz = 1;
-    sa.kp0 = m->kp0_sweep;
-    sa.kp1 = m->kp1;
-    sa.xf = xf_able ? 1 : 0;
-    if (sa.xf) xf_rows(m, sa);
-    sa.jt_rows = (sa.fkk == 2 && g.nw >= 2 * m->dh.n_chains && m->dh.n_chains <= 2 && m->dh.end0 <= kDhUnroll &&
-                  m->dh.n_steps - m->dh.end0 <= kDhUnroll && knobs().jt_waves != 0) ? 1 : 0;
-    sa.jt_waves = 0;   // J^T on wave 0 (fk_vjp_sel)
-    if (g.ys > 1) {
-        sa.partial = (float*)(base + w.partial);
-        sa.tile_done = (unsigned int*)(base + w.counters);
-    }
-    a.qa = qa;
-    a.qb = qb;
-    a.offs = p.offs;
-    a.frac = p.frac;
+    const MotionSweepPlan plan = motion_sweep_plan(m, tiles_max, acc, slots, a.sc);
+    const Geometry& g = plan.g;
+    a.open_end = opt->max_step > 0.f ? opt->open_end : 0;
+    hipError_t e = motion_prep(m, qa, qb, E, rule, a.open_end, wrap_mask, slots, status, n_samples, g.ys, tiles_max, a, st);
+    if (e != hipSuccess) return fail_hip(e, "motion cost prep launch");
     a.margin = margin;
     a.h = (float*)(base + w.h);
     a.dq = (float*)(base + w.dq);
     a.scores = m->C > 1 ? (float*)(base + w.scores) : nullptr;
     a.tile_on = m->C > 1 ? (int32_t*)(base + w.tile_on) : nullptr;
-    a.E = E;
     a.weight = weight;
-    a.res = opt->res;
-    a.open_end = p.open_end;
-    a.wrap_mask = wrap_mask;
-    auto skew_for = [&](bool score_only) {
-        return (g.nw == 16 && (sa.s_chunk >= 24 || knobs().skew > 0)) ? skew_rule(m->Cc, score_only)
-             : (g.nw == 8 && (sa.s_chunk >= 24 || knobs().skew8 > 0)) ? skew8_rule(score_only) : 0;
-    };
-    auto lds_for = [&](int acc_floats) {
-        return sizeof(float) * (((size_t)lds_plan(sa.dof, d_fk, m->frame_floats, g.nw > 1 ? g.red_slots : 0, acc_floats, true).total +
-                                 m->prog_floats + 3) & ~(size_t)3) + sizeof(float) * kMotionCostLdsFloats;
-    };
+    // per pass: the score pass and the gradient sweeps differ in their wave-group shares and in their LDS
     if (m->C == 1) {
-        sa.s_skew = skew_for(false);
-        e = launch(m->kf, m->Cc, MODE_GRAD_ROW, g.nw, lds_for(acc), tiles_max, a, st);
+        a.sc.s_skew = motion_skew(m, g, a.sc, false);
+        e = launch(m->kf, m->Cc, MODE_GRAD_ROW, g.nw, plan.lds, tiles_max, a, st);
     } else {
-        sa.s_skew = skew_for(true);
-        e = launch(m->kf, m->Cc, MODE_SCORE, g.nw, lds_for(m->Cc), tiles_max, a, st);
+        a.sc.s_skew = motion_skew(m, g, a.sc, true);
+        // (plan.lds is sized for Dt + Cc accumulators; the score pass folds Cc and its kernel carves its LDS for Cc)
+        e = launch(m->kf, m->Cc, MODE_SCORE, g.nw, motion_lds_bytes(m, g, m->Cc), tiles_max, a, st);
         if (e == hipSuccess) {
-            sa.s_skew = skew_for(false);
-            e = launch(m->kf, m->Cc, MODE_GRAD_UP, g.nw, lds_for(acc), tiles_max, a, st);
+            a.sc.s_skew = motion_skew(m, g, a.sc, false);
+            e = launch(m->kf, m->Cc, MODE_GRAD_UP, g.nw, plan.lds, tiles_max, a, st);
         }
     }
     if (e != hipSuccess) return fail_hip(e, "motion cost kernel launch");
     MotionReduceArgs r{};
     r.qa = qa;
     r.qb = qb;
-    r.offs = p.offs;
-    r.frac = p.frac;
-    r.status = p.first_hit;
+    r.offs = slots.offs;
+    r.frac = slots.frac;
+    r.status = status;
     r.h = a.h;
     r.dq = a.dq;
     r.cost = cost;
@@ -2287,7 +2205,7 @@ int dcx_motion_cost_ex(const dcx_model* m, const float* qa, const float* qb, int
     r.E = E;
     r.dof = m->fk.dof;
     r.res = opt->res;
-    r.open_end = p.open_end;
+    r.open_end = a.open_end;
     r.weight = weight;
     r.wrap_mask = wrap_mask;
     e = launch_motion_cost_reduce(r, st);

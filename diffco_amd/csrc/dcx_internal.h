@@ -33,38 +33,28 @@ inline int row_stride(int Dt, int C) {   // RowLayout<Dt, C>::RS
     return (Dt + C + (C > 1 ? 1 : 0) + 1 + al - 1) / al * al;
 }
 
+// the compiled widths once more, as a list to expand: DCX_FOREACH_WIDTH(X) is X(2) X(4) ... X(96) (kTemplateD's values), for the
+// per-width entry points' declarations and the switches that pick one
+#define DCX_FOREACH_WIDTH(X) \
+    X(2) X(4) X(6) X(8) X(12) X(16) X(18) X(21) X(24) X(27) X(30) X(32) X(36) X(42) X(48) X(54) X(60) X(64) X(72) X(84) X(96)
+
 // one entry point per compiled D (score_inst.hip, built once per width)
 typedef hipError_t (*launch_fn)(int kf, int cc, int mode, int nw, size_t lds_bytes, int64_t n_blocks,
                                 const ScoreArgs& args, hipStream_t stream);
 #define DCX_DECLARE_LAUNCH(D) \
     hipError_t launch_score_D##D(int, int, int, int, size_t, int64_t, const ScoreArgs&, hipStream_t);
-DCX_DECLARE_LAUNCH(2)  DCX_DECLARE_LAUNCH(4)  DCX_DECLARE_LAUNCH(6)  DCX_DECLARE_LAUNCH(8)
-DCX_DECLARE_LAUNCH(12) DCX_DECLARE_LAUNCH(16) DCX_DECLARE_LAUNCH(18) DCX_DECLARE_LAUNCH(21)
-DCX_DECLARE_LAUNCH(24) DCX_DECLARE_LAUNCH(27) DCX_DECLARE_LAUNCH(30) DCX_DECLARE_LAUNCH(32)
-DCX_DECLARE_LAUNCH(36) DCX_DECLARE_LAUNCH(42) DCX_DECLARE_LAUNCH(48) DCX_DECLARE_LAUNCH(54)
-DCX_DECLARE_LAUNCH(60) DCX_DECLARE_LAUNCH(64) DCX_DECLARE_LAUNCH(72) DCX_DECLARE_LAUNCH(84)
-DCX_DECLARE_LAUNCH(96)
+DCX_FOREACH_WIDTH(DCX_DECLARE_LAUNCH)
 #undef DCX_DECLARE_LAUNCH
 // the one-sweep Jacobian (jac_kernel.h), one entry point per compiled D; hipErrorNotSupported where it is not instantiated
 typedef hipError_t (*jac_fn)(int kf, int cc, int nw, size_t lds_bytes, int64_t n_blocks, const ScoreArgs& args, hipStream_t stream);
 #define DCX_DECLARE_JAC(D) hipError_t launch_jac_D##D(int, int, int, size_t, int64_t, const ScoreArgs&, hipStream_t);
-DCX_DECLARE_JAC(2)  DCX_DECLARE_JAC(4)  DCX_DECLARE_JAC(6)  DCX_DECLARE_JAC(8)
-DCX_DECLARE_JAC(12) DCX_DECLARE_JAC(16) DCX_DECLARE_JAC(18) DCX_DECLARE_JAC(21)
-DCX_DECLARE_JAC(24) DCX_DECLARE_JAC(27) DCX_DECLARE_JAC(30) DCX_DECLARE_JAC(32)
-DCX_DECLARE_JAC(36) DCX_DECLARE_JAC(42) DCX_DECLARE_JAC(48) DCX_DECLARE_JAC(54)
-DCX_DECLARE_JAC(60) DCX_DECLARE_JAC(64) DCX_DECLARE_JAC(72) DCX_DECLARE_JAC(84)
-DCX_DECLARE_JAC(96)
+DCX_FOREACH_WIDTH(DCX_DECLARE_JAC)
 #undef DCX_DECLARE_JAC
 // config #5 as one persistent launch (traj_fused.h), one entry point per compiled D as well
 // (cc > 1: the two-sweep form for several classes, compiled up to D = 24 for RQKernel(p = 2) / Polyharmonic(1); hipErrorNotSupported elsewhere)
 typedef hipError_t (*traj_fused_fn)(int kf, int cc, int nw, size_t lds_bytes, int n_paths, const TrajFusedArgs& args, hipStream_t stream);
 #define DCX_DECLARE_TRAJ(D) hipError_t launch_traj_fused_D##D(int, int, int, size_t, int, const TrajFusedArgs&, hipStream_t);
-DCX_DECLARE_TRAJ(2)  DCX_DECLARE_TRAJ(4)  DCX_DECLARE_TRAJ(6)  DCX_DECLARE_TRAJ(8)
-DCX_DECLARE_TRAJ(12) DCX_DECLARE_TRAJ(16) DCX_DECLARE_TRAJ(18) DCX_DECLARE_TRAJ(21)
-DCX_DECLARE_TRAJ(24) DCX_DECLARE_TRAJ(27) DCX_DECLARE_TRAJ(30) DCX_DECLARE_TRAJ(32)
-DCX_DECLARE_TRAJ(36) DCX_DECLARE_TRAJ(42) DCX_DECLARE_TRAJ(48) DCX_DECLARE_TRAJ(54)
-DCX_DECLARE_TRAJ(60) DCX_DECLARE_TRAJ(64) DCX_DECLARE_TRAJ(72) DCX_DECLARE_TRAJ(84)
-DCX_DECLARE_TRAJ(96)
+DCX_FOREACH_WIDTH(DCX_DECLARE_TRAJ)
 #undef DCX_DECLARE_TRAJ
 
 // aux_kernels.hip

@@ -1,10 +1,10 @@
-// motion_prep.hip — the first launches of dcx_check_motions and dcx_motion_cost (motion_kernel.h): per edge its sample count under the call's rule,
+// motion_prep.hip — the first launches of the motion calls (motion_tile.h): per edge its sample count under the call's rule,
 // the step fraction of the max_step rule, first_hit set to -1 (or -2 for an edge over max_samples), n_samples (one thread per
 // edge over the whole chip), then the exclusive scan of the counts into the work list's offsets (one workgroup: chunks of 1024
 // counts, each scanned by wave shuffles and one pass over the 16 wave totals) and the split launch's arrival counters zeroed.
 // (The first form did both in ONE workgroup, each thread a contiguous run of edges: 420 us of a 2.9 ms call at E = 65536.)
 #include <hip/hip_runtime.h>
-#include "motion_kernel.h"
+#include "motion_tile.h"
 #include "wrap_device.h"
 
 namespace dcx {

@@ -3,10 +3,8 @@
 // with the smallest k that attains it, the smallest c that attains v_k there and, on request, the gradient of worst[e] with
 // respect to qa[e] and qb[e] through that sample.
 //
-// The work list, the tile lookup (motion_cost_kernel.h motion_tile_lookup), the interpolation (motion_kernel.h motion_coord)
-// and the sweep are dcx_check_motions': the same rows, slices, wave-group shares and split launches for the same
-// (model, E, max_samples), so a sample's class scores are the bits the check compares.  Two differences from motion_kernel:
-// no early exit (every tile sweeps), and the answer step.
+// The tiles are scored as dcx_check_motions scores them (motion_tile.h: the same bits for the same (model, E, max_samples));
+// no early exit, every tile sweeps.
 //
 // Answer step (wave 0, or the last block of a split tile: where the scores are final).  Each live lane packs
 //     key = orderable(v) << 32 | (0xffffff - k) << 8 | (0xff - c)
@@ -19,9 +17,8 @@
 // motion_worst_finish.hip decodes the keys (one thread per edge), stages the worst sample and a one-hot upstream row for the
 // library's own score+gradient launch on those E points, and chains that gradient to the endpoints.
 #pragma once
-#include <hip/hip_runtime.h>
-#include <stdint.h>
-#include "motion_cost_kernel.h"
+#include "dcx_internal.h"
+#include "motion_tile.h"
 
 namespace dcx {
 
@@ -32,29 +29,16 @@ constexpr int kMotionWorstSampleLimit = (1 << 24) - 1;
 static_assert(10000 <= kMotionWorstSampleLimit, "documentation only: the Python layer's default max_samples fits the sample field");
 static_assert(DCX_MAX_C <= 256, "the key holds the class in 8 bits");
 
-struct MotionWorstArgs {
-    ScoreArgs sc;             // the sweep's arguments (first: reload_kernargs reads them at offset 0), as MotionArgs::sc
-    const float* qa;          // [E][dof]
-    const float* qb;          // [E][dof]
-    const int64_t* offs;      // [E + 1] exclusive scan of the sample counts (motion_prep.hip)
-    const float* frac;        // [E] max_step rule: (1 / L) * max_step
+struct MotionWorstArgs : MotionEdgeArgs {
     unsigned long long* keys; // [E] packed (value, sample, class) maxima; 0 = no sample yet
     const float* margin;      // [c_out] or null (0)
-    int64_t E;
-    int32_t res;              // > 0: the res rule; 0: the closed max_step rule
-    uint64_t wrap_mask;       // as MotionArgs::wrap_mask
 };
 
 // one entry point per compiled width (motion_worst_inst.hip)
 typedef hipError_t (*motion_worst_fn)(int kf, int cc, int nw, size_t lds, int64_t n_blocks, const MotionWorstArgs& a, hipStream_t stream);
 #define DCX_DECLARE_MOTION_WORST(D) \
     hipError_t launch_motion_worst_D##D(int, int, int, size_t, int64_t, const MotionWorstArgs&, hipStream_t);
-DCX_DECLARE_MOTION_WORST(2)  DCX_DECLARE_MOTION_WORST(4)  DCX_DECLARE_MOTION_WORST(6)  DCX_DECLARE_MOTION_WORST(8)
-DCX_DECLARE_MOTION_WORST(12) DCX_DECLARE_MOTION_WORST(16) DCX_DECLARE_MOTION_WORST(18) DCX_DECLARE_MOTION_WORST(21)
-DCX_DECLARE_MOTION_WORST(24) DCX_DECLARE_MOTION_WORST(27) DCX_DECLARE_MOTION_WORST(30) DCX_DECLARE_MOTION_WORST(32)
-DCX_DECLARE_MOTION_WORST(36) DCX_DECLARE_MOTION_WORST(42) DCX_DECLARE_MOTION_WORST(48) DCX_DECLARE_MOTION_WORST(54)
-DCX_DECLARE_MOTION_WORST(60) DCX_DECLARE_MOTION_WORST(64) DCX_DECLARE_MOTION_WORST(72) DCX_DECLARE_MOTION_WORST(84)
-DCX_DECLARE_MOTION_WORST(96)
+DCX_FOREACH_WIDTH(DCX_DECLARE_MOTION_WORST)
 #undef DCX_DECLARE_MOTION_WORST
 
 // the finish (motion_worst_finish.hip): keys decoded into the answers; with gradients, the worst samples and their one-hot
@@ -86,91 +70,43 @@ __host__ __device__ inline uint32_t motion_worst_orderable(uint32_t bits) { retu
 __host__ __device__ inline uint32_t motion_worst_unorder(uint32_t o) { return (o & 0x80000000u) ? (o & 0x7fffffffu) : ~o; }
 
 #ifdef __HIPCC__
-// one configuration per lane: motion_kernel without the early exit, then the packed maximum per edge segment.
-// LDS: lds_plan(...).total + prog_floats rounded to 4, then kMotionLdsFloats (mo_off), as motion_kernel.
-template <int D, int KF, int CC, int MAXT, int XF = 0 /* 1: the expanded form, 2: its spare-slot form (score_kernel.h sweep_rows SP) */>
+template <int D, int KF, int CC, int MAXT, int XF = 0 /* motion_tile.h motion_sweep */>
 __global__ __launch_bounds__(MAXT, sweep_min_waves(D, CC, KF)) void motion_worst_kernel(const MotionWorstArgs m, int32_t mo_off) {
     extern __shared__ __attribute__((aligned(16))) float smem[];
     const ScoreArgs& a = m.sc;
-    constexpr int ACC = CC;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int nw = blockDim.x >> 6;
-    const int dof = a.dof;
-    const LdsPlan lp = lds_plan(dof, a.d_fk, a.frame_floats, nw > 1 ? a.red_slots : 0, ACC, true);
-    float* sQ = smem + lp.q;
-    float* sX = smem + lp.x;
-    float* sF = smem + lp.f;
-    float* sRed = smem + lp.red;
-    int64_t* sEnd = reinterpret_cast<int64_t*>(smem + mo_off);   // [64]
-    int32_t* sEdge = reinterpret_cast<int32_t*>(smem + mo_off + 128);
-    int32_t* sK = sEdge + 64;
-    int32_t* sN = sEdge + 128;
-
-    const int64_t E = m.E;
-    const int64_t total = m.offs[E];
+    const LdsPlan lp = lds_plan(a.dof, a.d_fk, a.frame_floats, nw > 1 ? a.red_slots : 0, CC, true);
+    const MotionTile t = motion_tile_view(smem, lp, mo_off);
+    const int64_t total = m.offs[m.E];
     const int64_t tile = blockIdx.x;
-    if (tile * 64 >= total) return;   // past the end of the work list (the grid is sized from E * max_samples): before any staging
+    if (tile * 64 >= total) return;   // past the end of the work list: before any staging
     const FkWalk fw = fk_stage_sel(a.fkk, a.fk, a.fk_dwords, a.dh, smem + lp.fk, threadIdx.x, blockDim.x);
-    const bool split = a.partial != nullptr;
+    const bool split = a.partial != nullptr;   // (read before the sweep, as the fold and hand-over below were written)
     const int64_t base = tile * 64;
     const int nb = (int)((total - base) < 64 ? (total - base) : 64);
-    if (wave == 0) motion_tile_lookup(m.offs, E, base, nb, sEnd, sEdge, sK, sN);
+    if (wave == 0) motion_tile_lookup(m.offs, m.E, base, nb, t);
     __syncthreads();
-    float sc[CC];
+    float sc[CC], up[CC], x[D], gx[D];
 #pragma unroll
-    for (int c = 0; c < CC; ++c) sc[c] = 0.0f;
-    {
-        // ---- the rows of sQ: this tile's 64 samples, interpolated from their edges (motion_kernel's prologue) ----
-        for (int i = threadIdx.x; i < 64 * dof; i += blockDim.x) {
-            const int l = i / dof, j = i - l * dof;
-            const int64_t e = sEdge[l];
-            const int k = sK[l];
-            const float qa = m.qa[e * dof + j], qb = m.qb[e * dof + j];
-            sQ[i] = motion_coord(qa, qb, k, m.res, k == sN[l] - 1, m.frac + e, (m.wrap_mask >> j) & 1ull);
-        }
-        __syncthreads();
-        const int lane = threadIdx.x & 63;
-        fk_trig_sel(fw, a.dh, sQ + lane * dof, sF + lane, wave, nw);
-        __syncthreads();
-        if (a.fkk == 2 && a.jt_rows) dh2_chain_rows_sel(fw.dh, a.dh, sX + lane, sF + lane, wave);   // (score_kernel's two forms)
-        else if (wave == 0) fk_chain_sel(fw, a.dh, sQ + lane * dof, sX + lane, sF + lane);
-        __syncthreads();
-        float x[D];
-        if (a.d_fk == D) {
-#pragma unroll
-            for (int k = 0; k < D; ++k) x[k] = sX[k * 64 + lane];
-        } else {
-#pragma unroll
-            for (int k = 0; k < D; ++k) x[k] = (k < a.d_fk) ? sX[k * 64 + lane] : 0.0f;
-        }
-        if constexpr (XF != 0) {   // the expanded form's centred features (score_kernel.h)
-            cfloat_ptr cen = (cfloat_ptr)(uintptr_t)a.centre;
-#pragma unroll
-            for (int k = 0; k < D; ++k) x[k] -= cen[k];
-        }
-        if (nw > 1) __syncthreads();   // X is dead: the partial sums reuse its LDS
-        const int ybase = blockIdx.y * a.s_super;
-        const int yend = (ybase + a.s_super < a.S) ? (ybase + a.s_super) : a.S;
-        int j0, j1;
-        wave_slice(wave, nw, a.s_chunk, a.s_skew, ybase, yend, j0, j1);
-        float up[CC];
-        float gx[D];
-#pragma unroll
-        for (int c = 0; c < CC; ++c) up[c] = 0.0f;
-        sweep_rows<D, KF, CC, MODE_SCORE, XF != 0, 0, false, XF == 2>(a, x, up, j0, j1, sc, gx);
-    }
-    // ---- epilogue: the block's partial sums meet on wave 0 in motion_kernel's order (the same bits as the check's scores) ----
+    for (int c = 0; c < CC; ++c) sc[c] = up[c] = 0.0f;
+    motion_tile_features<D, XF>(m, t, fw, false, wave, nw, x);
+    motion_sweep<D, KF, CC, MODE_SCORE, XF>(a, x, up, wave, nw, sc, gx);
+    // The fold and the hand-over stand here as text, not as motion_fold_block<CC, 0, false> / motion_split_handover<CC, 0>
+    // (motion_tile.h), whose bodies they repeat word for word: with the two as inlined calls the compiler schedules this
+    // kernel's sweep in another order, 1.7 - 2.1 % slower at E = 65536 (profiles/r18_motion_refactor_timing.txt).
     const auto& b = reload_kernargs<MotionWorstArgs>();
     const int lane = fresh_lane();
+    float* sRed = t.sRed;
     if (nw > 1 && b.sc.red_slots == nw) {
-        float* mine = sRed + (size_t)wave * ACC * 64 + lane;
+        float* mine = sRed + (size_t)wave * CC * 64 + lane;
 #pragma unroll
         for (int c = 0; c < CC; ++c) mine[c * 64] = sc[c];
         __syncthreads();
         if (wave == 0) {
             for (int w = 1; w < nw; ++w)
 #pragma unroll
-                for (int c = 0; c < CC; ++c) sc[c] += sRed[((size_t)w * ACC + c) * 64 + lane];
+                for (int c = 0; c < CC; ++c) sc[c] += sRed[((size_t)w * CC + c) * 64 + lane];
         }
     } else if (nw > 1) {
         for (int w = 1; w < nw; ++w) {
@@ -188,9 +124,7 @@ __global__ __launch_bounds__(MAXT, sweep_min_waves(D, CC, KF)) void motion_worst
     }
     if (wave != 0) return;
     if (split) {
-        // motion_kernel's in-launch hand-over: publish write-through, drain, count; the last block of the tile to arrive adds
-        // the ys rows in the order y = 0, 1, ... and answers for the tile
-        float* out = b.sc.partial + (tile * b.sc.ys + blockIdx.y) * ACC * 64 + lane;
+        float* out = b.sc.partial + (tile * b.sc.ys + blockIdx.y) * CC * 64 + lane;
 #pragma unroll
         for (int c = 0; c < CC; ++c) __hip_atomic_store(out + c * 64, sc[c], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -200,12 +134,12 @@ __global__ __launch_bounds__(MAXT, sweep_min_waves(D, CC, KF)) void motion_worst
         if (arrived != (unsigned int)b.sc.ys - 1u) return;
         if (lane == 0) b.sc.tile_done[tile * kCounterStride] = 0u;   // ready for the next launch on this work buffer
         asm volatile("" ::: "memory");
-        const float* part = b.sc.partial + tile * b.sc.ys * ACC * 64 + lane;
+        const float* part = b.sc.partial + tile * b.sc.ys * CC * 64 + lane;
 #pragma unroll
         for (int c = 0; c < CC; ++c) sc[c] = 0.0f;
         for (int y = 0; y < b.sc.ys; ++y)
 #pragma unroll
-            for (int c = 0; c < CC; ++c) sc[c] += __hip_atomic_load(part + ((size_t)y * ACC + c) * 64, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            for (int c = 0; c < CC; ++c) sc[c] += __hip_atomic_load(part + ((size_t)y * CC + c) * 64, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     }
     // ---- the answer: v = max_c (score_c - margin_c) and the first class that attains it (a NaN difference never wins: it
     // counts as -inf); the key, its maximum over the lane's edge segment, one atomic per segment ----
@@ -220,22 +154,21 @@ __global__ __launch_bounds__(MAXT, sweep_min_waves(D, CC, KF)) void motion_worst
         }
     }
     v += 0.0f;   // -0 becomes +0: equal values, equal keys
-    const int k = sK[lane];
+    const int k = t.sK[lane];
     const bool on = lane < nb;   // (the lanes behind the work list's end repeat its last sample)
     unsigned long long key = 0ull;
     if (on)
         key = ((unsigned long long)motion_worst_orderable(__float_as_uint(v)) << 32) |
               ((unsigned long long)(0xffffffu - (unsigned int)k) << 8) | (unsigned long long)(0xffu - (unsigned int)cbest);
-    const uint64_t starts = __builtin_amdgcn_ballot_w64(k == 0 || lane == 0);
-    const uint64_t upto = (lane == 63) ? ~0ull : ((1ull << (lane + 1)) - 1ull);
-    const int seg0 = 63 - __clzll(starts & upto);              // first lane of this lane's edge in the wave
+    uint64_t starts;
+    const int seg0 = motion_segment_start(k, lane, starts);
 #pragma unroll
     for (int d = 1; d < 64; d <<= 1) {   // inclusive max-scan inside the segment
         const unsigned long long o = __shfl_up(key, d, 64);
         if (lane - d >= seg0 && o > key) key = o;
     }
     const bool seg_last = lane == 63 || ((starts >> (lane + 1)) & 1ull) != 0;
-    if (seg_last && key != 0ull) atomicMax(b.keys + sEdge[lane], key);
+    if (seg_last && key != 0ull) atomicMax(b.keys + t.sEdge[lane], key);
 }
 #endif  // __HIPCC__
 

@@ -13,7 +13,7 @@
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include "rrt_kernel.h"
-#include "motion_kernel.h"
+#include "motion_tile.h"
 #include "wrap_device.h"
 
 namespace dcx {

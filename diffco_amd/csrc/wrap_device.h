@@ -1,5 +1,5 @@
 // wrap_device.h — angles on the circle, shared by the escape loop (traj_kernels.hip) and the motion calls (motion_prep.hip,
-// motion_kernel.h, motion_cost_kernel.h, motion_cost_reduce.hip): one definition, one rounding (include/dcx.h pins it).
+// motion_tile.h, motion_cost_reduce.hip): one definition, one rounding (include/dcx.h pins it).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>

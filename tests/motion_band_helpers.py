@@ -111,7 +111,7 @@ def _fma32(a, b, c):
 
 
 def listed_points32(qa, qb, mask, edges, samples, res=None, max_step=None):
-    """the configurations of the samples (edges[i], samples[i]) as the device forms them (motion_kernel.h motion_coord), fp32:
+    """the configurations of the samples (edges[i], samples[i]) as the device forms them (motion_tile.h motion_coord), fp32:
     masked coordinates operation by operation (motion_wrap_helpers.motion_samples_wrapped, the wrap tests' restatement);
     unmasked coordinates with the last product and sum of helpers.motion_samples' expression fused, as the compiler contracts
     them: qa + d (k / res) -> fma(d, k / res, qa), qa + k (d frac) -> fma(k, d frac, qa); the closed rule's target is qb."""

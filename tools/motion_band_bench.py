@@ -1,7 +1,8 @@
 """Hybrid motion checks on the headline model (Baxter DH-7, Polyharmonic(1,1), S = 2000): ScoreModel.motion_band_raw (a fixed
 list capacity: nothing read back) against dcx_motion_worst without gradients - the same sweep work on the same plan, with the
-other answer step - from this library and, with --parent-lib, from another build of the library (the parent commit's,
-tools/build_variant.sh) timed in a fresh child process per round; against dcx_check_motions with the early exit switched off;
+other answer step - from this library; with --parent-lib, both calls also from another build of the library (the parent
+commit's, tools/build_variant.sh), timed in a fresh child process per round (tools/motion_bench.py parent_round; a build
+that predates dcx_motion_band times dcx_motion_worst alone); against dcx_check_motions with the early exit switched off;
 and against the host composition (host_motion_band over ScoreModel.score_raw: the points built in torch, one score launch, the
 masks, a segment reduction and `nonzero`).  tools/motion_bench.py's edges: 8 - 64 samples (max_step rule, max_samples = 64),
 two sets: free (a band above every score: nothing listed) and cluttered (lo / hi at the 20th / 40th percentile of the sample
@@ -13,9 +14,9 @@ One JSON line per (E, set) on stdout: microseconds per call (CUDA events around 
 interleaved three times (median of the three medians; the three medians of motion_worst are printed as its run-to-run spread).
 """
 import argparse
+import ctypes
 import json
 import os
-import subprocess
 import sys
 
 import torch
@@ -39,21 +40,26 @@ def edges(E, lo, hi, dev):
 
 
 def child(args):
-    """one round of dcx_motion_worst without gradients on the library DCX_LIB names: a JSON line of medians per (E, margin)"""
+    """--child E:lo:hi: one round of dcx_motion_worst without gradients (margin lo) and of dcx_motion_band on the library DCX_LIB
+    names: a JSON line {leg: median microseconds}"""
     import bench
     from motion_bench import timed
     from diffco_amd import _lib
-    for name in [k for k in _lib.SYMBOLS if k.startswith("dcx_motion_band")]:   # (the other build may predate the call)
-        del _lib.SYMBOLS[name]
+    has_band = hasattr(ctypes.CDLL(_lib.LIB_PATH), "dcx_motion_band")
+    if not has_band:   # (the other build predates the call)
+        for name in [k for k in _lib.SYMBOLS if k.startswith("dcx_motion_band")]:
+            del _lib.SYMBOLS[name]
     _lib.require_gpu()
     dev = torch.device("cuda", 0)
     w = bench.make_workload("headline", 1024, dev)
-    m, lo, hi = w["model"], w["lo"].to(dev), w["hi"].to(dev)
-    out = {}
-    for spec in args.child:
-        E, margin = spec.split(":")
-        qa, qb, _ = edges(int(E), lo, hi, dev)
-        out[spec] = timed(lambda: m.motion_worst_raw(qa, qb, max_step=STEP, margin=float(margin), max_samples=64), args.iters)
+    m = w["model"]
+    E, b_lo, b_hi = args.child.split(":")
+    qa, qb, _ = edges(int(E), w["lo"].to(dev), w["hi"].to(dev), dev)
+    kw = dict(max_step=STEP, max_samples=64)
+    out = {"motion_worst_us": timed(lambda: m.motion_worst_raw(qa, qb, margin=float(b_lo), **kw), args.iters)}
+    if has_band:
+        cap = int(m.motion_worst_raw(qa, qb, **kw)[3].sum())
+        out["motion_band_us"] = timed(lambda: m.motion_band_raw(qa, qb, float(b_lo), float(b_hi), unc_cap=cap, **kw), args.iters)
     print(json.dumps(out), flush=True)
 
 
@@ -61,13 +67,13 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--edges", type=int, nargs="+", default=[4096, 65536])
     ap.add_argument("--iters", type=int, default=50)
-    ap.add_argument("--parent-lib", default=None, help="another build of libdcx.so whose dcx_motion_worst is timed in child processes")
-    ap.add_argument("--child", nargs="+", default=None, help=argparse.SUPPRESS)
+    ap.add_argument("--parent-lib", default=None, help="another build of libdcx.so whose dcx_motion_worst and dcx_motion_band are timed in child processes")
+    ap.add_argument("--child", default=None, help=argparse.SUPPRESS)
     args = ap.parse_args()
     if args.child:
         return child(args)
     import bench
-    from motion_bench import timed
+    from motion_bench import add_parent_rounds, parent_round, timed
     from diffco_amd import _lib
     from diffco_amd._perceptron import host_motion_band
     lib = _lib.require_gpu()
@@ -91,11 +97,8 @@ def main():
                        verdicts=[int((r["verdict"] == v).sum()) for v in (0, 1, 2)])
             band, band_noq, worst, check, parent = [], [], [], [], []
             for _ in range(3):
-                if args.parent_lib:   # a fresh process on the other library: this one keeps its own
-                    env = dict(os.environ, DCX_LIB=os.path.abspath(args.parent_lib))
-                    p = subprocess.run([sys.executable, os.path.abspath(__file__), "--iters", str(args.iters), "--child", f"{E}:{b_lo}"],
-                                       env=env, capture_output=True, text=True, check=True)
-                    parent.append(list(json.loads(p.stdout.strip().splitlines()[-1]).values())[0])
+                if args.parent_lib:
+                    parent.append(parent_round(__file__, args.parent_lib, f"{E}:{b_lo}:{b_hi}", ["--iters", str(args.iters)]))
                 worst.append(timed(lambda: m.motion_worst_raw(qa, qb, margin=b_lo, **kw), args.iters))
                 band.append(timed(lambda: m.motion_band_raw(qa, qb, b_lo, b_hi, unc_cap=cap, **kw), args.iters))
                 band_noq.append(timed(lambda: m.motion_band_raw(qa, qb, b_lo, b_hi, unc_cap=cap, want_q=False, **kw), args.iters))
@@ -106,9 +109,7 @@ def main():
             res["motion_worst_us_x3"] = [round(x, 1) for x in worst]
             res["motion_worst_us"] = med(worst)
             res["motion_worst_spread"] = round((max(worst) - min(worst)) / min(worst), 4)
-            if parent:
-                res["parent_motion_worst_us_x3"] = [round(x, 1) for x in parent]
-                res["parent_motion_worst_us"] = med(parent)
+            add_parent_rounds(res, parent)
             res["motion_band_us_x3"] = [round(x, 1) for x in band]
             res["motion_band_us"] = med(band)
             res["motion_band_no_q_us"] = med(band_noq)
@@ -120,6 +121,8 @@ def main():
             res["ratio_vs_motion_worst"] = round(res["motion_band_us"] / res["motion_worst_us"], 3)
             if parent:
                 res["ratio_vs_parent_motion_worst"] = round(res["motion_band_us"] / res["parent_motion_worst_us"], 3)
+                if "parent_motion_band_us" in res:
+                    res["ratio_vs_parent_motion_band"] = round(res["motion_band_us"] / res["parent_motion_band_us"], 3)
             res["speedup_vs_host"] = round(res["host_composition_us"] / res["motion_band_us"], 2)
             print(json.dumps(res), flush=True)
 

@@ -39,6 +39,23 @@ def timed(fn, iters, warmup=3):
     return ts[len(ts) // 2]
 
 
+def child(args):
+    """--child E:margin[,margin ...] (--models: the one model): dcx_motion_cost on the library DCX_LIB names"""
+    sys.path.insert(0, os.path.join(ROOT, "tools"))
+    import bench
+    from motion_bench import bench_edges
+    from diffco_amd import _lib
+    _lib.require_gpu()
+    dev = torch.device("cuda", 0)
+    w = bench.make_workload(args.models[0], 1024, dev)
+    m = w["model"]
+    E, margin = args.child.split(":")
+    qa, qb, _ = bench_edges(int(E), w["lo"].to(dev), w["hi"].to(dev), dev, 0.05, m.dof)
+    kw = dict(wrap=(1 << m.dof) - 1) if args.wrap else {}
+    call = lambda: m.motion_cost_raw(qa, qb, max_step=0.05, margin=[float(x) for x in margin.split(",")], max_samples=64, **kw)  # noqa: E731
+    print(json.dumps({"motion_cost_us": timed(call, args.iters)}), flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--edges", type=int, nargs="+", default=[4096, 65536])
@@ -46,7 +63,14 @@ def main():
     ap.add_argument("--rounds", type=int, default=3)
     ap.add_argument("--models", nargs="+", default=["headline", "cfg3"])
     ap.add_argument("--wrap", action="store_true", help="all joints masked: dcx_motion_cost_ex along the shortest arc")
+    ap.add_argument("--parent-lib", default=None, help="another build of libdcx.so whose dcx_motion_cost is timed in child processes "
+                                                       "(tools/motion_bench.py parent_round), interleaved with this library's rounds")
+    ap.add_argument("--child", default=None, help=argparse.SUPPRESS)
     args = ap.parse_args()
+    if args.child:
+        return child(args)
+    sys.path.insert(0, os.path.join(ROOT, "tools"))
+    from motion_bench import add_parent_rounds, parent_round
     import bench
     from diffco_amd import _lib
     from diffco_amd._perceptron import host_motion_cost
@@ -99,12 +123,18 @@ def main():
                     "check_motions_us": lambda: m.check_motions(qa, qb, max_step=step, margin=margin, max_samples=64, **kw),
                 }
                 rounds = {k: [] for k in list(calls) + ["host_composition_us"]}
+                parent = []
                 for _ in range(args.rounds):   # interleaved
+                    if args.parent_lib:
+                        parent.append(parent_round(__file__, args.parent_lib, f"{E}:{','.join(repr(float(x)) for x in margin)}",
+                                                   ["--iters", str(args.iters), "--models", name] + (["--wrap"] if args.wrap else [])))
                     for k, fn in calls.items():
                         rounds[k].append(timed(fn, args.iters))
                     rounds["host_composition_us"].append(timed(host, max(3, args.iters // 5)))
                 for k, v in rounds.items():
                     res[k] = round(sorted(v)[len(v) // 2], 1)
+                res["motion_cost_us_x3"] = [round(x, 1) for x in rounds["motion_cost_us"]]
+                add_parent_rounds(res, parent)
                 hc = host_motion_cost(lambda p: m.score(p), qa, qb, max_step=step, margin=mg_t, max_samples=64, wrap=wrap or 0)
                 res["host_cost_max_rel_diff"] = float((hc - cost).abs().max() / cost.abs().max().clamp(min=1e-30))
                 res["ratio_vs_hinge_grad"] = round(res["motion_cost_us"] / res["hinge_grad_materialised_us"], 3)
