@@ -312,6 +312,39 @@ def knn(queries, points, k, wrap=None, max_dist=None, exclude_self=False, self_o
     return idx, dist2
 
 
+def rrt_extract_paths(state, W, out=None):
+    """the solved paths of an RRT state (dcx_rrt_extract_paths; `state` maps nodes [R, 2, cap, dof] float32, parent [R, 2, cap],
+    status [R], link [R, 2] (int32) to contiguous tensors on one GPU): (path [R, W, dof] float32, count [R] int32) there.
+    count[r] = n where problem r's n waypoints fit and were written, -n where n > W (the row is left as it is: zeros), 0 for a
+    problem without a path.  W = 0 asks for the sizes alone.  `out`: the [R, W, dof] tensor to write into.  One launch on torch's current stream, nothing read back."""
+    lib = _lib.require_gpu()
+    nodes = state["nodes"]
+    if nodes.dim() != 4 or nodes.device.type != "cuda":
+        raise ValueError("rrt_extract_paths: state['nodes'] must be a [R, 2, cap, dof] tensor on a GPU")
+    dev = nodes.device
+    R, _, cap, dof = (int(v) for v in nodes.shape)
+    kinds = dict(nodes=torch.float32, parent=torch.int32, status=torch.int32, link=torch.int32)
+    shapes = dict(nodes=(R, 2, cap, dof), parent=(R, 2, cap), status=(R,), link=(R, 2))
+    for name, dt in kinds.items():
+        t = state[name]
+        if t.dtype != dt or t.device != dev or not t.is_contiguous() or tuple(t.shape) != shapes[name]:
+            raise ValueError(f"rrt_extract_paths: state[{name!r}] must be a contiguous {dt} tensor {shapes[name]} on {dev}")
+    W = int(W)
+    if W < 0:
+        raise ValueError("rrt_extract_paths: W must be >= 0")
+    if out is None:
+        path = torch.zeros((R, W, dof), device=dev, dtype=torch.float32)
+    else:
+        path = out
+        if path.dtype != torch.float32 or path.device != dev or not path.is_contiguous() or tuple(path.shape) != (R, W, dof):
+            raise ValueError(f"rrt_extract_paths: out must be a contiguous float32 tensor {(R, W, dof)} on {dev}")
+    count = torch.zeros(R, device=dev, dtype=torch.int32)
+    st = _lib.RrtState(state["nodes"].data_ptr(), state["parent"].data_ptr(), 0, state["status"].data_ptr(), state["link"].data_ptr(), 0)
+    with _on_device(dev):
+        _lib.check(lib.dcx_rrt_extract_paths(dev.index, C.byref(st), R, cap, dof, _ptr(path), _ptr(count), W, _stream(dev)))
+    return path, count
+
+
 def compose_path_cost(edge_cost, paths, dof):
     """[T] costs of paths [T, W, dof] from an edge-cost callable edge_cost(qa, qb, open_end) under the max_step rule: the
     open-ended edges p[i] -> p[i + 1] plus the zero-length edge p[-1] -> p[-1] (its one sample is p[-1]) cover the points of
@@ -561,6 +594,35 @@ class ScoreModel:
         with _on_device(self.dev):
             _lib.check(self._lib.dcx_rrt_connect_run(self._h, C.byref(st), R, _ptr(samples), T, int(round0), C.byref(opt), _ptr(mg),
                                                      _ptr(work), nbytes, self._st()))
+
+    def shortcut_run(self, state, draws, max_step, max_samples, margin=0., wrap=None):
+        """T rounds of batched path shortcutting (dcx_path_shortcut_run) on the caller's state, in place: `state` maps path
+        [R, W, dof] float32, count [R] and accepted [R] (int32) to contiguous tensors on the model's device; draws [T, R, P, 2]
+        float32 there.  The rounds are enqueued on torch's current stream; nothing is read back (capturable).  `margin` as
+        check_motions."""
+        if draws.dim() != 4:
+            raise ValueError("shortcut_run: draws must be [T, R, P, 2]")
+        T, R, P = (int(v) for v in draws.shape[:3])
+        path = state["path"]
+        if path.dim() != 3:
+            raise ValueError("shortcut_run: state['path'] must be [R, W, dof]")
+        W = int(path.shape[1])
+        kinds = dict(path=torch.float32, count=torch.int32, accepted=torch.int32)
+        shapes = dict(path=(R, W, self.dof), count=(R,), accepted=(R,))
+        for name, dt in kinds.items():
+            t = state[name]
+            if t.dtype != dt or t.device != self.dev or not t.is_contiguous() or tuple(t.shape) != shapes[name]:
+                raise ValueError(f"shortcut_run: state[{name!r}] must be a contiguous {dt} tensor {shapes[name]} on {self.dev}")
+        if draws.dtype != torch.float32 or draws.device != self.dev or not draws.is_contiguous() or draws.shape[3] != 2:
+            raise ValueError(f"shortcut_run: draws must be a contiguous float32 tensor [T, R, P, 2] on {self.dev}")
+        st = _lib.ShortcutState(*(state[n].data_ptr() for n in kinds))
+        opt = _lib.ShortcutOpts(float(max_step), int(max_samples), P, W, wrap_mask(wrap, self.dof), (C.c_int64 * 2)(0, 0))
+        mg = self._motion_margin(margin)
+        nbytes = int(self._lib.dcx_path_shortcut_work_bytes(self._h, R, P))
+        work = torch.empty(max(nbytes, 1), device=self.dev, dtype=torch.uint8)
+        with _on_device(self.dev):
+            _lib.check(self._lib.dcx_path_shortcut_run(self._h, C.byref(st), R, _ptr(draws), T, C.byref(opt), _ptr(mg), _ptr(work),
+                                                       nbytes, self._st()))
 
     def _motion_margin(self, margin):
         """the motion calls' margin argument: None (all zero), or [C] device floats (a device tensor stays on the device)"""

@@ -21,6 +21,7 @@
 #include "traj_dense.h"
 #include "knn_kernel.h"
 #include "rrt_kernel.h"
+#include "shortcut_kernel.h"
 
 using namespace dcx;
 
@@ -2605,7 +2606,110 @@ int dcx_rrt_connect_run(const dcx_model* m, const dcx_rrt_state* state, int64_t 
     return DCX_OK;
 }
 
-int dcx_debug_clock_probe(int device, uint64_t* out4, uint64_t wall_ticks, int32_t* wall_clock_khz, void* stream) {
+// ---- batched path shortcutting (shortcut_kernel.h): the size query and the call share the checks and shortcut_plan ----------
+static int shortcut_check_sizes(const dcx_model* m, int64_t R, int32_t slots) {
+    if (!m) return fail(DCX_ERR_INVALID, "shortcut: model is NULL");
+    if (R < 0) return fail(DCX_ERR_INVALID, "shortcut: R < 0");
+    if (slots < 1 || slots > DCX_SHORTCUT_MAX_SLOTS)
+        return fail(DCX_ERR_INVALID, "shortcut: slots must be in [1, DCX_SHORTCUT_MAX_SLOTS]");
+    if (R > INT32_MAX / slots) return fail(DCX_ERR_UNSUPPORTED, "shortcut: more than 2^31 - 1 edges per round");
+    return DCX_OK;
+}
+
+size_t dcx_path_shortcut_work_bytes(const dcx_model* m, int64_t R, int32_t slots) {
+    if (shortcut_check_sizes(m, R, slots)) return 0;
+    return shortcut_plan(R, slots, m->fk.dof, motion_work(R * slots).total).total;
+}
+
+int dcx_path_shortcut_run(const dcx_model* m, const dcx_shortcut_state* state, int64_t R, const float* draws, int32_t T,
+                          const dcx_shortcut_opts* opt, const float* margin, void* work, size_t work_bytes, void* stream) {
+    // every argument is checked before anything touches the model's device
+    if (!opt) return fail(DCX_ERR_INVALID, "shortcut: options are NULL");
+    if (T < 0) return fail(DCX_ERR_INVALID, "shortcut: T < 0");
+    if (int rc = shortcut_check_sizes(m, R, opt->slots)) return rc;
+    if (!(opt->max_step > 0.f)) return fail(DCX_ERR_INVALID, "shortcut: max_step must be > 0");
+    if (opt->max_samples < 1) return fail(DCX_ERR_INVALID, "shortcut: max_samples must be >= 1");
+    if (opt->W < 1 || opt->W > DCX_SHORTCUT_MAX_WAYPOINTS)
+        return fail(DCX_ERR_INVALID, "shortcut: W must be in [1, DCX_SHORTCUT_MAX_WAYPOINTS]");
+    if (opt->reserved[0] || opt->reserved[1]) return fail(DCX_ERR_INVALID, "shortcut: reserved fields must be 0");
+    if (opt->wrap_mask != 0 && m->fk.dof < 64 && (opt->wrap_mask >> m->fk.dof) != 0)
+        return fail(DCX_ERR_INVALID, "shortcut: wrap_mask has a bit at or above dof");
+    if (R > 0 && (!state || !state->path || !state->count || !state->accepted))
+        return fail(DCX_ERR_INVALID, "shortcut: state or one of its pointers is NULL");
+    if (R > 0 && T > 0 && !draws) return fail(DCX_ERR_INVALID, "shortcut: draws is NULL");
+    if (R > 0 && !work) return fail(DCX_ERR_INVALID, "shortcut: work is NULL");
+    const int64_t E = R * opt->slots;
+    const MotionWork mw = motion_work(E);
+    const ShortcutPlan plan = shortcut_plan(R, opt->slots, m->fk.dof, mw.total);
+    if (R > 0 && work_bytes < plan.total)
+        return fail(DCX_ERR_INVALID, "shortcut: the workspace is smaller than dcx_path_shortcut_work_bytes");
+    if (R == 0 || T == 0) return DCX_OK;
+    // what dcx_check_motions_ex could still refuse depends on (model, E, max_samples) alone: refused here, before the first launch
+    if (m->fk.dof < 1 || m->fk.dof > DCX_MAX_DOF) return fail(DCX_ERR_UNSUPPORTED, "shortcut: dof outside 1 .. DCX_MAX_DOF");
+    if ((E * (int64_t)opt->max_samples + 63) / 64 > 0x7fffffffLL)
+        return fail(DCX_ERR_UNSUPPORTED, "shortcut: R * slots * max_samples too large for one launch");
+    if (!motion_for(m->Dt)) return fail(DCX_ERR_UNSUPPORTED, "shortcut: no motion kernel for this feature width");
+    if (int rc = set_device(m->device)) return rc;
+    hipStream_t st = (hipStream_t)stream;
+    char* base = (char*)work;
+    ShortcutArgs a{};
+    a.path = state->path;
+    a.count = state->count;
+    a.accepted = state->accepted;
+    a.qa = (float*)(base + plan.qa);
+    a.qb = (float*)(base + plan.qb);
+    a.first_hit = (int32_t*)(base + plan.first_hit);
+    a.picks = (int32_t*)(base + plan.picks);
+    a.R = (int32_t)R;
+    a.P = opt->slots;
+    a.W = opt->W;
+    a.dof = m->fk.dof;
+    dcx_motion_opts mo{};
+    mo.max_step = opt->max_step;
+    mo.max_samples = opt->max_samples;
+    for (int32_t t = 0; t < T; ++t) {
+        a.draws = draws + (int64_t)t * E * 2;
+        hipError_t e = launch_shortcut_pick(a, st);
+        if (e != hipSuccess) return fail_hip(e, "shortcut pick launch");
+        if (int rc = dcx_check_motions_ex(m, a.qa, a.qb, E, &mo, margin, (int32_t*)(base + plan.first_hit), nullptr, work, mw.total,
+                                          opt->wrap_mask, stream))
+            return rc;
+        e = launch_shortcut_commit(a, st);
+        if (e != hipSuccess) return fail_hip(e, "shortcut commit launch");
+    }
+    return DCX_OK;
+}
+
+int dcx_rrt_extract_paths(int device, const dcx_rrt_state* state, int64_t R, int32_t cap, int32_t dof, float* path, int32_t* count,
+                          int32_t W, void* stream) {
+    if (R < 0) return fail(DCX_ERR_INVALID, "extract: R < 0");
+    if (cap < 1 || cap > DCX_RRT_MAX_CAP) return fail(DCX_ERR_INVALID, "extract: cap must be in [1, DCX_RRT_MAX_CAP]");
+    if (dof < 1) return fail(DCX_ERR_INVALID, "extract: dof < 1");
+    if (W < 0) return fail(DCX_ERR_INVALID, "extract: W < 0");
+    if (R > 0 && (!state || !state->nodes || !state->parent || !state->status || !state->link))
+        return fail(DCX_ERR_INVALID, "extract: state or one of its nodes, parent, status and link pointers is NULL");
+    if (R > 0 && !count) return fail(DCX_ERR_INVALID, "extract: count is NULL");
+    if (R > 0 && W > 0 && !path) return fail(DCX_ERR_INVALID, "extract: path is NULL with W > 0");
+    if (R > INT32_MAX) return fail(DCX_ERR_UNSUPPORTED, "extract: more than 2^31 - 1 problems");
+    if (R == 0) return DCX_OK;
+    if (int rc = set_device(device)) return rc;
+    ExtractArgs a{};
+    a.nodes = state->nodes;
+    a.parent = state->parent;
+    a.status = state->status;
+    a.link = state->link;
+    a.path = path;
+    a.count = count;
+    a.R = (int32_t)R;
+    a.cap = cap;
+    a.dof = dof;
+    a.W = W;
+    const hipError_t e = launch_rrt_extract(a, (hipStream_t)stream);
+    if (e != hipSuccess) return fail_hip(e, "extract launch");
+    return DCX_OK;
+}
+
+int dcx_debug_clock_probe(int device, uint64_t* out4,uint64_t wall_ticks, int32_t* wall_clock_khz, void* stream) {
     if (!out4 || wall_ticks < 1 || wall_ticks > (1ull << 32)) return fail(DCX_ERR_INVALID, "clock probe: out4 is NULL or wall_ticks out of range");
     if (int rc = set_device(device)) return rc;
     if (wall_clock_khz) {

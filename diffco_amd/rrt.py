@@ -9,7 +9,8 @@ state, bit for bit, for equal samples) and the baseline it is measured against. 
 has such a `check_motions`.
 
 The path of a solved problem is walked from `parent` on the host: start, ..., link node of tree 0, link node of tree 1, ...,
-goal; it is what `fused_adam_traj_optimize` takes as `init_solution`.
+goal; it is what `fused_adam_traj_optimize` takes as `init_solution`.  `RRTResult.path_tensor` gives the same rows as one
+[R, W, dof] tensor, written on the device for a state on the GPU (dcx_rrt_extract_paths): what `shortcut.shortcut_paths` takes.
 """
 import math
 
@@ -37,6 +38,32 @@ class RRTResult:
 
     def state(self):
         return {name: getattr(self, name) for name in _STATE}
+
+    def path_tensor(self, W=None):
+        """(path [R, W, dof] float32, count [R] int32) on the state's device: the rows of `paths` as one tensor, what
+        shortcut.shortcut_paths takes.  count[r] is the path's waypoints, 0 without a path, and -n where its n waypoints do
+        not fit into W (that row is left as it is: zeros).  A state on the GPU goes through dcx_rrt_extract_paths (one launch,
+        the parents never leave the device); W=None asks for the sizes first and reads their maximum back once.  A state on the
+        CPU is walked on the host."""
+        if self.nodes.device.type == "cuda":
+            st = self.state()
+            if W is None:
+                sizes = _ops.rrt_extract_paths(st, 0)[1]
+                W = int((-sizes).max()) if len(sizes) else 0
+            return _ops.rrt_extract_paths(st, W)
+        R, dof = len(self.status), self.nodes.shape[3]
+        status, link = self.status.tolist(), self.link.tolist()
+        rows = [_walk(self.nodes, self.parent, link[r], r) if status[r] == SOLVED else None for r in range(R)]
+        if W is None:
+            W = max([0] + [len(p) for p in rows if p is not None])
+        path = torch.zeros((R, int(W), dof), dtype=torch.float32)
+        count = torch.zeros(R, dtype=torch.int32)
+        for r, p in enumerate(rows):
+            if p is not None:
+                count[r] = len(p) if len(p) <= W else -len(p)
+                if len(p) <= W:
+                    path[r, :len(p)] = p
+        return path, count
 
 
 # ---- fp32 arithmetic of the contract in torch ops, one rounded operation at a time ------------------------------------------
@@ -236,19 +263,25 @@ class _Plan:
                 rounds.append(0 if status[r] == BLOCKED else rounds_run)
                 lengths.append(float("nan"))
                 continue
-            walk = [[], []]
-            for t in (0, 1):
-                i = link[r][t]
-                while i >= 0:
-                    walk[t].append(i)
-                    i = int(parent[r, t, i])
-            i0 = torch.tensor(walk[0][::-1], dtype=torch.int64, device=nodes.device)
-            i1 = torch.tensor(walk[1], dtype=torch.int64, device=nodes.device)
-            p = torch.cat([nodes[r, 0][i0], nodes[r, 1][i1]])
+            p = _walk(nodes, parent, link[r], r)
             paths.append(p)
             rounds.append(solved[r] + 1)
             lengths.append(float(_ops.wrapped_delta(p[:-1], p[1:], self.mask).norm(dim=1).sum()))
         return RRTResult(route, st, paths, torch.tensor(rounds, dtype=torch.int64), torch.tensor(lengths, dtype=torch.float32))
+
+
+def _walk(nodes, parent, link_r, r):
+    """the path of solved problem r from `parent` (on the CPU): tree 0 from its root to the link node, tree 1 from its link node
+    to its root"""
+    walk = [[], []]
+    for t in (0, 1):
+        i = link_r[t]
+        while i >= 0:
+            walk[t].append(i)
+            i = int(parent[r, t, i])
+    i0 = torch.tensor(walk[0][::-1], dtype=torch.int64, device=nodes.device)
+    i1 = torch.tensor(walk[1], dtype=torch.int64, device=nodes.device)
+    return torch.cat([nodes[r, 0][i0], nodes[r, 1][i1]])
 
 
 def _append(st, r_all, tree, app, pts, par, cap):

@@ -1,0 +1,253 @@
+"""Batched path shortcutting over a collision checker: R piecewise-straight paths simplified in lockstep, P attempts per path and
+round - try the straight motion between two waypoints and cut out what lies between.
+
+`shortcut_paths` runs the fused pass (dcx_path_shortcut_run: the pick and the in-place compaction in HIP, the edge checks through
+the fused motion sweep, nothing read back between rounds) where the checker's own `check_motions` would take the fused route
+and the paths are on the GPU, and `host_shortcut_paths` everywhere else.  `host_shortcut_paths` is the same contract
+(include/dcx.h, "batched path shortcutting") composed of torch indexing and the checker's `check_motions(..., return_first=True)`
+on the same fixed batch of R * P edges: the referee of the fused pass (equal path[:count], count and accepted, bit for bit, for
+equal draws) and the baseline it is measured against.  It runs on CPU tensors with any checker that has such a `check_motions`.
+
+The paths of `rrt.rrt_connect` come as one tensor from `RRTResult.path_tensor()`; what leaves here is what
+`fused_adam_traj_optimize` takes as `init_solution`.
+"""
+import math
+
+import torch
+
+from . import _ops
+from .rrt import _Edges, _edge_plan, _f32, _div, _fused_model, _length, _sample, _transform_of
+
+__all__ = ["shortcut_paths", "host_shortcut_paths", "ShortcutResult"]
+
+MAX_SLOTS = 16            # DCX_SHORTCUT_MAX_SLOTS
+MAX_WAYPOINTS = 1 << 16   # DCX_SHORTCUT_MAX_WAYPOINTS
+
+
+class ShortcutResult:
+    """path [R, W, dof]: row k < count[r] is waypoint k of path r (rows beyond are unspecified);  count [R] int32;  accepted [R]
+    int32: the shortcuts applied;  paths: per path a [count, dof] tensor or None where count < 2;  lengths_before, lengths [R]:
+    the paths' lengths under the checks' metric before (after `subdivide`, which does not change them) and after (nan without a
+    path);  route: "fused" or "host"."""
+
+    def __init__(self, route, path, count, accepted, lengths_before, lengths):
+        self.route, self.path, self.count, self.accepted = route, path, count, accepted
+        self.lengths_before, self.lengths = lengths_before, lengths
+        self.paths = [path[r, :n] if n >= 2 else None for r, n in enumerate(count.tolist())]
+
+
+def _lengths(path, count, mask):
+    """[R] float32 on the CPU: the sum of the segments' lengths (the wrapped delta on masked coordinates), nan where count < 2"""
+    R, W, _ = path.shape
+    out = torch.full((R,), float("nan"), dtype=torch.float32)
+    if R == 0 or W < 2:
+        return out
+    seg = _ops.wrapped_delta(path[:, :-1], path[:, 1:], mask).norm(dim=2)
+    live = torch.arange(W - 1, device=path.device)[None, :] < (count.to(torch.int64)[:, None] - 1)
+    total = torch.where(live, seg, torch.zeros_like(seg)).sum(dim=1).cpu()
+    return torch.where(count.cpu() >= 2, total, out)
+
+
+def _subdivide(p, step, mask):
+    """the path p [n, dof] with, on every segment longer than `step`, the interior points of the max_step rule of stride `step`
+    inserted (rrt.py's _edge_plan and _sample: the points the motion calls would sample on that segment)"""
+    if len(p) < 2:
+        return p
+    qa, qb = p[:-1], p[1:]
+    d, frac, _ = _edge_plan(qa, qb, step, 1, mask)
+    n = (torch.ceil(_length(d) * _div(_f32(1.0, p.device), _f32(step, p.device))) + 1.0)
+    n = torch.where(torch.isfinite(n), n, torch.full_like(n, 2.0)).to(torch.int64).tolist()
+    rows = []
+    for e in range(len(qa)):
+        rows.append(qa[e:e + 1])
+        if n[e] > 2:
+            k = torch.arange(1, n[e] - 1, device=p.device)
+            rows.append(_sample(qa[e][None].expand(len(k), -1), d[e][None].expand(len(k), -1), frac[e][None].expand(len(k)), k, mask))
+    rows.append(qb[-1:])
+    return torch.cat(rows)
+
+
+class _Pass:
+    """what both routes share: the arguments, the state, the draws, the loop"""
+
+    def __init__(self, checker, paths, counts, dev, max_step, wrap, slots, rounds, rounds_per_call, sampler, seed, max_samples,
+                 subdivide):
+        self.max_step = float(max_step)
+        if not self.max_step > 0:
+            raise ValueError("shortcut_paths: max_step must be > 0")
+        self.P, self.rounds, self.chunk = int(slots), int(rounds), max(int(rounds_per_call), 1)
+        if not 1 <= self.P <= MAX_SLOTS:
+            raise ValueError(f"shortcut_paths: slots must be in [1, {MAX_SLOTS}], got {slots}")
+        if self.rounds < 0:
+            raise ValueError(f"shortcut_paths: rounds must be >= 0, got {rounds}")
+        if subdivide is not None and not float(subdivide) > 0:
+            raise ValueError("shortcut_paths: subdivide must be > 0")
+        self.dev = dev
+        if torch.is_tensor(paths):
+            if paths.dim() != 3 or counts is None:
+                raise ValueError("shortcut_paths: a tensor of paths must be [R, W, dof] and come with `counts` [R]")
+            path = paths.detach().to(device=dev, dtype=torch.float32)
+            count = torch.as_tensor(counts).detach().to(device=dev).reshape(-1)
+            if len(count) != len(path) or count.dtype.is_floating_point or bool(((count < 0) | (count > path.shape[1])).any()):
+                raise ValueError(f"shortcut_paths: counts must be {len(path)} integers in [0, {path.shape[1]}]")
+            rows = [path[r, :n] if n else None for r, n in enumerate(count.tolist())]
+            self.dof = int(path.shape[2])
+        else:
+            if counts is not None:
+                raise ValueError("shortcut_paths: `counts` goes with a tensor of paths; a list carries its own lengths")
+            rows = [None if p is None else torch.as_tensor(p).detach().to(device=dev, dtype=torch.float32) for p in paths]
+            shaped = [p for p in rows if p is not None]
+            if any(p.dim() != 2 for p in shaped) or len({int(p.shape[1]) for p in shaped}) > 1:
+                raise ValueError("shortcut_paths: every path must be a [W_r, dof] tensor of the same dof")
+            if not shaped:
+                raise ValueError("shortcut_paths: a list of paths needs at least one path (its dof); pass a tensor with counts")
+            self.dof = int(shaped[0].shape[1])
+        if self.dof < 1:
+            raise ValueError("shortcut_paths: dof must be >= 1")
+        self.mask = _ops.wrap_mask(wrap, self.dof, _transform_of(checker))
+        if subdivide is not None:
+            rows = [None if p is None else _subdivide(p, float(subdivide), self.mask) for p in rows]
+        self.R = len(rows)
+        W = max([1] + [len(p) for p in rows if p is not None])
+        if W > MAX_WAYPOINTS:
+            raise ValueError(f"shortcut_paths: a path has {W} waypoints, more than {MAX_WAYPOINTS}")
+        self.W = W
+        self.st = dict(path=torch.zeros((self.R, W, self.dof), dtype=torch.float32, device=dev),
+                       count=torch.zeros(self.R, dtype=torch.int32, device=dev),
+                       accepted=torch.zeros(self.R, dtype=torch.int32, device=dev))
+        for r, p in enumerate(rows):
+            if p is not None and len(p):
+                self.st["path"][r, :len(p)] = p
+                self.st["count"][r] = len(p)
+        self.lengths_before = _lengths(self.st["path"], self.st["count"], self.mask)   # (the one read-back before the loop)
+        if max_samples is None:
+            # a straight motion between two waypoints is never longer than the path between them
+            known = self.lengths_before[torch.isfinite(self.lengths_before)]
+            longest = float(known.max()) if len(known) else 0.0
+            max_samples = min(_ops.MOTION_MAX_SAMPLES, int(math.ceil(longest / self.max_step)) + 2)
+            if len(known) < int((self.st["count"] >= 2).sum()):   # a path of unknown length (NaN or infinite waypoints)
+                max_samples = _ops.MOTION_MAX_SAMPLES
+        self.max_samples = int(max_samples)
+        if self.max_samples < 1:
+            raise ValueError(f"shortcut_paths: max_samples must be >= 1, got {max_samples}")
+        if sampler is None:
+            gen = torch.Generator(device=dev)
+            gen.manual_seed(int(seed))
+
+            def sampler(T, R, P):   # one draw per round: the stream of draws does not depend on rounds_per_call
+                return torch.stack([torch.rand((R, P, 2), generator=gen, device=dev) for _ in range(T)]) \
+                    if T else torch.zeros((0, R, P, 2), device=dev)
+        self.sampler = sampler
+
+    def loop(self, run_chunk):
+        g = 0
+        while g < self.rounds and self.R:
+            T = min(self.chunk, self.rounds - g)
+            draws = torch.as_tensor(self.sampler(T, self.R, self.P)).to(device=self.dev, dtype=torch.float32).contiguous()
+            if tuple(draws.shape) != (T, self.R, self.P, 2):
+                raise ValueError(f"shortcut_paths: the sampler returned {tuple(draws.shape)}, expected {(T, self.R, self.P, 2)}")
+            run_chunk(draws)
+            g += T
+
+    def result(self, route):
+        st = self.st
+        return ShortcutResult(route, st["path"], st["count"], st["accepted"], self.lengths_before,
+                              _lengths(st["path"], st["count"], self.mask))
+
+
+def _pick(count, u):
+    """(i, j, live) [R, P] of include/dcx.h's pick for the draws u [R, P, 2]: float32, one rounded operation at a time"""
+    n = count.to(torch.int64)[:, None]
+    u0, u1 = u[..., 0], u[..., 1]
+    live = (n >= 3) & (u0 >= 0) & (u0 < 1) & (u1 >= 0) & (u1 < 1)
+    zero = torch.zeros_like(u0)
+    u0, u1, n = torch.where(live, u0, zero), torch.where(live, u1, zero), n.clamp(min=3)
+    i = torch.minimum((u0 * (n - 2).to(torch.float32)).to(torch.int64), n - 3)
+    m = n - 2 - i
+    j = i + 2 + torch.minimum((u1 * m.to(torch.float32)).to(torch.int64), m - 1)
+    return i, j, live
+
+
+def _host_round(ps, edges, u, record=None):
+    """one round of the contract on the state tensors, in place"""
+    st, R, P, W, dof = ps.st, ps.R, ps.P, ps.W, ps.dof
+    path, dev = st["path"], ps.dev
+    i, j, live = _pick(st["count"], u)
+    r_all = torch.arange(R, device=dev)[:, None]
+    root = path[:, :1].expand(R, P, dof)
+    qa = torch.where(live[..., None], path[r_all, i], root)
+    qb = torch.where(live[..., None], path[r_all, j], root)
+    first = edges.first_hit(qa.reshape(-1, dof), qb.reshape(-1, dof), root.reshape(-1, dof))[0].reshape(R, P)
+    free = live & (first == -1)
+    applied = torch.zeros_like(free)
+    for p in range(P):   # slot order: a free slot is applied iff it crosses none that was applied before it
+        ok = free[:, p].clone()
+        for q in range(p):
+            ok &= ~applied[:, q] | (j[:, p] <= i[:, q]) | (j[:, q] <= i[:, p])
+        applied[:, p] = ok
+    if record is not None:
+        record(live, first, free, applied)
+    k = torch.arange(W, device=dev)[None, :, None]                                   # [1, W, 1]
+    ia, ja, on = i[:, None, :], j[:, None, :], applied[:, None, :]                   # [R, 1, P]
+    dead = (on & (ia < k) & (k < ja)).any(dim=2)                                     # [R, W]
+    shift = torch.where(on & (ja <= k), ja - ia - 1, torch.zeros_like(ja)).sum(dim=2)
+    keep = ~dead & (k[:, :, 0] < st["count"].to(torch.int64)[:, None])
+    rr, kk = torch.nonzero(keep, as_tuple=True)
+    moved = path[rr, kk]   # (a copy: read before anything is written)
+    path[rr, kk - shift[rr, kk]] = moved
+    st["count"].copy_(keep.sum(dim=1).to(torch.int32))
+    st["accepted"] += applied.sum(dim=1).to(torch.int32)
+
+
+def host_shortcut_paths(checker, paths, counts=None, *, max_step, wrap=None, slots=4, rounds=64, rounds_per_call=32, sampler=None,
+                        seed=0, margin=0., max_samples=None, subdivide=None, _record=None):
+    """shortcut_paths' contract as the loop a user would write from the library's other calls: per round the pick and the
+    compaction as torch indexing, ONE `checker.check_motions(..., return_first=True)` call on the fixed batch of R * slots
+    edges.  The state lives on the device of the paths.  `margin` is passed on to the checker's check_motions only where it is
+    not 0."""
+    first = paths if torch.is_tensor(paths) else next((p for p in paths if p is not None), None)
+    dev = torch.as_tensor(first).device if first is not None else torch.device("cpu")
+    ps = _Pass(checker, paths, counts, dev, max_step, wrap, slots, rounds, rounds_per_call, sampler, seed, max_samples, subdivide)
+    edges = _Edges(checker, ps.max_step, ps.max_samples, ps.mask, margin)
+
+    def run_chunk(draws):
+        for u in draws:
+            _host_round(ps, edges, u, _record)
+
+    ps.loop(run_chunk)
+    return ps.result("host")
+
+
+def shortcut_paths(checker, paths, counts=None, *, max_step, wrap=None, slots=4, rounds=64, rounds_per_call=32, sampler=None,
+                   seed=0, margin=0., max_samples=None, subdivide=None):
+    """Shorten R piecewise-straight paths under `checker` by random vertex shortcuts: a ShortcutResult.
+    paths: a list of [W_r, dof] tensors or None, or a [R, W, dof] tensor with counts [R];  max_step: the stride of every edge
+    check;  wrap (as check_motions: None, True, a bitmask, one bool per coordinate): the circular coordinates, walked along
+    their shortest arc;  slots: attempts per path and round (1 .. 16);  rounds: how many;  sampler(T, R, P) -> [T, R, P, 2] in
+    [0, 1) (default: uniform, seeded by `seed`);  margin: a sample collides where score - margin > 0, on top of the checker's
+    own threshold;  max_samples: the most samples of one edge (default: from the longest path: one read-back before the loop);
+    subdivide=step: first insert, on every segment longer than `step`, the max_step-rule points of stride `step`, so that vertex
+    shortcuts have somewhere to land on long edges.
+    The fused pass (result.route == "fused") runs for kernel_perceptrons.DiffCo, RBFDiffCo and ForwardKinematicsDiffCo whose
+    transform fuses, on paths that are on the GPU; everything else goes through host_shortcut_paths ("host")."""
+    first = paths if torch.is_tensor(paths) else next((p for p in paths if p is not None), None)
+    dev0 = torch.as_tensor(first).device if first is not None else torch.device("cpu")
+    got = _fused_model(checker, dev0) if dev0.type == "cuda" else None
+    if got is None:
+        return host_shortcut_paths(checker, paths, counts, max_step=max_step, wrap=wrap, slots=slots, rounds=rounds,
+                                   rounds_per_call=rounds_per_call, sampler=sampler, seed=seed, margin=margin,
+                                   max_samples=max_samples, subdivide=subdivide)
+    model, base = got
+    if isinstance(base, (int, float)) and isinstance(margin, (int, float)):
+        mg = float(base) + float(margin)
+    else:   # one per class on either side
+        mg = (torch.as_tensor(base, dtype=torch.float32).reshape(-1).to(model.dev)
+              + torch.as_tensor(margin, dtype=torch.float32).reshape(-1).to(model.dev))
+    ps = _Pass(checker, paths, counts, model.dev, max_step, wrap, slots, rounds, rounds_per_call, sampler, seed, max_samples, subdivide)
+    mg_dev = model._motion_margin(mg)   # on the device once: no copy from the host per chunk
+
+    def run_chunk(draws):
+        model.shortcut_run(ps.st, draws, ps.max_step, ps.max_samples, margin=0. if mg_dev is None else mg_dev, wrap=ps.mask)
+
+    ps.loop(run_chunk)
+    return ps.result("fused")

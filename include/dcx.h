@@ -726,6 +726,76 @@ size_t dcx_rrt_work_bytes(const dcx_model* m, int64_t R, int32_t slots);
 int dcx_rrt_connect_run(const dcx_model* m, const dcx_rrt_state* state, int64_t R, const float* samples, int32_t T, int64_t round0,
                         const dcx_rrt_opts* opts, const float* margin, void* work, size_t work_bytes, void* stream);
 
+/* ---- batched path shortcutting and RRT path extraction (added under DCX_VERSION 109) ---------------------- */
+/* R piecewise-straight paths simplified in lockstep, P = opts->slots shortcut attempts per path and round: try the straight
+ * motion between two waypoints and cut out what lies between (the path simplifier a planner's user expects before the paths go
+ * to the optimisers; the reference's scripts/motion_planner.py gets it from OMPL).  All path logic runs on the device, the edge
+ * checks are dcx_check_motions_ex's own launches, and nothing is read back between rounds.
+ * State (dcx_shortcut_state; caller-owned device memory, R paths, W = opts->W):
+ *   path [R, W, dof] float          row k < count[r] is waypoint k of path r
+ *   count [R] int32                 0 .. W: the path's waypoints (a count above W is the caller's error: read as W)
+ *   accepted [R] int32              shortcuts applied so far (the call adds to it)
+ * Round t = 0 .. T - 1, path r, slot p < P, n = count[r] as it stands at the start of the round:
+ *   1. pick, with (u0, u1) = draws[t, r, p, :]: the slot is idle if n < 3 or if either draw fails u >= 0 && u < 1 (a NaN fails
+ *      it).  Otherwise, in fp32 with each operation rounded alone and the cast truncating:
+ *        i = min((int)(u0 * (float)(n - 2)), n - 3),  m = n - 2 - i,  j = i + 2 + min((int)(u1 * (float)m), m - 1)
+ *      so 0 <= i, i + 2 <= j <= n - 1
+ *   2. check: the edge path[r, i] -> path[r, j] is checked by dcx_check_motions_ex (the closed max_step rule, opts->max_samples,
+ *      margin, wrap_mask): first_hit == -1 makes the slot free, anything else (-2 included) rejects it
+ *   3. apply: slots are taken in ascending order.  A free slot p is applied iff every already applied slot q of this round and
+ *      path satisfies j_p <= i_q || j_q <= i_p (the interiors are disjoint and the intervals do not cross; an exact duplicate
+ *      therefore loses)
+ *   4. compact: waypoint k survives iff no applied (i, j) has i < k < j.  Survivors keep their order and their bits and move to
+ *      index k - sum over the applied (i, j) with j <= k of (j - i - 1).  count[r] becomes the number of survivors, accepted[r]
+ *      grows by the number of applied slots, rows at and beyond the new count are unspecified; path[r, 0] and
+ *      path[r, count - 1] never change
+ * Fixed batch: every round submits exactly R * P edges in (r, p) order.  An idle slot submits path[r, 0] -> path[r, 0] (one
+ *   sample, its verdict ignored; that row must be readable even for count[r] == 0), so the geometry of the motion sweep never
+ *   depends on the state: the call can be captured, and a referee that submits the same batch to dcx_check_motions_ex gets the
+ *   same verdicts.
+ * dcx_path_shortcut_run enqueues T rounds on the caller's stream: per round one pick launch, the launches of
+ *   dcx_check_motions_ex, one commit launch.  No allocation, no synchronisation, no atomic decides any order, nothing read
+ *   back; repeated calls give the same bits, and T rounds in one call equal T calls of one round each.
+ *   draws [T, R, P, 2] device floats;  margin [C] device floats, NULL = 0.
+ * work: dcx_path_shortcut_work_bytes(model, R, slots) bytes of device memory, the caller's (dcx_check_motions' workspace for
+ *   R * P edges, then the per-slot scratch: the edge batch qa and qb, first_hit and the picks); initialised by the call itself.
+ * Argument errors (DCX_ERR_INVALID, before any device work): NULL model / opts; NULL state, state pointer, draws (T > 0) or
+ *   work with R > 0; R < 0 or T < 0; max_step <= 0 or NaN; max_samples < 1; slots outside 1 .. DCX_SHORTCUT_MAX_SLOTS; W outside
+ *   1 .. DCX_SHORTCUT_MAX_WAYPOINTS; a wrap_mask bit at or above dof; a reserved field not 0; work_bytes below
+ *   dcx_path_shortcut_work_bytes.  R * slots above 2^31 - 1, R * slots * max_samples too large for one launch, dof above
+ *   DCX_MAX_DOF and a feature width without a motion kernel are DCX_ERR_UNSUPPORTED.  R = 0 or T = 0 launches nothing.
+ *   dcx_path_shortcut_work_bytes is 0 for arguments the call refuses.                                                        */
+#define DCX_SHORTCUT_MAX_SLOTS 16
+#define DCX_SHORTCUT_MAX_WAYPOINTS 65536
+typedef struct dcx_shortcut_state {
+    float*   path;          /* [R, W, dof]                                                                  */
+    int32_t* count;         /* [R]: 0 .. W                                                                  */
+    int32_t* accepted;      /* [R]: shortcuts applied so far (the call adds to it)                          */
+} dcx_shortcut_state;
+typedef struct dcx_shortcut_opts {
+    float    max_step;     /* > 0: the sampling stride of every edge check                                  */
+    int32_t  max_samples;  /* >= 1: an edge needing more samples is rejected; it sizes the sweep launches   */
+    int32_t  slots;        /* P, 1 .. DCX_SHORTCUT_MAX_SLOTS                                                */
+    int32_t  W;            /* rows per path, 1 .. DCX_SHORTCUT_MAX_WAYPOINTS                                */
+    uint64_t wrap_mask;    /* bit j: coordinate j is an angle, walked along the shortest arc                */
+    int64_t  reserved[2];  /* 0                                                                             */
+} dcx_shortcut_opts;
+size_t dcx_path_shortcut_work_bytes(const dcx_model* m, int64_t R, int32_t slots);
+int dcx_path_shortcut_run(const dcx_model* m, const dcx_shortcut_state* state, int64_t R, const float* draws, int32_t T,
+                          const dcx_shortcut_opts* opts, const float* margin, void* work, size_t work_bytes, void* stream);
+/* The solved paths of a dcx_rrt_state as rows of path [R, W, dof], one launch on `device`, without a model.
+ *   status[r] == 1: the path is tree 0 from its root to link[r, 0], then tree 1 from link[r, 1] to its root, n waypoints (a
+ *     direct solve, link = (0, 0), is [start, goal]).  n <= W writes them to path[r, 0 .. n - 1] and sets count[r] = n; n > W
+ *     leaves the row untouched and sets count[r] = -n, so W = 0 (path may then be NULL) is the size query.
+ *   status[r] != 1: count[r] = 0.
+ *   Each walk is bounded by cap hops: a chain that leaves 0 .. cap - 1 or does not reach parent -1 by then gives count[r] = 0,
+ *     and nothing is read out of bounds.
+ * Argument errors (DCX_ERR_INVALID): R < 0; cap outside 1 .. DCX_RRT_MAX_CAP; dof < 1; W < 0; with R > 0 a NULL state, nodes,
+ *   parent, status, link or count, or a NULL path with W > 0.  R above 2^31 - 1 is DCX_ERR_UNSUPPORTED.  R = 0 launches
+ *   nothing.                                                                                                                 */
+int dcx_rrt_extract_paths(int device, const dcx_rrt_state* state, int64_t R, int32_t cap, int32_t dof,
+                          float* path, int32_t* count, int32_t W, void* stream);
+
 /* ---- kernel-perceptron trainer (producer of the path's state) ----------------------- */
 /* DiffCo.train_perceptron kernel_perceptrons.py:98-137 and MultiDiffCo.train_perceptron
  * deprecated/MultiDiffCo.py:50-83 as one persistent launch: worst-margin search, lazily filled kernel rows,
