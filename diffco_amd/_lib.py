@@ -96,6 +96,11 @@ SYMBOLS = {
     "dcx_path_shortcut_run": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, _c_fp, C.c_int32, C.c_void_p, _c_fp, C.c_void_p,
                                         C.c_size_t, C.c_void_p]),
     "dcx_rrt_extract_paths": (C.c_int, [C.c_int, C.c_void_p, C.c_int64, C.c_int32, C.c_int32, _c_fp, _c_fp, C.c_int32, C.c_void_p]),
+    # roadmap queries: min-plus relaxation over the roadmap's CSR for Q start/goal pairs, and their routes as one tensor
+    "dcx_sssp_run": (C.c_int, [C.c_int, C.c_void_p, C.c_int64, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p,
+                               C.c_void_p]),
+    "dcx_sssp_extract_paths": (C.c_int, [C.c_int, C.c_void_p, _c_fp, C.c_int32, C.c_void_p, C.c_int32, C.c_int64, C.c_int32, C.c_void_p,
+                                         _c_fp, _c_fp, C.c_void_p, _c_fp, _c_fp, C.c_void_p, _c_fp, C.c_int32, C.c_void_p]),
     "dcx_solve_work_bytes": (C.c_size_t, [C.c_int64, C.c_int64]),
     "dcx_solve": (C.c_int, [C.c_int, _c_fp, _c_fp, C.c_int64, C.c_int64, _c_fp, C.c_void_p, C.c_size_t, C.c_void_p, C.c_int32,
                             C.c_void_p]),
@@ -170,6 +175,21 @@ class ShortcutOpts(C.Structure):
     """ctypes mirror of dcx_shortcut_opts (include/dcx.h)"""
     _fields_ = [("max_step", C.c_float), ("max_samples", C.c_int32), ("slots", C.c_int32), ("W", C.c_int32),
                 ("wrap_mask", C.c_uint64), ("reserved", C.c_int64 * 2)]
+
+
+class Graph(C.Structure):
+    """ctypes mirror of dcx_graph (include/dcx.h)"""
+    _fields_ = [(n, C.c_void_p) for n in ("rowptr", "col", "weight")] + [("N", C.c_int64), ("nnz", C.c_int64), ("reserved", C.c_int64 * 2)]
+
+
+class SsspState(C.Structure):
+    """ctypes mirror of dcx_sssp_state (include/dcx.h)"""
+    _fields_ = [("dist", C.c_void_p), ("pred", C.c_void_p), ("reserved", C.c_int64 * 2)]
+
+
+class SsspLinks(C.Structure):
+    """ctypes mirror of dcx_sssp_links (include/dcx.h)"""
+    _fields_ = [("idx", C.c_void_p), ("len", C.c_void_p), ("reserved", C.c_int64 * 2)]
 
 
 class MotionCostOpts(C.Structure):

@@ -345,6 +345,105 @@ def rrt_extract_paths(state, W, out=None):
     return path, count
 
 
+def _sssp_tensor(fn, name, t, dtype, shape, dev):
+    if not isinstance(t, torch.Tensor) or t.dtype != dtype or t.device != dev or not t.is_contiguous() or tuple(t.shape) != tuple(shape):
+        raise ValueError(f"{fn}: {name} must be a contiguous {dtype} tensor {tuple(shape)} on {dev}")
+    return t
+
+
+def _sssp_graph(fn, rowptr, col, weight):
+    """dcx_graph of a CSR on one GPU: (the struct, N, device).  Shapes, kinds and placement are checked; the CSR's contents
+    (sorted rows, symmetry, weights >= 0) are the caller's, as include/dcx.h says."""
+    if not isinstance(rowptr, torch.Tensor) or rowptr.device.type != "cuda" or rowptr.dim() != 1 or len(rowptr) < 1:
+        raise ValueError(f"{fn}: rowptr must be an int32 tensor [N + 1] on a GPU")
+    dev = rowptr.device
+    N = len(rowptr) - 1
+    _sssp_tensor(fn, "rowptr", rowptr, torch.int32, (N + 1,), dev)
+    if not isinstance(col, torch.Tensor) or col.dim() != 1:
+        raise ValueError(f"{fn}: col must be an int32 tensor [nnz]")
+    nnz = len(col)
+    _sssp_tensor(fn, "col", col, torch.int32, (nnz,), dev)
+    _sssp_tensor(fn, "weight", weight, torch.float32, (nnz,), dev)
+    return _lib.Graph(rowptr.data_ptr(), col.data_ptr() if nnz else 0, weight.data_ptr() if nnz else 0, N, nnz, (C.c_int64 * 2)(0, 0)), N, dev
+
+
+def sssp_run(rowptr, col, weight, link_idx, link_len, dist, pred, round0, n_rounds, changed=None):
+    """rounds round0 .. round0 + n_rounds - 1 of the min-plus relaxation over the CSR (rowptr, col, weight) for Q queries
+    (dcx_sssp_run; include/dcx.h, "roadmap queries"): the state dist [2, N, Q] float32 and pred [N, Q] int32 is advanced in
+    place, round 0 sets it from the start links link_idx / link_len [Q, k] (int32, -1 = no link / float32).  Returns changed
+    int32 [n_rounds] on the device: 1 where the round changed anything.  Everything is a contiguous tensor on one GPU; the
+    launches go to torch's current stream, nothing is allocated (with `changed` given) or read back."""
+    fn = "sssp_run"
+    lib = _lib.require_gpu()
+    g, N, dev = _sssp_graph(fn, rowptr, col, weight)
+    if not isinstance(dist, torch.Tensor) or dist.dim() != 3:
+        raise ValueError(f"{fn}: dist must be a float32 tensor [2, N, Q]")
+    Q = int(dist.shape[2])
+    _sssp_tensor(fn, "dist", dist, torch.float32, (2, N, Q), dev)
+    _sssp_tensor(fn, "pred", pred, torch.int32, (N, Q), dev)
+    if not isinstance(link_idx, torch.Tensor) or link_idx.dim() != 2:
+        raise ValueError(f"{fn}: link_idx must be an int32 tensor [Q, k]")
+    k = int(link_idx.shape[1])
+    _sssp_tensor(fn, "link_idx", link_idx, torch.int32, (Q, k), dev)
+    _sssp_tensor(fn, "link_len", link_len, torch.float32, (Q, k), dev)
+    round0, n_rounds = int(round0), int(n_rounds)
+    if round0 < 0 or n_rounds < 0:
+        raise ValueError(f"{fn}: round0 and n_rounds must be >= 0")
+    if changed is None:
+        changed = torch.zeros(n_rounds, device=dev, dtype=torch.int32)
+    _sssp_tensor(fn, "changed", changed, torch.int32, (n_rounds,), dev)
+    st = _lib.SsspState(dist.data_ptr(), pred.data_ptr(), (C.c_int64 * 2)(0, 0))
+    links = _lib.SsspLinks(link_idx.data_ptr(), link_len.data_ptr(), (C.c_int64 * 2)(0, 0))
+    with _on_device(dev):
+        _lib.check(lib.dcx_sssp_run(dev.index, C.byref(g), Q, C.byref(links), k, C.byref(st), round0, n_rounds, _ptr(changed),
+                                    _stream(dev)))
+    return changed
+
+
+def sssp_extract_paths(rowptr, col, weight, nodes, dist, pred, rounds_done, mode, starts, goals, goal_idx, goal_len, direct_len, W,
+                       out=None):
+    """the routes of Q queries after rounds_done rounds of sssp_run (dcx_sssp_extract_paths): (path [Q, W, dof] float32, count
+    [Q] int32, length [Q] float32) on the state's GPU.  mode [Q] int32: 0 no path, 1 the two-point path (start, goal) of length
+    direct_len, 2 the shortest route through the goal links goal_idx / goal_len [Q, k].  count[q] = n where the n waypoints
+    fit and were written, -n where n > W (the row is left as it is: zeros), 0 without a route; W = 0 asks for the sizes
+    alone.  `out`: the [Q, W, dof] tensor to write into.  One launch on torch's current stream, nothing read back."""
+    fn = "sssp_extract_paths"
+    lib = _lib.require_gpu()
+    g, N, dev = _sssp_graph(fn, rowptr, col, weight)
+    if not isinstance(dist, torch.Tensor) or dist.dim() != 3:
+        raise ValueError(f"{fn}: dist must be a float32 tensor [2, N, Q]")
+    Q = int(dist.shape[2])
+    _sssp_tensor(fn, "dist", dist, torch.float32, (2, N, Q), dev)
+    _sssp_tensor(fn, "pred", pred, torch.int32, (N, Q), dev)
+    if not isinstance(nodes, torch.Tensor) or nodes.dim() != 2:
+        raise ValueError(f"{fn}: nodes must be a float32 tensor [N, dof]")
+    dof = int(nodes.shape[1])
+    _sssp_tensor(fn, "nodes", nodes, torch.float32, (N, dof), dev)
+    if not isinstance(goal_idx, torch.Tensor) or goal_idx.dim() != 2:
+        raise ValueError(f"{fn}: goal_idx must be an int32 tensor [Q, k]")
+    k = int(goal_idx.shape[1])
+    _sssp_tensor(fn, "goal_idx", goal_idx, torch.int32, (Q, k), dev)
+    _sssp_tensor(fn, "goal_len", goal_len, torch.float32, (Q, k), dev)
+    _sssp_tensor(fn, "mode", mode, torch.int32, (Q,), dev)
+    _sssp_tensor(fn, "starts", starts, torch.float32, (Q, dof), dev)
+    _sssp_tensor(fn, "goals", goals, torch.float32, (Q, dof), dev)
+    _sssp_tensor(fn, "direct_len", direct_len, torch.float32, (Q,), dev)
+    W, rounds_done = int(W), int(rounds_done)
+    if W < 0 or rounds_done < 1:
+        raise ValueError(f"{fn}: W must be >= 0 and rounds_done >= 1")
+    path = torch.zeros((Q, W, dof), device=dev, dtype=torch.float32) if out is None else out
+    _sssp_tensor(fn, "out", path, torch.float32, (Q, W, dof), dev)
+    count = torch.zeros(Q, device=dev, dtype=torch.int32)
+    length = torch.full((Q,), float("inf"), device=dev, dtype=torch.float32)
+    st = _lib.SsspState(dist.data_ptr(), pred.data_ptr(), (C.c_int64 * 2)(0, 0))
+    links = _lib.SsspLinks(goal_idx.data_ptr(), goal_len.data_ptr(), (C.c_int64 * 2)(0, 0))
+    with _on_device(dev):
+        _lib.check(lib.dcx_sssp_extract_paths(dev.index, C.byref(g), _ptr(nodes), dof, C.byref(st), rounds_done, Q, k, _ptr(mode),
+                                              _ptr(starts), _ptr(goals), C.byref(links), _ptr(direct_len), _ptr(path), _ptr(count),
+                                              _ptr(length), W, _stream(dev)))
+    return path, count, length
+
+
 def compose_path_cost(edge_cost, paths, dof):
     """[T] costs of paths [T, W, dof] from an edge-cost callable edge_cost(qa, qb, open_end) under the max_step rule: the
     open-ended edges p[i] -> p[i + 1] plus the zero-length edge p[-1] -> p[-1] (its one sample is p[-1]) cover the points of

@@ -22,6 +22,7 @@
 #include "knn_kernel.h"
 #include "rrt_kernel.h"
 #include "shortcut_kernel.h"
+#include "sssp_kernel.h"
 
 using namespace dcx;
 
@@ -2706,6 +2707,101 @@ int dcx_rrt_extract_paths(int device, const dcx_rrt_state* state, int64_t R, int
     a.W = W;
     const hipError_t e = launch_rrt_extract(a, (hipStream_t)stream);
     if (e != hipSuccess) return fail_hip(e, "extract launch");
+    return DCX_OK;
+}
+
+// ---- roadmap queries (sssp_kernel.h): both calls share the checks of the graph, the state and the sizes ----------------------
+static int sssp_check(const dcx_graph* g, const dcx_sssp_state* st, const dcx_sssp_links* links, int64_t Q, int32_t k) {
+    if (!g || !st || !links) return fail(DCX_ERR_INVALID, "sssp: graph, state or links is NULL");
+    if (Q < 0 || g->N < 0 || g->nnz < 0) return fail(DCX_ERR_INVALID, "sssp: Q < 0, N < 0 or nnz < 0");
+    if (k < 1 || k > DCX_KNN_MAX_K) return fail(DCX_ERR_INVALID, "sssp: k must be in [1, DCX_KNN_MAX_K]");
+    if (g->reserved[0] || g->reserved[1] || st->reserved[0] || st->reserved[1] || links->reserved[0] || links->reserved[1])
+        return fail(DCX_ERR_INVALID, "sssp: reserved fields must be 0");
+    return DCX_OK;
+}
+
+// (Q > 0) the pointers both calls read, then what int32 indexing and one launch take
+static int sssp_check_state(const dcx_graph* g, const dcx_sssp_state* st, int64_t Q) {
+    if (!g->rowptr || (g->nnz > 0 && (!g->col || !g->weight))) return fail(DCX_ERR_INVALID, "sssp: rowptr, col or weight is NULL");
+    if (g->N > 0 && (!st->dist || !st->pred)) return fail(DCX_ERR_INVALID, "sssp: dist or pred is NULL");
+    if (g->N > INT32_MAX - 1 || g->nnz > INT32_MAX || (g->N > 0 && Q > INT32_MAX / g->N))
+        return fail(DCX_ERR_UNSUPPORTED, "sssp: N, nnz or N * Q beyond int32 indexing");
+    if (Q > INT32_MAX || !sssp_grid_ok(g->N, Q)) return fail(DCX_ERR_UNSUPPORTED, "sssp: more query blocks than one launch takes");
+    return DCX_OK;
+}
+
+int dcx_sssp_run(int device, const dcx_graph* graph, int64_t Q, const dcx_sssp_links* links, int32_t k, const dcx_sssp_state* state,
+                 int32_t round0, int32_t n_rounds, int32_t* changed, void* stream) {
+    if (int rc = sssp_check(graph, state, links, Q, k)) return rc;
+    if (round0 < 0) return fail(DCX_ERR_INVALID, "sssp: round0 < 0");
+    if (n_rounds < 0) return fail(DCX_ERR_INVALID, "sssp: n_rounds < 0");
+    if (Q == 0) return DCX_OK;
+    if (int rc = sssp_check_state(graph, state, Q)) return rc;
+    if (n_rounds > 0 && !changed) return fail(DCX_ERR_INVALID, "sssp: changed is NULL");
+    if (round0 == 0 && n_rounds > 0 && (!links->idx || !links->len)) return fail(DCX_ERR_INVALID, "sssp: a link array is NULL");
+    if (round0 > INT32_MAX - n_rounds) return fail(DCX_ERR_UNSUPPORTED, "sssp: round0 + n_rounds beyond int32");
+    if (n_rounds == 0) return DCX_OK;
+    if (int rc = set_device(device)) return rc;
+    hipStream_t st = (hipStream_t)stream;
+    if (const hipError_t e = launch_sssp_zero(changed, n_rounds, st); e != hipSuccess) return fail_hip(e, "sssp flags launch");
+    if (graph->N == 0) return DCX_OK;   // no node: nothing to relax, nothing changes
+    SsspArgs a{};
+    a.rowptr = graph->rowptr;
+    a.col = graph->col;
+    a.weight = graph->weight;
+    a.link_idx = links->idx;
+    a.link_len = links->len;
+    a.dist = state->dist;
+    a.pred = state->pred;
+    a.N = (int32_t)graph->N;
+    a.nnz = (int32_t)graph->nnz;
+    a.Q = (int32_t)Q;
+    a.k = k;
+    for (int32_t i = 0; i < n_rounds; ++i) {
+        const int32_t t = round0 + i;
+        const hipError_t e = t == 0 ? launch_sssp_init(a, changed + i, st)
+                                    : launch_sssp_relax(a, t, i > 0 ? changed + i - 1 : nullptr, changed + i, st);
+        if (e != hipSuccess) return fail_hip(e, "sssp round launch");
+    }
+    return DCX_OK;
+}
+
+int dcx_sssp_extract_paths(int device, const dcx_graph* graph, const float* nodes, int32_t dof, const dcx_sssp_state* state,
+                           int32_t rounds_done, int64_t Q, int32_t k, const int32_t* mode, const float* starts, const float* goals,
+                           const dcx_sssp_links* goal_links, const float* direct_len, float* path, int32_t* count, float* length,
+                           int32_t W, void* stream) {
+    if (int rc = sssp_check(graph, state, goal_links, Q, k)) return rc;
+    if (dof < 1 || dof > 64) return fail(DCX_ERR_INVALID, "sssp: dof must be in [1, 64]");
+    if (rounds_done < 1) return fail(DCX_ERR_INVALID, "sssp: rounds_done < 1");
+    if (W < 0) return fail(DCX_ERR_INVALID, "sssp: W < 0");
+    if (Q == 0) return DCX_OK;
+    if (int rc = sssp_check_state(graph, state, Q)) return rc;
+    if (!goal_links->idx || !goal_links->len) return fail(DCX_ERR_INVALID, "sssp: a link array is NULL");
+    if (graph->N > 0 && !nodes) return fail(DCX_ERR_INVALID, "sssp: nodes is NULL");
+    if (!mode || !starts || !goals || !direct_len || !count || !length)
+        return fail(DCX_ERR_INVALID, "sssp: mode, starts, goals, direct_len, count or length is NULL");
+    if (W > 0 && !path) return fail(DCX_ERR_INVALID, "sssp: path is NULL with W > 0");
+    if (int rc = set_device(device)) return rc;
+    SsspExtractArgs a{};
+    a.nodes = nodes;
+    a.dist = state->dist + (graph->N > 0 ? (int64_t)((rounds_done - 1) & 1) * graph->N * Q : 0);
+    a.pred = state->pred;
+    a.mode = mode;
+    a.starts = starts;
+    a.goals = goals;
+    a.goal_idx = goal_links->idx;
+    a.goal_len = goal_links->len;
+    a.direct_len = direct_len;
+    a.path = path;
+    a.count = count;
+    a.length = length;
+    a.N = (int32_t)graph->N;
+    a.Q = (int32_t)Q;
+    a.k = k;
+    a.dof = dof;
+    a.W = W;
+    const hipError_t e = launch_sssp_extract(a, (hipStream_t)stream);
+    if (e != hipSuccess) return fail_hip(e, "sssp extract launch");
     return DCX_OK;
 }
 

@@ -6,13 +6,17 @@ dist2 is bit for bit the squared edge length `check_motions(query, point, wrap=.
 a node set into the undirected edge list of a PRM, and `Roadmap` chains it with a checker's `check_motions` and scipy's
 Dijkstra.  The checker is any object with `is_collision(q)` (or `collision(q)`) and `check_motions(starts, targets,
 max_step=..., wrap=...)`: DiffCo, the collision_checkers facades, HybridForwardKinematicsDiffCo.
+
+`Roadmap.query_batch` is the multi-query half: Q start/goal pairs answered by synchronous min-plus relaxation over the roadmap's
+CSR (the fused HIP calls _ops.sssp_run and _ops.sssp_extract_paths; `host_sssp` and `host_extract_paths` state the same contract
+in torch ops: CPU tensors, the referee and the baseline), the routes in one [Q, W, dof] tensor (`RoadmapPaths`).
 """
 import numpy as np
 import torch
 
 from . import _ops
 
-__all__ = ["knn", "host_knn", "knn_edges", "Roadmap"]
+__all__ = ["knn", "host_knn", "knn_edges", "Roadmap", "RoadmapPaths", "host_sssp", "host_extract_paths"]
 
 _EMPTY = torch.iinfo(torch.int64).max   # the key of an unfilled slot: above every real key (bits(dist2) << 32 | index)
 
@@ -99,6 +103,145 @@ def knn_edges(nodes, k, wrap=None, max_dist=None, transform=None):
     return torch.stack([torch.div(keys, max(N, 1), rounding_mode="floor"), keys % max(N, 1)], dim=1)
 
 
+def _bits_key(cand, slot):
+    """int64 keys bits(cand) << 32 | slot: among non-negative floats the order of the keys is that of (value, slot), +inf last"""
+    return (cand.contiguous().view(torch.int32).to(torch.int64) << 32) | slot
+
+
+def host_sssp(rowptr, col, weight, link_idx, link_len, rounds=None, state_bytes=1 << 28):
+    """dcx_sssp_run's contract (include/dcx.h, "roadmap queries") in plain torch ops on the tensors' own device: Jacobi rounds
+    of the min-plus relaxation over the symmetric CSR (rowptr [N + 1], col, weight [nnz]) for the Q queries whose start
+    links are link_idx / link_len [Q, k] (-1 = no link).  Every candidate is one rounded float32 add, the first minimum in
+    row order wins (keys bits(cand) << 32 | slot and a min), and dist / pred change on a strict decrease only.
+    Returns (dist [N, Q] float32, pred [N, Q] int32, changed int32 [rounds]): the state after `rounds` rounds, round 0 (the
+    links) included; rounds=None runs until a round changes nothing, that round included (at most N + 1).
+    The rows are padded to the largest degree and the queries taken in chunks, so that a chunk's keys stay under
+    `state_bytes`."""
+    rowptr, col, weight = torch.as_tensor(rowptr), torch.as_tensor(col), torch.as_tensor(weight)
+    link_idx, link_len = torch.as_tensor(link_idx), torch.as_tensor(link_len)
+    dev = rowptr.device
+    N, Q = len(rowptr) - 1, len(link_idx)
+    if rowptr.dim() != 1 or N < 0 or col.shape != weight.shape or col.dim() != 1 or link_idx.dim() != 2 or link_idx.shape != link_len.shape:
+        raise ValueError("host_sssp: rowptr [N + 1], col and weight [nnz], link_idx and link_len [Q, k]")
+    cap = N + 1 if rounds is None else int(rounds)
+    if cap < 0:
+        raise ValueError("host_sssp: rounds must be >= 0")
+    rp = rowptr.to(torch.int64)
+    nnz = len(col)
+    deg = rp[1:] - rp[:-1]
+    D = int(deg.max()) if N > 0 else 0
+    slot = torch.arange(D, device=dev)
+    valid = slot[None, :] < deg[:, None]                                             # [N, D]
+    ent = (rp[:-1, None] + slot[None, :]).clamp(max=max(nnz - 1, 0))
+    nb = col.to(torch.int64)[ent] if nnz else torch.zeros((N, D), dtype=torch.int64, device=dev)
+    valid = valid & (nb >= 0) & (nb < N)
+    nb = nb.clamp(0, max(N - 1, 0))
+    w = weight.to(torch.float32)[ent] if nnz else torch.zeros((N, D), dtype=torch.float32, device=dev)
+    li = link_idx.to(torch.int64)
+    real = (li >= 0) & (li < N)
+    dist = torch.full((N, Q), float("inf"), dtype=torch.float32, device=dev)
+    pred = torch.full((N, Q), -1, dtype=torch.int32, device=dev)
+    changed = torch.zeros(cap, dtype=torch.int32, device=dev)
+    if cap == 0 or Q == 0:
+        return dist, pred, changed
+    qq = torch.arange(Q, device=dev)[:, None].expand_as(li)
+    dist[li[real], qq[real]] = link_len.to(torch.float32)[real]
+    changed[0] = int(bool(real.any()))
+    if N == 0:
+        return dist, pred, changed
+    qc = max(1, int(state_bytes) // max(8 * N * max(D, 1), 1))
+    for t in range(1, cap):
+        if int(changed[t - 1]) == 0:
+            break   # (the rounds left change nothing either: their flags stay 0)
+        new = dist.clone()
+        any_change = False
+        for q0 in range(0, Q, qc):
+            old = dist[:, q0:q0 + qc]                                               # [N, Qc]
+            if D == 0:
+                continue
+            cand = old[nb] + w[:, :, None]                                          # [N, D, Qc]: one rounded add each
+            keys = torch.where(valid[:, :, None], _bits_key(cand, slot[None, :, None]), torch.full((), _EMPTY, dtype=torch.int64, device=dev))
+            best = keys.min(dim=1).values                                           # [N, Qc]
+            bc = torch.where(best == _EMPTY, torch.full_like(old, float("inf")), (best >> 32).to(torch.int32).view(torch.float32))
+            bu = torch.gather(nb, 1, (best & 0xFFFFFFFF).clamp(max=max(D - 1, 0)))
+            win = bc < old
+            new[:, q0:q0 + qc] = torch.where(win, bc, old)
+            pred[:, q0:q0 + qc] = torch.where(win, bu.to(torch.int32), pred[:, q0:q0 + qc])
+            any_change = any_change or bool(win.any())
+        dist = new
+        changed[t] = int(any_change)
+    return dist, pred, changed
+
+
+def host_extract_paths(nodes, dist, pred, mode, starts, goals, goal_idx, goal_len, direct_len, W=None):
+    """dcx_sssp_extract_paths' contract in plain torch ops on the tensors' own device: (path [Q, W, dof] in the nodes' dtype,
+    count [Q] int32, length [Q] float32) from the state (dist, pred [N, Q]) of host_sssp.  mode 0: no path; mode 1: (start,
+    goal) and direct_len; mode 2: the first goal slot, in slot order, with the least dist[goal_idx][q] + goal_len (one rounded
+    float32 add), then pred walked back to -1.  count[q] = n where the n waypoints fit in W and were written, -n where they
+    do not (the row stays zero), 0 without a route.  W=None: the longest route's size (at least 2)."""
+    nodes = torch.as_tensor(nodes)
+    dev = nodes.device
+    N, dof = nodes.shape
+    Q, k = goal_idx.shape
+    mode = torch.as_tensor(mode).to(device=dev, dtype=torch.int64)
+    gi = goal_idx.to(torch.int64)
+    real = (gi >= 0) & (gi < N) & (mode == 2)[:, None]
+    qq = torch.arange(Q, device=dev)
+    slot = torch.arange(k, device=dev)[None, :]
+    if N > 0:
+        cand = dist[gi.clamp(0, N - 1), qq[:, None]] + goal_len.to(torch.float32)
+    else:
+        cand = torch.full((Q, k), float("inf"), dtype=torch.float32, device=dev)
+    keys = torch.where(real, _bits_key(cand, slot), torch.full((), _EMPTY, dtype=torch.int64, device=dev))
+    best = keys.min(dim=1).values if k > 0 else torch.full((Q,), _EMPTY, dtype=torch.int64, device=dev)
+    inf = torch.full((Q,), float("inf"), dtype=torch.float32, device=dev)
+    length = torch.where(best == _EMPTY, inf, (best >> 32).to(torch.int32).view(torch.float32))
+    routed = length < inf                                                            # (an inf or NaN sum is no route)
+    last = torch.where(routed, torch.gather(gi, 1, (best & 0xFFFFFFFF).clamp(max=max(k - 1, 0))[:, None])[:, 0], torch.full_like(best, -1))
+    # the walks, goal side first: chain[h, q] is the node h hops before the goal link's, -1 past the walk's end
+    chain = []
+    cur = last
+    while bool((cur >= 0).any()):
+        if len(chain) >= N:                                                          # a walk that has not ended after N nodes
+            routed = routed & (cur < 0)
+            break
+        chain.append(cur)
+        cur = torch.where(cur >= 0, pred[cur.clamp(min=0), qq].to(torch.int64), cur)
+    chain = torch.stack(chain) if chain else torch.zeros((0, Q), dtype=torch.int64, device=dev)
+    depth = (chain >= 0).sum(dim=0) * routed
+    length = torch.where(mode == 1, torch.as_tensor(direct_len).to(device=dev, dtype=torch.float32), torch.where(routed, length, inf))
+    n = torch.where(mode == 1, torch.full_like(depth, 2), torch.where(routed, depth + 2, torch.zeros_like(depth)))
+    if W is None:
+        W = max(int(n.max()) if Q else 0, 2)
+    W = int(W)
+    fits = (n > 0) & (n <= W)
+    count = torch.where(fits, n, -n).to(torch.int32)
+    path = torch.zeros((Q, W, dof), dtype=nodes.dtype, device=dev)
+    qf = fits.nonzero().reshape(-1)
+    if len(qf):
+        path[qf, 0] = torch.as_tensor(starts).to(device=dev, dtype=nodes.dtype)[qf]
+        path[qf, n[qf] - 1] = torch.as_tensor(goals).to(device=dev, dtype=nodes.dtype)[qf]
+    on = (chain >= 0) & (fits & routed & (mode == 2))[None, :]
+    h, q = on.nonzero(as_tuple=True)
+    if len(h):
+        path[q, depth[q] - h] = nodes[chain[h, q]]
+    return path, count, length
+
+
+class RoadmapPaths:
+    """What Roadmap.query_batch returns: path [Q, W, dof], count [Q] int32 (n where query q's n waypoints are in path[q, :n],
+    0 where there is no route, -n where n > W), length [Q] float32 (+inf without a route), mode [Q] int32 (0 an endpoint
+    collides, 1 the direct motion is free, 2 over the roadmap), rounds (relaxation rounds run, round 0 included) and route
+    ('fused' or 'host').  `path, count` go into shortcut_paths as they are."""
+
+    def __init__(self, path, count, length, mode, rounds, route):
+        self.path, self.count, self.length, self.mode, self.rounds, self.route = path, count, length, mode, rounds, route
+
+    def paths(self):
+        """a list with, per query, its waypoints [n, dof] or None"""
+        return [self.path[q, :n] if n > 0 else None for q, n in enumerate(self.count.tolist())]
+
+
 class _Checker:
     """the two calls a roadmap needs, whatever the checker calls them: `is_collision` (DiffCo) or `collision` (the facades,
     whose scores keep a trailing class axis), and `check_motions`"""
@@ -135,6 +278,7 @@ class Roadmap:
         w = lengths.detach().cpu().numpy().astype(np.float64)
         self.graph = csr_matrix((np.concatenate([w, w]), (np.concatenate([e[:, 0], e[:, 1]]), np.concatenate([e[:, 1], e[:, 0]]))),
                                 shape=(n, n))
+        self._csr = None
 
     @classmethod
     def build(cls, checker, nodes, k, max_step, wrap=None, max_dist=None, **check_kw):
@@ -155,6 +299,123 @@ class Roadmap:
         q = torch.as_tensor(q).reshape(-1, self.nodes.shape[1])
         idx, d2 = knn(q, self.nodes, 1, wrap=self.wrap_mask)
         return idx[:, 0], d2[:, 0]
+
+    def csr(self):
+        """(rowptr int32 [n + 1], col int32 [nnz], weight float32 [nnz]) on the nodes' device: the roadmap as the symmetric CSR
+        dcx_sssp_run reads (every edge in both rows, each row sorted by col).  Built once from `edges` and `lengths`."""
+        if self._csr is None:
+            n, dev = len(self.nodes), self.nodes.device
+            e = self.edges.to(dev)
+            w = self.lengths.detach().to(device=dev, dtype=torch.float32)
+            i, j = torch.cat([e[:, 0], e[:, 1]]), torch.cat([e[:, 1], e[:, 0]])
+            order = torch.sort(i * max(n, 1) + j).indices      # (i, j) pairs are distinct: no tie to break
+            rowptr = torch.zeros(n + 1, dtype=torch.int64, device=dev)
+            rowptr[1:] = torch.cumsum(torch.bincount(i, minlength=n), dim=0)
+            self._csr = (rowptr.to(torch.int32), j[order].to(torch.int32).contiguous(), torch.cat([w, w])[order].contiguous())
+        return self._csr
+
+    STATE_BUDGET = 1 << 28   # bytes of relaxation state query_batch holds at a time: 12 bytes per (node, query)
+
+    def query_batch(self, starts, goals, k=None, rounds_per_call=8, max_rounds=None, max_waypoints=None, route=None):
+        """`query` for Q start/goal pairs at once, as a RoadmapPaths: the shortest routes over the roadmap in one
+        [Q, W, dof] tensor that goes into shortcut_paths as it is.  The checker is called three times whatever Q is (the 2Q
+        endpoints, the Q direct motions, the 2Qk links to each endpoint's k nearest nodes); the shortest paths are the fixed
+        point of synchronous min-plus relaxation in float32 (include/dcx.h, "roadmap queries"), so a length is the float32 sum
+        of its route's segments in path order, where `query` sums in float64.
+        Device tensors take the fused calls (_ops.sssp_run in chunks of `rounds_per_call` rounds, one flag slice read back
+        per chunk, until a round changes nothing or `max_rounds`, default the number of nodes, have run; then
+        _ops.sssp_extract_paths), CPU tensors host_sssp and host_extract_paths; `route` ('fused' / 'host') forces one.
+        `max_waypoints`: W; None sizes it by the longest route (one more number read back).  The queries are taken in chunks
+        of Q such that the relaxation state (two float32 distance buffers and an int32 predecessor per node and query) stays
+        within STATE_BUDGET = 256 MiB."""
+        nodes, mask = self.nodes, self.wrap_mask
+        dev, dof, n = nodes.device, nodes.shape[1], len(nodes)
+        starts = torch.as_tensor(starts).reshape(-1, dof).to(device=dev, dtype=nodes.dtype)
+        goals = torch.as_tensor(goals).reshape(-1, dof).to(device=dev, dtype=nodes.dtype)
+        Q = len(starts)
+        if len(goals) != Q:
+            raise ValueError(f"query_batch: {Q} starts and {len(goals)} goals")
+        if route is None:
+            route = "fused" if dev.type == "cuda" else "host"
+        if route not in ("fused", "host") or (route == "fused" and dev.type != "cuda"):
+            raise ValueError("query_batch: route is 'fused' (a roadmap on a GPU) or 'host'")
+        kk = min(int(self.k if k is None else k), 64)
+        if kk < 1 or int(rounds_per_call) < 1:
+            raise ValueError("query_batch: k and rounds_per_call must be >= 1")
+        # 1, 2: the endpoints and the direct motions
+        ends = torch.cat([starts, goals])
+        if Q:
+            hit = self.checker.collides(ends).to(dev)
+            bad = hit[:Q] | hit[Q:]
+        else:
+            bad = torch.zeros(0, dtype=torch.bool, device=dev)
+        blocked = self.checker.motions(starts, goals, self.max_step, mask, **self.check_kw)
+        direct_len = _ops.wrapped_delta(starts, goals, mask).norm(dim=1).to(torch.float32)
+        two = torch.full((Q,), 2, dtype=torch.int32, device=dev)
+        mode = torch.where(bad, torch.zeros_like(two), torch.where(blocked, two, torch.ones_like(two)))
+        # 3: every endpoint's links to its k nearest nodes, one fixed-shape batch (an unfilled slot checks a node against itself)
+        if Q and n:
+            idx, _ = knn(ends, nodes, kk, wrap=mask)
+            qa = ends.repeat_interleave(kk, dim=0)
+            qb = nodes[idx.to(torch.int64).clamp(min=0).reshape(-1)]
+            free = ~self.checker.motions(qa, qb, self.max_step, mask, **self.check_kw).reshape(2 * Q, kk)
+            link_idx = torch.where(free & (idx >= 0), idx, torch.full_like(idx, -1))
+            link_len = _ops.wrapped_delta(qa, qb, mask).norm(dim=1).to(torch.float32).reshape(2 * Q, kk)
+        else:
+            link_idx = torch.full((2 * Q, kk), -1, dtype=torch.int32, device=dev)
+            link_len = torch.zeros((2 * Q, kk), dtype=torch.float32, device=dev)
+        # (only the queries that go over the roadmap keep their start links: the others would only hold the rounds up)
+        start_idx = torch.where((mode == 2)[:, None], link_idx[:Q], torch.full_like(link_idx[:Q], -1)).contiguous()
+        start_len, goal_idx, goal_len = link_len[:Q].contiguous(), link_idx[Q:].contiguous(), link_len[Q:].contiguous()
+        # 4, 5: relaxation and extraction, a chunk of queries at a time
+        rowptr, col, weight = self.csr()
+        cap = max(1, int(n if max_rounds is None else max_rounds))
+        rpc = int(rounds_per_call)
+        qchunk = max(1, self.STATE_BUDGET // (12 * max(n, 1)))
+        qchunk -= qchunk % 64 if qchunk >= 64 else 0
+        fused = route == "fused"
+        if fused:
+            nodes32, starts32, goals32 = (t.to(torch.float32).contiguous() for t in (nodes, starts, goals))
+        W = None if max_waypoints is None else int(max_waypoints)
+        parts, rounds = [], 0
+        for q0 in range(0, Q, qchunk):
+            s = slice(q0, q0 + qchunk)
+            Qc = len(mode[s])
+            if fused:
+                dist = torch.empty((2, n, Qc), dtype=torch.float32, device=dev)
+                pred = torch.empty((n, Qc), dtype=torch.int32, device=dev)
+                done, took = 0, None
+                while done < cap and took is None:
+                    m = min(rpc, cap - done)
+                    flags = _ops.sssp_run(rowptr, col, weight, start_idx[s], start_len[s], dist, pred, done, m).tolist()
+                    if 0 in flags:
+                        took = done + flags.index(0) + 1
+                    done += m
+                args = (rowptr, col, weight, nodes32, dist, pred, done, mode[s], starts32[s], goals32[s], goal_idx[s], goal_len[s],
+                        direct_len[s])
+                Wc = W
+                if Wc is None:
+                    Wc = max(-int(_ops.sssp_extract_paths(*args, 0)[1].min()), 2)
+                part = _ops.sssp_extract_paths(*args, Wc)
+            else:
+                d, p, flags = host_sssp(rowptr, col, weight, start_idx[s], start_len[s], rounds=cap)
+                flags = flags.tolist()
+                took = flags.index(0) + 1 if 0 in flags else None
+                part = host_extract_paths(nodes, d, p, mode[s], starts[s], goals[s], goal_idx[s], goal_len[s], direct_len[s], W)
+            rounds = max(rounds, cap if took is None else took)
+            parts.append(part)
+        if len(parts) == 1:
+            path, count, length = parts[0]
+        else:
+            Wmax = max([p[0].shape[1] for p in parts] + [2 if W is None else W])
+            path = torch.zeros((Q, Wmax, dof), dtype=torch.float32 if fused else nodes.dtype, device=dev)
+            q0 = 0
+            for p in parts:
+                path[q0:q0 + len(p[0]), :p[0].shape[1]] = p[0]
+                q0 += len(p[0])
+            count = torch.cat([p[1] for p in parts]) if parts else torch.zeros(0, dtype=torch.int32, device=dev)
+            length = torch.cat([p[2] for p in parts]) if parts else torch.zeros(0, dtype=torch.float32, device=dev)
+        return RoadmapPaths(path, count, length, mode, rounds, route)
 
     def query(self, start, goal, k=None):
         """(waypoints [W, dof], length) of the shortest route start -> goal over the roadmap, or None where an endpoint

@@ -796,6 +796,75 @@ int dcx_path_shortcut_run(const dcx_model* m, const dcx_shortcut_state* state, i
 int dcx_rrt_extract_paths(int device, const dcx_rrt_state* state, int64_t R, int32_t cap, int32_t dof,
                           float* path, int32_t* count, int32_t W, void* stream);
 
+/* ---- roadmap queries (added under DCX_VERSION 109) -------------------------------------------------------- */
+/* Shortest paths over a roadmap for Q start/goal pairs at once: synchronous min-plus relaxation in fp32 without atomics
+ * (dcx_sssp_run), then the routes as rows of one [Q, W, dof] tensor (dcx_sssp_extract_paths), on `device`, without a model.
+ * Graph (dcx_graph; caller-owned device memory): the roadmap as a symmetric CSR
+ *   rowptr [N + 1] int32, col [nnz] int32, weight [nnz] float
+ *   Every row is sorted by col, each neighbour appears once, there are no self loops, and an entry (v, u, w) has its mirror
+ *   (u, v, w).  Weights are lengths: >= 0, possibly +inf, never NaN.  The calls do NOT check any of this.  Memory safety alone
+ *   is kept: a row's range is clipped to 0 .. nnz and an entry whose col lies outside 0 .. N - 1 is skipped.
+ * State (dcx_sssp_state; caller-owned device memory), for Q independent queries:
+ *   dist [2, N, Q] float     two buffers, node-major and query-minor: dist[b][v][q]
+ *   pred [N, Q] int32        the node the current dist[v][q] was reached from, -1 for none
+ * Round 0 (initialisation): query q has up to k start links (links->idx[q, s], links->len[q, s]), s < k.  An index of -1 means
+ *   no link (as does any index outside 0 .. N - 1); the real indices of one query are distinct.  dist[0][v][q] is the link's
+ *   length where v is linked and +inf elsewhere, dist[1] is +inf everywhere, pred is -1 everywhere.  changed is 1 iff any
+ *   link of any query is real.
+ * Round t >= 1 reads dist[(t - 1) & 1] only (dist_old) and writes dist[t & 1] (dist_new).  For node v and query q:
+ *   cand = min over the entries e of row v, in row order, of (dist_old[col_e][q] + weight_e), each sum a single rounded fp32 add
+ *   u    = the col of the first entry that attains the minimum
+ *   cand < dist_old[v][q]:  dist_new[v][q] = cand and pred[v][q] = u
+ *   otherwise:              dist_new[v][q] = dist_old[v][q] and pred[v][q] is untouched (an inf or NaN candidate never wins)
+ *   pred changes on a strict decrease only, so the predecessor walks end at a linked node within N steps, zero-length edges
+ *   and weights absorbed by rounding included; fp32 addition is monotone, so the fixed point is unique: that of a Dijkstra
+ *   accumulating in fp32 from the links.
+ * dcx_sssp_run enqueues rounds round0 .. round0 + n_rounds - 1 on the caller's stream; links is read when round0 == 0 only.
+ *   changed [n_rounds] device int32: the call zeroes it, then changed[t - round0] = 1 is stored (a plain store) by whoever
+ *   changed a (v, q) in round t.  A round whose predecessor INSIDE THE SAME CALL has changed == 0 returns at once: both buffers
+ *   are equal by then.  The state after round t does not depend on how the rounds are split over calls or on the launch
+ *   geometry; once a round reports 0 every later round does, and dist[0] == dist[1].
+ *   Launches: one that zeroes changed, then round 0 as a fill and a scatter and every later round as one launch (a wave per
+ *   (node, 64 queries)).  No allocation, no synchronisation, no atomic, nothing read back: the call can be captured.
+ * dcx_sssp_extract_paths, one launch, a wave per query; rounds_done >= 1 rounds have run and dist[(rounds_done - 1) & 1] is
+ * read.  mode [Q] int32, starts / goals [Q, dof], nodes [N, dof], goal links as the start links, direct_len [Q]:
+ *   mode 0 (an endpoint collides; any value but 1 and 2 is taken as 0): count = 0, length = +inf
+ *   mode 1 (the direct motion is free): the path is (start, goal), n = 2, length = direct_len[q]
+ *   mode 2: length = min over the goal slots s, in slot order, of (dist[idx[q, s]][q] + len[q, s]), the first slot attaining it
+ *     wins; +inf (or no real slot) means no route: count = 0.  Otherwise pred is walked back from that node to -1, at most N
+ *     steps (a walk that does not end by then, or leaves 0 .. N - 1: count = 0, length = +inf), and the path is start, the
+ *     walk's nodes in forward order, goal: n = hops + 2 waypoints.  length is thus a float32 sum in path order.
+ *   count[q] = n where the n waypoints fit in W and were written to path[q, 0 .. n - 1]; -n where n > W, the row left as it is:
+ *   W = 0 (path may then be NULL) asks for the sizes alone.  length[q] is set either way.
+ * Argument errors (DCX_ERR_INVALID, before any device work): NULL graph / state / links; a negative Q, N or nnz; k outside
+ *   1 .. DCX_KNN_MAX_K; dof outside 1 .. 64; round0 < 0, n_rounds < 0, rounds_done < 1, W < 0; a reserved field not 0; with
+ *   Q > 0 a NULL rowptr, dist, pred, changed (n_rounds > 0), link array (dcx_sssp_run: when round0 == 0), col or weight
+ *   (nnz > 0), nodes (N > 0), mode, starts, goals, direct_len, count or length, or a NULL path with W > 0.  N, nnz or N * Q
+ *   beyond int32 indexing and a grid beyond one launch are DCX_ERR_UNSUPPORTED.  Q == 0 returns 0 and touches nothing.       */
+typedef struct dcx_graph {
+    const int32_t* rowptr;   /* [N + 1]                                                                     */
+    const int32_t* col;      /* [nnz]                                                                       */
+    const float*   weight;   /* [nnz]                                                                       */
+    int64_t  N, nnz;
+    int64_t  reserved[2];    /* 0                                                                           */
+} dcx_graph;
+typedef struct dcx_sssp_state {
+    float*   dist;           /* [2, N, Q]                                                                   */
+    int32_t* pred;           /* [N, Q]                                                                      */
+    int64_t  reserved[2];    /* 0                                                                           */
+} dcx_sssp_state;
+typedef struct dcx_sssp_links {
+    const int32_t* idx;      /* [Q, k]: -1 = no link                                                        */
+    const float*   len;      /* [Q, k]                                                                      */
+    int64_t  reserved[2];    /* 0                                                                           */
+} dcx_sssp_links;
+int dcx_sssp_run(int device, const dcx_graph* graph, int64_t Q, const dcx_sssp_links* links, int32_t k,
+                 const dcx_sssp_state* state, int32_t round0, int32_t n_rounds, int32_t* changed, void* stream);
+int dcx_sssp_extract_paths(int device, const dcx_graph* graph, const float* nodes, int32_t dof, const dcx_sssp_state* state,
+                           int32_t rounds_done, int64_t Q, int32_t k, const int32_t* mode, const float* starts, const float* goals,
+                           const dcx_sssp_links* goal_links, const float* direct_len, float* path, int32_t* count, float* length,
+                           int32_t W, void* stream);
+
 /* ---- kernel-perceptron trainer (producer of the path's state) ----------------------- */
 /* DiffCo.train_perceptron kernel_perceptrons.py:98-137 and MultiDiffCo.train_perceptron
  * deprecated/MultiDiffCo.py:50-83 as one persistent launch: worst-margin search, lazily filled kernel rows,
