@@ -312,6 +312,14 @@ def knn(queries, points, k, wrap=None, max_dist=None, exclude_self=False, self_o
     return idx, dist2
 
 
+def _check_tensor(label, t, dtype, shape, dev, kind=None):
+    """raises ValueError unless t is a contiguous `dtype` tensor of `shape` on `dev`.  `label`: how the message names it;
+    `kind`: how it names the expected tensor where that is not "<dtype> tensor <shape>"."""
+    if not isinstance(t, torch.Tensor) or t.dtype != dtype or t.device != dev or not t.is_contiguous() or tuple(t.shape) != tuple(shape):
+        raise ValueError(f"{label} must be a contiguous {kind or f'{dtype} tensor {tuple(shape)}'} on {dev}")
+    return t
+
+
 def rrt_extract_paths(state, W, out=None):
     """the solved paths of an RRT state (dcx_rrt_extract_paths; `state` maps nodes [R, 2, cap, dof] float32, parent [R, 2, cap],
     status [R], link [R, 2] (int32) to contiguous tensors on one GPU): (path [R, W, dof] float32, count [R] int32) there.
@@ -326,29 +334,19 @@ def rrt_extract_paths(state, W, out=None):
     kinds = dict(nodes=torch.float32, parent=torch.int32, status=torch.int32, link=torch.int32)
     shapes = dict(nodes=(R, 2, cap, dof), parent=(R, 2, cap), status=(R,), link=(R, 2))
     for name, dt in kinds.items():
-        t = state[name]
-        if t.dtype != dt or t.device != dev or not t.is_contiguous() or tuple(t.shape) != shapes[name]:
-            raise ValueError(f"rrt_extract_paths: state[{name!r}] must be a contiguous {dt} tensor {shapes[name]} on {dev}")
+        _check_tensor(f"rrt_extract_paths: state[{name!r}]", state[name], dt, shapes[name], dev)
     W = int(W)
     if W < 0:
         raise ValueError("rrt_extract_paths: W must be >= 0")
     if out is None:
         path = torch.zeros((R, W, dof), device=dev, dtype=torch.float32)
     else:
-        path = out
-        if path.dtype != torch.float32 or path.device != dev or not path.is_contiguous() or tuple(path.shape) != (R, W, dof):
-            raise ValueError(f"rrt_extract_paths: out must be a contiguous float32 tensor {(R, W, dof)} on {dev}")
+        path = _check_tensor("rrt_extract_paths: out", out, torch.float32, (R, W, dof), dev, kind=f"float32 tensor {(R, W, dof)}")
     count = torch.zeros(R, device=dev, dtype=torch.int32)
     st = _lib.RrtState(state["nodes"].data_ptr(), state["parent"].data_ptr(), 0, state["status"].data_ptr(), state["link"].data_ptr(), 0)
     with _on_device(dev):
         _lib.check(lib.dcx_rrt_extract_paths(dev.index, C.byref(st), R, cap, dof, _ptr(path), _ptr(count), W, _stream(dev)))
     return path, count
-
-
-def _sssp_tensor(fn, name, t, dtype, shape, dev):
-    if not isinstance(t, torch.Tensor) or t.dtype != dtype or t.device != dev or not t.is_contiguous() or tuple(t.shape) != tuple(shape):
-        raise ValueError(f"{fn}: {name} must be a contiguous {dtype} tensor {tuple(shape)} on {dev}")
-    return t
 
 
 def _sssp_graph(fn, rowptr, col, weight):
@@ -358,12 +356,12 @@ def _sssp_graph(fn, rowptr, col, weight):
         raise ValueError(f"{fn}: rowptr must be an int32 tensor [N + 1] on a GPU")
     dev = rowptr.device
     N = len(rowptr) - 1
-    _sssp_tensor(fn, "rowptr", rowptr, torch.int32, (N + 1,), dev)
+    _check_tensor(f"{fn}: rowptr", rowptr, torch.int32, (N + 1,), dev)
     if not isinstance(col, torch.Tensor) or col.dim() != 1:
         raise ValueError(f"{fn}: col must be an int32 tensor [nnz]")
     nnz = len(col)
-    _sssp_tensor(fn, "col", col, torch.int32, (nnz,), dev)
-    _sssp_tensor(fn, "weight", weight, torch.float32, (nnz,), dev)
+    _check_tensor(f"{fn}: col", col, torch.int32, (nnz,), dev)
+    _check_tensor(f"{fn}: weight", weight, torch.float32, (nnz,), dev)
     return _lib.Graph(rowptr.data_ptr(), col.data_ptr() if nnz else 0, weight.data_ptr() if nnz else 0, N, nnz, (C.c_int64 * 2)(0, 0)), N, dev
 
 
@@ -379,19 +377,19 @@ def sssp_run(rowptr, col, weight, link_idx, link_len, dist, pred, round0, n_roun
     if not isinstance(dist, torch.Tensor) or dist.dim() != 3:
         raise ValueError(f"{fn}: dist must be a float32 tensor [2, N, Q]")
     Q = int(dist.shape[2])
-    _sssp_tensor(fn, "dist", dist, torch.float32, (2, N, Q), dev)
-    _sssp_tensor(fn, "pred", pred, torch.int32, (N, Q), dev)
+    _check_tensor(f"{fn}: dist", dist, torch.float32, (2, N, Q), dev)
+    _check_tensor(f"{fn}: pred", pred, torch.int32, (N, Q), dev)
     if not isinstance(link_idx, torch.Tensor) or link_idx.dim() != 2:
         raise ValueError(f"{fn}: link_idx must be an int32 tensor [Q, k]")
     k = int(link_idx.shape[1])
-    _sssp_tensor(fn, "link_idx", link_idx, torch.int32, (Q, k), dev)
-    _sssp_tensor(fn, "link_len", link_len, torch.float32, (Q, k), dev)
+    _check_tensor(f"{fn}: link_idx", link_idx, torch.int32, (Q, k), dev)
+    _check_tensor(f"{fn}: link_len", link_len, torch.float32, (Q, k), dev)
     round0, n_rounds = int(round0), int(n_rounds)
     if round0 < 0 or n_rounds < 0:
         raise ValueError(f"{fn}: round0 and n_rounds must be >= 0")
     if changed is None:
         changed = torch.zeros(n_rounds, device=dev, dtype=torch.int32)
-    _sssp_tensor(fn, "changed", changed, torch.int32, (n_rounds,), dev)
+    _check_tensor(f"{fn}: changed", changed, torch.int32, (n_rounds,), dev)
     st = _lib.SsspState(dist.data_ptr(), pred.data_ptr(), (C.c_int64 * 2)(0, 0))
     links = _lib.SsspLinks(link_idx.data_ptr(), link_len.data_ptr(), (C.c_int64 * 2)(0, 0))
     with _on_device(dev):
@@ -413,26 +411,26 @@ def sssp_extract_paths(rowptr, col, weight, nodes, dist, pred, rounds_done, mode
     if not isinstance(dist, torch.Tensor) or dist.dim() != 3:
         raise ValueError(f"{fn}: dist must be a float32 tensor [2, N, Q]")
     Q = int(dist.shape[2])
-    _sssp_tensor(fn, "dist", dist, torch.float32, (2, N, Q), dev)
-    _sssp_tensor(fn, "pred", pred, torch.int32, (N, Q), dev)
+    _check_tensor(f"{fn}: dist", dist, torch.float32, (2, N, Q), dev)
+    _check_tensor(f"{fn}: pred", pred, torch.int32, (N, Q), dev)
     if not isinstance(nodes, torch.Tensor) or nodes.dim() != 2:
         raise ValueError(f"{fn}: nodes must be a float32 tensor [N, dof]")
     dof = int(nodes.shape[1])
-    _sssp_tensor(fn, "nodes", nodes, torch.float32, (N, dof), dev)
+    _check_tensor(f"{fn}: nodes", nodes, torch.float32, (N, dof), dev)
     if not isinstance(goal_idx, torch.Tensor) or goal_idx.dim() != 2:
         raise ValueError(f"{fn}: goal_idx must be an int32 tensor [Q, k]")
     k = int(goal_idx.shape[1])
-    _sssp_tensor(fn, "goal_idx", goal_idx, torch.int32, (Q, k), dev)
-    _sssp_tensor(fn, "goal_len", goal_len, torch.float32, (Q, k), dev)
-    _sssp_tensor(fn, "mode", mode, torch.int32, (Q,), dev)
-    _sssp_tensor(fn, "starts", starts, torch.float32, (Q, dof), dev)
-    _sssp_tensor(fn, "goals", goals, torch.float32, (Q, dof), dev)
-    _sssp_tensor(fn, "direct_len", direct_len, torch.float32, (Q,), dev)
+    _check_tensor(f"{fn}: goal_idx", goal_idx, torch.int32, (Q, k), dev)
+    _check_tensor(f"{fn}: goal_len", goal_len, torch.float32, (Q, k), dev)
+    _check_tensor(f"{fn}: mode", mode, torch.int32, (Q,), dev)
+    _check_tensor(f"{fn}: starts", starts, torch.float32, (Q, dof), dev)
+    _check_tensor(f"{fn}: goals", goals, torch.float32, (Q, dof), dev)
+    _check_tensor(f"{fn}: direct_len", direct_len, torch.float32, (Q,), dev)
     W, rounds_done = int(W), int(rounds_done)
     if W < 0 or rounds_done < 1:
         raise ValueError(f"{fn}: W must be >= 0 and rounds_done >= 1")
     path = torch.zeros((Q, W, dof), device=dev, dtype=torch.float32) if out is None else out
-    _sssp_tensor(fn, "out", path, torch.float32, (Q, W, dof), dev)
+    _check_tensor(f"{fn}: out", path, torch.float32, (Q, W, dof), dev)
     count = torch.zeros(Q, device=dev, dtype=torch.int32)
     length = torch.full((Q,), float("inf"), device=dev, dtype=torch.float32)
     st = _lib.SsspState(dist.data_ptr(), pred.data_ptr(), (C.c_int64 * 2)(0, 0))
@@ -643,30 +641,16 @@ class ScoreModel:
         still answer -2).  A given max_samples reads nothing back (capturable).
         `wrap` (wrap_mask: an int bitmask or one bool per coordinate): those coordinates are angles on the circle and the
         edge runs along their shortest arc (dcx_check_motions_ex; the res rule's points are utils.anglin's)."""
-        if (res is None) == (max_step is None):
-            raise ValueError("check_motions takes exactly one of res and max_step")
-        mask = wrap_mask(wrap, self.dof)
-        qa32 = _f32(torch.as_tensor(qa).reshape(-1, self.dof), self.dev)
-        qb32 = _f32(torch.as_tensor(qb).reshape(-1, self.dof), self.dev)
-        if qa32.shape != qb32.shape:
-            raise ValueError(f"{len(qa32)} start and {len(qb32)} target configurations")
-        E = len(qa32)
-        if max_samples is None:
-            max_samples = int(res) if res is not None else motion_bound(qa32, qb32, max_step, wrap=mask)
-        opt = _lib.MotionOpts(int(res) if res is not None else 0, float(max_step) if max_step is not None else 0.0, int(max_samples), 0)
-        mg = None
-        if torch.is_tensor(margin) and margin.device == self.dev:
-            # a device tensor stays on the device (no copy through the host: the call can be captured in a graph)
-            mg = margin.detach().to(torch.float32).reshape(-1).expand(self.C).contiguous()
-        elif torch.is_tensor(margin) or not (isinstance(margin, (int, float)) and float(margin) == 0.0):
-            mg = torch.tensor(list(self.margins(margin)), dtype=torch.float32).to(self.dev)
+        qa32, qb32, E, res, max_step, max_samples, mask = self._motion_args("check_motions", qa, qb, res, max_step, max_samples, wrap)
+        opt = _lib.MotionOpts(res, max_step, max_samples, 0)
+        mg = self._motion_margin(margin)
         first = torch.empty(E, device=self.dev, dtype=torch.int32)
         n = torch.empty(E, device=self.dev, dtype=torch.int32)
         nbytes = self._lib.dcx_motion_work_bytes(self._h, E)
-        work = torch.empty(max(int(nbytes), 1), device=self.dev, dtype=torch.uint8)
+        work = self._work(nbytes)
         with _on_device(self.dev):
             _lib.check(self._lib.dcx_check_motions_ex(self._h, _ptr(qa32), _ptr(qb32), E, C.byref(opt), _ptr(mg), _ptr(first),
-                                                      _ptr(n), _ptr(work), int(nbytes), mask, self._st()))
+                                                      _ptr(n), _ptr(work), nbytes, mask, self._st()))
         return first, n
 
     def rrt_connect_run(self, state, samples, round0, range, max_step, max_samples, cap, margin=0., wrap=None):
@@ -679,17 +663,15 @@ class ScoreModel:
                      solved_round=torch.int32)
         shapes = dict(nodes=(R, 2, cap, self.dof), parent=(R, 2, cap), count=(R, 2), status=(R,), link=(R, 2), solved_round=(R,))
         for name, dt in kinds.items():
-            t = state[name]
-            if t.dtype != dt or t.device != self.dev or not t.is_contiguous() or tuple(t.shape) != shapes[name]:
-                raise ValueError(f"rrt_connect_run: state[{name!r}] must be a contiguous {dt} tensor {shapes[name]} on {self.dev}")
-        if samples.dtype != torch.float32 or samples.device != self.dev or not samples.is_contiguous() or samples.shape[3] != self.dof:
-            raise ValueError(f"rrt_connect_run: samples must be a contiguous float32 tensor [T, R, P, {self.dof}] on {self.dev}")
+            _check_tensor(f"rrt_connect_run: state[{name!r}]", state[name], dt, shapes[name], self.dev)
+        _check_tensor("rrt_connect_run: samples", samples, torch.float32, (T, R, P, self.dof), self.dev,
+                      kind=f"float32 tensor [T, R, P, {self.dof}]")
         st = _lib.RrtState(*(state[n].data_ptr() for n in kinds))
         opt = _lib.RrtOpts(float(range), float(max_step), int(max_samples), P, int(cap), 0, wrap_mask(wrap, self.dof),
                            (C.c_int64 * 2)(0, 0))
         mg = self._motion_margin(margin)
-        nbytes = int(self._lib.dcx_rrt_work_bytes(self._h, R, P))
-        work = torch.empty(max(nbytes, 1), device=self.dev, dtype=torch.uint8)
+        nbytes = self._lib.dcx_rrt_work_bytes(self._h, R, P)
+        work = self._work(nbytes)
         with _on_device(self.dev):
             _lib.check(self._lib.dcx_rrt_connect_run(self._h, C.byref(st), R, _ptr(samples), T, int(round0), C.byref(opt), _ptr(mg),
                                                      _ptr(work), nbytes, self._st()))
@@ -709,23 +691,43 @@ class ScoreModel:
         kinds = dict(path=torch.float32, count=torch.int32, accepted=torch.int32)
         shapes = dict(path=(R, W, self.dof), count=(R,), accepted=(R,))
         for name, dt in kinds.items():
-            t = state[name]
-            if t.dtype != dt or t.device != self.dev or not t.is_contiguous() or tuple(t.shape) != shapes[name]:
-                raise ValueError(f"shortcut_run: state[{name!r}] must be a contiguous {dt} tensor {shapes[name]} on {self.dev}")
-        if draws.dtype != torch.float32 or draws.device != self.dev or not draws.is_contiguous() or draws.shape[3] != 2:
-            raise ValueError(f"shortcut_run: draws must be a contiguous float32 tensor [T, R, P, 2] on {self.dev}")
+            _check_tensor(f"shortcut_run: state[{name!r}]", state[name], dt, shapes[name], self.dev)
+        _check_tensor("shortcut_run: draws", draws, torch.float32, (T, R, P, 2), self.dev, kind="float32 tensor [T, R, P, 2]")
         st = _lib.ShortcutState(*(state[n].data_ptr() for n in kinds))
         opt = _lib.ShortcutOpts(float(max_step), int(max_samples), P, W, wrap_mask(wrap, self.dof), (C.c_int64 * 2)(0, 0))
         mg = self._motion_margin(margin)
-        nbytes = int(self._lib.dcx_path_shortcut_work_bytes(self._h, R, P))
-        work = torch.empty(max(nbytes, 1), device=self.dev, dtype=torch.uint8)
+        nbytes = self._lib.dcx_path_shortcut_work_bytes(self._h, R, P)
+        work = self._work(nbytes)
         with _on_device(self.dev):
             _lib.check(self._lib.dcx_path_shortcut_run(self._h, C.byref(st), R, _ptr(draws), T, C.byref(opt), _ptr(mg), _ptr(work),
                                                        nbytes, self._st()))
 
+    def _motion_args(self, name, qa, qb, res, max_step, max_samples, wrap):
+        """what every motion call starts with: (qa32, qb32 [E, dof] fp32 on the device, E, res, max_step, max_samples, mask) with
+        the rule as the options struct holds it (0 / 0.0 for the one not given).  max_samples=None is `res`, or under max_step
+        motion_bound's (one read-back)."""
+        if (res is None) == (max_step is None):
+            raise ValueError(f"{name} takes exactly one of res and max_step")
+        mask = wrap_mask(wrap, self.dof)
+        # (as_tensor costs 0.3 us even on a tensor: skipping it there pays for this method's own call)
+        qa32 = _f32((qa if isinstance(qa, torch.Tensor) else torch.as_tensor(qa)).reshape(-1, self.dof), self.dev)
+        qb32 = _f32((qb if isinstance(qb, torch.Tensor) else torch.as_tensor(qb)).reshape(-1, self.dof), self.dev)
+        if qa32.shape != qb32.shape:
+            raise ValueError(f"{len(qa32)} start and {len(qb32)} target configurations")
+        if max_samples is None:
+            max_samples = int(res) if res is not None else motion_bound(qa32, qb32, max_step, wrap=mask)
+        return (qa32, qb32, len(qa32), int(res) if res is not None else 0, float(max_step) if max_step is not None else 0.0,
+                int(max_samples), mask)
+
+    def _work(self, nbytes):
+        """a call's workspace of nbytes (what its dcx_*_work_bytes answers): torch's caching allocator is the per-device cache
+        (a freed block is reused on its stream, no hipMalloc)"""
+        return torch.empty(max(nbytes, 1), device=self.dev, dtype=torch.uint8)
+
     def _motion_margin(self, margin):
         """the motion calls' margin argument: None (all zero), or [C] device floats (a device tensor stays on the device)"""
         if torch.is_tensor(margin) and margin.device == self.dev:
+            # (no copy through the host: the call can be captured in a graph)
             return margin.detach().to(torch.float32).reshape(-1).expand(self.C).contiguous()
         if torch.is_tensor(margin) or not (isinstance(margin, (int, float)) and float(margin) == 0.0):
             return torch.tensor(list(self.margins(margin)), dtype=torch.float32).to(self.dev)
@@ -741,28 +743,18 @@ class ScoreModel:
         Edges over `max_samples` answer NaN.  max_samples=None under max_step derives the bound from the longest edge (one
         read-back); a given bound reads nothing back (capturable).  Four launches (C > 1: five) on torch's current stream.
         `wrap`: as check_motions (dcx_motion_cost_ex); the gradients' unit direction is that of the wrapped edge."""
-        if (res is None) == (max_step is None):
-            raise ValueError("motion_cost takes exactly one of res and max_step")
-        mask = wrap_mask(wrap, self.dof)
-        qa32 = _f32(torch.as_tensor(qa).reshape(-1, self.dof), self.dev)
-        qb32 = _f32(torch.as_tensor(qb).reshape(-1, self.dof), self.dev)
-        if qa32.shape != qb32.shape:
-            raise ValueError(f"{len(qa32)} start and {len(qb32)} target configurations")
-        E = len(qa32)
-        if max_samples is None:
-            max_samples = int(res) if res is not None else motion_bound(qa32, qb32, max_step, wrap=mask)
-        opt = _lib.MotionCostOpts(int(res) if res is not None else 0, float(max_step) if max_step is not None else 0.0,
-                                  int(max_samples), 1 if open_end else 0)
+        qa32, qb32, E, res, max_step, max_samples, mask = self._motion_args("motion_cost", qa, qb, res, max_step, max_samples, wrap)
+        opt = _lib.MotionCostOpts(res, max_step, max_samples, 1 if open_end else 0)
         mg = self._motion_margin(margin)
         cost = torch.empty(E, device=self.dev, dtype=torch.float32)
         ga = torch.empty((E, self.dof), device=self.dev, dtype=torch.float32)
         gb = torch.empty((E, self.dof), device=self.dev, dtype=torch.float32)
         n = torch.empty(E, device=self.dev, dtype=torch.int32)
-        nbytes = self._lib.dcx_motion_cost_work_bytes(self._h, E, int(max_samples))
-        work = torch.empty(max(int(nbytes), 1), device=self.dev, dtype=torch.uint8)
+        nbytes = self._lib.dcx_motion_cost_work_bytes(self._h, E, max_samples)
+        work = self._work(nbytes)
         with _on_device(self.dev):
             _lib.check(self._lib.dcx_motion_cost_ex(self._h, _ptr(qa32), _ptr(qb32), E, C.byref(opt), _ptr(mg), float(weight),
-                                                    _ptr(cost), _ptr(ga), _ptr(gb), _ptr(n), _ptr(work), int(nbytes), mask,
+                                                    _ptr(cost), _ptr(ga), _ptr(gb), _ptr(n), _ptr(work), nbytes, mask,
                                                     self._st()))
         return cost, ga, gb, n
 
@@ -791,17 +783,8 @@ class ScoreModel:
         with respect to qa[e] and qb[e] through that sample.  Edges over `max_samples`: NaN / -2 / -1, NaN gradient rows.
         `res`, `max_step`, `margin`, `max_samples` (None: the bound of motion_bound; a given bound reads nothing back and
         the call can be captured) and `wrap` as check_motions."""
-        if (res is None) == (max_step is None):
-            raise ValueError("motion_worst takes exactly one of res and max_step")
-        mask = wrap_mask(wrap, self.dof)
-        qa32 = _f32(torch.as_tensor(qa).reshape(-1, self.dof), self.dev)
-        qb32 = _f32(torch.as_tensor(qb).reshape(-1, self.dof), self.dev)
-        if qa32.shape != qb32.shape:
-            raise ValueError(f"{len(qa32)} start and {len(qb32)} target configurations")
-        E = len(qa32)
-        if max_samples is None:
-            max_samples = int(res) if res is not None else motion_bound(qa32, qb32, max_step, wrap=mask)
-        opt = _lib.MotionOpts(int(res) if res is not None else 0, float(max_step) if max_step is not None else 0.0, int(max_samples), 0)
+        qa32, qb32, E, res, max_step, max_samples, mask = self._motion_args("motion_worst", qa, qb, res, max_step, max_samples, wrap)
+        opt = _lib.MotionOpts(res, max_step, max_samples, 0)
         mg = self._motion_margin(margin)
         worst = torch.empty(E, device=self.dev, dtype=torch.float32)
         idx = torch.empty(E, device=self.dev, dtype=torch.int32)
@@ -810,10 +793,10 @@ class ScoreModel:
         ga = torch.empty((E, self.dof), device=self.dev, dtype=torch.float32) if grad else None
         gb = torch.empty((E, self.dof), device=self.dev, dtype=torch.float32) if grad else None
         nbytes = self._lib.dcx_motion_worst_work_bytes(self._h, E)
-        work = torch.empty(max(int(nbytes), 1), device=self.dev, dtype=torch.uint8)
+        work = self._work(nbytes)
         with _on_device(self.dev):
             _lib.check(self._lib.dcx_motion_worst(self._h, _ptr(qa32), _ptr(qb32), E, C.byref(opt), _ptr(mg), _ptr(worst), _ptr(idx),
-                                                  _ptr(cls), _ptr(n), _ptr(ga), _ptr(gb), _ptr(work), int(nbytes), mask, self._st()))
+                                                  _ptr(cls), _ptr(n), _ptr(ga), _ptr(gb), _ptr(work), nbytes, mask, self._st()))
         return (worst, idx, cls, n, ga, gb) if grad else (worst, idx, cls, n)
 
     def motion_worst(self, qa, qb, res=None, max_step=None, margin=0., max_samples=None, wrap=None):
@@ -839,25 +822,16 @@ class ScoreModel:
         max_samples is given and lo / hi are numbers or device tensors).  A dict of device tensors: verdict, first_hit,
         n_samples, n_uncertain [E] int32, unc_total [1] int64, unc_edge, unc_sample [unc_cap] int32, unc_q [unc_cap, dof]
         fp32 (None without want_q).  Only the first min(unc_total, unc_cap) list entries are written."""
-        if (res is None) == (max_step is None):
-            raise ValueError("motion_band takes exactly one of res and max_step")
-        mask = wrap_mask(wrap, self.dof)
-        qa32 = _f32(torch.as_tensor(qa).reshape(-1, self.dof), self.dev)
-        qb32 = _f32(torch.as_tensor(qb).reshape(-1, self.dof), self.dev)
-        if qa32.shape != qb32.shape:
-            raise ValueError(f"{len(qa32)} start and {len(qb32)} target configurations")
+        qa32, qb32, E, res, max_step, max_samples, mask = self._motion_args("motion_band", qa, qb, res, max_step, max_samples, wrap)
         on_dev = lambda t: torch.is_tensor(t) and t.device == self.dev
         if not (on_dev(lo) or on_dev(hi)):   # (device thresholds are not read back: there hit wins, as in the C call)
             bad = [c for c, (l, h) in enumerate(zip(self.margins(lo), self.margins(hi))) if l > h]
             if bad:
                 raise ValueError(f"motion_band: lo > hi for class {bad[0]}")
-        E = len(qa32)
         cap = int(unc_cap)
         if cap < 0:
             raise ValueError("motion_band: a negative list capacity")
-        if max_samples is None:
-            max_samples = int(res) if res is not None else motion_bound(qa32, qb32, max_step, wrap=mask)
-        opt = _lib.MotionOpts(int(res) if res is not None else 0, float(max_step) if max_step is not None else 0.0, int(max_samples), 0)
+        opt = _lib.MotionOpts(res, max_step, max_samples, 0)
         lo_t, hi_t = self._motion_margin(lo), self._motion_margin(hi)
         i32 = lambda *shape: torch.empty(shape, device=self.dev, dtype=torch.int32)
         r = dict(verdict=i32(E), first_hit=i32(E), n_samples=i32(E), n_uncertain=i32(E),
@@ -865,11 +839,11 @@ class ScoreModel:
                  unc_q=torch.empty((cap, self.dof), device=self.dev, dtype=torch.float32) if want_q else None)
         out = _lib.MotionBandOut(*(_ptr(r[k]) for k in ("verdict", "first_hit", "n_samples", "n_uncertain", "unc_total",
                                                         "unc_edge", "unc_sample", "unc_q")), cap)
-        nbytes = self._lib.dcx_motion_band_work_bytes(self._h, E, int(max_samples))
-        work = torch.empty(max(int(nbytes), 1), device=self.dev, dtype=torch.uint8)
+        nbytes = self._lib.dcx_motion_band_work_bytes(self._h, E, max_samples)
+        work = self._work(nbytes)
         with _on_device(self.dev):
             _lib.check(self._lib.dcx_motion_band(self._h, _ptr(qa32), _ptr(qb32), E, C.byref(opt), _ptr(lo_t), _ptr(hi_t),
-                                                 C.byref(out), _ptr(work), int(nbytes), mask, self._st()))
+                                                 C.byref(out), _ptr(work), nbytes, mask, self._st()))
         return r
 
     def motion_band(self, qa, qb, lo, hi, res=None, max_step=None, max_samples=None, wrap=None, max_uncertain=None, want_q=True):
@@ -979,9 +953,20 @@ class _ScoreFn(torch.autograd.Function):
         return g.to(device=ctx.in_device, dtype=ctx.in_dtype).reshape(ctx.in_shape), None
 
 
-class _MotionCostFn(torch.autograd.Function):
-    """cost = motion_cost(qa, qb) [E]: ONE dcx_motion_cost call forms the cost and both endpoint gradients; backward scales
-    them by the upstream (no second derivatives)."""
+class _EndpointGradFn(torch.autograd.Function):
+    """f(qa, qb, model, kw) whose forward saves d f[e] / d qa[e] and d f[e] / d qb[e] in the inputs' shapes: backward scales them
+    by the upstream of the first output (no second derivatives)"""
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, up, *_):
+        ga, gb = ctx.saved_tensors
+        up = up.reshape((-1,) + (1,) * (ga.dim() - 1))
+        return (up * ga if ctx.needs_input_grad[0] else None), (up * gb if ctx.needs_input_grad[1] else None), None, None
+
+
+class _MotionCostFn(_EndpointGradFn):
+    """cost = motion_cost(qa, qb) [E]: ONE dcx_motion_cost call forms the cost and both endpoint gradients"""
 
     @staticmethod
     def forward(ctx, qa, qb, model, kw):
@@ -990,17 +975,9 @@ class _MotionCostFn(torch.autograd.Function):
                               gb.to(device=qb.device, dtype=qb.dtype).reshape(qb.shape))
         return cost.to(device=qa.device, dtype=qa.dtype)
 
-    @staticmethod
-    @once_differentiable
-    def backward(ctx, gc):
-        ga, gb = ctx.saved_tensors
-        up = gc.reshape((-1,) + (1,) * (ga.dim() - 1))
-        return (up * ga if ctx.needs_input_grad[0] else None), (up * gb if ctx.needs_input_grad[1] else None), None, None
 
-
-class _MotionWorstFn(torch.autograd.Function):
-    """(worst, idx, cls) = motion_worst(qa, qb): ONE dcx_motion_worst call forms the peak and both endpoint gradients; backward
-    scales them by the upstream (no second derivatives)."""
+class _MotionWorstFn(_EndpointGradFn):
+    """(worst, idx, cls) = motion_worst(qa, qb): ONE dcx_motion_worst call forms the peak and both endpoint gradients"""
 
     @staticmethod
     def forward(ctx, qa, qb, model, kw):
@@ -1009,10 +986,3 @@ class _MotionWorstFn(torch.autograd.Function):
                               gb.to(device=qb.device, dtype=qb.dtype).reshape(qb.shape))
         ctx.mark_non_differentiable(idx, cls)
         return worst.to(device=qa.device, dtype=qa.dtype), idx, cls
-
-    @staticmethod
-    @once_differentiable
-    def backward(ctx, gw, _gi, _gc):
-        ga, gb = ctx.saved_tensors
-        up = gw.reshape((-1,) + (1,) * (ga.dim() - 1))
-        return (up * ga if ctx.needs_input_grad[0] else None), (up * gb if ctx.needs_input_grad[1] else None), None, None

@@ -7,6 +7,8 @@ foreign kernel callable the same algorithm runs as a host loop below, filling ke
 the reference does.  Behaviour restated from the reference: DiffCo.train_perceptron
 kernel_perceptrons.py:98-137 and MultiDiffCo.train_perceptron deprecated/MultiDiffCo.py:50-83.
 """
+from typing import NamedTuple
+
 import torch
 
 from . import _ops
@@ -171,6 +173,12 @@ def kernel_spec(kernel_func):
     return spec
 
 
+def _foreign(m, transform):
+    """True where `transform` is a foreign callable: the model `m` has no FK of its own, the transform runs in torch and only
+    what follows it fuses.  The motion calls then take the host route."""
+    return m.desc.kind == 0 and transform is not None
+
+
 class FusedScorer:
     """Caches the ScoreModel built from (transform, kernel, supports, weights) and rebuilds it when any of them
     changes.  The cache holds strong references to the two tensors it was built from and compares by identity plus
@@ -236,7 +244,7 @@ class FusedScorer:
         dev = point.device if point.device.type == "cuda" else (
             support_feat.device if support_feat.device.type == "cuda" else None)
         m = self.model(transform, kernel_func, support_feat, weights, dev)
-        if m.desc.kind == 0 and transform is not None:
+        if _foreign(m, transform):
             # foreign transform: run it in torch (its own autograd), fuse everything after it
             feats = transform(point)
             return m.score(feats.reshape(len(feats), -1))
@@ -249,10 +257,61 @@ class FusedScorer:
         self._key, self._model, self._sup, self._w, self._fast = None, None, None, None, None
 
 
-# ---- batched motion checks ---------------------------------------------------------------------------------------------------
+# ---- the motion calls' source ------------------------------------------------------------------------------------------------
+class MotionSource(NamedTuple):
+    """what a checker's motion calls run on: the checker itself (`owner.last_route` says which route the last call took:
+    "fused" or "host"), its FusedScorer and the state the scorer's model is built from.  A checker builds one per call."""
+    owner: object
+    fused: object
+    transform: object
+    kernel_func: object
+    support_feat: object
+    weights: object
+
+    def wrap_mask(self, wrap, dof):
+        """_ops.wrap_mask; True: the mask of the robot that owns `transform`"""
+        return _ops.wrap_mask(wrap, dof, self.transform)
+
+    def model(self, device=None):
+        """the ScoreModel, on `device` where that is a GPU, else where the supports live"""
+        sf = self.support_feat
+        dev = device if device is not None and device.type == "cuda" else (sf.device if sf.device.type == "cuda" else None)
+        return self.fused.model(self.transform, self.kernel_func, sf, self.weights, dev)
+
+    def score(self, p):
+        """the host route's score callable (keeps autograd)"""
+        return self.fused.score(self.transform, self.kernel_func, self.support_feat, self.weights, p)
+
+    def score_detached(self, p):
+        return self.score(p).detach()
+
+    def route(self, name, qa, qb, res, max_step, wrap):
+        """what every motion call starts with: (qa, qb, mask, model, host).  host is None on the fused route (no transform, or a
+        diffco_amd robot's fkine: one call into the library) and the endpoints as float32 on the model's device on the host
+        route (a foreign callable: the host composition over `score`).  The ValueErrors come before anything touches the
+        device."""
+        if (res is None) == (max_step is None):
+            raise ValueError(f"{name} takes exactly one of res and max_step")
+        qa, qb = torch.as_tensor(qa), torch.as_tensor(qb)
+        mask = self.wrap_mask(wrap, qa.shape[-1])
+        m = self.model(qa.device)
+        if _foreign(m, self.transform):
+            self.owner.last_route = "host"
+            return qa, qb, mask, m, (qa.to(device=m.dev, dtype=torch.float32), qb.to(device=m.dev, dtype=torch.float32))
+        self.owner.last_route = "fused"
+        return qa, qb, mask, m, None
+
+
+def _raise_over(name, over, hint="pass a larger max_samples or max_step"):
+    """raises ValueError for the edges flagged in `over` [E] bool: those over max_samples (a read-back)"""
+    if bool(over.any()):
+        bad = over.nonzero().reshape(-1)[:8].tolist()
+        raise ValueError(f"{name}: edges {bad} need more than max_samples samples ({hint})")
+
+
+# ---- the host compositions' samples ------------------------------------------------------------------------------------------
 def _wrap_points(pts, mask):
     """the masked coordinates of the points brought back to [-pi, pi) (utils.wrap2pi; slope 1 under autograd)"""
-    import torch
     from .utils import wrap2pi
     if not mask:
         return pts
@@ -260,43 +319,91 @@ def _wrap_points(pts, mask):
     return torch.where(on, wrap2pi(pts), pts)
 
 
-def _motion_samples(qa, qb, res, max_step, max_samples, wrap):
-    """every checked edge's points, materialised (line_predict's / dense_path's arithmetic; `wrap`, a bitmask: utils.anglin's
-    on the masked coordinates): (pts [N, dof], edge [N], k [N], n [E] the counts the edges need, ok [E] within the limit)"""
-    import torch
-    E, dev = len(qa), qa.device
+def _edge_counts(qa, qb, res, max_step, wrap, open_end=False):
+    """(d [E, dof], L [E], n [E]) of the edges qa[e] -> qb[e]: the delta (`wrap`, a bitmask: along the shortest arc of the
+    masked coordinates), its length (None under the res rule) and the sample count of the rule (open_end: without the target)"""
     d = _ops.wrapped_delta(qa, qb, wrap)
     if res is not None:
-        n = torch.full((E,), int(res), dtype=torch.int64, device=dev)
-        frac = None
-    else:
-        L = d.norm(dim=-1)
-        n = torch.ceil(L / max_step).to(torch.int64) + 1
-        frac = max_step / L
+        return d, None, torch.full((len(qa),), int(res), dtype=torch.int64, device=qa.device)
+    L = d.norm(dim=-1)
+    steps = torch.ceil(L / max_step).to(torch.int64)
+    return d, L, steps if open_end else steps + 1
+
+
+class _SamplePlan(NamedTuple):
+    """which samples a host composition materialises: the edges' (d, L, n) of _edge_counts, ok [E] the edges within the limit,
+    n_ok [E] their counts (0 for the others), and per sample its edge [N] and index k [N]; edge e's samples start at offs[e]"""
+    d: object
+    L: object
+    n: object
+    ok: object
+    n_ok: object
+    edge: object
+    offs: object
+    k: object
+
+
+def _sample_plan(qa, qb, res, max_step, max_samples, wrap, open_end=False):
+    """the one index plan of the host compositions: the rule's counts, the limit (max_samples; None: `res`, or
+    MOTION_MAX_SAMPLES under max_step), and the flat (edge, k) list of the edges within it"""
+    d, L, n = _edge_counts(qa, qb, res, max_step, wrap, open_end)
     limit = int(res) if (max_samples is None and res is not None) else (
         _ops.MOTION_MAX_SAMPLES if max_samples is None else int(max_samples))
     ok = n <= limit
     n_ok = torch.where(ok, n, torch.zeros_like(n))
-    edge = torch.repeat_interleave(torch.arange(E, device=dev), n_ok)
+    edge = torch.repeat_interleave(torch.arange(len(qa), device=qa.device), n_ok)
     offs = torch.cumsum(n_ok, 0) - n_ok
-    k = torch.arange(len(edge), device=dev) - offs[edge]
+    k = torch.arange(len(edge), device=qa.device) - offs[edge]
+    return _SamplePlan(d, L, n, ok, n_ok, edge, offs, k)
+
+
+def _res_points(qa, d, edge, k, res, wrap):
+    """the res rule's points (Perceptron.line_predict's; utils.anglin's on the masked coordinates)"""
+    return _wrap_points(qa[edge] + d[edge] * (k.to(qa.dtype) / int(res))[:, None], wrap)
+
+
+def _check_points(qa, qb, d, L, n, edge, k, res, max_step, wrap):
+    """sample k[i] of the edge edge[i] in the check form: line_predict's / dense_path's arithmetic, what dcx_check_motions
+    walks - the step vector d * (max_step / L) scaled by k, and qb itself at the last sample.  (d, L, n): _edge_counts."""
     if res is not None:
-        pts = _wrap_points(qa[edge] + d[edge] * (k.to(qa.dtype) / int(res))[:, None], wrap)
-    else:
-        pts = _wrap_points(qa[edge] + k.to(qa.dtype)[:, None] * (d[edge] * frac[edge][:, None]), wrap)
+        return _res_points(qa, d, edge, k, res, wrap)
+    frac = max_step / L
+    pts = _wrap_points(qa[edge] + k.to(qa.dtype)[:, None] * (d[edge] * frac[edge][:, None]), wrap)
+    last = k == n[edge] - 1
+    return torch.where(last[:, None], qb[edge], pts)
+
+
+def _grad_points(qa, qb, d, L, n, edge, k, res, max_step, wrap, open_end):
+    """sample k[i] of the edge edge[i] in the differentiable form, what dcx_motion_cost / dcx_motion_worst walk: the unit
+    direction u = d / L scaled by k * max_step (it rounds differently from the check form), and qb at the last sample of a
+    closed edge.  Differentiable with respect to qa and qb."""
+    if res is not None:
+        return _res_points(qa, d, edge, k, res, wrap)
+    # u = d / L differentiably (the sample counts are constants); L = 0 edges have only the target sample
+    Ld = L[:, None]
+    u = d / torch.where(Ld > 0, Ld, torch.ones_like(Ld))
+    pts = _wrap_points(qa[edge] + (k.to(qa.dtype) * max_step)[:, None] * u[edge], wrap)
+    if not open_end:
         last = k == n[edge] - 1
         pts = torch.where(last[:, None], qb[edge], pts)
-    return pts, edge, k, n, ok
+    return pts
 
 
+def _motion_samples(qa, qb, res, max_step, max_samples, wrap):
+    """every checked edge's points, materialised in the check form: (pts [N, dof], the plan)"""
+    p = _sample_plan(qa, qb, res, max_step, max_samples, wrap)
+    return _check_points(qa, qb, p.d, p.L, p.n, p.edge, p.k, res, max_step, wrap), p
+
+
+# ---- batched motion checks ---------------------------------------------------------------------------------------------------
 def host_motions(score_fn, qa, qb, res=None, max_step=None, margin=0., max_samples=None, wrap=0):
     """the composition a caller would write without dcx_check_motions: every edge's points (line_predict's / dense_path's
     arithmetic; `wrap`, a bitmask: utils.anglin's on the masked coordinates) materialised, ONE score launch over all of them,
     the first hit per edge.  Same answers, (first_hit, n_samples)."""
-    import torch
     qa, qb = qa.reshape(len(qa), -1), qb.reshape(len(qb), -1)
     E, dev = len(qa), qa.device
-    pts, edge, k, n, ok = _motion_samples(qa, qb, res, max_step, max_samples, wrap)
+    pts, p = _motion_samples(qa, qb, res, max_step, max_samples, wrap)
+    n, ok, edge, k = p.n, p.ok, p.edge, p.k
     first = torch.full((E,), -1, dtype=torch.int64, device=dev)
     if len(pts):
         s = score_fn(pts).reshape(len(pts), -1)
@@ -310,44 +417,26 @@ def host_motions(score_fn, qa, qb, res=None, max_step=None, margin=0., max_sampl
     return first.to(torch.int32), n.clamp(max=2 ** 31 - 1).to(torch.int32)
 
 
-def check_motions(owner, fused, transform, kernel_func, support_feat, weights, qa, qb, res=None, max_step=None, margin=0.,
-                  max_samples=None, score_fn=None, wrap=None):
-    """(first_hit, n_samples) of the motions qa[e] -> qb[e] on the model `fused` holds: one dcx_check_motions call where the
-    transform fuses (none, or a diffco_amd robot's fkine), else the host composition (a foreign callable: its points through
-    `score_fn` in one launch).  owner.last_route says which ran: "fused" or "host".  `wrap` (_ops.wrap_mask; True: the mask
-    of the robot that owns `transform`): those coordinates run along their shortest arc."""
-    import torch
-    if (res is None) == (max_step is None):
-        raise ValueError("check_motions takes exactly one of res and max_step")
-    qa, qb = torch.as_tensor(qa), torch.as_tensor(qb)
-    mask = _ops.wrap_mask(wrap, qa.shape[-1], transform)
-    dev = qa.device if qa.device.type == "cuda" else (support_feat.device if support_feat.device.type == "cuda" else None)
-    m = fused.model(transform, kernel_func, support_feat, weights, dev)
-    if m.desc.kind == 0 and transform is not None:
-        owner.last_route = "host"
-        qa32 = qa.to(device=m.dev, dtype=torch.float32)
-        qb32 = qb.to(device=m.dev, dtype=torch.float32)
-        fn = score_fn or (lambda p: fused.score(transform, kernel_func, support_feat, weights, p))
-        return host_motions(lambda p: fn(p).detach(), qa32, qb32, res, max_step, margin, max_samples, mask)
-    owner.last_route = "fused"
+def check_motions(src, qa, qb, res=None, max_step=None, margin=0., max_samples=None, wrap=None):
+    """(first_hit, n_samples) of the motions qa[e] -> qb[e] on the source's model: one dcx_check_motions call on the fused
+    route, the host composition on the host route (MotionSource.route; the points scored in one launch).  `wrap`
+    (_ops.wrap_mask; True: the mask of the robot that owns the transform): those coordinates run along their shortest arc."""
+    qa, qb, mask, m, host = src.route("check_motions", qa, qb, res, max_step, wrap)
+    if host is not None:
+        return host_motions(src.score_detached, *host, res, max_step, margin, max_samples, mask)
     return m.check_motions(qa, qb, res=res, max_step=max_step, margin=margin, max_samples=max_samples, wrap=mask)
 
 
-def _motion_model(fused, transform, kernel_func, support_feat, weights, device=None, margin=0.):
-    """(ScoreModel, margin) where check_motions above takes the fused route on these arguments, else None (a foreign transform:
+def _motion_model(src, device=None, margin=0.):
+    """(ScoreModel, margin) where check_motions above takes the fused route on this source, else None (a foreign transform:
     the host composition).  What a planner needs to enqueue the fused motion checks itself (rrt.rrt_connect)."""
-    dev = device if device is not None and device.type == "cuda" else (support_feat.device if support_feat.device.type == "cuda" else None)
-    m = fused.model(transform, kernel_func, support_feat, weights, dev)
-    if m.desc.kind == 0 and transform is not None:
-        return None
-    return m, margin
+    m = src.model(device)
+    return None if _foreign(m, src.transform) else (m, margin)
 
 
 def motion_answer(first, return_first):
     """the facades' answer: collides [E] bool (+ first_hit); raises for edges over max_samples (a read-back)"""
-    if bool((first == -2).any()):
-        bad = (first == -2).nonzero().reshape(-1)[:8].tolist()
-        raise ValueError(f"check_motions: edges {bad} need more than max_samples samples (pass a larger max_samples or max_step)")
+    _raise_over("check_motions", first == -2)
     hit = first >= 0
     return (hit, first) if return_first else hit
 
@@ -357,10 +446,10 @@ def host_motion_band(score_fn, qa, qb, lo, hi, res=None, max_step=None, max_samp
     """the composition a caller would write without dcx_motion_band: host_motions' samples materialised, ONE score launch over
     all of them, the two thresholds, a segment reduction per edge and a `nonzero` for the list.  ScoreModel.motion_band's
     outputs in its order: (verdict, first_hit, n_uncertain, unc_edge, unc_sample, unc_q)."""
-    import torch
     qa, qb = qa.reshape(len(qa), -1), qb.reshape(len(qb), -1)
     E, dev = len(qa), qa.device
-    pts, edge, k, n, ok = _motion_samples(qa, qb, res, max_step, max_samples, wrap)
+    pts, p = _motion_samples(qa, qb, res, max_step, max_samples, wrap)
+    ok, edge, k = p.ok, p.edge, p.k
     big = torch.iinfo(torch.int64).max
     first = torch.full((E,), -1, dtype=torch.int64, device=dev)
     n_unc = torch.zeros(E, dtype=torch.int64, device=dev)
@@ -386,38 +475,24 @@ def host_motion_band(score_fn, qa, qb, lo, hi, res=None, max_step=None, max_samp
     return (verdict.to(i32), first.to(i32), n_unc.to(i32), edge[at].to(i32), k[at].to(i32), pts[at] if want_q else None)
 
 
-def motion_band(owner, fused, transform, kernel_func, support_feat, weights, qa, qb, lo, hi, res=None, max_step=None,
-                max_samples=None, score_fn=None, wrap=None, want_q=True):
-    """(verdict, first_hit, n_uncertain, unc_edge, unc_sample, unc_q) of the motions qa[e] -> qb[e] on the model `fused` holds:
-    dcx_motion_band where the transform fuses (none, or a diffco_amd robot's fkine), else the host composition (a foreign
-    callable through `score_fn`).  owner.last_route says which ran: "fused" or "host".  Both read the list's length back.
-    Raises ValueError where lo > hi.  `wrap`: as check_motions."""
-    import torch
-    if (res is None) == (max_step is None):
-        raise ValueError("motion_band takes exactly one of res and max_step")
-    qa, qb = torch.as_tensor(qa), torch.as_tensor(qb)
-    mask = _ops.wrap_mask(wrap, qa.shape[-1], transform)
-    dev = qa.device if qa.device.type == "cuda" else (support_feat.device if support_feat.device.type == "cuda" else None)
-    m = fused.model(transform, kernel_func, support_feat, weights, dev)
+def motion_band(src, qa, qb, lo, hi, res=None, max_step=None, max_samples=None, wrap=None, want_q=True):
+    """(verdict, first_hit, n_uncertain, unc_edge, unc_sample, unc_q) of the motions qa[e] -> qb[e] on the source's model:
+    dcx_motion_band on the fused route, the host composition on the host route (MotionSource.route).  Both read the list's
+    length back.  Raises ValueError where lo > hi.  `wrap`: as check_motions."""
+    qa, qb, mask, m, host = src.route("motion_band", qa, qb, res, max_step, wrap)
     kw = dict(res=res, max_step=max_step, max_samples=max_samples, wrap=mask, want_q=want_q)
-    if m.desc.kind == 0 and transform is not None:
-        owner.last_route = "host"
+    if host is not None:
         lo_c, hi_c = list(m.margins(lo)), list(m.margins(hi))
         if any(l > h for l, h in zip(lo_c, hi_c)):
             raise ValueError("motion_band: lo > hi")
-        fn = score_fn or (lambda p: fused.score(transform, kernel_func, support_feat, weights, p))
-        qa_d, qb_d = qa.to(device=m.dev, dtype=torch.float32), qb.to(device=m.dev, dtype=torch.float32)
-        return host_motion_band(lambda p: fn(p).detach(), qa_d, qb_d, lo_c, hi_c, **kw)
-    owner.last_route = "fused"
+        return host_motion_band(src.score_detached, *host, lo_c, hi_c, **kw)
     return m.motion_band(qa, qb, lo, hi, **kw)
 
 
-def score_band(owner, fused, transform, kernel_func, support_feat, weights, q, lo, hi, score_fn=None):
+def score_band(src, q, lo, hi):
     """(label [B] int32, unc_idx [U] int64) of the configurations q: motion_band(q, q, res=1), one sample per "edge", on
     either route"""
-    import torch
-    verdict, _, _, unc_edge, _, _ = motion_band(owner, fused, transform, kernel_func, support_feat, weights, q, q, lo, hi, res=1,
-                                                score_fn=score_fn, want_q=False)
+    verdict, _, _, unc_edge, _, _ = motion_band(src, q, q, lo, hi, res=1, want_q=False)
     return verdict, unc_edge.to(torch.int64)
 
 
@@ -427,33 +502,11 @@ def host_motion_cost(score_fn, qa, qb, res=None, max_step=None, margin=0., weigh
     (check_motions' arithmetic; `wrap`, a bitmask: the wrapped delta and wrapped points, both of slope 1), scored through
     autograd, the hinge reduced per edge with index_add.  [E] costs, differentiable with respect to qa and qb; NaN for an
     edge over max_samples."""
-    import torch
     qa, qb = qa.reshape(len(qa), -1), qb.reshape(len(qb), -1)
     E, dev = len(qa), qa.device
-    d = _ops.wrapped_delta(qa, qb, wrap)
-    if res is not None:
-        n = torch.full((E,), int(res), dtype=torch.int64, device=dev)
-    else:
-        L = d.detach().norm(dim=-1)
-        steps = torch.ceil(L / max_step).to(torch.int64)
-        n = steps if open_end else steps + 1
-    limit = int(res) if (max_samples is None and res is not None) else (
-        _ops.MOTION_MAX_SAMPLES if max_samples is None else int(max_samples))
-    ok = n <= limit
-    n_ok = torch.where(ok, n, torch.zeros_like(n))
-    edge = torch.repeat_interleave(torch.arange(E, device=dev), n_ok)
-    offs = torch.cumsum(n_ok, 0) - n_ok
-    k = torch.arange(len(edge), device=dev) - offs[edge]
-    if res is not None:
-        pts = _wrap_points(qa[edge] + d[edge] * (k.to(qa.dtype) / int(res))[:, None], wrap)
-    else:
-        # u = d / L differentiably (the sample counts are constants); L = 0 edges have only the target sample
-        Ld = d.norm(dim=-1, keepdim=True)
-        u = d / torch.where(Ld > 0, Ld, torch.ones_like(Ld))
-        pts = _wrap_points(qa[edge] + (k.to(qa.dtype) * max_step)[:, None] * u[edge], wrap)
-        if not open_end:
-            last = k == n[edge] - 1
-            pts = torch.where(last[:, None], qb[edge], pts)
+    p = _sample_plan(qa, qb, res, max_step, max_samples, wrap, open_end)
+    ok, edge = p.ok, p.edge
+    pts = _grad_points(qa, qb, p.d, p.L, p.n, edge, p.k, res, max_step, wrap, open_end)
     cost = torch.zeros(E, dtype=qa.dtype, device=dev)
     if len(pts):
         s = score_fn(pts).reshape(len(pts), -1)
@@ -464,50 +517,31 @@ def host_motion_cost(score_fn, qa, qb, res=None, max_step=None, margin=0., weigh
     return torch.where(ok, cost, torch.full_like(cost, float("nan")))
 
 
-def motion_cost(owner, fused, transform, kernel_func, support_feat, weights, qa, qb, res=None, max_step=None, margin=0., weight=1.,
-                open_end=False, max_samples=None, score_fn=None, wrap=None):
-    """[E] differentiable motion costs on the model `fused` holds: one dcx_motion_cost call where the transform fuses (none, or
-    a diffco_amd robot's fkine), else the host composition (a foreign callable through `score_fn`).  owner.last_route says
-    which ran: "fused" or "host".  Raises ValueError for edges over max_samples (a read-back).  `wrap`: as check_motions."""
-    import torch
-    if (res is None) == (max_step is None):
-        raise ValueError("motion_cost takes exactly one of res and max_step")
-    qa, qb = torch.as_tensor(qa), torch.as_tensor(qb)
-    mask = _ops.wrap_mask(wrap, qa.shape[-1], transform)
-    dev = qa.device if qa.device.type == "cuda" else (support_feat.device if support_feat.device.type == "cuda" else None)
-    m = fused.model(transform, kernel_func, support_feat, weights, dev)
+def motion_cost(src, qa, qb, res=None, max_step=None, margin=0., weight=1., open_end=False, max_samples=None, wrap=None):
+    """[E] differentiable motion costs on the source's model: one dcx_motion_cost call on the fused route, the host
+    composition on the host route (MotionSource.route).  Raises ValueError for edges over max_samples (a read-back).
+    `wrap`: as check_motions."""
+    qa, qb, mask, m, host = src.route("motion_cost", qa, qb, res, max_step, wrap)
     kw = dict(res=res, max_step=max_step, margin=margin, weight=weight, open_end=open_end, max_samples=max_samples, wrap=mask)
-    if m.desc.kind == 0 and transform is not None:
-        owner.last_route = "host"
-        fn = score_fn or (lambda p: fused.score(transform, kernel_func, support_feat, weights, p))
-        qa_d, qb_d = qa.to(device=m.dev, dtype=torch.float32), qb.to(device=m.dev, dtype=torch.float32)
-        cost = host_motion_cost(fn, qa_d, qb_d, **kw).to(device=qa.device, dtype=qa.dtype)
+    if host is not None:
+        cost = host_motion_cost(src.score, *host, **kw).to(device=qa.device, dtype=qa.dtype)
     else:
-        owner.last_route = "fused"
         cost = m.motion_cost(qa, qb, **kw)
-    if bool(torch.isnan(cost).any()):
-        bad = torch.isnan(cost).nonzero().reshape(-1)[:8].tolist()
-        raise ValueError(f"motion_cost: edges {bad} need more than max_samples samples (or hold non-finite values)")
+    _raise_over("motion_cost", torch.isnan(cost), "or hold non-finite values")
     return cost
 
 
-
-def path_cost(owner, fused, transform, kernel_func, support_feat, weights, paths, max_step, margin=0., weight=1., max_samples=None,
-              score_fn=None, wrap=None):
+def path_cost(src, paths, max_step, margin=0., weight=1., max_samples=None, wrap=None):
     """[T] differentiable collision costs of paths [T, W, dof] (ScoreModel.path_cost's composition over either route)"""
-    import torch
     paths = torch.as_tensor(paths)
     dof = paths.shape[-1]
-    kw = dict(max_step=max_step, margin=margin, weight=weight, max_samples=max_samples, score_fn=score_fn,
-              wrap=_ops.wrap_mask(wrap, dof, transform))
-    return _ops.compose_path_cost(lambda a, b, open_end: motion_cost(owner, fused, transform, kernel_func, support_feat, weights, a,
-                                                                     b, open_end=open_end, **kw), paths, dof)
+    kw = dict(max_step=max_step, margin=margin, weight=weight, max_samples=max_samples, wrap=src.wrap_mask(wrap, dof))
+    return _ops.compose_path_cost(lambda a, b, open_end: motion_cost(src, a, b, open_end=open_end, **kw), paths, dof)
 
 
 # ---- worst-sample motion queries ---------------------------------------------------------------------------------------------
 def _first_where(at, dim):
     """the smallest index along `dim` where `at` holds (argmax of a tie is unspecified in torch: a min over masked indices)"""
-    import torch
     n = at.shape[dim]
     shape = [1] * at.dim()
     shape[dim] = n
@@ -521,30 +555,11 @@ def host_motion_worst(score_fn, qa, qb, res=None, max_step=None, margin=0., max_
     segment arg-max: (worst [E], idx [E] int32, cls [E] int32, n_samples [E] int32).  worst[e] = max over the edge's samples
     of max_c (score_c - margin_c) (a NaN score counts as -inf), the smallest sample that attains it, the smallest class that
     attains it there; differentiable with respect to qa and qb through that sample.  An edge over max_samples: NaN / -2 / -1."""
-    import torch
     qa, qb = qa.reshape(len(qa), -1), qb.reshape(len(qb), -1)
     E, dev = len(qa), qa.device
-    d = _ops.wrapped_delta(qa, qb, wrap)
-    if res is not None:
-        n = torch.full((E,), int(res), dtype=torch.int64, device=dev)
-    else:
-        L = d.detach().norm(dim=-1)
-        n = torch.ceil(L / max_step).to(torch.int64) + 1
-    limit = int(res) if (max_samples is None and res is not None) else (
-        _ops.MOTION_MAX_SAMPLES if max_samples is None else int(max_samples))
-    ok = n <= limit
-    n_ok = torch.where(ok, n, torch.zeros_like(n))
-    edge = torch.repeat_interleave(torch.arange(E, device=dev), n_ok)
-    offs = torch.cumsum(n_ok, 0) - n_ok
-    k = torch.arange(len(edge), device=dev) - offs[edge]
-    if res is not None:
-        pts = _wrap_points(qa[edge] + d[edge] * (k.to(qa.dtype) / int(res))[:, None], wrap)
-    else:
-        # u = d / L differentiably (the sample counts are constants); L = 0 edges have only the target sample
-        Ld = d.norm(dim=-1, keepdim=True)
-        u = d / torch.where(Ld > 0, Ld, torch.ones_like(Ld))
-        pts = _wrap_points(qa[edge] + (k.to(qa.dtype) * max_step)[:, None] * u[edge], wrap)
-        pts = torch.where((k == n[edge] - 1)[:, None], qb[edge], pts)
+    p = _sample_plan(qa, qb, res, max_step, max_samples, wrap)
+    n, ok, n_ok, edge, offs, k = p.n, p.ok, p.n_ok, p.edge, p.offs, p.k
+    pts = _grad_points(qa, qb, p.d, p.L, n, edge, k, res, max_step, wrap, False)
     nan = float("nan")
     worst = torch.full((E,), nan, dtype=qa.dtype, device=dev)
     idx = torch.full((E,), -2, dtype=torch.int64, device=dev)
@@ -571,41 +586,25 @@ def host_motion_worst(score_fn, qa, qb, res=None, max_step=None, margin=0., max_
     return worst, idx.to(torch.int32), cls.to(torch.int32), n.clamp(max=2 ** 31 - 1).to(torch.int32)
 
 
-def motion_worst(owner, fused, transform, kernel_func, support_feat, weights, qa, qb, res=None, max_step=None, margin=0.,
-                 max_samples=None, score_fn=None, wrap=None):
-    """(worst [E], idx [E], cls [E]) of the motions qa[e] -> qb[e] on the model `fused` holds: one dcx_motion_worst call where
-    the transform fuses (none, or a diffco_amd robot's fkine), else the host composition (a foreign callable through
-    `score_fn`).  worst is differentiable with respect to qa and qb.  owner.last_route says which ran: "fused" or "host".
-    Raises ValueError for edges over max_samples (a read-back).  `wrap`: as check_motions."""
-    import torch
-    if (res is None) == (max_step is None):
-        raise ValueError("motion_worst takes exactly one of res and max_step")
-    qa, qb = torch.as_tensor(qa), torch.as_tensor(qb)
-    mask = _ops.wrap_mask(wrap, qa.shape[-1], transform)
-    dev = qa.device if qa.device.type == "cuda" else (support_feat.device if support_feat.device.type == "cuda" else None)
-    m = fused.model(transform, kernel_func, support_feat, weights, dev)
+def motion_worst(src, qa, qb, res=None, max_step=None, margin=0., max_samples=None, wrap=None):
+    """(worst [E], idx [E], cls [E]) of the motions qa[e] -> qb[e] on the source's model: one dcx_motion_worst call on the
+    fused route, the host composition on the host route (MotionSource.route).  worst is differentiable with respect to qa
+    and qb.  Raises ValueError for edges over max_samples (a read-back).  `wrap`: as check_motions."""
+    qa, qb, mask, m, host = src.route("motion_worst", qa, qb, res, max_step, wrap)
     kw = dict(res=res, max_step=max_step, margin=margin, max_samples=max_samples, wrap=mask)
-    if m.desc.kind == 0 and transform is not None:
-        owner.last_route = "host"
-        fn = score_fn or (lambda p: fused.score(transform, kernel_func, support_feat, weights, p))
-        qa_d, qb_d = qa.to(device=m.dev, dtype=torch.float32), qb.to(device=m.dev, dtype=torch.float32)
-        worst, idx, cls, _ = host_motion_worst(fn, qa_d, qb_d, **kw)
+    if host is not None:
+        worst, idx, cls, _ = host_motion_worst(src.score, *host, **kw)
         worst = worst.to(device=qa.device, dtype=qa.dtype)
     else:
-        owner.last_route = "fused"
         worst, idx, cls = m.motion_worst(qa, qb, **kw)
-    if bool((idx == -2).any()):
-        bad = (idx == -2).nonzero().reshape(-1)[:8].tolist()
-        raise ValueError(f"motion_worst: edges {bad} need more than max_samples samples (pass a larger max_samples or max_step)")
+    _raise_over("motion_worst", idx == -2)
     return worst, idx, cls
 
 
-def path_worst(owner, fused, transform, kernel_func, support_feat, weights, paths, max_step, margin=0., max_samples=None,
-               score_fn=None, wrap=None):
+def path_worst(src, paths, max_step, margin=0., max_samples=None, wrap=None):
     """(worst [T], segment [T], sample [T]) of paths [T, W, dof] (ScoreModel.path_worst's composition over either route)"""
-    import torch
     paths = torch.as_tensor(paths)
     dof = paths.shape[-1]
-    kw = dict(max_step=max_step, margin=margin, max_samples=max_samples, score_fn=score_fn, wrap=_ops.wrap_mask(wrap, dof, transform))
-    return _ops.compose_path_worst(lambda a, b: motion_worst(owner, fused, transform, kernel_func, support_feat, weights, a, b, **kw),
-                                   paths, dof)
+    kw = dict(max_step=max_step, margin=margin, max_samples=max_samples, wrap=src.wrap_mask(wrap, dof))
+    return _ops.compose_path_worst(lambda a, b: motion_worst(src, a, b, **kw), paths, dof)
+

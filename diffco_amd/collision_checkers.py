@@ -17,7 +17,7 @@ import os
 import time
 import torch
 
-from . import kernel
+from . import _ops, _perceptron, kernel
 from .kernel_perceptrons import DiffCo
 from .urdf import MultiURDFRobotFK, URDFRobotFK
 
@@ -209,66 +209,51 @@ class RBFDiffCo(CollisionChecker):
         (line_predict's).  bool [E]; with return_first also the first colliding sample index (-1 = free).
         `wrap` (None, True: the robot's own circular coordinates, an int bitmask or one bool per coordinate): those
         coordinates are angles and the edge runs along their shortest arc."""
-        from ._perceptron import check_motions, motion_answer
-        bias = self.safety_bias if bias is None else bias
-        margin = -bias if not torch.is_tensor(bias) else -bias.detach().reshape(-1)
+        first, _ = _perceptron.check_motions(self._poly_source(), q_start, q_end, res=res, max_step=max_step, margin=self._margin(bias),
+                                             max_samples=max_samples, wrap=wrap)
+        return _perceptron.motion_answer(first, return_first)
+
+    def _poly_source(self):
+        """what the motion calls run on: the perceptron's poly_score state; this checker reports the route (last_route)"""
         p = self.perceptron
-        first, _ = check_motions(self, p._poly_fused, p.transform, p.rbf_kernel, p.support_transformed, p.rbf_nodes,
-                                 q_start, q_end, res=res, max_step=max_step, margin=margin, max_samples=max_samples, wrap=wrap)
-        return motion_answer(first, return_first)
+        return _perceptron.MotionSource(self, p._poly_fused, p.transform, p.rbf_kernel, p.support_transformed, p.rbf_nodes)
+
+    def _margin(self, bias=None):
+        """the motion calls' margin for a bias (None: safety_bias): score + bias > 0 is score - margin > 0"""
+        bias = self.safety_bias if bias is None else bias
+        return -bias if not torch.is_tensor(bias) else -bias.detach().reshape(-1)
 
     def _rrt_model(self, device=None):
         """(ScoreModel, margin) of check_motions' fused route - the safety bias becomes the margin - or None where it takes the
         host route (rrt.rrt_connect)"""
-        from ._perceptron import _motion_model
-        bias = self.safety_bias
-        margin = -bias if not torch.is_tensor(bias) else -bias.detach().reshape(-1)
-        p = self.perceptron
-        return _motion_model(p._poly_fused, p.transform, p.rbf_kernel, p.support_transformed, p.rbf_nodes, device, margin)
+        return _perceptron._motion_model(self._poly_source(), device, self._margin())
 
     def motion_cost(self, q_start, q_end, max_step=None, res=None, bias=None, weight=1., open_end=False, max_samples=None,
                     wrap=None):
         """[E] collision costs of the motions q_start[e] -> q_end[e] by `collision_score`: weight * sum over the samples of
         max(0, poly score + bias) (bias defaults to safety_bias), differentiable with respect to both endpoints.  Exactly one
         rule, as check_motions (open_end drops the target sample under max_step; `wrap` as there)."""
-        from ._perceptron import motion_cost
-        bias = self.safety_bias if bias is None else bias
-        margin = -bias if not torch.is_tensor(bias) else -bias.detach().reshape(-1)
-        p = self.perceptron
-        return motion_cost(self, p._poly_fused, p.transform, p.rbf_kernel, p.support_transformed, p.rbf_nodes, q_start, q_end,
-                           res=res, max_step=max_step, margin=margin, weight=weight, open_end=open_end, max_samples=max_samples,
-                           wrap=wrap)
+        return _perceptron.motion_cost(self._poly_source(), q_start, q_end, res=res, max_step=max_step, margin=self._margin(bias),
+                                       weight=weight, open_end=open_end, max_samples=max_samples, wrap=wrap)
 
     def path_cost(self, paths, max_step, bias=None, weight=1., max_samples=None, wrap=None):
         """[T] collision costs of paths [T, W, dof] by `collision_score` over utils.dense_path(p, max_step)'s points,
         differentiable with respect to every waypoint (`wrap` as check_motions: per segment)"""
-        from ._perceptron import path_cost
-        bias = self.safety_bias if bias is None else bias
-        margin = -bias if not torch.is_tensor(bias) else -bias.detach().reshape(-1)
-        p = self.perceptron
-        return path_cost(self, p._poly_fused, p.transform, p.rbf_kernel, p.support_transformed, p.rbf_nodes, paths, max_step,
-                         margin=margin, weight=weight, max_samples=max_samples, wrap=wrap)
+        return _perceptron.path_cost(self._poly_source(), paths, max_step, margin=self._margin(bias), weight=weight,
+                                     max_samples=max_samples, wrap=wrap)
 
     def motion_worst(self, q_start, q_end, max_step=None, res=None, bias=None, max_samples=None, wrap=None):
         """(worst [E], sample [E], class [E]) of the motions q_start[e] -> q_end[e]: the peak of `collision_score` (poly score
         + bias; bias defaults to safety_bias) over check_motions' samples and the first sample that attains it.  worst is
         differentiable with respect to both endpoints.  Exactly one rule and `wrap` as check_motions."""
-        from ._perceptron import motion_worst
-        bias = self.safety_bias if bias is None else bias
-        margin = -bias if not torch.is_tensor(bias) else -bias.detach().reshape(-1)
-        p = self.perceptron
-        return motion_worst(self, p._poly_fused, p.transform, p.rbf_kernel, p.support_transformed, p.rbf_nodes, q_start, q_end,
-                            res=res, max_step=max_step, margin=margin, max_samples=max_samples, wrap=wrap)
+        return _perceptron.motion_worst(self._poly_source(), q_start, q_end, res=res, max_step=max_step, margin=self._margin(bias),
+                                        max_samples=max_samples, wrap=wrap)
 
     def path_worst(self, paths, max_step, bias=None, max_samples=None, wrap=None):
         """(worst [T], segment [T], sample [T]) of paths [T, W, dof] by `collision_score` (the closed max_step rule per segment,
         the first maximum in (segment, sample) order); worst is differentiable with respect to every waypoint"""
-        from ._perceptron import path_worst
-        bias = self.safety_bias if bias is None else bias
-        margin = -bias if not torch.is_tensor(bias) else -bias.detach().reshape(-1)
-        p = self.perceptron
-        return path_worst(self, p._poly_fused, p.transform, p.rbf_kernel, p.support_transformed, p.rbf_nodes, paths, max_step,
-                          margin=margin, max_samples=max_samples, wrap=wrap)
+        return _perceptron.path_worst(self._poly_source(), paths, max_step, margin=self._margin(bias), max_samples=max_samples,
+                                      wrap=wrap)
 
     def motion_bias_sweep(self, q_start, q_end, biases, max_step=None, res=None, max_samples=None, wrap=None):
         """bool [len(biases), E]: would the motion q_start[e] -> q_end[e] collide under each candidate bias?  ONE worst-sample
@@ -394,10 +379,6 @@ class HybridForwardKinematicsDiffCo(ForwardKinematicsDiffCo):
             raise ValueError(f"the uncertainty band must be >= 0, got {band}")
         return band
 
-    def _poly_args(self):
-        p = self.perceptron
-        return p._poly_fused, p.transform, p.rbf_kernel, p.support_transformed, p.rbf_nodes
-
     def _gt(self, q, device):
         self.last_gt_checks += len(q)
         return torch.as_tensor(self.gt_check_func(q)).reshape(-1).to(device=device, dtype=torch.bool)
@@ -417,9 +398,8 @@ class HybridForwardKinematicsDiffCo(ForwardKinematicsDiffCo):
                 i = s.argmax()
                 labels[i] = self._gt(q2[i:i + 1], labels.device)[0]
             return labels.reshape(shape)
-        from ._perceptron import score_band
         band = self._band(band)
-        label, unc_idx = score_band(self, *self._poly_args(), q2, -band, band)
+        label, unc_idx = _perceptron.score_band(self._poly_source(), q2, -band, band)
         labels = (label == 1).to(q2.device)
         if len(unc_idx):
             unc_idx = unc_idx.to(q2.device)
@@ -435,13 +415,12 @@ class HybridForwardKinematicsDiffCo(ForwardKinematicsDiffCo):
         collides iff one of its listed samples does.  Lazy: one dcx_motion_worst call at bias 0; only the worst sample of each
         edge whose peak lies in the band is ground-truth checked, and the edge takes its label (the sample returned with
         return_first is then the edge's worst sample, not its first one above the band)."""
-        from ._perceptron import motion_band, motion_worst
         band = self._band(band)
         self.last_gt_checks = 0
         q_start, q_end = torch.as_tensor(q_start), torch.as_tensor(q_end)
         kw = dict(res=res, max_step=max_step, max_samples=max_samples, wrap=wrap)
         if self.lazy_line_check:
-            worst, idx, _ = motion_worst(self, *self._poly_args(), q_start, q_end, margin=0., **kw)
+            worst, idx, _ = _perceptron.motion_worst(self._poly_source(), q_start, q_end, margin=0., **kw)
             worst, first = worst.detach(), idx.to(torch.int64)
             hit = worst > band
             unc = ~hit & ~(worst <= -band)
@@ -453,10 +432,8 @@ class HybridForwardKinematicsDiffCo(ForwardKinematicsDiffCo):
                 hit[e] = gt
                 first[e] = torch.where(gt, first[e], torch.full_like(first[e], -1))
             return (hit, first.to(torch.int32)) if return_first else hit
-        verdict, first, _, unc_edge, unc_sample, unc_q = motion_band(self, *self._poly_args(), q_start, q_end, -band, band, **kw)
-        if bool((verdict == -2).any()):
-            bad = (verdict == -2).nonzero().reshape(-1)[:8].tolist()
-            raise ValueError(f"check_motions: edges {bad} need more than max_samples samples (pass a larger max_samples or max_step)")
+        verdict, first, _, unc_edge, unc_sample, unc_q = _perceptron.motion_band(self._poly_source(), q_start, q_end, -band, band, **kw)
+        _perceptron._raise_over("check_motions", verdict == -2)
         hit = verdict == 1
         first = first.clone()
         if len(unc_edge):
@@ -473,17 +450,10 @@ class HybridForwardKinematicsDiffCo(ForwardKinematicsDiffCo):
         return None
 
     def _motion_points(self, q_start, q_end, edges, samples, res, max_step, wrap):
-        """sample samples[i] of the edge edges[i]: the points the host composition materialises (_perceptron._motion_samples)"""
-        from . import _ops
-        from ._perceptron import _wrap_points
+        """sample samples[i] of the edge edges[i]: the points the host composition materialises (_perceptron._check_points)"""
         qa = q_start.reshape(-1, q_start.shape[-1])[edges.to(q_start.device)]
         qb = q_end.reshape(-1, q_end.shape[-1])[edges.to(q_end.device)]
         mask = _ops.wrap_mask(wrap, qa.shape[-1], self.perceptron.transform)
-        d = _ops.wrapped_delta(qa, qb, mask)
-        k = samples.to(device=qa.device, dtype=qa.dtype)[:, None]
-        if res is not None:
-            return _wrap_points(qa + d * (k / int(res)), mask)
-        L = d.norm(dim=-1, keepdim=True)
-        n = torch.ceil(L / max_step) + 1
-        pts = _wrap_points(qa + k * (d * (max_step / L)), mask)
-        return torch.where(k == n - 1, qb, pts)
+        d, L, n = _perceptron._edge_counts(qa, qb, res, max_step, mask)
+        each = torch.arange(len(qa), device=qa.device)
+        return _perceptron._check_points(qa, qb, d, L, n, each, samples.to(qa.device), res, max_step, mask)

@@ -12,7 +12,7 @@ from time import time
 
 import torch
 
-from . import kernel
+from . import _perceptron, kernel
 from ._perceptron import FusedScorer, fit_system, run_trainer, solve_system, sub_block
 
 
@@ -207,47 +207,39 @@ class DiffCo(CollisionChecker):
         some class (`margin`: a number or one per class).  Exactly one of `res` / `max_step`.  bool [E] (+ first index).
         `wrap` (None, True: the `fkine` owner's circular coordinates, an int bitmask or one bool per coordinate): those
         coordinates are angles and the edge runs along their shortest arc."""
-        from ._perceptron import check_motions, motion_answer
-        if self.fkine is not None:
-            args = (self._rbf_fused, self.fkine, self.rbf_kernel, self.support_fkine, self.rbf_nodes)
-        else:
-            args = (self._rbf_fused, None, self.rbf_kernel, self.support_points, self.rbf_nodes)
-        first, _ = check_motions(self, *args, starts, targets, res=res, max_step=max_step, margin=margin, max_samples=max_samples,
-                                 wrap=wrap)
-        return motion_answer(first, return_first)
+        first, _ = _perceptron.check_motions(self._rbf_source(), starts, targets, res=res, max_step=max_step, margin=margin,
+                                             max_samples=max_samples, wrap=wrap)
+        return _perceptron.motion_answer(first, return_first)
 
-    def _rbf_args(self):
-        if self.fkine is not None:
-            return (self._rbf_fused, self.fkine, self.rbf_kernel, self.support_fkine, self.rbf_nodes)
-        return (self._rbf_fused, None, self.rbf_kernel, self.support_points, self.rbf_nodes)
+    def _rbf_source(self):
+        """what the motion calls run on: the `rbf_score` state"""
+        feats = self.support_fkine if self.fkine is not None else self.support_points
+        return _perceptron.MotionSource(self, self._rbf_fused, self.fkine, self.rbf_kernel, feats, self.rbf_nodes)
 
     def motion_cost(self, starts, targets, res=None, max_step=None, margin=0., weight=1., open_end=False, max_samples=None,
                     wrap=None):
         """[E] collision costs of the motions starts[e] -> targets[e] under the `rbf_score` state: weight * sum over the
         samples of sum_c max(0, rbf_score_c - margin_c) (`margin`: a number or one per class), differentiable with respect to
         starts and targets.  Exactly one of `res` / `max_step` (check_motions' samples and `wrap`; open_end drops the target)."""
-        from ._perceptron import motion_cost
-        return motion_cost(self, *self._rbf_args(), starts, targets, res=res, max_step=max_step, margin=margin, weight=weight,
-                           open_end=open_end, max_samples=max_samples, wrap=wrap)
+        return _perceptron.motion_cost(self._rbf_source(), starts, targets, res=res, max_step=max_step, margin=margin, weight=weight,
+                                       open_end=open_end, max_samples=max_samples, wrap=wrap)
 
     def path_cost(self, paths, max_step, margin=0., weight=1., max_samples=None, wrap=None):
         """[T] collision costs of paths [T, W, dof] over utils.dense_path(p, max_step)'s points, differentiable w.r.t. every waypoint"""
-        from ._perceptron import path_cost
-        return path_cost(self, *self._rbf_args(), paths, max_step, margin=margin, weight=weight, max_samples=max_samples, wrap=wrap)
+        return _perceptron.path_cost(self._rbf_source(), paths, max_step, margin=margin, weight=weight, max_samples=max_samples,
+                                     wrap=wrap)
 
     def motion_worst(self, starts, targets, res=None, max_step=None, margin=0., max_samples=None, wrap=None):
         """(worst [E], sample [E], class [E]) of the motions starts[e] -> targets[e] under the `rbf_score` state: the peak of
         max_c (rbf_score_c - margin_c) over check_motions' samples, the first sample that attains it and the first class that
         attains it there (MultiDiffCo: the binding obstacle).  worst is differentiable with respect to starts and targets."""
-        from ._perceptron import motion_worst
-        return motion_worst(self, *self._rbf_args(), starts, targets, res=res, max_step=max_step, margin=margin,
-                            max_samples=max_samples, wrap=wrap)
+        return _perceptron.motion_worst(self._rbf_source(), starts, targets, res=res, max_step=max_step, margin=margin,
+                                        max_samples=max_samples, wrap=wrap)
 
     def path_worst(self, paths, max_step, margin=0., max_samples=None, wrap=None):
         """(worst [T], segment [T], sample [T]) of paths [T, W, dof] under the `rbf_score` state (the closed max_step rule per
         segment, the first maximum in (segment, sample) order); worst is differentiable w.r.t. every waypoint"""
-        from ._perceptron import path_worst
-        return path_worst(self, *self._rbf_args(), paths, max_step, margin=margin, max_samples=max_samples, wrap=wrap)
+        return _perceptron.path_worst(self._rbf_source(), paths, max_step, margin=margin, max_samples=max_samples, wrap=wrap)
 
     def poly_score(self, point):
         if point.ndim == 1:

@@ -18,7 +18,7 @@ from time import time
 
 import torch as th
 
-from . import _ops, kernel
+from . import _ops, _perceptron, kernel
 from ._perceptron import FusedScorer, device_trainer_spec, fit_system, run_trainer, sub_block
 
 
@@ -305,46 +305,42 @@ class DiffCo(Perceptron):
         return_first also the first colliding sample index (-1 = free).  One fused launch (plus a small one) for all edges.
         `wrap` (None, True: the robot's own circular coordinates, an int bitmask or one bool per coordinate): those
         coordinates are angles and the edge runs along their shortest arc."""
-        from ._perceptron import check_motions, motion_answer
-        first, _ = check_motions(self, self._score_fused, self.transform, self.kernel_func, self.support_transformed, self.gains,
-                                 starts, targets, res=res, max_step=max_step, max_samples=max_samples, wrap=wrap)
-        return motion_answer(first, return_first)
+        first, _ = _perceptron.check_motions(self._score_source(), starts, targets, res=res, max_step=max_step,
+                                             max_samples=max_samples, wrap=wrap)
+        return _perceptron.motion_answer(first, return_first)
+
+    def _score_source(self):
+        """what the motion calls run on: the `score` state"""
+        return _perceptron.MotionSource(self, self._score_fused, self.transform, self.kernel_func, self.support_transformed, self.gains)
 
     def _rrt_model(self, device=None):
         """(ScoreModel, margin) of check_motions' fused route, or None where it takes the host route (rrt.rrt_connect)"""
-        from ._perceptron import _motion_model
-        return _motion_model(self._score_fused, self.transform, self.kernel_func, self.support_transformed, self.gains, device)
+        return _perceptron._motion_model(self._score_source(), device)
 
     def motion_cost(self, starts, targets, res=None, max_step=None, margin=0., weight=1., open_end=False, max_samples=None,
                     wrap=None):
         """[E] collision costs of the motions starts[e] -> targets[e]: weight * sum over the samples of max(0, score - margin),
         differentiable with respect to starts and targets.  Exactly one rule, as check_motions (open_end drops the target
         sample under max_step; `wrap` as there).  One fused call (dcx_motion_cost) for all edges."""
-        from ._perceptron import motion_cost
-        return motion_cost(self, self._score_fused, self.transform, self.kernel_func, self.support_transformed, self.gains,
-                           starts, targets, res=res, max_step=max_step, margin=margin, weight=weight, open_end=open_end,
-                           max_samples=max_samples, wrap=wrap)
+        return _perceptron.motion_cost(self._score_source(), starts, targets, res=res, max_step=max_step, margin=margin, weight=weight,
+                                       open_end=open_end, max_samples=max_samples, wrap=wrap)
 
     def path_cost(self, paths, max_step, margin=0., weight=1., max_samples=None, wrap=None):
         """[T] collision costs of paths [T, W, dof] over utils.dense_path(p, max_step)'s points, differentiable w.r.t. every waypoint"""
-        from ._perceptron import path_cost
-        return path_cost(self, self._score_fused, self.transform, self.kernel_func, self.support_transformed, self.gains, paths,
-                         max_step, margin=margin, weight=weight, max_samples=max_samples, wrap=wrap)
+        return _perceptron.path_cost(self._score_source(), paths, max_step, margin=margin, weight=weight, max_samples=max_samples,
+                                     wrap=wrap)
 
     def motion_worst(self, starts, targets, res=None, max_step=None, margin=0., max_samples=None, wrap=None):
         """how close do the motions starts[e] -> targets[e] come?  (worst [E], sample [E], class [E]): the peak of score - margin
         over check_motions' samples (exactly one rule; `wrap` as there), the first sample that attains it and the class (0).
         worst is differentiable with respect to starts and targets through that sample.  One fused call (dcx_motion_worst)."""
-        from ._perceptron import motion_worst
-        return motion_worst(self, self._score_fused, self.transform, self.kernel_func, self.support_transformed, self.gains,
-                            starts, targets, res=res, max_step=max_step, margin=margin, max_samples=max_samples, wrap=wrap)
+        return _perceptron.motion_worst(self._score_source(), starts, targets, res=res, max_step=max_step, margin=margin,
+                                        max_samples=max_samples, wrap=wrap)
 
     def path_worst(self, paths, max_step, margin=0., max_samples=None, wrap=None):
         """(worst [T], segment [T], sample [T]) of paths [T, W, dof]: the peak of score - margin over every segment's samples
         (the closed max_step rule), the first maximum in (segment, sample) order; worst is differentiable w.r.t. every waypoint"""
-        from ._perceptron import path_worst
-        return path_worst(self, self._score_fused, self.transform, self.kernel_func, self.support_transformed, self.gains, paths,
-                          max_step, margin=margin, max_samples=max_samples, wrap=wrap)
+        return _perceptron.path_worst(self._score_source(), paths, max_step, margin=margin, max_samples=max_samples, wrap=wrap)
 
     def motion_band(self, starts, targets, lo, hi, res=None, max_step=None, max_samples=None, wrap=None, want_q=True):
         """hybrid motion checks on `score`: (verdict, first_hit, n_uncertain, unc_edge, unc_sample, unc_q) of the motions
@@ -352,16 +348,13 @@ class DiffCo(Perceptron):
         above lo (or is NaN), else 0, and the (edge, sample)-ordered list of the uncertain samples of the verdict-2 edges with
         their configurations, for a ground-truth checker.  One fused call (dcx_motion_band) where the transform fuses, the
         host composition for a foreign callable (`last_route`).  Raises ValueError where lo > hi."""
-        from ._perceptron import motion_band
-        return motion_band(self, self._score_fused, self.transform, self.kernel_func, self.support_transformed, self.gains,
-                           starts, targets, lo, hi, res=res, max_step=max_step, max_samples=max_samples, wrap=wrap, want_q=want_q)
+        return _perceptron.motion_band(self._score_source(), starts, targets, lo, hi, res=res, max_step=max_step,
+                                       max_samples=max_samples, wrap=wrap, want_q=want_q)
 
     def score_band(self, point, lo, hi):
         """(label [N] int32, unc_idx [U] int64): 1 where `score` lies above hi, 0 where it is at or below lo, 2 between (or NaN),
         and the ascending indices of the label-2 configurations: motion_band with one sample per edge"""
-        from ._perceptron import score_band
-        return score_band(self, self._score_fused, self.transform, self.kernel_func, self.support_transformed, self.gains,
-                          point, lo, hi)
+        return _perceptron.score_band(self._score_source(), point, lo, hi)
 
     def poly_score(self, point=None, transformed_point=None):
         """sum_j K_rbf(T(q), support_j) rbf_nodes_j  ->  [N, 1]; `transformed_point` skips the FK."""

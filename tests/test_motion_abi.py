@@ -88,11 +88,11 @@ def test_motion_argument_errors_before_any_device_use():
 
 
 def test_facade_rejects_two_rules_without_gpu():
-    from diffco_amd._perceptron import check_motions
+    from diffco_amd._perceptron import MotionSource, check_motions
 
     class Owner:
         pass
     with pytest.raises(ValueError, match="exactly one"):
-        check_motions(Owner(), None, None, None, None, None, [[0.0]], [[1.0]], res=4, max_step=0.1)
+        check_motions(MotionSource(Owner(), None, None, None, None, None), [[0.0]], [[1.0]], res=4, max_step=0.1)
     with pytest.raises(ValueError, match="exactly one"):
-        check_motions(Owner(), None, None, None, None, None, [[0.0]], [[1.0]])
+        check_motions(MotionSource(Owner(), None, None, None, None, None), [[0.0]], [[1.0]])

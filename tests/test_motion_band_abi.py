@@ -151,13 +151,13 @@ def test_work_bytes_grows_with_the_samples():
 
 
 def test_python_layers_reject_bad_rules_without_a_device():
-    from diffco_amd._perceptron import motion_band
+    from diffco_amd._perceptron import MotionSource, motion_band
 
     class _Owner:
         pass
     with pytest.raises(ValueError, match="exactly one of res and max_step"):
-        motion_band(_Owner(), None, None, None, None, None, [[0.0, 0.0]], [[1.0, 1.0]], -1.0, 1.0)
+        motion_band(MotionSource(_Owner(), None, None, None, None, None), [[0.0, 0.0]], [[1.0, 1.0]], -1.0, 1.0)
     with pytest.raises(ValueError, match="exactly one of res and max_step"):
-        motion_band(_Owner(), None, None, None, None, None, [[0.0, 0.0]], [[1.0, 1.0]], -1.0, 1.0, res=4, max_step=0.1)
+        motion_band(MotionSource(_Owner(), None, None, None, None, None), [[0.0, 0.0]], [[1.0, 1.0]], -1.0, 1.0, res=4, max_step=0.1)
     with pytest.raises(ValueError, match="wrap=True"):
-        motion_band(_Owner(), None, None, None, None, None, [[0.0, 0.0]], [[1.0, 1.0]], -1.0, 1.0, res=4, wrap=True)
+        motion_band(MotionSource(_Owner(), None, None, None, None, None), [[0.0, 0.0]], [[1.0, 1.0]], -1.0, 1.0, res=4, wrap=True)

@@ -111,11 +111,11 @@ def test_motion_cost_argument_errors_before_any_device_use():
 
 
 def test_facade_rejects_two_rules_without_gpu():
-    from diffco_amd._perceptron import motion_cost
+    from diffco_amd._perceptron import MotionSource, motion_cost
 
     class Owner:
         pass
     with pytest.raises(ValueError, match="exactly one"):
-        motion_cost(Owner(), None, None, None, None, None, [[0.0]], [[1.0]], res=4, max_step=0.1)
+        motion_cost(MotionSource(Owner(), None, None, None, None, None), [[0.0]], [[1.0]], res=4, max_step=0.1)
     with pytest.raises(ValueError, match="exactly one"):
-        motion_cost(Owner(), None, None, None, None, None, [[0.0]], [[1.0]])
+        motion_cost(MotionSource(Owner(), None, None, None, None, None), [[0.0]], [[1.0]])

@@ -116,16 +116,16 @@ def test_work_bytes_monotone_and_zero_for_null():
 
 
 def test_python_layers_reject_bad_rules_without_a_device():
-    from diffco_amd._perceptron import motion_worst, path_worst
+    from diffco_amd._perceptron import MotionSource, motion_worst, path_worst
     import torch
 
     class _Owner:
         pass
     with pytest.raises(ValueError, match="exactly one of res and max_step"):
-        motion_worst(_Owner(), None, None, None, None, None, [[0.0, 0.0]], [[1.0, 1.0]])
+        motion_worst(MotionSource(_Owner(), None, None, None, None, None), [[0.0, 0.0]], [[1.0, 1.0]])
     with pytest.raises(ValueError, match="exactly one of res and max_step"):
-        motion_worst(_Owner(), None, None, None, None, None, [[0.0, 0.0]], [[1.0, 1.0]], res=4, max_step=0.1)
+        motion_worst(MotionSource(_Owner(), None, None, None, None, None), [[0.0, 0.0]], [[1.0, 1.0]], res=4, max_step=0.1)
     with pytest.raises(ValueError, match="wrap=True"):
-        motion_worst(_Owner(), None, None, None, None, None, [[0.0, 0.0]], [[1.0, 1.0]], res=4, wrap=True)
+        motion_worst(MotionSource(_Owner(), None, None, None, None, None), [[0.0, 0.0]], [[1.0, 1.0]], res=4, wrap=True)
     with pytest.raises(ValueError, match="wrap=True"):
-        path_worst(_Owner(), None, lambda q: q, None, None, None, torch.zeros(1, 3, 2), 0.1, wrap=True)
+        path_worst(MotionSource(_Owner(), None, lambda q: q, None, None, None), torch.zeros(1, 3, 2), 0.1, wrap=True)

@@ -185,11 +185,11 @@ def test_wrap_true_on_urdf_robots_is_their_continuous_joints():
 
 
 def test_facades_reject_wrap_true_without_an_owner():
-    from diffco_amd._perceptron import check_motions, motion_cost, path_cost
+    from diffco_amd._perceptron import MotionSource, check_motions, motion_cost, path_cost
     for fn in (check_motions, motion_cost):
         with pytest.raises(ValueError, match="wrap=True"):
-            fn(_Owner(), None, None, None, None, None, [[0.0, 0.0]], [[1.0, 1.0]], res=4, wrap=True)
+            fn(MotionSource(_Owner(), None, None, None, None, None), [[0.0, 0.0]], [[1.0, 1.0]], res=4, wrap=True)
         with pytest.raises(ValueError, match="at or above dof"):
-            fn(_Owner(), None, None, None, None, None, [[0.0, 0.0]], [[1.0, 1.0]], res=4, wrap=4)
+            fn(MotionSource(_Owner(), None, None, None, None, None), [[0.0, 0.0]], [[1.0, 1.0]], res=4, wrap=4)
     with pytest.raises(ValueError, match="wrap=True"):
-        path_cost(_Owner(), None, lambda q: q, None, None, None, torch.zeros(1, 3, 2), 0.1, wrap=True)
+        path_cost(MotionSource(_Owner(), None, lambda q: q, None, None, None), torch.zeros(1, 3, 2), 0.1, wrap=True)
