@@ -101,6 +101,10 @@ SYMBOLS = {
                                C.c_void_p]),
     "dcx_sssp_extract_paths": (C.c_int, [C.c_int, C.c_void_p, _c_fp, C.c_int32, C.c_void_p, C.c_int32, C.c_int64, C.c_int32, C.c_void_p,
                                          _c_fp, _c_fp, C.c_void_p, _c_fp, _c_fp, C.c_void_p, _c_fp, C.c_int32, C.c_void_p]),
+    # batched path resampling: R paths of uneven length as rows of T waypoints, equally spaced in arc length (no model)
+    "dcx_path_resample_work_bytes": (C.c_size_t, [C.c_int64, C.c_int32]),
+    "dcx_path_resample": (C.c_int, [C.c_int, _c_fp, _c_fp, C.c_int64, C.c_int32, C.c_int32, C.c_uint64, C.c_int32, _c_fp, _c_fp, _c_fp,
+                                    C.c_void_p, C.c_size_t, C.c_void_p]),
     "dcx_solve_work_bytes": (C.c_size_t, [C.c_int64, C.c_int64]),
     "dcx_solve": (C.c_int, [C.c_int, _c_fp, _c_fp, C.c_int64, C.c_int64, _c_fp, C.c_void_p, C.c_size_t, C.c_void_p, C.c_int32,
                             C.c_void_p]),

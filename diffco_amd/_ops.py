@@ -349,6 +349,37 @@ def rrt_extract_paths(state, W, out=None):
     return path, count
 
 
+def path_resample(path, count, T, mask=0, out=None):
+    """R paths resampled to T waypoints each, equally spaced in arc length (dcx_path_resample; path [R, W, dof] float32 and count
+    [R] int32, contiguous on one GPU; mask: the wrap bitmask): (out [R, T, dof] float32, out_count [R] int32, length [R] float32)
+    there.  out_count[r] is T, or 0 for a row without a path (count < 2, or a length that is NaN or infinite): that row of `out`
+    is left as it is, zeros.  `out`: the [R, T, dof] tensor to write into.  One launch on torch's current stream, nothing read
+    back."""
+    lib = _lib.require_gpu()
+    if not isinstance(path, torch.Tensor) or path.dim() != 3 or path.device.type != "cuda":
+        raise ValueError("path_resample: path must be a [R, W, dof] tensor on a GPU")
+    dev = path.device
+    R, W, dof = (int(v) for v in path.shape)
+    _check_tensor("path_resample: path", path, torch.float32, (R, W, dof), dev)
+    _check_tensor("path_resample: count", count, torch.int32, (R,), dev)
+    T, mask = int(T), int(mask)
+    if mask < 0 or mask >> dof:
+        raise ValueError(f"wrap mask {mask:#x} has a bit at or above dof = {dof}")
+    if out is None:
+        out = torch.zeros((R, max(T, 0), dof), device=dev, dtype=torch.float32)
+    else:
+        _check_tensor("path_resample: out", out, torch.float32, (R, T, dof), dev)
+    out_count = torch.zeros(R, device=dev, dtype=torch.int32)
+    length = torch.full((R,), float("nan"), device=dev, dtype=torch.float32)
+    nbytes = int(lib.dcx_path_resample_work_bytes(R, W))
+    # as the motion calls: torch's caching allocator is the per-device cache (a freed block is reused on its stream, no hipMalloc)
+    work = torch.empty(max(nbytes, 1), device=dev, dtype=torch.uint8)
+    with _on_device(dev):
+        _lib.check(lib.dcx_path_resample(dev.index, _ptr(path), _ptr(count), R, W, dof, mask, T, _ptr(out), _ptr(out_count),
+                                         _ptr(length), _ptr(work), work.numel(), _stream(dev)))
+    return out, out_count, length
+
+
 def _sssp_graph(fn, rowptr, col, weight):
     """dcx_graph of a CSR on one GPU: (the struct, N, device).  Shapes, kinds and placement are checked; the CSR's contents
     (sorted rows, symmetry, weights >= 0) are the caller's, as include/dcx.h says."""

@@ -22,6 +22,7 @@
 #include "knn_kernel.h"
 #include "rrt_kernel.h"
 #include "shortcut_kernel.h"
+#include "resample_kernel.h"
 #include "sssp_kernel.h"
 
 using namespace dcx;
@@ -2707,6 +2708,55 @@ int dcx_rrt_extract_paths(int device, const dcx_rrt_state* state, int64_t R, int
     a.W = W;
     const hipError_t e = launch_rrt_extract(a, (hipStream_t)stream);
     if (e != hipSuccess) return fail_hip(e, "extract launch");
+    return DCX_OK;
+}
+
+// ---- batched path resampling (resample_kernel.h): the size query and the call share the checks and resample_plan -------------
+static int resample_check_sizes(int64_t R, int32_t W) {
+    if (R < 0) return fail(DCX_ERR_INVALID, "resample: R < 0");
+    if (W < 1 || W > DCX_SHORTCUT_MAX_WAYPOINTS) return fail(DCX_ERR_INVALID, "resample: W must be in [1, DCX_SHORTCUT_MAX_WAYPOINTS]");
+    return DCX_OK;
+}
+
+size_t dcx_path_resample_work_bytes(int64_t R, int32_t W) {
+    if (resample_check_sizes(R, W) || R > INT32_MAX) return 0;
+    return resample_plan(R, W).total;
+}
+
+int dcx_path_resample(int device, const float* path, const int32_t* count, int64_t R, int32_t W, int32_t dof, uint64_t wrap_mask,
+                      int32_t T, float* out, int32_t* out_count, float* length, void* work, size_t work_bytes, void* stream) {
+    // every argument is checked before anything touches the device
+    if (int rc = resample_check_sizes(R, W)) return rc;
+    if (T < 2 || T > DCX_SHORTCUT_MAX_WAYPOINTS) return fail(DCX_ERR_INVALID, "resample: T must be in [2, DCX_SHORTCUT_MAX_WAYPOINTS]");
+    if (dof < 1) return fail(DCX_ERR_INVALID, "resample: dof < 1");
+    if (wrap_mask != 0 && dof < 64 && (wrap_mask >> dof) != 0)
+        return fail(DCX_ERR_INVALID, "resample: wrap_mask has a bit at or above dof");
+    if (R > 0 && (!path || !count)) return fail(DCX_ERR_INVALID, "resample: path or count is NULL");
+    if (R > 0 && (!out || !out_count)) return fail(DCX_ERR_INVALID, "resample: out or out_count is NULL");
+    if (R > 0 && !work) return fail(DCX_ERR_INVALID, "resample: work is NULL");
+    if (R > INT32_MAX) return fail(DCX_ERR_UNSUPPORTED, "resample: more than 2^31 - 1 paths");
+    if (dof > DCX_MAX_DOF) return fail(DCX_ERR_UNSUPPORTED, "resample: dof above DCX_MAX_DOF");
+    const ResamplePlan plan = resample_plan(R, W);
+    if (R > 0 && work_bytes < plan.total)
+        return fail(DCX_ERR_INVALID, "resample: the workspace is smaller than dcx_path_resample_work_bytes");
+    if (R == 0) return DCX_OK;
+    if (int rc = set_device(device)) return rc;
+    char* base = (char*)work;
+    ResampleArgs a{};
+    a.path = path;
+    a.count = count;
+    a.out = out;
+    a.out_count = out_count;
+    a.length = length;
+    a.work_c = (float*)(base + plan.c);
+    a.work_len = (float*)(base + plan.len);
+    a.wrap_mask = wrap_mask;
+    a.R = (int32_t)R;
+    a.W = W;
+    a.dof = dof;
+    a.T = T;
+    const hipError_t e = launch_path_resample(a, (hipStream_t)stream);
+    if (e != hipSuccess) return fail_hip(e, "resample launch");
     return DCX_OK;
 }
 

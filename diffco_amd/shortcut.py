@@ -8,8 +8,9 @@ and the paths are on the GPU, and `host_shortcut_paths` everywhere else.  `host_
 on the same fixed batch of R * P edges: the referee of the fused pass (equal path[:count], count and accepted, bit for bit, for
 equal draws) and the baseline it is measured against.  It runs on CPU tensors with any checker that has such a `check_motions`.
 
-The paths of `rrt.rrt_connect` come as one tensor from `RRTResult.path_tensor()`; what leaves here is what
-`fused_adam_traj_optimize` takes as `init_solution`.
+The paths of `rrt.rrt_connect` come as one tensor from `RRTResult.path_tensor()`; what leaves here - one [R, W, dof] tensor with a
+count per path - is what `resample.resample_paths` brings to one waypoint count and `traj.optimize_paths` optimises as R problems
+at once (a single path, read back, is still a valid `init_solution` of `fused_adam_traj_optimize`).
 """
 import math
 
@@ -67,6 +68,41 @@ def _subdivide(p, step, mask):
     return torch.cat(rows)
 
 
+def _path_tensor(who, paths, counts, dev):
+    """(path [R, W, dof] float32, count [R]) on `dev` of a tensor of paths with its counts, or the ValueError of the mistake
+    (one flag read back: whether every count lies in 0 .. W)"""
+    if paths.dim() != 3 or counts is None:
+        raise ValueError(f"{who}: a tensor of paths must be [R, W, dof] and come with `counts` [R]")
+    path = paths.detach().to(device=dev, dtype=torch.float32)
+    count = torch.as_tensor(counts).detach().to(device=dev).reshape(-1)
+    if len(count) != len(path) or count.dtype.is_floating_point or bool(((count < 0) | (count > path.shape[1])).any()):
+        raise ValueError(f"{who}: counts must be {len(path)} integers in [0, {path.shape[1]}]")
+    return path, count
+
+
+def _path_rows(who, paths, counts, dev):
+    """(rows, dof) of the two forms a batch of paths comes in - a list of [W_r, dof] tensors or None, or a [R, W, dof] tensor
+    with counts [R]: per path a float32 [n, dof] tensor on `dev`, or None.  `who` names the caller in the ValueErrors
+    (shortcut_paths and resample.resample_paths take the same forms and refuse the same mistakes)."""
+    if torch.is_tensor(paths):
+        path, count = _path_tensor(who, paths, counts, dev)
+        rows = [path[r, :n] if n else None for r, n in enumerate(count.tolist())]
+        dof = int(path.shape[2])
+    else:
+        if counts is not None:
+            raise ValueError(f"{who}: `counts` goes with a tensor of paths; a list carries its own lengths")
+        rows = [None if p is None else torch.as_tensor(p).detach().to(device=dev, dtype=torch.float32) for p in paths]
+        shaped = [p for p in rows if p is not None]
+        if any(p.dim() != 2 for p in shaped) or len({int(p.shape[1]) for p in shaped}) > 1:
+            raise ValueError(f"{who}: every path must be a [W_r, dof] tensor of the same dof")
+        if not shaped:
+            raise ValueError(f"{who}: a list of paths needs at least one path (its dof); pass a tensor with counts")
+        dof = int(shaped[0].shape[1])
+    if dof < 1:
+        raise ValueError(f"{who}: dof must be >= 1")
+    return rows, dof
+
+
 class _Pass:
     """what both routes share: the arguments, the state, the draws, the loop"""
 
@@ -83,27 +119,7 @@ class _Pass:
         if subdivide is not None and not float(subdivide) > 0:
             raise ValueError("shortcut_paths: subdivide must be > 0")
         self.dev = dev
-        if torch.is_tensor(paths):
-            if paths.dim() != 3 or counts is None:
-                raise ValueError("shortcut_paths: a tensor of paths must be [R, W, dof] and come with `counts` [R]")
-            path = paths.detach().to(device=dev, dtype=torch.float32)
-            count = torch.as_tensor(counts).detach().to(device=dev).reshape(-1)
-            if len(count) != len(path) or count.dtype.is_floating_point or bool(((count < 0) | (count > path.shape[1])).any()):
-                raise ValueError(f"shortcut_paths: counts must be {len(path)} integers in [0, {path.shape[1]}]")
-            rows = [path[r, :n] if n else None for r, n in enumerate(count.tolist())]
-            self.dof = int(path.shape[2])
-        else:
-            if counts is not None:
-                raise ValueError("shortcut_paths: `counts` goes with a tensor of paths; a list carries its own lengths")
-            rows = [None if p is None else torch.as_tensor(p).detach().to(device=dev, dtype=torch.float32) for p in paths]
-            shaped = [p for p in rows if p is not None]
-            if any(p.dim() != 2 for p in shaped) or len({int(p.shape[1]) for p in shaped}) > 1:
-                raise ValueError("shortcut_paths: every path must be a [W_r, dof] tensor of the same dof")
-            if not shaped:
-                raise ValueError("shortcut_paths: a list of paths needs at least one path (its dof); pass a tensor with counts")
-            self.dof = int(shaped[0].shape[1])
-        if self.dof < 1:
-            raise ValueError("shortcut_paths: dof must be >= 1")
+        rows, self.dof = _path_rows("shortcut_paths", paths, counts, dev)
         self.mask = _ops.wrap_mask(wrap, self.dof, _transform_of(checker))
         if subdivide is not None:
             rows = [None if p is None else _subdivide(p, float(subdivide), self.mask) for p in rows]

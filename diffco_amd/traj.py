@@ -277,6 +277,58 @@ def _dense_adam_traj_optimize(robot, model, prob, inits, options, lr, wrap, t0, 
             'dense_frozen_on_bound': [int(i) for i in torch.nonzero(over).reshape(-1)]}
 
 
+def optimize_paths(robot, dist_est, paths, counts=None, *, n_waypoints, options, wrap=None):
+    """R different planning problems optimised at once from their planned paths: `paths` / `counts` (what rrt_connect's
+    path_tensor(), Roadmap.query_batch and shortcut_paths return, or a list of [W_r, dof] tensors or None) are resampled to
+    n_waypoints waypoints each (resample.resample_paths: the endpoints keep their bits) and the R rows run as ONE DenseAdamRun -
+    its rows are independent problems: fixed endpoints, `done`, `steps` and the best paths are all per row.  No walk over the
+    paths on the host between the stages; the summaries are read back once at the end.
+
+    options: 'MAXITER', 'max_speed', 'safety_margin', 'extra_optimizer_options'['lr'], 'dense_max_samples',
+    'stationary_grad_norm' and 'fused_chunk', as fused_adam_traj_optimize reads them under 'dense_check' (the restart keys
+    'NUM_RE_TRIALS', 'N_WAYPOINTS', 'init_solution' and 'seed' are not read: nothing is drawn).  `wrap` as on the motion calls.
+    A row without a path after resampling (count 0) enters the run frozen - no step is taken on it - and answers None.
+    Returns a list with one entry per input path, in order: None, or a dict with 'success', 'cost' (select_trial's policy on
+    that row alone: the best valid path and its objective, else the lowest-loss path), 'solution' (the [n_waypoints, dof] device
+    tensor), 'steps', 'cnt_check' (the samples scored for it) and 'frozen_on_bound' (a segment outgrew dense_max_samples)."""
+    from .resample import resample_paths
+    model = _resolve_model(dist_est)
+    if robot.fk_desc().key() != model.desc.key():
+        raise ValueError("the checker's transform is not this robot's fkine: the fused step shares one FK")
+    res = resample_paths(paths, counts, n_waypoints=n_waypoints, wrap=wrap, transform=robot.fkine)
+    R, T, dof = res.path.shape
+    if R == 0:
+        return []
+    mask = _ops.wrap_mask(wrap, dof, robot.fkine)
+    max_iter = int(options['MAXITER'])
+    lr = options.get('extra_optimizer_options', {}).get('lr', 5e-1)
+    run = DenseAdamRun(model, robot.limits, res.path.to(model.dev), lr, options.get('safety_margin', 0.0), options['max_speed'],
+                       max_samples=options.get('dense_max_samples'), wrap=mask, grad_tol=options.get('stationary_grad_norm'))
+    t = run.t
+    dead = res.count.to(model.dev) == 0
+    t['done'].copy_(dead.to(torch.int32))   # frozen from the start: the step kernel leaves a done row as it is
+    chunk = int(options.get('fused_chunk', 50))
+    while run.it < max_iter:
+        run.run(min(chunk, max_iter - run.it))
+        if run.it < max_iter and run.all_done():
+            break
+    # the one read-back of results: per row best_valid_obj, lowest_loss, lowest_obj, steps, n_checks, frozen on the bound, no path
+    summ = torch.stack([t['best_valid_obj'].double(), t['lowest_loss'].double(), t['lowest_obj'].double(), t['steps'].double(),
+                        run.n_checks.double(), (t['stats'][:, 7] == -2).double(), dead.double()], dim=1).cpu()
+    best_valid_path, lowest_path = t['best_valid_path'], t['lowest_path']
+    run.close()
+    records = []
+    for r in range(R):
+        if summ[r, 6]:
+            records.append(None)
+            continue
+        _, found, cost, _ = select_trial(summ[r:r + 1, 0].float(), summ[r:r + 1, 1].float(), summ[r:r + 1, 2].float(),
+                                         summ[r:r + 1, 3], T)
+        records.append({'success': found, 'cost': cost, 'solution': (best_valid_path if found else lowest_path)[r],
+                        'steps': int(summ[r, 3]), 'cnt_check': int(summ[r, 4]), 'frozen_on_bound': bool(summ[r, 5])})
+    return records
+
+
 def fused_adam_traj_optimize(robot, dist_est, start_cfg, target_cfg, options, group=None, wrap=None):
     """Drop-in for `optim.adam_traj_optimize` with all restarts batched on the GPU.  With an initialised
     torch.distributed `group` (or the default group when options['distributed'] is true) the restarts are sharded

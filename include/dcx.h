@@ -865,6 +865,55 @@ int dcx_sssp_extract_paths(int device, const dcx_graph* graph, const float* node
                            const dcx_sssp_links* goal_links, const float* direct_len, float* path, int32_t* count, float* length,
                            int32_t W, void* stream);
 
+/* ---- batched path resampling (added under DCX_VERSION 109) ------------------------------------------------ */
+/* R piecewise-straight paths of uneven length resampled to T waypoints each, equally spaced in arc length under the motion
+ * calls' metric: what joins the planners' paths (dcx_rrt_extract_paths, dcx_sssp_extract_paths, dcx_path_shortcut_run) to the
+ * trajectory optimisers, which take rows of one fixed length.  One launch on `device`, without a model.
+ *   path [R, W, dof] float, count [R] int32, wrap_mask: as for dcx_path_shortcut_run (a count above W is read as W)
+ *   out [R, T, dof] float           the resampled rows; must not overlap path
+ *   out_count [R] int32             T, or 0 for a row without a path
+ *   length [R] float                the path's length L; may be NULL
+ * Path r, n = min(count[r], W).  Every float operation is fp32 and rounded on its own unless said otherwise.
+ * No path: n < 2 gives out_count[r] = 0 and length[r] = NaN, and row r of out is not written.
+ * Segment lengths, e = 0 .. n - 2: d_e[j] = the delta of coordinate j of the motion path[r, e] -> path[r, e + 1] (the rounded
+ *   difference, wrapped to the shortest arc where bit j of wrap_mask is set: dcx_check_motions_ex's), and len_e the edge length
+ *   as the motion calls form it: the squares summed from +0 in coordinate order, product and sum rounded separately, then a
+ *   correctly rounded square root.
+ * Arc length at the waypoints, in a fixed association (a parallel implementation and a referee must add in the same order).
+ *   Chunk g covers segments 32 g .. 32 g + 31 (DCX_RESAMPLE_CHUNK):
+ *     within a chunk   p_{g,0} = +0,  p_{g,i+1} = p_{g,i} + len_{32 g + i};  the chunk total t_g is the last p of the chunk
+ *     across chunks    b_0 = +0,  b_{g+1} = b_g + t_g, taken in order
+ *     c_e = b_{e / 32} + p_{e / 32, e % 32} for e = 0 .. n - 1, and L = c_{n-1}
+ *   c is non-decreasing: lengths are >= 0 and fp addition is monotone in each operand, so p grows within a chunk, b grows
+ *   across chunks, and c_{32 g + 32} = b_g + t_g is not below any b_g + p_{g,i}.  The search below relies on it.
+ * Bad length: !(L < +inf) (NaN or infinite) gives out_count[r] = 0 and length[r] = L, and the row is not written.  (Every NaN
+ *   stored in length is the quiet NaN 0x7fc00000: which NaN an fp32 sum of NaNs yields is the hardware's choice.)
+ * Otherwise out_count[r] = T, length[r] = L, out[r, 0] takes the bits of path[r, 0], out[r, T - 1] the bits of
+ *   path[r, n - 1], and for 0 < t < T - 1:
+ *     step = L / (float)(T - 1), correctly rounded;  s = (float)t * step
+ *     e = the largest index in 0 .. n - 2 with c_e <= s (c_0 = 0 <= s: there is one), so zero-length segments are skipped and
+ *         an s that rounding pushed past L lands in the last segment
+ *     a = s - c_e
+ *     !(a < len_e):  out[r, t] takes the bits of path[r, e + 1]
+ *     else f = a / len_e, correctly rounded, and coordinate j is
+ *         wrap2pi(path[r, e, j] + f * d_e[j]), product and sum rounded alone, where bit j of the mask is set
+ *         fma(f, d_e[j], path[r, e, j]) elsewhere
+ *       (the split the motion calls' samples make).
+ * Launch behaviour: one call does no allocation and no synchronisation, no atomic decides any order, nothing is read back; it
+ *   can be captured, and repeated calls give the same bits.
+ * work: dcx_path_resample_work_bytes(R, W) bytes of device memory, the caller's (c and len of the rows too long for a block's
+ *   LDS, [R, W] floats each); written by the call before it is read.
+ * Argument errors (DCX_ERR_INVALID, before any device work): R < 0; W outside 1 .. DCX_SHORTCUT_MAX_WAYPOINTS; T outside
+ *   2 .. DCX_SHORTCUT_MAX_WAYPOINTS; dof < 1; a wrap_mask bit at or above dof; with R > 0 a NULL path, count, out, out_count or
+ *   work; work_bytes below dcx_path_resample_work_bytes.  R above 2^31 - 1 and dof above DCX_MAX_DOF are DCX_ERR_UNSUPPORTED.
+ *   R = 0 launches nothing and accepts NULLs.  dcx_path_resample_work_bytes is 0 for a refused R or W, and non-decreasing in R
+ *   and in W.                                                                                                                 */
+#define DCX_RESAMPLE_CHUNK 32
+size_t dcx_path_resample_work_bytes(int64_t R, int32_t W);
+int dcx_path_resample(int device, const float* path, const int32_t* count, int64_t R, int32_t W, int32_t dof,
+                      uint64_t wrap_mask, int32_t T, float* out, int32_t* out_count, float* length,
+                      void* work, size_t work_bytes, void* stream);
+
 /* ---- kernel-perceptron trainer (producer of the path's state) ----------------------- */
 /* DiffCo.train_perceptron kernel_perceptrons.py:98-137 and MultiDiffCo.train_perceptron
  * deprecated/MultiDiffCo.py:50-83 as one persistent launch: worst-margin search, lazily filled kernel rows,
