@@ -96,6 +96,10 @@ SYMBOLS = {
     "dcx_path_shortcut_run": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, _c_fp, C.c_int32, C.c_void_p, _c_fp, C.c_void_p,
                                         C.c_size_t, C.c_void_p]),
     "dcx_rrt_extract_paths": (C.c_int, [C.c_int, C.c_void_p, C.c_int64, C.c_int32, C.c_int32, _c_fp, _c_fp, C.c_int32, C.c_void_p]),
+    # partial shortcuts: chords between points inside segments, on the same state and options (W is also the capacity)
+    "dcx_path_shortcut_partial_work_bytes": (C.c_size_t, [C.c_void_p, C.c_int64, C.c_int32, C.c_int32]),
+    "dcx_path_shortcut_partial_run": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, _c_fp, C.c_int32, C.c_void_p, _c_fp, C.c_void_p,
+                                                C.c_size_t, C.c_void_p]),
     # roadmap queries: min-plus relaxation over the roadmap's CSR for Q start/goal pairs, and their routes as one tensor
     "dcx_sssp_run": (C.c_int, [C.c_int, C.c_void_p, C.c_int64, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p,
                                C.c_void_p]),

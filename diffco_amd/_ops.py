@@ -707,11 +707,12 @@ class ScoreModel:
             _lib.check(self._lib.dcx_rrt_connect_run(self._h, C.byref(st), R, _ptr(samples), T, int(round0), C.byref(opt), _ptr(mg),
                                                      _ptr(work), nbytes, self._st()))
 
-    def shortcut_run(self, state, draws, max_step, max_samples, margin=0., wrap=None):
-        """T rounds of batched path shortcutting (dcx_path_shortcut_run) on the caller's state, in place: `state` maps path
-        [R, W, dof] float32, count [R] and accepted [R] (int32) to contiguous tensors on the model's device; draws [T, R, P, 2]
-        float32 there.  The rounds are enqueued on torch's current stream; nothing is read back (capturable).  `margin` as
-        check_motions."""
+    def shortcut_run(self, state, draws, max_step, max_samples, margin=0., wrap=None, partial=False):
+        """T rounds of batched path shortcutting (dcx_path_shortcut_run; partial=True: dcx_path_shortcut_partial_run, chords
+        between points inside segments, W also the capacity a path may grow into) on the caller's state, in place: `state` maps
+        path [R, W, dof] float32, count [R] and accepted [R] (int32) to contiguous tensors on the model's device; draws
+        [T, R, P, 2] float32 there.  The rounds are enqueued on torch's current stream; nothing is read back (capturable).
+        `margin` as check_motions."""
         if draws.dim() != 4:
             raise ValueError("shortcut_run: draws must be [T, R, P, 2]")
         T, R, P = (int(v) for v in draws.shape[:3])
@@ -727,11 +728,13 @@ class ScoreModel:
         st = _lib.ShortcutState(*(state[n].data_ptr() for n in kinds))
         opt = _lib.ShortcutOpts(float(max_step), int(max_samples), P, W, wrap_mask(wrap, self.dof), (C.c_int64 * 2)(0, 0))
         mg = self._motion_margin(margin)
-        nbytes = self._lib.dcx_path_shortcut_work_bytes(self._h, R, P)
+        if partial:
+            nbytes, run = self._lib.dcx_path_shortcut_partial_work_bytes(self._h, R, P, W), self._lib.dcx_path_shortcut_partial_run
+        else:
+            nbytes, run = self._lib.dcx_path_shortcut_work_bytes(self._h, R, P), self._lib.dcx_path_shortcut_run
         work = self._work(nbytes)
         with _on_device(self.dev):
-            _lib.check(self._lib.dcx_path_shortcut_run(self._h, C.byref(st), R, _ptr(draws), T, C.byref(opt), _ptr(mg), _ptr(work),
-                                                       nbytes, self._st()))
+            _lib.check(run(self._h, C.byref(st), R, _ptr(draws), T, C.byref(opt), _ptr(mg), _ptr(work), nbytes, self._st()))
 
     def _motion_args(self, name, qa, qb, res, max_step, max_samples, wrap):
         """what every motion call starts with: (qa32, qb32 [E, dof] fp32 on the device, E, res, max_step, max_samples, mask) with

@@ -22,6 +22,7 @@
 #include "knn_kernel.h"
 #include "rrt_kernel.h"
 #include "shortcut_kernel.h"
+#include "shortcut_partial_kernel.h"
 #include "resample_kernel.h"
 #include "sssp_kernel.h"
 
@@ -2678,6 +2679,79 @@ int dcx_path_shortcut_run(const dcx_model* m, const dcx_shortcut_state* state, i
             return rc;
         e = launch_shortcut_commit(a, st);
         if (e != hipSuccess) return fail_hip(e, "shortcut commit launch");
+    }
+    return DCX_OK;
+}
+
+// ---- partial shortcuts (shortcut_partial_kernel.h): the size query and the call share the checks and shortcut_partial_plan ----
+static int shortcut_partial_check_sizes(const dcx_model* m, int64_t R, int32_t slots, int32_t W) {
+    if (int rc = shortcut_check_sizes(m, R, slots)) return rc;
+    if (W < 1 || W > DCX_SHORTCUT_MAX_WAYPOINTS) return fail(DCX_ERR_INVALID, "shortcut: W must be in [1, DCX_SHORTCUT_MAX_WAYPOINTS]");
+    return DCX_OK;
+}
+
+size_t dcx_path_shortcut_partial_work_bytes(const dcx_model* m, int64_t R, int32_t slots, int32_t W) {
+    if (shortcut_partial_check_sizes(m, R, slots, W)) return 0;
+    return shortcut_partial_plan(R, slots, W, m->fk.dof, motion_work(R * slots).total).total;
+}
+
+int dcx_path_shortcut_partial_run(const dcx_model* m, const dcx_shortcut_state* state, int64_t R, const float* draws, int32_t T,
+                                  const dcx_shortcut_opts* opt, const float* margin, void* work, size_t work_bytes, void* stream) {
+    // every argument is checked before anything touches the model's device: dcx_path_shortcut_run's checks
+    if (!opt) return fail(DCX_ERR_INVALID, "shortcut: options are NULL");
+    if (T < 0) return fail(DCX_ERR_INVALID, "shortcut: T < 0");
+    if (int rc = shortcut_partial_check_sizes(m, R, opt->slots, opt->W)) return rc;
+    if (!(opt->max_step > 0.f)) return fail(DCX_ERR_INVALID, "shortcut: max_step must be > 0");
+    if (opt->max_samples < 1) return fail(DCX_ERR_INVALID, "shortcut: max_samples must be >= 1");
+    if (opt->reserved[0] || opt->reserved[1]) return fail(DCX_ERR_INVALID, "shortcut: reserved fields must be 0");
+    if (opt->wrap_mask != 0 && m->fk.dof < 64 && (opt->wrap_mask >> m->fk.dof) != 0)
+        return fail(DCX_ERR_INVALID, "shortcut: wrap_mask has a bit at or above dof");
+    if (R > 0 && (!state || !state->path || !state->count || !state->accepted))
+        return fail(DCX_ERR_INVALID, "shortcut: state or one of its pointers is NULL");
+    if (R > 0 && T > 0 && !draws) return fail(DCX_ERR_INVALID, "shortcut: draws is NULL");
+    if (R > 0 && !work) return fail(DCX_ERR_INVALID, "shortcut: work is NULL");
+    const int64_t E = R * opt->slots;
+    const MotionWork mw = motion_work(E);
+    const ShortcutPartialPlan plan = shortcut_partial_plan(R, opt->slots, opt->W, m->fk.dof, mw.total);
+    if (R > 0 && work_bytes < plan.total)
+        return fail(DCX_ERR_INVALID, "shortcut: the workspace is smaller than dcx_path_shortcut_partial_work_bytes");
+    if (R == 0 || T == 0) return DCX_OK;
+    // what dcx_check_motions_ex could still refuse depends on (model, E, max_samples) alone: refused here, before the first launch
+    if (m->fk.dof < 1 || m->fk.dof > DCX_MAX_DOF) return fail(DCX_ERR_UNSUPPORTED, "shortcut: dof outside 1 .. DCX_MAX_DOF");
+    if ((E * (int64_t)opt->max_samples + 63) / 64 > 0x7fffffffLL)
+        return fail(DCX_ERR_UNSUPPORTED, "shortcut: R * slots * max_samples too large for one launch");
+    if (!motion_for(m->Dt)) return fail(DCX_ERR_UNSUPPORTED, "shortcut: no motion kernel for this feature width");
+    if (int rc = set_device(m->device)) return rc;
+    hipStream_t st = (hipStream_t)stream;
+    char* base = (char*)work;
+    ShortcutPartialArgs a{};
+    a.path = state->path;
+    a.count = state->count;
+    a.accepted = state->accepted;
+    a.qa = (float*)(base + plan.slot.qa);
+    a.qb = (float*)(base + plan.slot.qb);
+    a.first_hit = (int32_t*)(base + plan.slot.first_hit);
+    a.picks = (int32_t*)(base + plan.slot.picks);
+    a.stage = (float*)(base + plan.stage);
+    a.work_c = (float*)(base + plan.c);
+    a.work_len = (float*)(base + plan.len);
+    a.wrap_mask = opt->wrap_mask;
+    a.R = (int32_t)R;
+    a.P = opt->slots;
+    a.W = opt->W;
+    a.dof = m->fk.dof;
+    dcx_motion_opts mo{};
+    mo.max_step = opt->max_step;
+    mo.max_samples = opt->max_samples;
+    for (int32_t t = 0; t < T; ++t) {
+        a.draws = draws + (int64_t)t * E * 2;
+        hipError_t e = launch_shortcut_partial_pick(a, st);
+        if (e != hipSuccess) return fail_hip(e, "partial shortcut pick launch");
+        if (int rc = dcx_check_motions_ex(m, a.qa, a.qb, E, &mo, margin, (int32_t*)(base + plan.slot.first_hit), nullptr, work, mw.total,
+                                          opt->wrap_mask, stream))
+            return rc;
+        e = launch_shortcut_partial_commit(a, st);
+        if (e != hipSuccess) return fail_hip(e, "partial shortcut commit launch");
     }
     return DCX_OK;
 }

@@ -1,30 +1,22 @@
 // resample_kernels.hip — dcx_path_resample (include/dcx.h, "batched path resampling"; resample_kernel.h): R paths of uneven
 // length resampled to T waypoints each, equally spaced in arc length.  One block per path, five barrier-separated phases:
-//   lengths: one thread per segment: len_e from the two rows (neighbouring threads share the rows' cache lines: a row leaves
-//            HBM once)
-//   chunks:  one thread per chunk of 32 segments, sequentially inside the chunk: the contract's p, and the chunk's total
-//   totals:  one thread adds the chunk totals in order: the contract's b (at most 2048 dependent adds)
-//   finish:  c_e = b + p, one thread per waypoint; L = c_{n-1}
+//   lengths, chunks, totals, finish: the arc length c_e at the waypoints in the contract's association; L = c_{n-1}.  They
+//            are arclen_device.h's path_arc_length, which the partial shortcut's pick kernel runs too: one definition
 //   outputs: one thread per output float (t, j), so the stores are coalesced: the largest e with c_e <= s by a binary search
-//            over c (non-decreasing: the header says why), then the interpolation.  The dof threads of one waypoint repeat
-//            the search (<= 16 reads of c each) instead of sharing it through another barrier.
+//            over c (non-decreasing: the header says why), then the interpolation (arc_locate, arc_point).  The dof threads
+//            of one waypoint repeat the search (<= 16 reads of c each) instead of sharing it through another barrier.
 // Every loop runs the block over its range: neither n nor T is bounded by the block size.  c and len live in LDS (each chunk
 // of 32 padded by one word: the chunk threads' stride becomes 33 banks) or, for a path of more than kResampleLdsWaypoints
 // waypoints, in the workspace.  Nothing is atomic and nothing depends on the launch geometry: repeated calls give the same bits.
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include "resample_kernel.h"
-#include "wrap_device.h"
+#include "arclen_device.h"
 
 namespace dcx {
 namespace {
 
-template <bool kLds>
-__device__ __forceinline__ int slot(int e) {
-    return kLds ? e + (e >> 5) : e;
-}
-
-// c, ln: n entries each (slot()'s layout); sB: the chunk totals, then their exclusive sums
+// c, ln: n entries each (arc_slot's layout); sB: the chunk totals, then their exclusive sums
 template <bool kLds>
 __device__ __forceinline__ void resample_path(const ResampleArgs& a, const int64_t r, const int n, float* const c, float* const ln,
                                               float* const sB) {
@@ -33,57 +25,9 @@ __device__ __forceinline__ void resample_path(const ResampleArgs& a, const int64
     const uint64_t mask = a.wrap_mask;
     const float* const row = a.path + r * (int64_t)a.W * dof;
 
-    // lengths: motion_prep.hip's edge length, statement by statement
-    for (int e = tid; e < n - 1; e += kResampleThreads) {
-        const float* const qa = row + (int64_t)e * dof;
-        float l2 = 0.0f;
-        for (int j = 0; j < dof; ++j) {
-            const float d = motion_delta(qa[j], qa[dof + j], mask, j);
-            l2 = l2 + d * d;
-        }
-        ln[slot<kLds>(e)] = sqrtf(l2);   // (correctly rounded: motion_prep.hip says why not __fsqrt_rn)
-    }
-    __syncthreads();
+    path_arc_length<kLds>(row, n, dof, mask, c, ln, sB);   // lengths, chunks, totals, finish (arclen_device.h)
 
-    // chunks: p_{g,i} into c, the chunk's total into sB
-    const int chunks = (n + kResampleChunk - 1) / kResampleChunk;   // (of the n entries of c; <= kResampleMaxChunks)
-    for (int g = tid; g < chunks; g += kResampleThreads) {
-        float p = 0.0f;
-        const int e0 = g * kResampleChunk;
-        for (int i = 0; i < kResampleChunk; ++i) {
-            const int e = e0 + i;
-            if (e < n) c[slot<kLds>(e)] = p;
-            if (e < n - 1) p = p + ln[slot<kLds>(e)];
-        }
-        sB[g] = p;   // (the last chunk's total is never used)
-    }
-    __syncthreads();
-
-    // totals: b_g in order
-    if (tid == 0) {
-        float b = 0.0f;
-        for (int g0 = 0; g0 < chunks; g0 += 8) {   // eight totals per LDS round trip; the adds stay one chain
-            float t[8];
-#pragma unroll
-            for (int u = 0; u < 8; ++u) t[u] = g0 + u < chunks ? sB[g0 + u] : 0.0f;
-#pragma unroll
-            for (int u = 0; u < 8; ++u) {
-                const float before = b;
-                b = b + t[u];
-                t[u] = before;
-            }
-#pragma unroll
-            for (int u = 0; u < 8; ++u)
-                if (g0 + u < chunks) sB[g0 + u] = t[u];
-        }
-    }
-    __syncthreads();
-
-    // finish: c_e = b_{e / 32} + p_{e / 32, e % 32}
-    for (int e = tid; e < n; e += kResampleThreads) c[slot<kLds>(e)] = sB[e / kResampleChunk] + c[slot<kLds>(e)];
-    __syncthreads();
-
-    const float L = c[slot<kLds>(n - 1)];
+    const float L = c[arc_slot<kLds>(n - 1)];
     const bool ok = L < INFINITY;   // (block-uniform; a NaN fails it)
     if (tid == 0) {
         a.out_count[r] = ok ? T : 0;
@@ -106,27 +50,7 @@ __device__ __forceinline__ void resample_path(const ResampleArgs& a, const int64
             continue;
         }
         const float s = (float)t * step;
-        int lo = 0, hi = n - 2;   // c_0 = +0 <= s
-        while (lo < hi) {
-            const int mid = (lo + hi + 1) >> 1;
-            if (c[slot<kLds>(mid)] <= s) lo = mid;
-            else hi = mid - 1;
-        }
-        const float arc = s - c[slot<kLds>(lo)];
-        const float len = ln[slot<kLds>(lo)];
-        const float qa = row[(int64_t)lo * dof + j], qb = row[(int64_t)(lo + 1) * dof + j];
-        if (!(arc < len)) {
-            out[i] = qb;
-            continue;
-        }
-        const float f = __fdiv_rn(arc, len);
-        const float d = motion_delta(qa, qb, mask, j);
-        if ((mask >> j) & 1ull) {
-            const float p = f * d;
-            out[i] = wrap2pi_f32(qa + p);
-        } else {
-            out[i] = fmaf(f, d, qa);
-        }
+        out[i] = arc_point<kLds>(row, c, ln, dof, mask, arc_locate<kLds>(c, n, s), s, j);
     }
 }
 

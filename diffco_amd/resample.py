@@ -11,12 +11,10 @@ the referee of the fused call (equal path, count and lengths, bit for bit) and t
 import torch
 
 from . import _ops
-from .rrt import _div, _f32, _fma32, _length, _wrap
-from .shortcut import MAX_WAYPOINTS, _path_rows, _path_tensor
+from .rrt import _div, _f32
+from .shortcut import MAX_WAYPOINTS, _arc_length, _arc_points, _path_rows, _path_tensor
 
 __all__ = ["resample_paths", "host_resample_paths", "ResampleResult"]
-
-CHUNK = 32   # DCX_RESAMPLE_CHUNK
 
 
 class ResampleResult:
@@ -66,54 +64,20 @@ def _host(path, count, T, mask):
     if R == 0:
         return out, torch.zeros(0, dtype=torch.int32, device=dev), torch.zeros(0, dtype=torch.float32, device=dev)
     n = count.to(torch.int64).clamp(max=W)                                         # [R]
-    k = torch.arange(W, device=dev)[None, :]                                       # [1, W]
-    # segment e = 0 .. W - 1 (the last one has no end: it is never live); rows at and beyond n are never read into a result
-    nxt = torch.cat([path[:, 1:], path[:, -1:]], dim=1)
-    d = _ops.wrapped_delta(path, nxt, mask)                                        # [R, W, dof]
-    live = k < (n[:, None] - 1)
     zero = torch.zeros((), dtype=torch.float32, device=dev)
-    seg = torch.where(live, _length(d), zero)                                      # [R, W]: +0 where there is no segment
-
-    # arc length at the waypoints in the fixed association: 32 steps inside every chunk, then the chunk totals in order
-    G = (W + CHUNK - 1) // CHUNK
-    seg3 = torch.cat([seg, torch.zeros((R, G * CHUNK - W), dtype=torch.float32, device=dev)], dim=1).reshape(R, G, CHUNK)
-    p = torch.zeros((R, G), dtype=torch.float32, device=dev)
-    within = []
-    for i in range(CHUNK):
-        within.append(p)
-        p = p + seg3[:, :, i]
-    within = torch.stack(within, dim=2)                                            # [R, G, 32]: p_{g,i};  p is now t_g
-    b = torch.zeros(R, dtype=torch.float32, device=dev)
-    base = []
-    for g in range(G):
-        base.append(b)
-        b = b + p[:, g]
-    base = torch.stack(base, dim=1)                                                # [R, G]: b_g
-    c = (base[:, :, None] + within).reshape(R, G * CHUNK)[:, :W]                   # [R, W]
-    L = c.gather(1, (n - 1).clamp(min=0)[:, None])[:, 0]
+    # the arc length at the waypoints in the fixed association (shortcut.py's _arc_length: the partial shortcut's referee shares it)
+    arc = _arc_length(path, n, mask)
+    L = arc[3].gather(1, (n - 1).clamp(min=0)[:, None])[:, 0]
 
     has = n >= 2
     ok = has & (L < float("inf"))
     length = torch.where(has & ~torch.isnan(L), L, torch.full_like(L, float("nan")))   # (every NaN the one quiet NaN)
     out_count = torch.where(ok, torch.full_like(n, T), torch.zeros_like(n)).to(torch.int32)
 
-    # the output waypoints: the largest e in 0 .. n - 2 with c_e <= s
+    # the output waypoints: the largest e in 0 .. n - 2 with c_e <= s, then the interpolation
     step = _div(torch.where(ok, L, zero), _f32(float(T - 1), dev))
     s = torch.arange(T, device=dev).to(torch.float32)[None, :] * step[:, None]     # [R, T]
-    keys = torch.where(ok[:, None] & (k <= (n[:, None] - 2)), c, torch.full_like(c, float("inf")))
-    keys = torch.where(ok[:, None], keys, zero.expand_as(keys)).contiguous()
-    e = (torch.searchsorted(keys, s.contiguous(), right=True) - 1).clamp(min=0)
-    e = torch.minimum(e, (n[:, None] - 2).clamp(min=0))                            # [R, T]
-    arc = s - c.gather(1, e)
-    ln = seg.gather(1, e)
-    at = e[:, :, None].expand(R, T, dof)
-    qa, qb, de = path.gather(1, at), nxt.gather(1, at), d.gather(1, at)
-    f = _div(arc, ln)[:, :, None]
-    point = _fma32(f, de, qa)
-    if mask:
-        on = torch.tensor([bool((mask >> j) & 1) for j in range(dof)], device=dev)
-        point = torch.where(on, _wrap(qa + f * de, mask), point)
-    rows = torch.where((arc < ln)[:, :, None], point, qb)
+    rows = _arc_points(path, n, arc, s, ok, mask)[1]
     rows[:, 0] = path[:, 0]
     rows[:, T - 1] = path.gather(1, (n - 1).clamp(min=0)[:, None, None].expand(R, 1, dof))[:, 0]
     out = torch.where(ok[:, None, None], rows, out)

@@ -8,6 +8,11 @@ and the paths are on the GPU, and `host_shortcut_paths` everywhere else.  `host_
 on the same fixed batch of R * P edges: the referee of the fused pass (equal path[:count], count and accepted, bit for bit, for
 equal draws) and the baseline it is measured against.  It runs on CPU tensors with any checker that has such a `check_motions`.
 
+`partial=True` is the second mode (include/dcx.h, "Partial shortcuts"; dcx_path_shortcut_partial_run): a slot draws two arc-length
+positions on the path and tries the chord between the two points, inside segments, so corners are cut and not only vertices
+removed.  A slot inside two neighbouring segments adds a waypoint: the state's W is then the `capacity` the paths may grow into.
+Only the chord is checked; the two end pieces lie on segments the path already had (the header says what that does not promise).
+
 The paths of `rrt.rrt_connect` come as one tensor from `RRTResult.path_tensor()`; what leaves here - one [R, W, dof] tensor with a
 count per path - is what `resample.resample_paths` brings to one waypoint count and `traj.optimize_paths` optimises as R problems
 at once (a single path, read back, is still a valid `init_solution` of `fused_adam_traj_optimize`).
@@ -17,12 +22,13 @@ import math
 import torch
 
 from . import _ops
-from .rrt import _Edges, _edge_plan, _f32, _div, _fused_model, _length, _sample, _transform_of
+from .rrt import _Edges, _edge_plan, _f32, _div, _fma32, _fused_model, _length, _sample, _transform_of, _wrap
 
 __all__ = ["shortcut_paths", "host_shortcut_paths", "ShortcutResult"]
 
 MAX_SLOTS = 16            # DCX_SHORTCUT_MAX_SLOTS
 MAX_WAYPOINTS = 1 << 16   # DCX_SHORTCUT_MAX_WAYPOINTS
+CHUNK = 32                # DCX_RESAMPLE_CHUNK
 
 
 class ShortcutResult:
@@ -107,7 +113,7 @@ class _Pass:
     """what both routes share: the arguments, the state, the draws, the loop"""
 
     def __init__(self, checker, paths, counts, dev, max_step, wrap, slots, rounds, rounds_per_call, sampler, seed, max_samples,
-                 subdivide):
+                 subdivide, partial=False, capacity=None):
         self.max_step = float(max_step)
         if not self.max_step > 0:
             raise ValueError("shortcut_paths: max_step must be > 0")
@@ -118,6 +124,9 @@ class _Pass:
             raise ValueError(f"shortcut_paths: rounds must be >= 0, got {rounds}")
         if subdivide is not None and not float(subdivide) > 0:
             raise ValueError("shortcut_paths: subdivide must be > 0")
+        self.partial = bool(partial)
+        if capacity is not None and not self.partial:
+            raise ValueError("shortcut_paths: capacity goes with partial=True; vertex shortcuts never grow a path")
         self.dev = dev
         rows, self.dof = _path_rows("shortcut_paths", paths, counts, dev)
         self.mask = _ops.wrap_mask(wrap, self.dof, _transform_of(checker))
@@ -127,6 +136,11 @@ class _Pass:
         W = max([1] + [len(p) for p in rows if p is not None])
         if W > MAX_WAYPOINTS:
             raise ValueError(f"shortcut_paths: a path has {W} waypoints, more than {MAX_WAYPOINTS}")
+        if self.partial:   # W is also what a path may grow into: by default one round's worth of growth for any `slots`
+            longest, W = W, min(W + MAX_SLOTS, MAX_WAYPOINTS) if capacity is None else int(capacity)
+            if not longest <= W <= MAX_WAYPOINTS:
+                raise ValueError(f"shortcut_paths: capacity must be in [{longest}, {MAX_WAYPOINTS}] (the longest path .. the "
+                                 f"most rows of a path), got {capacity}")
         self.W = W
         self.st = dict(path=torch.zeros((self.R, W, self.dof), dtype=torch.float32, device=dev),
                        count=torch.zeros(self.R, dtype=torch.int32, device=dev),
@@ -215,35 +229,150 @@ def _host_round(ps, edges, u, record=None):
     st["accepted"] += applied.sum(dim=1).to(torch.int32)
 
 
+def _arc_length(path, n, mask):
+    """(nxt, d, seg, c) of include/dcx.h's arc length ("batched path resampling") for path [R, W, dof] and n [R] int64 <= W:
+    the rows' successors, the segments' wrapped deltas [R, W, dof], their lengths len_e [R, W] (+0 where there is no segment)
+    and the arc length at the waypoints c_e [R, W] in the fixed association - 32 steps inside every chunk, then the chunk
+    totals in order.  Shared by resample.py's referee and the partial shortcut's."""
+    R, W, _ = path.shape
+    dev = path.device
+    k = torch.arange(W, device=dev)[None, :]                                       # [1, W]
+    # segment e = 0 .. W - 1 (the last one has no end: it is never live); rows at and beyond n are never read into a result
+    nxt = torch.cat([path[:, 1:], path[:, -1:]], dim=1)
+    d = _ops.wrapped_delta(path, nxt, mask)                                        # [R, W, dof]
+    live = k < (n[:, None] - 1)
+    zero = torch.zeros((), dtype=torch.float32, device=dev)
+    seg = torch.where(live, _length(d), zero)                                      # [R, W]: +0 where there is no segment
+    G = (W + CHUNK - 1) // CHUNK
+    seg3 = torch.cat([seg, torch.zeros((R, G * CHUNK - W), dtype=torch.float32, device=dev)], dim=1).reshape(R, G, CHUNK)
+    p = torch.zeros((R, G), dtype=torch.float32, device=dev)
+    within = []
+    for i in range(CHUNK):
+        within.append(p)
+        p = p + seg3[:, :, i]
+    within = torch.stack(within, dim=2)                                            # [R, G, 32]: p_{g,i};  p is now t_g
+    b = torch.zeros(R, dtype=torch.float32, device=dev)
+    base = []
+    for g in range(G):
+        base.append(b)
+        b = b + p[:, g]
+    base = torch.stack(base, dim=1)                                                # [R, G]: b_g
+    c = (base[:, :, None] + within).reshape(R, G * CHUNK)[:, :W]                   # [R, W]
+    return nxt, d, seg, c
+
+
+def _arc_points(path, n, arc, s, ok, mask):
+    """(e [R, T], points [R, T, dof]) at the arc lengths s [R, T] of the paths with ok [R] (s must be 0 on the others), `arc`
+    being _arc_length's: the largest e in 0 .. n - 2 with c_e <= s, then the contract's interpolation - the bits of
+    path[r, e + 1] where !(s - c_e < len_e)"""
+    nxt, d, seg, c = arc
+    R, W, dof = path.shape
+    T = s.shape[1]
+    dev = path.device
+    k = torch.arange(W, device=dev)[None, :]
+    zero = torch.zeros((), dtype=torch.float32, device=dev)
+    keys = torch.where(ok[:, None] & (k <= (n[:, None] - 2)), c, torch.full_like(c, float("inf")))
+    keys = torch.where(ok[:, None], keys, zero.expand_as(keys)).contiguous()
+    e = (torch.searchsorted(keys, s.contiguous(), right=True) - 1).clamp(min=0)
+    e = torch.minimum(e, (n[:, None] - 2).clamp(min=0))                            # [R, T]
+    a = s - c.gather(1, e)
+    ln = seg.gather(1, e)
+    at = e[:, :, None].expand(R, T, dof)
+    qa, qb, de = path.gather(1, at), nxt.gather(1, at), d.gather(1, at)
+    f = _div(a, ln)[:, :, None]
+    point = _fma32(f, de, qa)
+    if mask:
+        on = torch.tensor([bool((mask >> j) & 1) for j in range(dof)], device=dev)
+        point = torch.where(on, _wrap(qa + f * de, mask), point)
+    return e, torch.where((a < ln)[:, :, None], point, qb)
+
+
+def _host_round_partial(ps, edges, u, record=None):
+    """one round of the partial contract on the state tensors, in place"""
+    st, R, P, W, dof = ps.st, ps.R, ps.P, ps.W, ps.dof
+    path, dev = st["path"], ps.dev
+    n = st["count"].to(torch.int64).clamp(min=0, max=W)
+    arc = _arc_length(path, n, ps.mask)
+    L = arc[3].gather(1, (n - 1).clamp(min=0)[:, None])[:, 0]
+    has = (n >= 3) & (L > 0) & (L < float("inf"))                                    # (a NaN fails it)
+    u0, u1 = u[..., 0], u[..., 1]
+    drawn = has[:, None] & (u0 >= 0) & (u0 < 1) & (u1 >= 0) & (u1 < 1)
+    zero = torch.zeros((), dtype=torch.float32, device=dev)
+    Lz = torch.where(has, L, zero)[:, None]
+    s0, s1 = torch.where(drawn, u0, zero) * Lz, torch.where(drawn, u1, zero) * Lz
+    sa, sb = torch.minimum(s0, s1), torch.maximum(s0, s1)
+    e, pts = _arc_points(path, n, arc, torch.cat([sa, sb], dim=1), has, ps.mask)
+    ea, eb, xa, xb = e[:, :P], e[:, P:], pts[:, :P], pts[:, P:]
+    live = drawn & (ea != eb)
+    root = path[:, :1].expand(R, P, dof)
+    qa = torch.where(live[..., None], xa, root)
+    qb = torch.where(live[..., None], xb, root)
+    first = edges.first_hit(qa.reshape(-1, dof), qb.reshape(-1, dof), root.reshape(-1, dof))[0].reshape(R, P)
+    free = live & (first == -1)
+    applied, apart, cnt = torch.zeros_like(free), torch.zeros_like(free), n.clone()
+    grow = 2 - (eb - ea)
+    for p in range(P):   # slot order: a free slot is applied iff it shares no segment with an applied one and the path has room
+        ok = free[:, p].clone()
+        for q in range(p):
+            ok &= ~applied[:, q] | (eb[:, p] < ea[:, q]) | (eb[:, q] < ea[:, p])
+        apart[:, p] = ok
+        ok = ok & (cnt + grow[:, p] <= W)
+        applied[:, p] = ok
+        cnt = torch.where(ok, cnt + grow[:, p], cnt)
+    if record is not None:
+        record(live, first, free, applied, dict(drawn=drawn, ea=ea, eb=eb, apart=apart, has=has))
+    k = torch.arange(W, device=dev)[None, :, None]                                   # [1, W, 1]
+    a3, b3, on = ea[:, None, :], eb[:, None, :], applied[:, None, :]                 # [R, 1, P]
+    dead = (on & (a3 < k) & (k <= b3)).any(dim=2)                                    # [R, W]
+    shift = torch.where(on & (b3 < k), 2 - (b3 - a3), torch.zeros_like(b3)).sum(dim=2)
+    keep = ~dead & (k[:, :, 0] < n[:, None])
+    rr, kk = torch.nonzero(keep, as_tuple=True)
+    moved = path[rr, kk]   # (a copy: read before anything is written; xa and xb are no views of the path either)
+    ra, pa = torch.nonzero(applied, as_tuple=True)
+    at = ea[ra, pa] + 1 + shift[ra, ea[ra, pa]]
+    path[rr, kk + shift[rr, kk]] = moved
+    path[ra, at] = xa[ra, pa]
+    path[ra, at + 1] = xb[ra, pa]
+    st["count"].copy_(cnt.to(torch.int32))
+    st["accepted"] += applied.sum(dim=1).to(torch.int32)
+
+
 def host_shortcut_paths(checker, paths, counts=None, *, max_step, wrap=None, slots=4, rounds=64, rounds_per_call=32, sampler=None,
-                        seed=0, margin=0., max_samples=None, subdivide=None, _record=None):
+                        seed=0, margin=0., max_samples=None, subdivide=None, partial=False, capacity=None, _record=None):
     """shortcut_paths' contract as the loop a user would write from the library's other calls: per round the pick and the
     compaction as torch indexing, ONE `checker.check_motions(..., return_first=True)` call on the fixed batch of R * slots
     edges.  The state lives on the device of the paths.  `margin` is passed on to the checker's check_motions only where it is
-    not 0."""
+    not 0.  partial, capacity: as shortcut_paths' (the partial contract in torch ops, one rounded fp32 operation at a time and
+    the arc length in the resampler's association; `_record` then gets a fifth argument, the round's drawn, ea, eb, apart, has)."""
     first = paths if torch.is_tensor(paths) else next((p for p in paths if p is not None), None)
     dev = torch.as_tensor(first).device if first is not None else torch.device("cpu")
-    ps = _Pass(checker, paths, counts, dev, max_step, wrap, slots, rounds, rounds_per_call, sampler, seed, max_samples, subdivide)
+    ps = _Pass(checker, paths, counts, dev, max_step, wrap, slots, rounds, rounds_per_call, sampler, seed, max_samples, subdivide,
+               partial, capacity)
     edges = _Edges(checker, ps.max_step, ps.max_samples, ps.mask, margin)
+    one_round = _host_round_partial if ps.partial else _host_round
 
     def run_chunk(draws):
         for u in draws:
-            _host_round(ps, edges, u, _record)
+            one_round(ps, edges, u, _record)
 
     ps.loop(run_chunk)
     return ps.result("host")
 
 
 def shortcut_paths(checker, paths, counts=None, *, max_step, wrap=None, slots=4, rounds=64, rounds_per_call=32, sampler=None,
-                   seed=0, margin=0., max_samples=None, subdivide=None):
-    """Shorten R piecewise-straight paths under `checker` by random vertex shortcuts: a ShortcutResult.
+                   seed=0, margin=0., max_samples=None, subdivide=None, partial=False, capacity=None):
+    """Shorten R piecewise-straight paths under `checker` by random shortcuts - between waypoints, or with partial=True between
+    points inside segments: a ShortcutResult.
     paths: a list of [W_r, dof] tensors or None, or a [R, W, dof] tensor with counts [R];  max_step: the stride of every edge
     check;  wrap (as check_motions: None, True, a bitmask, one bool per coordinate): the circular coordinates, walked along
     their shortest arc;  slots: attempts per path and round (1 .. 16);  rounds: how many;  sampler(T, R, P) -> [T, R, P, 2] in
     [0, 1) (default: uniform, seeded by `seed`);  margin: a sample collides where score - margin > 0, on top of the checker's
     own threshold;  max_samples: the most samples of one edge (default: from the longest path: one read-back before the loop);
     subdivide=step: first insert, on every segment longer than `step`, the max_step-rule points of stride `step`, so that vertex
-    shortcuts have somewhere to land on long edges.
+    shortcuts have somewhere to land on long edges;  partial=True: a slot draws two arc-length positions on the path and tries
+    the chord between the two points (it cuts corners; only the chord is checked, the end pieces lie on segments the path had);
+    capacity (partial only): the rows W of a path, which a slot inside two neighbouring segments grows by one - at least the
+    longest path, at most 65536, default the longest path + 16.
     The fused pass (result.route == "fused") runs for kernel_perceptrons.DiffCo, RBFDiffCo and ForwardKinematicsDiffCo whose
     transform fuses, on paths that are on the GPU; everything else goes through host_shortcut_paths ("host")."""
     first = paths if torch.is_tensor(paths) else next((p for p in paths if p is not None), None)
@@ -252,18 +381,20 @@ def shortcut_paths(checker, paths, counts=None, *, max_step, wrap=None, slots=4,
     if got is None:
         return host_shortcut_paths(checker, paths, counts, max_step=max_step, wrap=wrap, slots=slots, rounds=rounds,
                                    rounds_per_call=rounds_per_call, sampler=sampler, seed=seed, margin=margin,
-                                   max_samples=max_samples, subdivide=subdivide)
+                                   max_samples=max_samples, subdivide=subdivide, partial=partial, capacity=capacity)
     model, base = got
     if isinstance(base, (int, float)) and isinstance(margin, (int, float)):
         mg = float(base) + float(margin)
     else:   # one per class on either side
         mg = (torch.as_tensor(base, dtype=torch.float32).reshape(-1).to(model.dev)
               + torch.as_tensor(margin, dtype=torch.float32).reshape(-1).to(model.dev))
-    ps = _Pass(checker, paths, counts, model.dev, max_step, wrap, slots, rounds, rounds_per_call, sampler, seed, max_samples, subdivide)
+    ps = _Pass(checker, paths, counts, model.dev, max_step, wrap, slots, rounds, rounds_per_call, sampler, seed, max_samples, subdivide,
+               partial, capacity)
     mg_dev = model._motion_margin(mg)   # on the device once: no copy from the host per chunk
 
     def run_chunk(draws):
-        model.shortcut_run(ps.st, draws, ps.max_step, ps.max_samples, margin=0. if mg_dev is None else mg_dev, wrap=ps.mask)
+        model.shortcut_run(ps.st, draws, ps.max_step, ps.max_samples, margin=0. if mg_dev is None else mg_dev, wrap=ps.mask,
+                           partial=ps.partial)
 
     ps.loop(run_chunk)
     return ps.result("fused")

@@ -796,6 +796,54 @@ int dcx_path_shortcut_run(const dcx_model* m, const dcx_shortcut_state* state, i
 int dcx_rrt_extract_paths(int device, const dcx_rrt_state* state, int64_t R, int32_t cap, int32_t dof,
                           float* path, int32_t* count, int32_t W, void* stream);
 
+/* Partial shortcuts: the second mode, between points INSIDE segments (what OMPL's path simplifier does along a path).  The vertex
+ * mode above can only join two waypoints: it removes vertices and never cuts a corner, so a three-waypoint path around an
+ * obstacle is its fixed point.  Here a slot draws two arc-length positions on the path, checks the straight motion between the
+ * two points and, where it is free, replaces everything between them by that chord.  State and opts are dcx_shortcut_state and
+ * dcx_shortcut_opts as above; W is also the capacity a path may grow into (a slot inside two neighbouring segments adds a row).
+ * Round t = 0 .. T - 1, path r, n = min(count[r], W) as it stands at the start of the round; fp32, each operation rounded alone
+ * unless said otherwise:
+ *   1. arc length: len_e (e = 0 .. n - 2) and c_e (e = 0 .. n - 1) are exactly dcx_path_resample's (below): the wrapped deltas,
+ *      the squares summed from +0 in coordinate order, a correctly rounded sqrt, and its fixed association - chunks of
+ *      DCX_RESAMPLE_CHUNK, the chunk totals added in order.  L = c_{n-1}.  Every slot of the path is idle if n < 3 or
+ *      !(L > 0 && L < inf) (a NaN fails it).
+ *   2. pick, with (u0, u1) = draws[t, r, p, :]: the slot is idle if either draw fails u >= 0 && u < 1.  Otherwise s0 = u0 * L,
+ *      s1 = u1 * L, sa = min(s0, s1), sb = max(s0, s1), and for s in (sa, sb) the point at s is located as dcx_path_resample
+ *      locates an output waypoint, word for word: e = the largest index in 0 .. n - 2 with c_e <= s; a = s - c_e; if
+ *      !(a < len_e) the point takes the bits of path[r, e + 1]; else f = a / len_e, correctly rounded, and coordinate j is
+ *      wrap2pi(q + f * d) on masked coordinates (product and sum rounded alone) and fma(f, d, q) elsewhere, q = path[r, e, j]
+ *      and d the segment's wrapped delta.  That gives (ea, xa) and (eb, xb), ea <= eb.  ea == eb idles the slot: a chord inside
+ *      one straight segment gains nothing.
+ *   3. check: the edge xa -> xb is checked by dcx_check_motions_ex (the closed max_step rule, opts->max_samples, margin,
+ *      wrap_mask): first_hit == -1 makes the slot free, anything else (-2 included) rejects it.
+ *   4. apply: slots are taken in ascending order, with a running count cnt that starts at n.  A free slot p is applied iff every
+ *      already applied slot q of this round and path satisfies eb_p < ea_q || eb_q < ea_p (no segment is shared) and
+ *      cnt + 2 - (eb_p - ea_p) <= W; cnt then takes that value.  A slot with eb = ea + 1 grows the path by one row, every other
+ *      slot keeps or shrinks it.
+ *   5. rewrite: with the applied slots in path order 1, 2, ..., the new path is waypoints 0 .. ea_1, then xa_1, xb_1, waypoints
+ *      eb_1 + 1 .. ea_2, then xa_2, xb_2, and so on up to waypoint n - 1.  Surviving waypoints keep their bits; waypoint k moves
+ *      to index k + sum over the applied (ea, eb) with eb < k of (2 - (eb - ea)).  path[r, 0] and path[r, last] never change
+ *      (ea >= 0 and eb + 1 <= n - 1).  count[r] = cnt, accepted[r] grows by the number of applied slots, rows at and beyond the
+ *      new count are unspecified.
+ * Only the new middle edge is checked.  The two end pieces path[ea] -> xa and xb -> path[eb + 1] lie on segments the path
+ *   already had, but their max_step samples are not the old segment's samples, and xa, xb are rounded points beside, not on, the
+ *   old segment: a path whose every segment passed the check may hold an end piece that does not.  The call promises no more
+ *   than OMPL's simplifier does; a caller who needs every segment checked checks the final paths once.
+ * Fixed batch: every round submits exactly R * P edges in (r, p) order, an idle slot path[r, 0] -> path[r, 0], as above.
+ * dcx_path_shortcut_partial_run enqueues T rounds on the caller's stream: per round one pick launch, the launches of
+ *   dcx_check_motions_ex, one commit launch.  No allocation, no synchronisation, no atomic decides any order, nothing read
+ *   back; repeated calls give the same bits, and T rounds in one call equal T calls of one round each.  draws and margin as
+ *   above.
+ * work: dcx_path_shortcut_partial_work_bytes(model, R, slots, W) bytes of device memory, the caller's (the vertex mode's
+ *   workspace, then a [R, W, dof] stage for the rewritten rows and, for W above what a block's LDS holds, c and len [R, W]);
+ *   initialised by the call itself.
+ * Argument errors: as dcx_path_shortcut_run's, with work_bytes below dcx_path_shortcut_partial_work_bytes.  R = 0 or T = 0
+ *   launches nothing.  dcx_path_shortcut_partial_work_bytes is 0 for arguments the call refuses (W outside
+ *   1 .. DCX_SHORTCUT_MAX_WAYPOINTS among them) and non-decreasing in R, slots and W.                                        */
+size_t dcx_path_shortcut_partial_work_bytes(const dcx_model* m, int64_t R, int32_t slots, int32_t W);
+int dcx_path_shortcut_partial_run(const dcx_model* m, const dcx_shortcut_state* state, int64_t R, const float* draws, int32_t T,
+                                  const dcx_shortcut_opts* opts, const float* margin, void* work, size_t work_bytes, void* stream);
+
 /* ---- roadmap queries (added under DCX_VERSION 109) -------------------------------------------------------- */
 /* Shortest paths over a roadmap for Q start/goal pairs at once: synchronous min-plus relaxation in fp32 without atomics
  * (dcx_sssp_run), then the routes as rows of one [Q, W, dof] tensor (dcx_sssp_extract_paths), on `device`, without a model.
