@@ -483,17 +483,25 @@ constexpr bool p2_applies(int D, int CC, int KF) {
 // at few waves per SIMD trade one packed add per row for a shorter dependent chain)
 // NS (several classes, MODE_GRAD_UP): no score accumulation - a caller that already holds this batch's class scores (the persistent
 // trajectory kernel's second sweep) saves the CC fma per pair; sc[] comes back untouched
-template <int D, int KF, int CC, int MODE, bool XF = false, int NACC = 0, bool NS = false, bool SP = false>
+// PRE (SP only): the caller hands x_in over already centred and in the sweep's own order, x_in[D - 1] = e (score_body restages
+// the block's features once, in LDS), and takes the gradient back in that order: gx[D - 1] = e sum(c), no column index kept
+template <int D, int KF, int CC, int MODE, bool XF = false, int NACC = 0, bool NS = false, bool SP = false, bool PRE = false>
 __device__ __forceinline__ void sweep_rows(const ScoreArgs& a, const float (&x_in)[D], const float (&up)[CC], int j0, int j1,
                                            float (&sc)[CC], float (&gx)[D]) {
     static_assert(!NS || (CC > 1 && MODE == MODE_GRAD_UP), "NS: the gradient sweep of a multi-class model");
     static_assert(!SP || (XF && spare_applies(D, CC, KF) && xf_applies(D, CC, KF)), "the spare form: expanded, one class, D = 4, 8, 12");
+    static_assert(!PRE || SP, "pre-staged features: the spare form only");
     // SP: the features in the sweep's own order - the agreed column swapped with the last one.  The column's index stays in
     // a VGPR across the loop (its SGPRs all belong to the row pipeline) for the way back
     float x[D];
     float e_sp = 0.0f, tot_sp = 0.0f;   // x - v in the agreed column; the sweep's sum(c): the run totals taken at each flush
     int col_sp = 0;
-    if constexpr (SP) {
+    if constexpr (PRE) {
+        e_sp = x_in[D - 1];
+#pragma unroll
+        for (int k = 0; k + 1 < D; ++k) x[k] = x_in[k];
+        x[D - 1] = 0.0f;
+    } else if constexpr (SP) {
         const int c = a.spare - 1;
         e_sp = x_in[D - 1];
 #pragma unroll
@@ -1224,7 +1232,14 @@ __device__ __forceinline__ void sweep_rows(const ScoreArgs& a, const float (&x_i
 
     if constexpr (XFA && GRAD) {
         flush_x();
-        if constexpr (SP) {
+        if constexpr (PRE) {
+            // the sweep's own order stays: the caller undoes the exchange (score_body: by index, in the cross-wave fold).  The
+            // product stays here, per wave: sum_w e tot_w is not e sum_w tot_w bit for bit
+            const float gl = e_sp * tot_sp;
+#pragma unroll
+            for (int k = 0; k + 1 < D; ++k) gx[k] += -((k & 1) ? ga[k / 2].y : ga[k / 2].x);
+            gx[D - 1] += gl;
+        } else if constexpr (SP) {
             // back to the caller's column order: the agreed column's gradient is e sum(c)
             const int c = __builtin_amdgcn_readfirstlane(col_sp);
             const float gl = e_sp * tot_sp;
@@ -1476,15 +1491,42 @@ __device__ __forceinline__ void score_body(const ScoreArgs& a) {
     __syncthreads();
 
     DCX_TS(2);
+    if constexpr (SP) {
+        // The block's waves all sweep the same 64 configurations: the features are rewritten ONCE, in place, into the sweep's
+        // operands - column k centred (the one rounding x - c per feature, as ever), the agreed column and the last one
+        // exchanged, so that slot D - 1 holds e = x - v.  One wave per column: k, the centre's entry and the exchange partner are
+        // scalars.  The wave that has the agreed column takes the last one with it and reads both before it writes either.
+        // Padded widths (d_fk < D): the padding is agreed, so the last agreed column IS the last one (model_fill_host, pack_rows_kernel)
+        // - no exchange, and the columns that do not exist in LDS are formed where they are read.
+        cfloat_ptr cen = (cfloat_ptr)(uintptr_t)a.centre;
+        const int dfk = a.d_fk;
+        const int c = (dfk == D) ? a.spare - 1 : D - 1;
+        for (int k = wave; k < dfk; k += nw) {
+            if (k == D - 1 && c != D - 1) continue;   // travels with column c
+            const float u = sX[k * 64 + lane] - cen[k];
+            if (k == c && c != D - 1) {
+                const float v = sX[(D - 1) * 64 + lane] - cen[D - 1];
+                sX[k * 64 + lane] = v;
+                sX[(D - 1) * 64 + lane] = u;
+            } else {
+                sX[k * 64 + lane] = u;
+            }
+        }
+        if (nw > 1) __syncthreads();
+    }
     float x[D];
     if (a.d_fk == D) {  // the usual case (no padding to a compiled width): no per-feature branch on every wave
 #pragma unroll
         for (int k = 0; k < D; ++k) x[k] = sX[k * 64 + lane];
+    } else if constexpr (SP) {
+        cfloat_ptr cen = (cfloat_ptr)(uintptr_t)a.centre;
+#pragma unroll
+        for (int k = 0; k < D; ++k) x[k] = (k < a.d_fk) ? sX[k * 64 + lane] : 0.0f - cen[k];
     } else {
 #pragma unroll
         for (int k = 0; k < D; ++k) x[k] = (k < a.d_fk) ? sX[k * 64 + lane] : 0.0f;
     }
-    if constexpr (XF) {
+    if constexpr (XF && !SP) {
         // The expanded distance |x|^2 + |s|^2 - 2 x.s carries an absolute error ~2^-23 (|x|^2 + |s|^2) and its near-pair
         // rule is relative to |x|: both are about the distance of the data from the ORIGIN, which means nothing to a kernel
         // that depends on x - s only (kernel.py:73-79).  Rows and features are therefore shifted by the support centroid
@@ -1534,7 +1576,7 @@ __device__ __forceinline__ void score_body(const ScoreArgs& a) {
         const float* slice = smem + a.qt_off + base + ((wave & 3) * kQtSlices + (lane >> 4)) * (per * RSQ + 4);
         sweep_rows_lds<D, KF, GRAD>(a, x, slice, per, sc[0], gx);
     } else {
-        sweep_rows<D, KF, CC, MODE, XF, 0, false, SP>(a, x, up, j0, j1, sc, gx);
+        sweep_rows<D, KF, CC, MODE, XF, 0, false, SP, SP>(a, x, up, j0, j1, sc, gx);   // (SP: pre-staged, above)
     }
     DCX_TS(3);
     {   // ---- epilogue: everything below reads the kernel arguments afresh (reload_args) and re-derives what it needs ----
@@ -1569,6 +1611,8 @@ __device__ __forceinline__ void score_body(const ScoreArgs& a) {
     const bool split = b.partial != nullptr;
     const bool par_tail = nw > 1 && b.red_slots != 1 && (!split || b.tile_done != nullptr);
     bool r1_done = false;
+    int sp_cs = D - 1;   // (SP: the column that still stands exchanged with the last one in gx[]; D - 1 = none)
+    auto sp_slot = [&](int k) __attribute__((always_inline)) -> int { return (k == sp_cs) ? D - 1 : (k == D - 1) ? sp_cs : k; };
     if constexpr (QT && GRAD) {
         // QT: phase R1 of J^T needs the frames only - the waves that carry it are the first to leave the sweep (the LDS pipe
         // serves the oldest wave first: they finish ~5 k cycles before the last), so it runs HERE, into its own scratch columns,
@@ -1604,6 +1648,11 @@ __device__ __forceinline__ void score_body(const ScoreArgs& a) {
         const bool publisher = opoll && blockIdx.y != 0;
         unsigned long long* wout = opoll ? b.pwords + ((tile * b.ys + blockIdx.y) * ACC) * 64 + lane : nullptr;
         float* out = (split && !opoll) ? b.partial + (tile * b.ys + blockIdx.y) * ACC * 64 + lane : nullptr;
+        // SP: the waves left their gradient in the sweep's column order (sweep_rows PRE).  The exchange is undone HERE, by index:
+        // accumulator CC + c takes the partial rows of slot CC + D - 1 and the other way round - the same values added in the
+        // same order, under the caller's name, so everything behind the fold (publish, owner-polls, re-read, J^T, the gradient
+        // store) sees the caller's order.  Row 0 is folded in place, so ONE wave folds both slots - the one whose turn column c
+        // is - and reads both before it writes either; the turn of column D - 1 is skipped.
         auto fold_mine = [&](auto nwc) __attribute__((always_inline)) {
             constexpr int NWC = decltype(nwc)::value;
             const int nwr = NWC > 0 ? NWC : nw;
@@ -1629,11 +1678,57 @@ __device__ __forceinline__ void score_body(const ScoreArgs& a) {
                 else sRed[e * 64 + lane] = v;  // row 0's slot of accumulator e: only this wave reads or writes it
             }
         };
+        // (the spare form's fold, the exchange undone; the plain fold above stays word for word what it was)
+        auto fold_mine_sp = [&](auto nwc) __attribute__((always_inline)) {
+            constexpr int NWC = decltype(nwc)::value;
+            const int nwr = NWC > 0 ? NWC : nw;
+            const int csw = (b.d_fk == D) ? b.spare - 1 : D - 1;
+            auto fold_one = [&](int e) __attribute__((always_inline)) -> float {
+                float v;
+                if constexpr (NWC > 0) {
+                    float r[NWC > 0 ? NWC : 1];
+#pragma unroll
+                    for (int w = 0; w < NWC; ++w) r[w] = sRed[((size_t)w * ACC + e) * 64 + lane];
+                    v = r[0];
+#pragma unroll
+                    for (int w = 1; w < NWC; ++w) v += r[w];
+                } else {
+                    v = sRed[e * 64 + lane];
+                    for (int w = 1; w < nw; ++w) v += sRed[((size_t)w * ACC + e) * 64 + lane];
+                }
+                return v;
+            };
+            auto put = [&](int e, float v) __attribute__((always_inline)) {
+                if (publisher) __hip_atomic_store(wout + e * 64, ((unsigned long long)b.ptag << 32) | (unsigned long long)__float_as_uint(v), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                else if (split && !opoll) __hip_atomic_store(out + e * 64, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                else sRed[e * 64 + lane] = v;
+            };
+            const int e_ex = (csw != D - 1) ? CC + csw : -1, e_skip = (csw != D - 1) ? CC + D - 1 : -1;   // (-1: the identity exchange)
+            for (int e = wave; e < ACC; e += nwr) {
+                if (e == e_skip) continue;   // folded in the turn of column csw
+                if (e == e_ex) {
+                    const float vc = fold_one(CC + D - 1);   // e sum(c): the caller's column csw
+                    const float vl = fold_one(e);            // the caller's last column
+                    put(e, vc);
+                    put(CC + D - 1, vl);
+                } else {
+                    put(e, fold_one(e));
+                }
+            }
+        };
+        if constexpr (SP && GRAD) {
+            if (nw == 16) fold_mine_sp(std::integral_constant<int, 16>{});
+            else if (nw == 8) fold_mine_sp(std::integral_constant<int, 8>{});
+            else if (nw == 4) fold_mine_sp(std::integral_constant<int, 4>{});
+            else if (nw == 2) fold_mine_sp(std::integral_constant<int, 2>{});
+            else fold_mine_sp(std::integral_constant<int, 0>{});
+        } else {
         if (nw == 16) fold_mine(std::integral_constant<int, 16>{});
         else if (nw == 8) fold_mine(std::integral_constant<int, 8>{});
         else if (nw == 4) fold_mine(std::integral_constant<int, 4>{});
         else if (nw == 2) fold_mine(std::integral_constant<int, 2>{});
         else fold_mine(std::integral_constant<int, 0>{});
+        }
         DCX_TS(17);
         if (opoll) {
             if (publisher) return;
@@ -1776,6 +1871,10 @@ __device__ __forceinline__ void score_body(const ScoreArgs& a) {
         }
     } else {
     // ---- the one-wave forms (one wave per block, wide shapes folding through one LDS row, the finish-kernel mode) ----
+    // SP: no parallel fold on these paths - the gradient stays in the sweep's column order through the hand-overs below and
+    // the exchange is undone by index (sp_slot) where the ONE row leaves the registers: the finish kernel's partial row, the
+    // published row of the one-wave hand-over (its re-read is in the caller's order: sp_cs = D - 1 from there on), or G
+    if constexpr (SP && GRAD) sp_cs = (b.d_fk == D) ? b.spare - 1 : D - 1;
     if (nw > 1 && b.red_slots == 1) {
         // one LDS row: waves 1 .. nw-1 hand their partial sums to wave 0 in turn (same summation order as below)
         for (int w = 1; w < nw; ++w) {
@@ -1827,7 +1926,10 @@ __device__ __forceinline__ void score_body(const ScoreArgs& a) {
             // score_finish_kernel adds the ys partial rows in a fixed order (deterministic) and applies J^T
 #pragma unroll
             for (int c = 0; c < CC; ++c) out[c * 64] = sc[c];
-            if constexpr (GRAD) {
+            if constexpr (SP && GRAD) {
+#pragma unroll
+                for (int k = 0; k < D; ++k) out[(CC + sp_slot(k)) * 64] = gx[k];
+            } else if constexpr (GRAD) {
 #pragma unroll
                 for (int k = 0; k < D; ++k) out[(CC + k) * 64] = gx[k];
             }
@@ -1837,7 +1939,12 @@ __device__ __forceinline__ void score_body(const ScoreArgs& a) {
         // the row write-through, drain, count; the last block to arrive re-reads every row in the order y = 0, 1, ...
 #pragma unroll
         for (int c = 0; c < CC; ++c) __hip_atomic_store(out + c * 64, sc[c], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        if constexpr (GRAD) {
+        if constexpr (SP && GRAD) {
+#pragma unroll
+            for (int k = 0; k < D; ++k)
+                __hip_atomic_store(out + (CC + sp_slot(k)) * 64, gx[k], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            sp_cs = D - 1;
+        } else if constexpr (GRAD) {
 #pragma unroll
             for (int k = 0; k < D; ++k)
                 __hip_atomic_store(out + (CC + k) * 64, gx[k], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -1907,7 +2014,12 @@ __device__ __forceinline__ void score_body(const ScoreArgs& a) {
             if (b.upstream != nullptr) scale = b.upstream[b0 + (lane < nb ? lane : nb - 1)];
             if (b.hinge) scale = (sc[0] - b.hinge_margin > 0.0f) ? b.hinge_weight : 0.0f;
         }
-        if (b.d_fk == D) {
+        if constexpr (SP) {
+            // (padded widths: no exchange - sp_slot is the identity there)
+#pragma unroll
+            for (int k = 0; k < D; ++k)
+                if (k < b.d_fk) sG[sp_slot(k) * 64 + lane] = gx[k] * scale;
+        } else if (b.d_fk == D) {
 #pragma unroll
             for (int k = 0; k < D; ++k) sG[k * 64 + lane] = gx[k] * scale;
         } else {
