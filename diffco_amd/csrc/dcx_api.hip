@@ -25,6 +25,7 @@
 #include "shortcut_partial_kernel.h"
 #include "resample_kernel.h"
 #include "sssp_kernel.h"
+#include "work_layout.h"
 
 using namespace dcx;
 
@@ -114,6 +115,9 @@ int fail_hip(hipError_t e, const char* what) {
         hipError_t e__ = (call);                             \
         if (e__ != hipSuccess) return fail_hip(e__, #call);  \
     } while (0)
+
+// a wrap mask names a joint the model does not have (dof >= 64: every bit is a joint)
+inline bool mask_beyond_dof(uint64_t mask, int dof) { return mask != 0 && dof < 64 && (mask >> dof) != 0; }
 
 traj_fused_fn traj_fused_for(int Dt) {
     switch (Dt) {
@@ -1588,19 +1592,19 @@ struct EscapeWork {
     size_t m_off, v_off, score_off, grad_off, qa_off[2], idx_off[2], count_off, total;
 };
 EscapeWork escape_work(int dof, int C, int64_t B) {
-    auto up = [](size_t x) { return (x + 255) / 256 * 256; };
+    const size_t qd = (size_t)B * dof;   // floats of B configurations
+    WorkCarve c;
     EscapeWork w;
-    const size_t qd = up((size_t)B * dof * sizeof(float)), ib = up((size_t)B * sizeof(int32_t));
-    w.m_off = 0;
-    w.v_off = qd;
-    w.score_off = 2 * qd;
-    w.grad_off = w.score_off + up((size_t)B * C * sizeof(float));
-    w.qa_off[0] = w.grad_off + qd;      // compaction (compact_every > 0): the running loops' configurations, dense, ping-pong
-    w.qa_off[1] = w.qa_off[0] + qd;
-    w.idx_off[0] = w.qa_off[1] + qd;    // ... and which configurations of the caller's they are
-    w.idx_off[1] = w.idx_off[0] + ib;
-    w.count_off = w.idx_off[1] + ib;
-    w.total = w.count_off + 256;
+    w.m_off = c.take_n<float>(qd);
+    w.v_off = c.take_n<float>(qd);
+    w.score_off = c.take_n<float>((size_t)B * C);
+    w.grad_off = c.take_n<float>(qd);
+    w.qa_off[0] = c.take_n<float>(qd);      // compaction (compact_every > 0): the running loops' configurations, dense, ping-pong
+    w.qa_off[1] = c.take_n<float>(qd);
+    w.idx_off[0] = c.take_n<int32_t>((size_t)B);   // ... and which configurations of the caller's they are
+    w.idx_off[1] = c.take_n<int32_t>((size_t)B);
+    w.count_off = c.take(256);              // the compaction's count, a slot of its own
+    w.total = c.at;
     return w;
 }
 }  // namespace
@@ -1696,13 +1700,13 @@ struct MotionWork {
     size_t offs, frac, counters, partial, total;
 };
 MotionWork motion_work(int64_t E) {
-    auto up = [](size_t x) { return (x + 255) / 256 * 256; };
+    WorkCarve c;
     MotionWork w;
-    w.offs = 0;
-    w.frac = up((size_t)(E + 1) * sizeof(int64_t));
-    w.counters = w.frac + up((size_t)E * sizeof(float));
-    w.partial = w.counters + (size_t)kMotionSplitTiles * kCounterStride * sizeof(unsigned int);
-    w.total = w.partial + (size_t)kMotionSplitRows * DCX_MAX_C * 64 * sizeof(float);
+    w.offs = c.take_n<int64_t>((size_t)(E + 1));
+    w.frac = c.take_n<float>((size_t)E);
+    w.counters = c.take_n<unsigned int>((size_t)kMotionSplitTiles * kCounterStride);
+    w.partial = c.take_n<float>((size_t)kMotionSplitRows * DCX_MAX_C * 64);
+    w.total = c.at;
     return w;
 }
 // where a call's workspace keeps the work list and the split launch's room (dcx_motion_cost lays them out on its own)
@@ -1762,7 +1766,7 @@ struct MotionCheck {
         return DCX_OK;
     }
     int mask(const dcx_model* m, uint64_t wrap_mask) const {   // (mask 0, the plain call: the model is not read here)
-        if (wrap_mask != 0 && m->fk.dof < 64 && (wrap_mask >> m->fk.dof) != 0)
+        if (mask_beyond_dof(wrap_mask, m->fk.dof))
             return fail(DCX_ERR_INVALID, std::string(what) + ": wrap_mask has a bit at or above dof");
         return DCX_OK;
     }
@@ -1918,16 +1922,16 @@ struct MotionWorstWork {
     size_t status, keys, xstar, up, score, g, total;
 };
 MotionWorstWork motion_worst_work(const dcx_model* m, int64_t E) {
-    auto up = [](size_t x) { return (x + 255) / 256 * 256; };
     MotionWorstWork w;
     w.mw = motion_work(E);
-    w.status = w.mw.total;
-    w.keys = w.status + up((size_t)E * sizeof(int32_t));
-    w.xstar = w.keys + up((size_t)E * sizeof(unsigned long long));
-    w.up = w.xstar + up((size_t)E * m->fk.dof * sizeof(float));
-    w.score = w.up + up((size_t)E * m->C * sizeof(float));
-    w.g = w.score + up((size_t)E * m->C * sizeof(float));
-    w.total = w.g + up((size_t)E * m->fk.dof * sizeof(float));
+    WorkCarve c{w.mw.total};
+    w.status = c.take_n<int32_t>((size_t)E);
+    w.keys = c.take_n<unsigned long long>((size_t)E);
+    w.xstar = c.take_n<float>((size_t)E * m->fk.dof);
+    w.up = c.take_n<float>((size_t)E * m->C);
+    w.score = c.take_n<float>((size_t)E * m->C);
+    w.g = c.take_n<float>((size_t)E * m->fk.dof);
+    w.total = c.at;
     return w;
 }
 }  // namespace
@@ -2017,14 +2021,14 @@ struct MotionBandWork {
     size_t status, codes, uoffs, total;
 };
 MotionBandWork motion_band_work(int64_t E, int32_t max_samples) {
-    auto up = [](size_t x) { return (x + 255) / 256 * 256; };
     const size_t n = (size_t)E * (size_t)(max_samples > 0 ? max_samples : 0);
     MotionBandWork w;
     w.mw = motion_work(E);
-    w.status = w.mw.total;
-    w.codes = w.status + up((size_t)E * sizeof(int32_t));
-    w.uoffs = w.codes + up((n + 63) / 64 * 64);
-    w.total = w.uoffs + up((size_t)(E + 1) * sizeof(int64_t));
+    WorkCarve c{w.mw.total};
+    w.status = c.take_n<int32_t>((size_t)E);
+    w.codes = c.take((n + 63) / 64 * 64);
+    w.uoffs = c.take_n<int64_t>((size_t)(E + 1));
+    w.total = c.at;
     return w;
 }
 }  // namespace
@@ -2107,21 +2111,21 @@ struct MotionCostWork {
     size_t offs, frac, status, counters, partial, h, dq, scores, tile_on, total;
 };
 MotionCostWork motion_cost_work(const dcx_model* m, int64_t E, int32_t max_samples) {
-    auto up = [](size_t x) { return (x + 255) / 256 * 256; };
     const size_t n = (size_t)E * (size_t)(max_samples > 0 ? max_samples : 0);
     const size_t tiles = (n + 63) / 64;
     const size_t acc = (size_t)m->Dt + (size_t)m->Cc;
+    WorkCarve c;
     MotionCostWork w;
-    w.offs = 0;
-    w.frac = up((size_t)(E + 1) * sizeof(int64_t));
-    w.status = w.frac + up((size_t)E * sizeof(float));
-    w.counters = w.status + up((size_t)E * sizeof(int32_t));
-    w.partial = w.counters + (size_t)kMotionSplitTiles * kCounterStride * sizeof(unsigned int);
-    w.h = w.partial + up((size_t)kMotionSplitRows * acc * 64 * sizeof(float));
-    w.dq = w.h + up(n * sizeof(float));
-    w.scores = w.dq + up(n * (size_t)m->fk.dof * sizeof(float));
-    w.tile_on = w.scores + (m->C > 1 ? up(n * (size_t)m->C * sizeof(float)) : 0);
-    w.total = w.tile_on + (m->C > 1 ? up(tiles * sizeof(int32_t)) : 0);
+    w.offs = c.take_n<int64_t>((size_t)(E + 1));
+    w.frac = c.take_n<float>((size_t)E);
+    w.status = c.take_n<int32_t>((size_t)E);
+    w.counters = c.take_n<unsigned int>((size_t)kMotionSplitTiles * kCounterStride);
+    w.partial = c.take_n<float>((size_t)kMotionSplitRows * acc * 64);
+    w.h = c.take_n<float>(n);
+    w.dq = c.take_n<float>(n * (size_t)m->fk.dof);
+    w.scores = c.take_n<float>(m->C > 1 ? n * (size_t)m->C : 0);   // (several classes only: the class scores and the tile marks)
+    w.tile_on = c.take_n<int32_t>(m->C > 1 ? tiles : 0);
+    w.total = c.at;
     return w;
 }
 }  // namespace
@@ -2225,22 +2229,22 @@ struct TrajDenseWork {
     size_t qb, q_last, margin, c_cost, c_ga, c_gb, c_n, e_cost, e_ga, e_gb, e_n, motion, total;
 };
 TrajDenseWork traj_dense_work(const dcx_model* m, int64_t R, int64_t W, int32_t max_samples) {
-    auto up = [](size_t x) { return (x + 255) / 256 * 256; };
     const size_t E = (size_t)R * (size_t)W, dof = (size_t)m->fk.dof;
+    WorkCarve c;
     TrajDenseWork w;
-    w.qb = 0;
-    w.q_last = w.qb + up(E * dof * sizeof(float));
-    w.margin = w.q_last + up((size_t)R * dof * sizeof(float));
-    w.c_cost = w.margin + up(DCX_MAX_C * sizeof(float));
-    w.c_ga = w.c_cost + up((size_t)R * sizeof(float));
-    w.c_gb = w.c_ga + up((size_t)R * dof * sizeof(float));
-    w.c_n = w.c_gb + up((size_t)R * dof * sizeof(float));
-    w.e_cost = w.c_n + up((size_t)R * sizeof(int32_t));
-    w.e_ga = w.e_cost + up(E * sizeof(float));
-    w.e_gb = w.e_ga + up(E * dof * sizeof(float));
-    w.e_n = w.e_gb + up(E * dof * sizeof(float));
-    w.motion = w.e_n + up(E * sizeof(int32_t));
-    w.total = w.motion + motion_cost_work(m, (int64_t)E, max_samples).total;
+    w.qb = c.take_n<float>(E * dof);
+    w.q_last = c.take_n<float>((size_t)R * dof);
+    w.margin = c.take_n<float>(DCX_MAX_C);
+    w.c_cost = c.take_n<float>((size_t)R);
+    w.c_ga = c.take_n<float>((size_t)R * dof);
+    w.c_gb = c.take_n<float>((size_t)R * dof);
+    w.c_n = c.take_n<int32_t>((size_t)R);
+    w.e_cost = c.take_n<float>(E);
+    w.e_ga = c.take_n<float>(E * dof);
+    w.e_gb = c.take_n<float>(E * dof);
+    w.e_n = c.take_n<int32_t>(E);
+    w.motion = c.take(motion_cost_work(m, (int64_t)E, max_samples).total);
+    w.total = c.at;
     return w;
 }
 // (check_traj without col_score / col_grad, which the dense step does not read, and with the dense structs)
@@ -2261,7 +2265,7 @@ int check_traj_dense(const dcx_traj_state* st, const dcx_traj_opts* opt, const d
     if (!(dopt->stop_tol >= 0.f)) return fail(DCX_ERR_INVALID, "dense trajectory: stop_tol must be >= 0");
     if (dopt->reserved[0] || dopt->reserved[1] || dopt->reserved[2] || dopt->reserved[3])
         return fail(DCX_ERR_INVALID, "dense trajectory: reserved fields must be 0");
-    if (dof < 64 && ((dopt->wrap_mask >> dof) != 0 || (dopt->rewrap_mask >> dof) != 0))
+    if (mask_beyond_dof(dopt->wrap_mask, dof) || mask_beyond_dof(dopt->rewrap_mask, dof))
         return fail(DCX_ERR_INVALID, "dense trajectory: wrap_mask / rewrap_mask has a bit at or above dof");
     const int n_edge = (io->edge_cost ? 1 : 0) + (io->grad_a ? 1 : 0) + (io->grad_b ? 1 : 0) + (io->n_samples ? 1 : 0);
     if (n_edge != 0 && n_edge != 4) return fail(DCX_ERR_INVALID, "dense trajectory: give all four per-edge arrays or none");
@@ -2494,7 +2498,7 @@ int dcx_knn(int device, const float* queries, int64_t Q, const float* points, in
             int32_t* idx, float* dist2, void* work, size_t work_bytes, void* stream) {
     if (!opt) return fail(DCX_ERR_INVALID, "knn: options are NULL");
     if (int rc = knn_check_sizes(Q, N, dof, opt->k)) return rc;
-    if (dof < 64 && (opt->wrap_mask >> dof)) return fail(DCX_ERR_INVALID, "knn: wrap_mask has a bit at or above dof");
+    if (mask_beyond_dof(opt->wrap_mask, dof)) return fail(DCX_ERR_INVALID, "knn: wrap_mask has a bit at or above dof");
     if (!(opt->max_dist2 >= 0.0f)) return fail(DCX_ERR_INVALID, "knn: max_dist2 is NaN or negative");
     if (opt->self_offset < -1) return fail(DCX_ERR_INVALID, "knn: self_offset < -1");
     if (opt->reserved0 || opt->reserved1 || opt->reserved[0] || opt->reserved[1]) return fail(DCX_ERR_INVALID, "knn: reserved fields must be 0");
@@ -2524,17 +2528,71 @@ int dcx_knn(int device, const float* queries, int64_t Q, const float* points, in
     return DCX_OK;
 }
 
-// ---- batched RRT-Connect (rrt_kernel.h): the size query and the call share the checks and rrt_plan --------------------------
-static int rrt_check_sizes(const dcx_model* m, int64_t R, int32_t slots) {
-    if (!m) return fail(DCX_ERR_INVALID, "rrt: model is NULL");
-    if (R < 0) return fail(DCX_ERR_INVALID, "rrt: R < 0");
-    if (slots < 1 || slots > DCX_RRT_MAX_SLOTS) return fail(DCX_ERR_INVALID, "rrt: slots must be in [1, DCX_RRT_MAX_SLOTS]");
-    if (R > INT32_MAX / slots) return fail(DCX_ERR_UNSUPPORTED, "rrt: more than 2^31 - 1 edges per phase");
-    return DCX_OK;
-}
+// ---- the lockstep planners (rrt_kernel.h, shortcut_kernel.h, shortcut_partial_kernel.h): R problems, T rounds of
+// pick -> dcx_check_motions_ex on the R * slots edges -> commit on the caller's stream ------------------------------------------
+namespace {
+// The argument checks the planners repeat, `what` ("rrt", "shortcut") substituted into the messages, as MotionCheck's: a call's own
+// checks stand between them and the first failing check names the error, so the shared ones come as the runs they form.
+struct PlannerCheck {
+    const char* what;
+    int32_t max_slots;
+    const char* max_slots_name;
+    const char* per;   // what one edge batch belongs to: RRT's "phase", the shortcuts' "round"
+    int sizes(const dcx_model* m, int64_t R, int32_t slots) const {   // (the size queries' checks too)
+        if (!m) return fail(DCX_ERR_INVALID, std::string(what) + ": model is NULL");
+        if (R < 0) return fail(DCX_ERR_INVALID, std::string(what) + ": R < 0");
+        if (slots < 1 || slots > max_slots) return fail(DCX_ERR_INVALID, std::string(what) + ": slots must be in [1, " + max_slots_name + "]");
+        if (R > INT32_MAX / slots) return fail(DCX_ERR_UNSUPPORTED, std::string(what) + ": more than 2^31 - 1 edges per " + per);
+        return DCX_OK;
+    }
+    int sampling(float max_step, int32_t max_samples) const {
+        if (!(max_step > 0.f)) return fail(DCX_ERR_INVALID, std::string(what) + ": max_step must be > 0");
+        if (max_samples < 1) return fail(DCX_ERR_INVALID, std::string(what) + ": max_samples must be >= 1");
+        return DCX_OK;
+    }
+    // `state_ok`: the state and every pointer of it are there;  `feed`: the per-round input (`feed_name`), read when a round runs
+    int buffers(int64_t R, int32_t T, bool state_ok, const void* feed, const char* feed_name, const void* work) const {
+        if (R > 0 && !state_ok) return fail(DCX_ERR_INVALID, std::string(what) + ": state or one of its pointers is NULL");
+        if (R > 0 && T > 0 && !feed) return fail(DCX_ERR_INVALID, std::string(what) + ": " + feed_name + " is NULL");
+        if (R > 0 && !work) return fail(DCX_ERR_INVALID, std::string(what) + ": work is NULL");
+        return DCX_OK;
+    }
+    int workspace(int64_t R, size_t work_bytes, size_t need, const char* work_bytes_fn) const {
+        if (R > 0 && work_bytes < need) return fail(DCX_ERR_INVALID, std::string(what) + ": the workspace is smaller than " + work_bytes_fn);
+        return DCX_OK;
+    }
+    // what dcx_check_motions_ex could still refuse depends on (model, E, max_samples) alone: refused before the first launch
+    int launchable(const dcx_model* m, int64_t E, int32_t max_samples) const {
+        if (m->fk.dof < 1 || m->fk.dof > DCX_MAX_DOF) return fail(DCX_ERR_UNSUPPORTED, std::string(what) + ": dof outside 1 .. DCX_MAX_DOF");
+        if ((E * (int64_t)max_samples + 63) / 64 > 0x7fffffffLL)
+            return fail(DCX_ERR_UNSUPPORTED, std::string(what) + ": R * slots * max_samples too large for one launch");
+        if (!motion_for(m->Dt)) return fail(DCX_ERR_UNSUPPORTED, std::string(what) + ": no motion kernel for this feature width");
+        return DCX_OK;
+    }
+};
+constexpr PlannerCheck kRrtCheck{"rrt", DCX_RRT_MAX_SLOTS, "DCX_RRT_MAX_SLOTS", "phase"};
+constexpr PlannerCheck kShortcutCheck{"shortcut", DCX_SHORTCUT_MAX_SLOTS, "DCX_SHORTCUT_MAX_SLOTS", "round"};
 
+// A round's edge batch: its E = R * slots edges, the motion workspace at the head of the planner's, the sampling rule - and,
+// between a round's pick and its commit, the motion check itself, its answers into the plan's first_hit slot
+struct PlannerEdges {
+    const dcx_model* m;
+    int64_t E;
+    MotionWork mw;
+    dcx_motion_opts mo;
+    const float* margin;
+    void* work;
+    uint64_t wrap_mask;
+    void* stream;
+    int check(const float* qa, const float* qb, const int32_t* first_hit) const {
+        return dcx_check_motions_ex(m, qa, qb, E, &mo, margin, const_cast<int32_t*>(first_hit), nullptr, work, mw.total, wrap_mask, stream);
+    }
+};
+}  // namespace
+
+// ---- batched RRT-Connect (rrt_kernel.h): the size query and the call share the checks and rrt_plan --------------------------
 size_t dcx_rrt_work_bytes(const dcx_model* m, int64_t R, int32_t slots) {
-    if (rrt_check_sizes(m, R, slots)) return 0;
+    if (kRrtCheck.sizes(m, R, slots)) return 0;
     return rrt_plan(R, slots, m->fk.dof, motion_work(R * slots).total).total;
 }
 
@@ -2543,29 +2601,21 @@ int dcx_rrt_connect_run(const dcx_model* m, const dcx_rrt_state* state, int64_t 
     // every argument is checked before anything touches the model's device
     if (!opt) return fail(DCX_ERR_INVALID, "rrt: options are NULL");
     if (T < 0) return fail(DCX_ERR_INVALID, "rrt: T < 0");
-    if (int rc = rrt_check_sizes(m, R, opt->slots)) return rc;
+    if (int rc = kRrtCheck.sizes(m, R, opt->slots)) return rc;
     if (round0 < 0 || round0 > INT32_MAX - (int64_t)T) return fail(DCX_ERR_INVALID, "rrt: round0 < 0 or round0 + T above 2^31 - 1");
     if (!(opt->range > 0.f)) return fail(DCX_ERR_INVALID, "rrt: range must be > 0");
-    if (!(opt->max_step > 0.f)) return fail(DCX_ERR_INVALID, "rrt: max_step must be > 0");
-    if (opt->max_samples < 1) return fail(DCX_ERR_INVALID, "rrt: max_samples must be >= 1");
+    if (int rc = kRrtCheck.sampling(opt->max_step, opt->max_samples)) return rc;
     if (opt->cap < 1 || opt->cap > DCX_RRT_MAX_CAP) return fail(DCX_ERR_INVALID, "rrt: cap must be in [1, DCX_RRT_MAX_CAP]");
     if (opt->reserved0 || opt->reserved[0] || opt->reserved[1]) return fail(DCX_ERR_INVALID, "rrt: reserved fields must be 0");
-    if (opt->wrap_mask != 0 && m->fk.dof < 64 && (opt->wrap_mask >> m->fk.dof) != 0)
-        return fail(DCX_ERR_INVALID, "rrt: wrap_mask has a bit at or above dof");
-    if (R > 0 && (!state || !state->nodes || !state->parent || !state->count || !state->status || !state->link || !state->solved_round))
-        return fail(DCX_ERR_INVALID, "rrt: state or one of its pointers is NULL");
-    if (R > 0 && T > 0 && !samples) return fail(DCX_ERR_INVALID, "rrt: samples is NULL");
-    if (R > 0 && !work) return fail(DCX_ERR_INVALID, "rrt: work is NULL");
-    const int64_t E = R * opt->slots;
-    const MotionWork mw = motion_work(E);
-    const RrtPlan plan = rrt_plan(R, opt->slots, m->fk.dof, mw.total);
-    if (R > 0 && work_bytes < plan.total) return fail(DCX_ERR_INVALID, "rrt: the workspace is smaller than dcx_rrt_work_bytes");
+    if (int rc = MotionCheck{kRrtCheck.what}.mask(m, opt->wrap_mask)) return rc;
+    const bool state_ok = state && state->nodes && state->parent && state->count && state->status && state->link && state->solved_round;
+    if (int rc = kRrtCheck.buffers(R, T, state_ok, samples, "samples", work)) return rc;
+    const PlannerEdges ed{m, R * opt->slots, motion_work(R * opt->slots), {0, opt->max_step, opt->max_samples, 0}, margin, work,
+                          opt->wrap_mask, stream};
+    const RrtPlan plan = rrt_plan(R, opt->slots, m->fk.dof, ed.mw.total);
+    if (int rc = kRrtCheck.workspace(R, work_bytes, plan.total, "dcx_rrt_work_bytes")) return rc;
     if (R == 0 || T == 0) return DCX_OK;
-    // what dcx_check_motions_ex could still refuse depends on (model, E, max_samples) alone: refused here, before the first launch
-    if (m->fk.dof < 1 || m->fk.dof > DCX_MAX_DOF) return fail(DCX_ERR_UNSUPPORTED, "rrt: dof outside 1 .. DCX_MAX_DOF");
-    if ((E * (int64_t)opt->max_samples + 63) / 64 > 0x7fffffffLL)
-        return fail(DCX_ERR_UNSUPPORTED, "rrt: R * slots * max_samples too large for one launch");
-    if (!motion_for(m->Dt)) return fail(DCX_ERR_UNSUPPORTED, "rrt: no motion kernel for this feature width");
+    if (int rc = kRrtCheck.launchable(m, ed.E, opt->max_samples)) return rc;
     if (int rc = set_device(m->device)) return rc;
     hipStream_t st = (hipStream_t)stream;
     char* base = (char*)work;
@@ -2582,26 +2632,21 @@ int dcx_rrt_connect_run(const dcx_model* m, const dcx_rrt_state* state, int64_t 
     a.added = (int32_t*)(base + plan.added);
     a.first_hit = (int32_t*)(base + plan.first_hit);
     a.full = (int32_t*)(base + plan.full);
-    a.frac = (const float*)(base + mw.frac);
+    a.frac = (const float*)(base + ed.mw.frac);
     a.R = (int32_t)R;
     a.P = opt->slots;
     a.cap = opt->cap;
     a.dof = m->fk.dof;
     a.range = opt->range;
     a.wrap_mask = opt->wrap_mask;
-    dcx_motion_opts mo{};
-    mo.max_step = opt->max_step;
-    mo.max_samples = opt->max_samples;
     for (int32_t t = 0; t < T; ++t) {
         a.round = (int32_t)(round0 + t);
         a.tree = a.round & 1;
-        a.samples = samples + (int64_t)t * E * a.dof;
+        a.samples = samples + (int64_t)t * ed.E * a.dof;
         for (a.phase = 1; a.phase <= 2; ++a.phase) {
             hipError_t e = launch_rrt_nearest(a, st);
             if (e != hipSuccess) return fail_hip(e, "rrt nearest launch");
-            if (int rc = dcx_check_motions_ex(m, a.qa, a.qb, E, &mo, margin, (int32_t*)(base + plan.first_hit), nullptr, work, mw.total,
-                                              opt->wrap_mask, stream))
-                return rc;
+            if (int rc = ed.check(a.qa, a.qb, a.first_hit)) return rc;
             e = launch_rrt_commit(a, st);
             if (e != hipSuccess) return fail_hip(e, "rrt commit launch");
         }
@@ -2609,118 +2654,45 @@ int dcx_rrt_connect_run(const dcx_model* m, const dcx_rrt_state* state, int64_t 
     return DCX_OK;
 }
 
-// ---- batched path shortcutting (shortcut_kernel.h): the size query and the call share the checks and shortcut_plan ----------
-static int shortcut_check_sizes(const dcx_model* m, int64_t R, int32_t slots) {
-    if (!m) return fail(DCX_ERR_INVALID, "shortcut: model is NULL");
-    if (R < 0) return fail(DCX_ERR_INVALID, "shortcut: R < 0");
-    if (slots < 1 || slots > DCX_SHORTCUT_MAX_SLOTS)
-        return fail(DCX_ERR_INVALID, "shortcut: slots must be in [1, DCX_SHORTCUT_MAX_SLOTS]");
-    if (R > INT32_MAX / slots) return fail(DCX_ERR_UNSUPPORTED, "shortcut: more than 2^31 - 1 edges per round");
-    return DCX_OK;
-}
-
-size_t dcx_path_shortcut_work_bytes(const dcx_model* m, int64_t R, int32_t slots) {
-    if (shortcut_check_sizes(m, R, slots)) return 0;
-    return shortcut_plan(R, slots, m->fk.dof, motion_work(R * slots).total).total;
-}
-
-int dcx_path_shortcut_run(const dcx_model* m, const dcx_shortcut_state* state, int64_t R, const float* draws, int32_t T,
-                          const dcx_shortcut_opts* opt, const float* margin, void* work, size_t work_bytes, void* stream) {
-    // every argument is checked before anything touches the model's device
-    if (!opt) return fail(DCX_ERR_INVALID, "shortcut: options are NULL");
-    if (T < 0) return fail(DCX_ERR_INVALID, "shortcut: T < 0");
-    if (int rc = shortcut_check_sizes(m, R, opt->slots)) return rc;
-    if (!(opt->max_step > 0.f)) return fail(DCX_ERR_INVALID, "shortcut: max_step must be > 0");
-    if (opt->max_samples < 1) return fail(DCX_ERR_INVALID, "shortcut: max_samples must be >= 1");
-    if (opt->W < 1 || opt->W > DCX_SHORTCUT_MAX_WAYPOINTS)
-        return fail(DCX_ERR_INVALID, "shortcut: W must be in [1, DCX_SHORTCUT_MAX_WAYPOINTS]");
-    if (opt->reserved[0] || opt->reserved[1]) return fail(DCX_ERR_INVALID, "shortcut: reserved fields must be 0");
-    if (opt->wrap_mask != 0 && m->fk.dof < 64 && (opt->wrap_mask >> m->fk.dof) != 0)
-        return fail(DCX_ERR_INVALID, "shortcut: wrap_mask has a bit at or above dof");
-    if (R > 0 && (!state || !state->path || !state->count || !state->accepted))
-        return fail(DCX_ERR_INVALID, "shortcut: state or one of its pointers is NULL");
-    if (R > 0 && T > 0 && !draws) return fail(DCX_ERR_INVALID, "shortcut: draws is NULL");
-    if (R > 0 && !work) return fail(DCX_ERR_INVALID, "shortcut: work is NULL");
-    const int64_t E = R * opt->slots;
-    const MotionWork mw = motion_work(E);
-    const ShortcutPlan plan = shortcut_plan(R, opt->slots, m->fk.dof, mw.total);
-    if (R > 0 && work_bytes < plan.total)
-        return fail(DCX_ERR_INVALID, "shortcut: the workspace is smaller than dcx_path_shortcut_work_bytes");
-    if (R == 0 || T == 0) return DCX_OK;
-    // what dcx_check_motions_ex could still refuse depends on (model, E, max_samples) alone: refused here, before the first launch
-    if (m->fk.dof < 1 || m->fk.dof > DCX_MAX_DOF) return fail(DCX_ERR_UNSUPPORTED, "shortcut: dof outside 1 .. DCX_MAX_DOF");
-    if ((E * (int64_t)opt->max_samples + 63) / 64 > 0x7fffffffLL)
-        return fail(DCX_ERR_UNSUPPORTED, "shortcut: R * slots * max_samples too large for one launch");
-    if (!motion_for(m->Dt)) return fail(DCX_ERR_UNSUPPORTED, "shortcut: no motion kernel for this feature width");
-    if (int rc = set_device(m->device)) return rc;
-    hipStream_t st = (hipStream_t)stream;
-    char* base = (char*)work;
-    ShortcutArgs a{};
-    a.path = state->path;
-    a.count = state->count;
-    a.accepted = state->accepted;
-    a.qa = (float*)(base + plan.qa);
-    a.qb = (float*)(base + plan.qb);
-    a.first_hit = (int32_t*)(base + plan.first_hit);
-    a.picks = (int32_t*)(base + plan.picks);
-    a.R = (int32_t)R;
-    a.P = opt->slots;
-    a.W = opt->W;
-    a.dof = m->fk.dof;
-    dcx_motion_opts mo{};
-    mo.max_step = opt->max_step;
-    mo.max_samples = opt->max_samples;
-    for (int32_t t = 0; t < T; ++t) {
-        a.draws = draws + (int64_t)t * E * 2;
-        hipError_t e = launch_shortcut_pick(a, st);
-        if (e != hipSuccess) return fail_hip(e, "shortcut pick launch");
-        if (int rc = dcx_check_motions_ex(m, a.qa, a.qb, E, &mo, margin, (int32_t*)(base + plan.first_hit), nullptr, work, mw.total,
-                                          opt->wrap_mask, stream))
-            return rc;
-        e = launch_shortcut_commit(a, st);
-        if (e != hipSuccess) return fail_hip(e, "shortcut commit launch");
-    }
-    return DCX_OK;
-}
-
-// ---- partial shortcuts (shortcut_partial_kernel.h): the size query and the call share the checks and shortcut_partial_plan ----
-static int shortcut_partial_check_sizes(const dcx_model* m, int64_t R, int32_t slots, int32_t W) {
-    if (int rc = shortcut_check_sizes(m, R, slots)) return rc;
+// ---- batched path shortcutting (shortcut_kernel.h, shortcut_partial_kernel.h): the size queries and the calls share the checks
+// and the plans; the two modes share one body: the vertex mode's workspace is the slot part of the partial mode's --------------
+static int shortcut_check_W(int32_t W) {
     if (W < 1 || W > DCX_SHORTCUT_MAX_WAYPOINTS) return fail(DCX_ERR_INVALID, "shortcut: W must be in [1, DCX_SHORTCUT_MAX_WAYPOINTS]");
     return DCX_OK;
 }
 
+size_t dcx_path_shortcut_work_bytes(const dcx_model* m, int64_t R, int32_t slots) {
+    if (kShortcutCheck.sizes(m, R, slots)) return 0;
+    return shortcut_plan(R, slots, m->fk.dof, motion_work(R * slots).total).total;
+}
+
 size_t dcx_path_shortcut_partial_work_bytes(const dcx_model* m, int64_t R, int32_t slots, int32_t W) {
-    if (shortcut_partial_check_sizes(m, R, slots, W)) return 0;
+    if (kShortcutCheck.sizes(m, R, slots) || shortcut_check_W(W)) return 0;
     return shortcut_partial_plan(R, slots, W, m->fk.dof, motion_work(R * slots).total).total;
 }
 
-int dcx_path_shortcut_partial_run(const dcx_model* m, const dcx_shortcut_state* state, int64_t R, const float* draws, int32_t T,
-                                  const dcx_shortcut_opts* opt, const float* margin, void* work, size_t work_bytes, void* stream) {
-    // every argument is checked before anything touches the model's device: dcx_path_shortcut_run's checks
+static int shortcut_run(bool partial, const dcx_model* m, const dcx_shortcut_state* state, int64_t R, const float* draws, int32_t T,
+                        const dcx_shortcut_opts* opt, const float* margin, void* work, size_t work_bytes, void* stream) {
+    // every argument is checked before anything touches the model's device; the partial mode's size query takes W, so it checks
+    // W with the sizes, the vertex mode behind max_samples
     if (!opt) return fail(DCX_ERR_INVALID, "shortcut: options are NULL");
     if (T < 0) return fail(DCX_ERR_INVALID, "shortcut: T < 0");
-    if (int rc = shortcut_partial_check_sizes(m, R, opt->slots, opt->W)) return rc;
-    if (!(opt->max_step > 0.f)) return fail(DCX_ERR_INVALID, "shortcut: max_step must be > 0");
-    if (opt->max_samples < 1) return fail(DCX_ERR_INVALID, "shortcut: max_samples must be >= 1");
+    if (int rc = kShortcutCheck.sizes(m, R, opt->slots)) return rc;
+    if (int rc = partial ? shortcut_check_W(opt->W) : DCX_OK) return rc;
+    if (int rc = kShortcutCheck.sampling(opt->max_step, opt->max_samples)) return rc;
+    if (int rc = partial ? DCX_OK : shortcut_check_W(opt->W)) return rc;
     if (opt->reserved[0] || opt->reserved[1]) return fail(DCX_ERR_INVALID, "shortcut: reserved fields must be 0");
-    if (opt->wrap_mask != 0 && m->fk.dof < 64 && (opt->wrap_mask >> m->fk.dof) != 0)
-        return fail(DCX_ERR_INVALID, "shortcut: wrap_mask has a bit at or above dof");
-    if (R > 0 && (!state || !state->path || !state->count || !state->accepted))
-        return fail(DCX_ERR_INVALID, "shortcut: state or one of its pointers is NULL");
-    if (R > 0 && T > 0 && !draws) return fail(DCX_ERR_INVALID, "shortcut: draws is NULL");
-    if (R > 0 && !work) return fail(DCX_ERR_INVALID, "shortcut: work is NULL");
-    const int64_t E = R * opt->slots;
-    const MotionWork mw = motion_work(E);
-    const ShortcutPartialPlan plan = shortcut_partial_plan(R, opt->slots, opt->W, m->fk.dof, mw.total);
-    if (R > 0 && work_bytes < plan.total)
-        return fail(DCX_ERR_INVALID, "shortcut: the workspace is smaller than dcx_path_shortcut_partial_work_bytes");
+    if (int rc = MotionCheck{kShortcutCheck.what}.mask(m, opt->wrap_mask)) return rc;
+    if (int rc = kShortcutCheck.buffers(R, T, state && state->path && state->count && state->accepted, draws, "draws", work)) return rc;
+    const PlannerEdges ed{m, R * opt->slots, motion_work(R * opt->slots), {0, opt->max_step, opt->max_samples, 0}, margin, work,
+                          opt->wrap_mask, stream};
+    ShortcutPartialPlan plan{};   // (vertex mode: the slot part alone)
+    if (partial) plan = shortcut_partial_plan(R, opt->slots, opt->W, m->fk.dof, ed.mw.total);
+    else plan.total = (plan.slot = shortcut_plan(R, opt->slots, m->fk.dof, ed.mw.total)).total;
+    if (int rc = kShortcutCheck.workspace(R, work_bytes, plan.total,
+                                          partial ? "dcx_path_shortcut_partial_work_bytes" : "dcx_path_shortcut_work_bytes")) return rc;
     if (R == 0 || T == 0) return DCX_OK;
-    // what dcx_check_motions_ex could still refuse depends on (model, E, max_samples) alone: refused here, before the first launch
-    if (m->fk.dof < 1 || m->fk.dof > DCX_MAX_DOF) return fail(DCX_ERR_UNSUPPORTED, "shortcut: dof outside 1 .. DCX_MAX_DOF");
-    if ((E * (int64_t)opt->max_samples + 63) / 64 > 0x7fffffffLL)
-        return fail(DCX_ERR_UNSUPPORTED, "shortcut: R * slots * max_samples too large for one launch");
-    if (!motion_for(m->Dt)) return fail(DCX_ERR_UNSUPPORTED, "shortcut: no motion kernel for this feature width");
+    if (int rc = kShortcutCheck.launchable(m, ed.E, opt->max_samples)) return rc;
     if (int rc = set_device(m->device)) return rc;
     hipStream_t st = (hipStream_t)stream;
     char* base = (char*)work;
@@ -2732,7 +2704,7 @@ int dcx_path_shortcut_partial_run(const dcx_model* m, const dcx_shortcut_state* 
     a.qb = (float*)(base + plan.slot.qb);
     a.first_hit = (int32_t*)(base + plan.slot.first_hit);
     a.picks = (int32_t*)(base + plan.slot.picks);
-    a.stage = (float*)(base + plan.stage);
+    a.stage = (float*)(base + plan.stage);   // (stage, work_c, work_len, wrap_mask: the partial mode's alone)
     a.work_c = (float*)(base + plan.c);
     a.work_len = (float*)(base + plan.len);
     a.wrap_mask = opt->wrap_mask;
@@ -2740,20 +2712,26 @@ int dcx_path_shortcut_partial_run(const dcx_model* m, const dcx_shortcut_state* 
     a.P = opt->slots;
     a.W = opt->W;
     a.dof = m->fk.dof;
-    dcx_motion_opts mo{};
-    mo.max_step = opt->max_step;
-    mo.max_samples = opt->max_samples;
+    ShortcutArgs v{a.path, a.count, a.accepted, nullptr, a.qa, a.qb, a.first_hit, a.picks, a.R, a.P, a.W, a.dof};   // the vertex mode's
     for (int32_t t = 0; t < T; ++t) {
-        a.draws = draws + (int64_t)t * E * 2;
-        hipError_t e = launch_shortcut_partial_pick(a, st);
-        if (e != hipSuccess) return fail_hip(e, "partial shortcut pick launch");
-        if (int rc = dcx_check_motions_ex(m, a.qa, a.qb, E, &mo, margin, (int32_t*)(base + plan.slot.first_hit), nullptr, work, mw.total,
-                                          opt->wrap_mask, stream))
-            return rc;
-        e = launch_shortcut_partial_commit(a, st);
-        if (e != hipSuccess) return fail_hip(e, "partial shortcut commit launch");
+        a.draws = v.draws = draws + (int64_t)t * ed.E * 2;
+        hipError_t e = partial ? launch_shortcut_partial_pick(a, st) : launch_shortcut_pick(v, st);
+        if (e != hipSuccess) return fail_hip(e, partial ? "partial shortcut pick launch" : "shortcut pick launch");
+        if (int rc = ed.check(v.qa, v.qb, v.first_hit)) return rc;
+        e = partial ? launch_shortcut_partial_commit(a, st) : launch_shortcut_commit(v, st);
+        if (e != hipSuccess) return fail_hip(e, partial ? "partial shortcut commit launch" : "shortcut commit launch");
     }
     return DCX_OK;
+}
+
+int dcx_path_shortcut_run(const dcx_model* m, const dcx_shortcut_state* state, int64_t R, const float* draws, int32_t T,
+                          const dcx_shortcut_opts* opt, const float* margin, void* work, size_t work_bytes, void* stream) {
+    return shortcut_run(false, m, state, R, draws, T, opt, margin, work, work_bytes, stream);
+}
+
+int dcx_path_shortcut_partial_run(const dcx_model* m, const dcx_shortcut_state* state, int64_t R, const float* draws, int32_t T,
+                                  const dcx_shortcut_opts* opt, const float* margin, void* work, size_t work_bytes, void* stream) {
+    return shortcut_run(true, m, state, R, draws, T, opt, margin, work, work_bytes, stream);
 }
 
 int dcx_rrt_extract_paths(int device, const dcx_rrt_state* state, int64_t R, int32_t cap, int32_t dof, float* path, int32_t* count,
@@ -2803,8 +2781,7 @@ int dcx_path_resample(int device, const float* path, const int32_t* count, int64
     if (int rc = resample_check_sizes(R, W)) return rc;
     if (T < 2 || T > DCX_SHORTCUT_MAX_WAYPOINTS) return fail(DCX_ERR_INVALID, "resample: T must be in [2, DCX_SHORTCUT_MAX_WAYPOINTS]");
     if (dof < 1) return fail(DCX_ERR_INVALID, "resample: dof < 1");
-    if (wrap_mask != 0 && dof < 64 && (wrap_mask >> dof) != 0)
-        return fail(DCX_ERR_INVALID, "resample: wrap_mask has a bit at or above dof");
+    if (mask_beyond_dof(wrap_mask, dof)) return fail(DCX_ERR_INVALID, "resample: wrap_mask has a bit at or above dof");
     if (R > 0 && (!path || !count)) return fail(DCX_ERR_INVALID, "resample: path or count is NULL");
     if (R > 0 && (!out || !out_count)) return fail(DCX_ERR_INVALID, "resample: out or out_count is NULL");
     if (R > 0 && !work) return fail(DCX_ERR_INVALID, "resample: work is NULL");

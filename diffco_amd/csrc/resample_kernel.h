@@ -10,6 +10,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "../../include/dcx.h"
+#include "work_layout.h"
 
 namespace dcx {
 
@@ -30,12 +31,12 @@ struct ResamplePlan {
 };
 
 inline ResamplePlan resample_plan(int64_t R, int32_t W) {
-    auto up = [](size_t x) { return (x + 255) / 256 * 256; };
     const size_t rows = W > kResampleLdsWaypoints ? (size_t)R * (size_t)W : 0;
+    WorkCarve c;
     ResamplePlan w;
-    w.c = 0;
-    w.len = w.c + up(rows * sizeof(float));
-    w.total = w.len + up(rows * sizeof(float));
+    w.c = c.take_n<float>(rows);
+    w.len = c.take_n<float>(rows);
+    w.total = c.at;
     if (R > 0 && w.total == 0) w.total = 256;   // (never 0 for a call that launches: `work` is a real pointer)
     return w;
 }

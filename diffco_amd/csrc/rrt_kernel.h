@@ -1,6 +1,6 @@
 // rrt_kernel.h — what dcx_rrt_connect_run's host side (dcx_api.hip) and its kernels (rrt_kernels.hip) share: the launches'
 // arguments and THE plan of the workspace.  dcx_rrt_work_bytes and dcx_rrt_connect_run both call rrt_plan, so the workspace a
-// caller was told to bring is the one the rounds use.
+// caller was told to bring is the one the rounds use.  (The planners' shared checks: dcx_api.hip PlannerCheck, PlannerEdges.)
 //
 // One round of R problems is six steps on the caller's stream (include/dcx.h, "batched RRT-Connect"):
 //   nearest + steer (phase 1) -> dcx_check_motions_ex on the R * P edges -> commit (phase 1)
@@ -11,6 +11,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "../../include/dcx.h"
+#include "work_layout.h"
 
 namespace dcx {
 
@@ -19,7 +20,7 @@ constexpr int kRrtMaxSlots = DCX_RRT_MAX_SLOTS;   // P: a lane's best keys are k
 constexpr int kRrtRegDof = 8;       // node rows of up to this many coordinates sit in registers while the P slots read them
 constexpr unsigned long long kRrtEmpty = ~0ull;   // "no admissible node": above every real key (knn_kernel.h kKnnEmpty)
 
-// the workspace: dcx_check_motions' for E = R * P edges first (its offsets are motion_work's), then the per-slot scratch
+// the workspace (work_layout.h): dcx_check_motions' for E = R * P edges first (motion_work's offsets), then the per-slot scratch
 struct RrtPlan {
     size_t qa, qb;        // [E, dof] floats: the edge batch
     size_t near;          // [E] int32: the edge's start node in its tree, -1 for a slot with nothing to check
@@ -30,16 +31,17 @@ struct RrtPlan {
 };
 
 inline RrtPlan rrt_plan(int64_t R, int32_t P, int32_t dof, size_t motion_bytes) {
-    auto up = [](size_t x) { return (x + 255) / 256 * 256; };
     const size_t E = (size_t)R * (size_t)P;
+    WorkCarve c;
+    c.take(motion_bytes);   // dcx_check_motions' workspace, at the head
     RrtPlan w;
-    w.qa = up(motion_bytes);
-    w.qb = w.qa + up(E * dof * sizeof(float));
-    w.near = w.qb + up(E * dof * sizeof(float));
-    w.added = w.near + up(E * sizeof(int32_t));
-    w.first_hit = w.added + up(E * sizeof(int32_t));
-    w.full = w.first_hit + up(E * sizeof(int32_t));
-    w.total = w.full + up((size_t)R * sizeof(int32_t));
+    w.qa = c.take_n<float>(E * dof);
+    w.qb = c.take_n<float>(E * dof);
+    w.near = c.take_n<int32_t>(E);
+    w.added = c.take_n<int32_t>(E);
+    w.first_hit = c.take_n<int32_t>(E);
+    w.full = c.take_n<int32_t>((size_t)R);
+    w.total = c.at;
     return w;
 }
 

@@ -1,6 +1,7 @@
 // shortcut_kernel.h — what dcx_path_shortcut_run's and dcx_rrt_extract_paths' host side (dcx_api.hip) and their kernels
 // (shortcut_kernels.hip) share: the launches' arguments and THE plan of the workspace.  dcx_path_shortcut_work_bytes and
-// dcx_path_shortcut_run both call shortcut_plan, so the workspace a caller was told to bring is the one the rounds use.
+// dcx_path_shortcut_run both call shortcut_plan, so the workspace a caller was told to bring is the one the rounds use.  The
+// call shares its host body with the partial mode (dcx_api.hip shortcut_run) and its checks with RRT-Connect (PlannerCheck).
 //
 // One round of R paths is three steps on the caller's stream (include/dcx.h, "batched path shortcutting"):
 //   pick -> dcx_check_motions_ex on the R * P edges -> commit
@@ -10,6 +11,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "../../include/dcx.h"
+#include "work_layout.h"
 
 namespace dcx {
 
@@ -17,7 +19,7 @@ constexpr int kShortcutMaxSlots = DCX_SHORTCUT_MAX_SLOTS;   // P: the commit's s
 constexpr int kShortcutThreads = 256;   // threads of a commit block
 constexpr int kShortcutChunk = 4;       // floats a commit thread holds in registers between a chunk's reads and its writes
 
-// the workspace: dcx_check_motions' for E = R * P edges first (its offsets are motion_work's), then the per-slot scratch
+// the workspace (work_layout.h): dcx_check_motions' for E = R * P edges first (motion_work's offsets), then the per-slot scratch
 struct ShortcutPlan {
     size_t qa, qb;        // [E, dof] floats: the edge batch
     size_t first_hit;     // [E] int32: the motion check's answers
@@ -26,14 +28,15 @@ struct ShortcutPlan {
 };
 
 inline ShortcutPlan shortcut_plan(int64_t R, int32_t P, int32_t dof, size_t motion_bytes) {
-    auto up = [](size_t x) { return (x + 255) / 256 * 256; };
     const size_t E = (size_t)R * (size_t)P;
+    WorkCarve c;
+    c.take(motion_bytes);   // dcx_check_motions' workspace, at the head
     ShortcutPlan w;
-    w.qa = up(motion_bytes);
-    w.qb = w.qa + up(E * dof * sizeof(float));
-    w.first_hit = w.qb + up(E * dof * sizeof(float));
-    w.picks = w.first_hit + up(E * sizeof(int32_t));
-    w.total = w.picks + up(E * 2 * sizeof(int32_t));
+    w.qa = c.take_n<float>(E * dof);
+    w.qb = c.take_n<float>(E * dof);
+    w.first_hit = c.take_n<int32_t>(E);
+    w.picks = c.take_n<int32_t>(E * 2);
+    w.total = c.at;
     return w;
 }
 

@@ -1,7 +1,7 @@
 // shortcut_partial_kernel.h — what dcx_path_shortcut_partial_run's host side (dcx_api.hip) and its kernels
 // (shortcut_partial_kernels.hip) share: the launches' arguments and THE plan of the workspace.
 // dcx_path_shortcut_partial_work_bytes and dcx_path_shortcut_partial_run both call shortcut_partial_plan, so the workspace a
-// caller was told to bring is the one the rounds use.
+// caller was told to bring is the one the rounds use.  The host body is the vertex mode's (dcx_api.hip shortcut_run).
 //
 // One round of R paths is three steps on the caller's stream (include/dcx.h, "Partial shortcuts"):
 //   pick -> dcx_check_motions_ex on the R * P edges -> commit
@@ -25,15 +25,15 @@ struct ShortcutPartialPlan {
 };
 
 inline ShortcutPartialPlan shortcut_partial_plan(int64_t R, int32_t P, int32_t W, int32_t dof, size_t motion_bytes) {
-    auto up = [](size_t x) { return (x + 255) / 256 * 256; };
     const size_t rows = (size_t)R * (size_t)W;
     const size_t arc = W > kResampleLdsWaypoints ? rows : 0;
     ShortcutPartialPlan w;
     w.slot = shortcut_plan(R, P, dof, motion_bytes);
-    w.stage = w.slot.total;
-    w.c = w.stage + up(rows * (size_t)dof * sizeof(float));
-    w.len = w.c + up(arc * sizeof(float));
-    w.total = w.len + up(arc * sizeof(float));
+    WorkCarve c{w.slot.total};   // the vertex mode's workspace, at the head
+    w.stage = c.take_n<float>(rows * (size_t)dof);
+    w.c = c.take_n<float>(arc);
+    w.len = c.take_n<float>(arc);
+    w.total = c.at;
     return w;
 }
 
