@@ -105,6 +105,12 @@ SYMBOLS = {
                                C.c_void_p]),
     "dcx_sssp_extract_paths": (C.c_int, [C.c_int, C.c_void_p, _c_fp, C.c_int32, C.c_void_p, C.c_int32, C.c_int64, C.c_int32, C.c_void_p,
                                          _c_fp, _c_fp, C.c_void_p, _c_fp, _c_fp, C.c_void_p, _c_fp, C.c_int32, C.c_void_p]),
+    # lazy roadmap queries: the unchecked edges of the current shortest routes as one ordered list, and the verdicts written back
+    "dcx_sssp_mark_routes_work_bytes": (C.c_size_t, [C.c_int64]),
+    "dcx_sssp_mark_routes": (C.c_int, [C.c_int, C.c_void_p, C.c_void_p, _c_fp, C.c_int32, C.c_void_p, C.c_int32, C.c_int64, C.c_int32,
+                                       C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, _c_fp, _c_fp, C.c_int64, C.c_void_p, C.c_void_p,
+                                       C.c_size_t, C.c_void_p]),
+    "dcx_graph_apply_checks": (C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     # batched path resampling: R paths of uneven length as rows of T waypoints, equally spaced in arc length (no model)
     "dcx_path_resample_work_bytes": (C.c_size_t, [C.c_int64, C.c_int32]),
     "dcx_path_resample": (C.c_int, [C.c_int, _c_fp, _c_fp, C.c_int64, C.c_int32, C.c_int32, C.c_uint64, C.c_int32, _c_fp, _c_fp, _c_fp,
@@ -198,6 +204,11 @@ class SsspState(C.Structure):
 class SsspLinks(C.Structure):
     """ctypes mirror of dcx_sssp_links (include/dcx.h)"""
     _fields_ = [("idx", C.c_void_p), ("len", C.c_void_p), ("reserved", C.c_int64 * 2)]
+
+
+class LazyGraph(C.Structure):
+    """ctypes mirror of dcx_lazy_graph (include/dcx.h)"""
+    _fields_ = [(n, C.c_void_p) for n in ("eid", "ent", "ends", "state")] + [("M", C.c_int64), ("reserved", C.c_int64 * 2)]
 
 
 class MotionCostOpts(C.Structure):

@@ -473,6 +473,103 @@ def sssp_extract_paths(rowptr, col, weight, nodes, dist, pred, rounds_done, mode
     return path, count, length
 
 
+def _lazy_graph(fn, lazy, nnz, dev):
+    """dcx_lazy_graph of lazy = (eid [nnz], ent [M, 2], ends [M, 2] int32, state [M] uint8) on the graph's GPU: (the struct, M)"""
+    eid, ent, ends, state = lazy
+    if not isinstance(state, torch.Tensor) or state.dim() != 1:
+        raise ValueError(f"{fn}: the edges' state must be a uint8 tensor [M]")
+    M = len(state)
+    _check_tensor(f"{fn}: eid", eid, torch.int32, (nnz,), dev)
+    _check_tensor(f"{fn}: ent", ent, torch.int32, (M, 2), dev)
+    _check_tensor(f"{fn}: ends", ends, torch.int32, (M, 2), dev)
+    _check_tensor(f"{fn}: the edges' state", state, torch.uint8, (M,), dev)
+    return _lib.LazyGraph(eid.data_ptr() if nnz else 0, ent.data_ptr() if M else 0, ends.data_ptr() if M else 0,
+                          state.data_ptr() if M else 0, M, (C.c_int64 * 2)(0, 0)), M
+
+
+def sssp_mark_routes(rowptr, col, weight, lazy, nodes, dist, pred, rounds_done, mode, goal_idx, goal_len, capacity, out=None,
+                     work=None):
+    """the still unchecked edges of the routes Q queries have after rounds_done rounds of sssp_run (dcx_sssp_mark_routes;
+    include/dcx.h, "lazy roadmap queries"), lazy = (eid [nnz], ent [M, 2], ends [M, 2] int32, state [M] uint8).  Returns
+    (pending [Q] int32, list [capacity] int32, qa, qb [capacity, dof] float32, n_out [2] int32) on the GPU: n_out = (total,
+    n = min(total, capacity)), list[:n] the marked edge ids in ascending order, qa[:n] / qb[:n] their ends' rows of nodes; the
+    entries from n on are left as they are (zeros in fresh tensors).  `out`: the five tensors to write into; `work`: a uint8
+    tensor of at least dcx_sssp_mark_routes_work_bytes(M) bytes.  Four launches on torch's current stream, nothing allocated
+    (with `out` and `work` given) or read back.  With Q = 0 or M = 0 nothing is launched and fresh tensors are zeros."""
+    fn = "sssp_mark_routes"
+    lib = _lib.require_gpu()
+    g, N, dev = _sssp_graph(fn, rowptr, col, weight)
+    lz, M = _lazy_graph(fn, lazy, len(col), dev)
+    if not isinstance(dist, torch.Tensor) or dist.dim() != 3:
+        raise ValueError(f"{fn}: dist must be a float32 tensor [2, N, Q]")
+    Q = int(dist.shape[2])
+    _check_tensor(f"{fn}: dist", dist, torch.float32, (2, N, Q), dev)
+    _check_tensor(f"{fn}: pred", pred, torch.int32, (N, Q), dev)
+    if not isinstance(nodes, torch.Tensor) or nodes.dim() != 2:
+        raise ValueError(f"{fn}: nodes must be a float32 tensor [N, dof]")
+    dof = int(nodes.shape[1])
+    _check_tensor(f"{fn}: nodes", nodes, torch.float32, (N, dof), dev)
+    if not isinstance(goal_idx, torch.Tensor) or goal_idx.dim() != 2:
+        raise ValueError(f"{fn}: goal_idx must be an int32 tensor [Q, k]")
+    k = int(goal_idx.shape[1])
+    _check_tensor(f"{fn}: goal_idx", goal_idx, torch.int32, (Q, k), dev)
+    _check_tensor(f"{fn}: goal_len", goal_len, torch.float32, (Q, k), dev)
+    _check_tensor(f"{fn}: mode", mode, torch.int32, (Q,), dev)
+    capacity, rounds_done = int(capacity), int(rounds_done)
+    if capacity < 0 or rounds_done < 1:
+        raise ValueError(f"{fn}: capacity must be >= 0 and rounds_done >= 1")
+    if out is None:
+        out = (torch.zeros(Q, device=dev, dtype=torch.int32), torch.zeros(capacity, device=dev, dtype=torch.int32),
+               torch.zeros((capacity, dof), device=dev, dtype=torch.float32), torch.zeros((capacity, dof), device=dev, dtype=torch.float32),
+               torch.zeros(2, device=dev, dtype=torch.int32))
+    pending, lst, qa, qb, n_out = out
+    _check_tensor(f"{fn}: pending", pending, torch.int32, (Q,), dev)
+    _check_tensor(f"{fn}: list", lst, torch.int32, (capacity,), dev)
+    _check_tensor(f"{fn}: qa", qa, torch.float32, (capacity, dof), dev)
+    _check_tensor(f"{fn}: qb", qb, torch.float32, (capacity, dof), dev)
+    _check_tensor(f"{fn}: n_out", n_out, torch.int32, (2,), dev)
+    nbytes = int(lib.dcx_sssp_mark_routes_work_bytes(M))
+    if work is None:
+        work = torch.empty(max(nbytes, 1), device=dev, dtype=torch.uint8)
+    if not isinstance(work, torch.Tensor) or work.dtype != torch.uint8 or work.device != dev or not work.is_contiguous() or work.numel() < nbytes:
+        raise ValueError(f"{fn}: work must be a contiguous uint8 tensor of at least {nbytes} bytes on {dev}")
+    st = _lib.SsspState(dist.data_ptr(), pred.data_ptr(), (C.c_int64 * 2)(0, 0))
+    links = _lib.SsspLinks(goal_idx.data_ptr(), goal_len.data_ptr(), (C.c_int64 * 2)(0, 0))
+    with _on_device(dev):
+        _lib.check(lib.dcx_sssp_mark_routes(dev.index, C.byref(g), C.byref(lz), _ptr(nodes), dof, C.byref(st), rounds_done, Q, k,
+                                            _ptr(mode), C.byref(links), _ptr(pending), _ptr(lst), _ptr(qa), _ptr(qb), capacity,
+                                            _ptr(n_out), _ptr(work), work.numel(), _stream(dev)))
+    return pending, lst, qa, qb, n_out
+
+
+def graph_apply_checks(rowptr, col, weight, lazy, lst, n_out, hit, any_blocked=None):
+    """the verdicts of the edges sssp_mark_routes listed, written into the graph (dcx_graph_apply_checks): for i < n_out[1] (read
+    on the device) the state of edge lst[i] becomes 2 where hit[i] else 1, and both CSR entries of an edge that hit get the
+    weight +inf.  `weight` and the edges' state (lazy[3]) ARE WRITTEN.  hit: uint8 or bool, as long as lst (the capacity).
+    Returns any_blocked int32 [1] on the GPU.  Two launches on torch's current stream, nothing read back."""
+    fn = "graph_apply_checks"
+    lib = _lib.require_gpu()
+    g, N, dev = _sssp_graph(fn, rowptr, col, weight)
+    lz, M = _lazy_graph(fn, lazy, len(col), dev)
+    if not isinstance(lst, torch.Tensor) or lst.dim() != 1:
+        raise ValueError(f"{fn}: list must be an int32 tensor [capacity]")
+    cap = len(lst)
+    _check_tensor(f"{fn}: list", lst, torch.int32, (cap,), dev)
+    _check_tensor(f"{fn}: n_out", n_out, torch.int32, (2,), dev)
+    if isinstance(hit, torch.Tensor) and hit.dtype == torch.bool:
+        hit = hit.view(torch.uint8)
+    _check_tensor(f"{fn}: hit", hit, torch.uint8, (cap,), dev)
+    if any_blocked is None:
+        any_blocked = torch.zeros(1, device=dev, dtype=torch.int32)
+    _check_tensor(f"{fn}: any_blocked", any_blocked, torch.int32, (1,), dev)
+    if cap == 0:
+        return any_blocked
+    with _on_device(dev):
+        _lib.check(lib.dcx_graph_apply_checks(dev.index, C.byref(g), C.byref(lz), _ptr(lst), _ptr(n_out), _ptr(hit), _ptr(any_blocked),
+                                              _stream(dev)))
+    return any_blocked
+
+
 def compose_path_cost(edge_cost, paths, dof):
     """[T] costs of paths [T, W, dof] from an edge-cost callable edge_cost(qa, qb, open_end) under the max_step rule: the
     open-ended edges p[i] -> p[i + 1] plus the zero-length edge p[-1] -> p[-1] (its one sample is p[-1]) cover the points of

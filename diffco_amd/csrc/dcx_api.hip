@@ -25,6 +25,7 @@
 #include "shortcut_partial_kernel.h"
 #include "resample_kernel.h"
 #include "sssp_kernel.h"
+#include "sssp_lazy_kernel.h"
 #include "work_layout.h"
 
 using namespace dcx;
@@ -2903,6 +2904,102 @@ int dcx_sssp_extract_paths(int device, const dcx_graph* graph, const float* node
     a.W = W;
     const hipError_t e = launch_sssp_extract(a, (hipStream_t)stream);
     if (e != hipSuccess) return fail_hip(e, "sssp extract launch");
+    return DCX_OK;
+}
+
+// ---- lazy roadmap queries (sssp_lazy_kernel.h): the checks of the edges' arrays, shared by both calls -------------------------
+static int lazy_check(const dcx_graph* g, const dcx_lazy_graph* lz) {
+    if (!g || !lz) return fail(DCX_ERR_INVALID, "lazy: graph or lazy is NULL");
+    if (g->N < 0 || g->nnz < 0 || lz->M < 0) return fail(DCX_ERR_INVALID, "lazy: N < 0, nnz < 0 or M < 0");
+    if (g->reserved[0] || g->reserved[1] || lz->reserved[0] || lz->reserved[1])
+        return fail(DCX_ERR_INVALID, "lazy: reserved fields must be 0");
+    return DCX_OK;
+}
+
+size_t dcx_sssp_mark_routes_work_bytes(int64_t M) {
+    if (M < 1 || M > INT32_MAX) return 0;
+    return lazy_plan(M).total;
+}
+
+int dcx_sssp_mark_routes(int device, const dcx_graph* graph, const dcx_lazy_graph* lazy, const float* nodes, int32_t dof,
+                         const dcx_sssp_state* state, int32_t rounds_done, int64_t Q, int32_t k, const int32_t* mode,
+                         const dcx_sssp_links* goal_links, int32_t* pending, int32_t* list, float* qa, float* qb, int64_t capacity,
+                         int32_t* n_out, void* work, size_t work_bytes, void* stream) {
+    if (int rc = lazy_check(graph, lazy)) return rc;
+    if (int rc = sssp_check(graph, state, goal_links, Q, k)) return rc;
+    if (dof < 1 || dof > 64) return fail(DCX_ERR_INVALID, "lazy: dof must be in [1, 64]");
+    if (rounds_done < 1) return fail(DCX_ERR_INVALID, "lazy: rounds_done < 1");
+    if (capacity < 0) return fail(DCX_ERR_INVALID, "lazy: capacity < 0");
+    if (Q == 0 || lazy->M == 0) return DCX_OK;
+    if (!graph->rowptr || (graph->nnz > 0 && !graph->col)) return fail(DCX_ERR_INVALID, "lazy: rowptr or col is NULL");
+    if (graph->N > 0 && (!state->dist || !state->pred)) return fail(DCX_ERR_INVALID, "lazy: dist or pred is NULL");
+    if (graph->N > INT32_MAX - 1 || graph->nnz > INT32_MAX || lazy->M > INT32_MAX || (graph->N > 0 && Q > INT32_MAX / graph->N))
+        return fail(DCX_ERR_UNSUPPORTED, "lazy: N, nnz, M or N * Q beyond int32 indexing");
+    if (Q > INT32_MAX) return fail(DCX_ERR_UNSUPPORTED, "lazy: more queries than one launch takes");
+    if ((graph->nnz > 0 && !lazy->eid) || !lazy->ent || !lazy->ends || !lazy->state)
+        return fail(DCX_ERR_INVALID, "lazy: eid, ent, ends or the edges' state is NULL");
+    if (!goal_links->idx || !goal_links->len) return fail(DCX_ERR_INVALID, "lazy: a link array is NULL");
+    if (graph->N > 0 && !nodes) return fail(DCX_ERR_INVALID, "lazy: nodes is NULL");
+    if (!mode || !pending || !n_out) return fail(DCX_ERR_INVALID, "lazy: mode, pending or n_out is NULL");
+    if (capacity > 0 && (!list || !qa || !qb)) return fail(DCX_ERR_INVALID, "lazy: list, qa or qb is NULL with capacity > 0");
+    const LazyPlan plan = lazy_plan(lazy->M);
+    if (!work || (reinterpret_cast<uintptr_t>(work) & 15) || work_bytes < plan.total)
+        return fail(DCX_ERR_INVALID, "lazy: the workspace is NULL, misaligned or smaller than dcx_sssp_mark_routes_work_bytes");
+    if (int rc = set_device(device)) return rc;
+    char* const base = static_cast<char*>(work);
+    LazyMarkArgs a{};
+    a.rowptr = graph->rowptr;
+    a.col = graph->col;
+    a.eid = lazy->eid;
+    a.ends = lazy->ends;
+    a.state = lazy->state;
+    a.nodes = nodes;
+    a.dist = state->dist + (graph->N > 0 ? (int64_t)((rounds_done - 1) & 1) * graph->N * Q : 0);
+    a.pred = state->pred;
+    a.mode = mode;
+    a.goal_idx = goal_links->idx;
+    a.goal_len = goal_links->len;
+    a.pending = pending;
+    a.list = list;
+    a.qa = qa;
+    a.qb = qb;
+    a.n_out = n_out;
+    a.mark = reinterpret_cast<uint8_t*>(base + plan.mark);
+    a.offs = reinterpret_cast<int32_t*>(base + plan.offs);
+    a.groups = plan.groups;
+    a.capacity = capacity;
+    a.N = (int32_t)graph->N;
+    a.nnz = (int32_t)graph->nnz;
+    a.M = (int32_t)lazy->M;
+    a.Q = (int32_t)Q;
+    a.k = k;
+    a.dof = dof;
+    const hipError_t e = launch_lazy_mark_routes(a, (hipStream_t)stream);
+    if (e != hipSuccess) return fail_hip(e, "lazy mark launch");
+    return DCX_OK;
+}
+
+int dcx_graph_apply_checks(int device, const dcx_graph* graph, const dcx_lazy_graph* lazy, const int32_t* list,
+                           const int32_t* n_out, const uint8_t* hit, int32_t* any_blocked, void* stream) {
+    if (int rc = lazy_check(graph, lazy)) return rc;
+    if (lazy->M == 0) return DCX_OK;
+    if (graph->nnz > INT32_MAX || lazy->M > INT32_MAX) return fail(DCX_ERR_UNSUPPORTED, "lazy: nnz or M beyond int32 indexing");
+    if ((graph->nnz > 0 && !graph->weight) || !lazy->ent || !lazy->state)
+        return fail(DCX_ERR_INVALID, "lazy: weight, ent or the edges' state is NULL");
+    if (!list || !n_out || !hit || !any_blocked) return fail(DCX_ERR_INVALID, "lazy: list, n_out, hit or any_blocked is NULL");
+    if (int rc = set_device(device)) return rc;
+    LazyApplyArgs a{};
+    a.weight = const_cast<float*>(graph->weight);   // (the contract: this call's graph is the caller's to change)
+    a.ent = lazy->ent;
+    a.state = lazy->state;
+    a.list = list;
+    a.n_out = n_out;
+    a.hit = hit;
+    a.any_blocked = any_blocked;
+    a.nnz = (int32_t)graph->nnz;
+    a.M = (int32_t)lazy->M;
+    const hipError_t e = launch_lazy_apply(a, (hipStream_t)stream);
+    if (e != hipSuccess) return fail_hip(e, "lazy apply launch");
     return DCX_OK;
 }
 

@@ -10,13 +10,19 @@ max_step=..., wrap=...)`: DiffCo, the collision_checkers facades, HybridForwardK
 `Roadmap.query_batch` is the multi-query half: Q start/goal pairs answered by synchronous min-plus relaxation over the roadmap's
 CSR (the fused HIP calls _ops.sssp_run and _ops.sssp_extract_paths; `host_sssp` and `host_extract_paths` state the same contract
 in torch ops: CPU tensors, the referee and the baseline), the routes in one [Q, W, dof] tensor (`RoadmapPaths`).
+
+`Roadmap.build(..., lazy=True)` is the lazy PRM: no edge is checked until a shortest route uses it.  `query_batch` then loops
+relax - mark - check - apply (the fused HIP calls _ops.sssp_mark_routes and _ops.graph_apply_checks; `host_mark_routes` and
+`host_apply_checks` are their contract in torch ops) until every route stands on checked edges: for a checker whose motion
+checks are expensive (the hybrid one's ground truth) or whose model changes (`invalidate` after `checker.update`).
 """
 import numpy as np
 import torch
 
 from . import _ops
 
-__all__ = ["knn", "host_knn", "knn_edges", "Roadmap", "RoadmapPaths", "host_sssp", "host_extract_paths"]
+__all__ = ["knn", "host_knn", "knn_edges", "Roadmap", "RoadmapPaths", "host_sssp", "host_extract_paths", "host_mark_routes",
+           "host_apply_checks"]
 
 _EMPTY = torch.iinfo(torch.int64).max   # the key of an unfilled slot: above every real key (bits(dist2) << 32 | index)
 
@@ -182,8 +188,36 @@ def host_extract_paths(nodes, dist, pred, mode, starts, goals, goal_idx, goal_le
     nodes = torch.as_tensor(nodes)
     dev = nodes.device
     N, dof = nodes.shape
-    Q, k = goal_idx.shape
+    Q = len(goal_idx)
     mode = torch.as_tensor(mode).to(device=dev, dtype=torch.int64)
+    length, routed, chain = _walk_routes(N, dist, pred, mode, goal_idx, goal_len)
+    inf = torch.full((Q,), float("inf"), dtype=torch.float32, device=dev)
+    depth = (chain >= 0).sum(dim=0) * routed
+    length = torch.where(mode == 1, torch.as_tensor(direct_len).to(device=dev, dtype=torch.float32), torch.where(routed, length, inf))
+    n = torch.where(mode == 1, torch.full_like(depth, 2), torch.where(routed, depth + 2, torch.zeros_like(depth)))
+    if W is None:
+        W = max(int(n.max()) if Q else 0, 2)
+    W = int(W)
+    fits = (n > 0) & (n <= W)
+    count = torch.where(fits, n, -n).to(torch.int32)
+    path = torch.zeros((Q, W, dof), dtype=nodes.dtype, device=dev)
+    qf = fits.nonzero().reshape(-1)
+    if len(qf):
+        path[qf, 0] = torch.as_tensor(starts).to(device=dev, dtype=nodes.dtype)[qf]
+        path[qf, n[qf] - 1] = torch.as_tensor(goals).to(device=dev, dtype=nodes.dtype)[qf]
+    on = (chain >= 0) & (fits & routed & (mode == 2))[None, :]
+    h, q = on.nonzero(as_tuple=True)
+    if len(h):
+        path[q, depth[q] - h] = nodes[chain[h, q]]
+    return path, count, length
+
+
+def _walk_routes(N, dist, pred, mode, goal_idx, goal_len):
+    """the goal slot and the predecessor walk host_extract_paths and host_mark_routes share, for mode int64 [Q] on the state's
+    device: (length [Q] float32, +inf without a route; routed [Q] bool; chain [H, Q] int64, chain[h, q] the node h hops
+    before the goal link's, -1 past the walk's end)"""
+    dev = dist.device
+    Q, k = goal_idx.shape
     gi = goal_idx.to(torch.int64)
     real = (gi >= 0) & (gi < N) & (mode == 2)[:, None]
     qq = torch.arange(Q, device=dev)
@@ -208,34 +242,80 @@ def host_extract_paths(nodes, dist, pred, mode, starts, goals, goal_idx, goal_le
         chain.append(cur)
         cur = torch.where(cur >= 0, pred[cur.clamp(min=0), qq].to(torch.int64), cur)
     chain = torch.stack(chain) if chain else torch.zeros((0, Q), dtype=torch.int64, device=dev)
-    depth = (chain >= 0).sum(dim=0) * routed
-    length = torch.where(mode == 1, torch.as_tensor(direct_len).to(device=dev, dtype=torch.float32), torch.where(routed, length, inf))
-    n = torch.where(mode == 1, torch.full_like(depth, 2), torch.where(routed, depth + 2, torch.zeros_like(depth)))
-    if W is None:
-        W = max(int(n.max()) if Q else 0, 2)
-    W = int(W)
-    fits = (n > 0) & (n <= W)
-    count = torch.where(fits, n, -n).to(torch.int32)
-    path = torch.zeros((Q, W, dof), dtype=nodes.dtype, device=dev)
-    qf = fits.nonzero().reshape(-1)
-    if len(qf):
-        path[qf, 0] = torch.as_tensor(starts).to(device=dev, dtype=nodes.dtype)[qf]
-        path[qf, n[qf] - 1] = torch.as_tensor(goals).to(device=dev, dtype=nodes.dtype)[qf]
-    on = (chain >= 0) & (fits & routed & (mode == 2))[None, :]
-    h, q = on.nonzero(as_tuple=True)
-    if len(h):
-        path[q, depth[q] - h] = nodes[chain[h, q]]
-    return path, count, length
+    return length, routed, chain
+
+
+def host_mark_routes(rowptr, col, eid, ends, edge_state, nodes, dist, pred, mode, goal_idx, goal_len, capacity):
+    """dcx_sssp_mark_routes' contract (include/dcx.h, "lazy roadmap queries") in plain torch ops on the tensors' own device: the
+    still unknown edges (edge_state [M] uint8 == 0) on the routes the state (dist, pred [N, Q]) of host_sssp holds for the
+    mode-2 queries, found as host_extract_paths finds them.  A hop (v, u = pred[v][q]) is the first entry of row v whose col
+    is u, its edge eid[entry]; a hop without an entry or with an edge id outside 0 .. M - 1 is skipped.
+    Returns (pending [Q] int32: the unknown edges on query q's route; list [capacity] int32; qa, qb [capacity, dof] in the
+    nodes' dtype; n_out [2] int32 = (total, n = min(total, capacity))): list[:n] holds the n smallest marked edge ids in
+    ascending order, qa[:n] = nodes[ends[list[:n], 0]] and qb[:n] = nodes[ends[list[:n], 1]], the rest zeros."""
+    nodes = torch.as_tensor(nodes)
+    dev = nodes.device
+    N, dof = nodes.shape
+    Q, M, nnz, capacity = len(goal_idx), len(edge_state), len(col), int(capacity)
+    if capacity < 0:
+        raise ValueError("host_mark_routes: capacity must be >= 0")
+    mode = torch.as_tensor(mode).to(device=dev, dtype=torch.int64)
+    _, routed, chain = _walk_routes(N, dist, pred, mode, goal_idx, goal_len)
+    mark = torch.zeros(M, dtype=torch.bool, device=dev)
+    pending = torch.zeros(Q, dtype=torch.int32, device=dev)
+    if len(chain) > 1 and nnz and M:
+        on = (chain[1:] >= 0) & routed[None, :]
+        h, q = on.nonzero(as_tuple=True)
+        v, u = chain[:-1][h, q], chain[1:][h, q]
+        rp = rowptr.to(torch.int64)
+        beg, end = rp[v].clamp(min=0), rp[v + 1].clamp(max=nnz)
+        D = int((end - beg).max()) if len(v) else 0
+        if D > 0:
+            slot = torch.arange(D, device=dev)[None, :]
+            at = beg[:, None] + slot                                                 # [hops, D]
+            match = (at < end[:, None]) & (col.to(torch.int64)[at.clamp(max=nnz - 1)] == u[:, None])
+            first = torch.where(match, slot, torch.full_like(at, D)).min(dim=1).values
+            m = eid.to(torch.int64)[(beg + first).clamp(max=nnz - 1)]
+            unknown = (first < D) & (m >= 0) & (m < M)
+            unknown &= edge_state[m.clamp(0, M - 1)] == 0
+            mark[m[unknown]] = True
+            pending.index_add_(0, q[unknown], torch.ones_like(q[unknown], dtype=torch.int32))
+    ids = mark.nonzero().reshape(-1)
+    total = len(ids)
+    n = min(total, capacity)
+    lst = torch.zeros(capacity, dtype=torch.int32, device=dev)
+    qa, qb = torch.zeros((capacity, dof), dtype=nodes.dtype, device=dev), torch.zeros((capacity, dof), dtype=nodes.dtype, device=dev)
+    lst[:n] = ids[:n].to(torch.int32)
+    e = ends.to(torch.int64)[ids[:n]]
+    qa[:n], qb[:n] = nodes[e[:, 0]], nodes[e[:, 1]]
+    return pending, lst, qa, qb, torch.tensor([total, n], dtype=torch.int32, device=dev)
+
+
+def host_apply_checks(weight, ent, edge_state, lst, n_out, hit):
+    """dcx_graph_apply_checks' contract in plain torch ops, IN PLACE on weight [nnz] float32 and edge_state [M] uint8: for
+    i < n_out[1] the state of edge lst[i] becomes 2 where hit[i] else 1, and both CSR entries ent[lst[i]] of an edge that hit
+    get the weight +inf.  Returns any_blocked int32 [1]."""
+    n = int(n_out[1])
+    ids = lst[:n].to(torch.int64)
+    hit = torch.as_tensor(hit).to(device=ids.device).reshape(-1)[:n] != 0
+    edge_state[ids] = torch.where(hit, 2, 1).to(torch.uint8)
+    weight[ent.to(torch.int64)[ids[hit]].reshape(-1)] = float("inf")
+    return hit.any().to(torch.int32).reshape(1)
 
 
 class RoadmapPaths:
     """What Roadmap.query_batch returns: path [Q, W, dof], count [Q] int32 (n where query q's n waypoints are in path[q, :n],
     0 where there is no route, -n where n > W), length [Q] float32 (+inf without a route), mode [Q] int32 (0 an endpoint
     collides, 1 the direct motion is free, 2 over the roadmap), rounds (relaxation rounds run, round 0 included) and route
-    ('fused' or 'host').  `path, count` go into shortcut_paths as they are."""
+    ('fused' or 'host').  `path, count` go into shortcut_paths as they are.
+    A lazy roadmap's loop adds settled [Q] bool (false only where `max_iters` cut the loop while the query's route still stood on
+    unchecked edges: such a query has count 0 and length +inf), iters (relax-and-mark passes, the largest of the query chunks')
+    and checked (edges handed to the checker, over all chunks); an eager roadmap reports all-true, 1 and 0."""
 
-    def __init__(self, path, count, length, mode, rounds, route):
+    def __init__(self, path, count, length, mode, rounds, route, settled=None, iters=1, checked=0):
         self.path, self.count, self.length, self.mode, self.rounds, self.route = path, count, length, mode, rounds, route
+        self.settled = torch.ones(len(count), dtype=torch.bool, device=count.device) if settled is None else settled
+        self.iters, self.checked = iters, checked
 
     def paths(self):
         """a list with, per query, its waypoints [n, dof] or None"""
@@ -266,9 +346,14 @@ class Roadmap:
     """A probabilistic roadmap over `nodes`: `build` keeps the collision-free nodes, connects each to its k nearest under the
     motion metric and keeps the edges one `check_motions` call frees; `query` connects two configurations to it and returns
     the shortest route.  Attributes: nodes [n, dof] (the kept ones), kept [n] (their indices into the given nodes), edges
-    [M, 2] int64 (i < j, into `nodes`), lengths [M], graph (symmetric scipy.sparse.csr_matrix of the lengths)."""
+    [M, 2] int64 (i < j, into `nodes`), lengths [M], graph (symmetric scipy.sparse.csr_matrix of the lengths).
+    `build(..., lazy=True)` checks no edge: `edges` are then ALL the k-nearest candidates, in knn_edges' order (ascending
+    i * n + j: the position is the edge id), `edge_state` [M] uint8 on the nodes' device says what is known of each (0 unknown,
+    1 free, 2 blocked) and `lazy` is True.  `query_batch` checks the edges its shortest routes use and no others, and what it
+    learns stays: states persist across calls.  `validate` checks whatever is still unknown, `invalidate` forgets (the call
+    after the checker's model changed).  `graph` is the candidate graph at build time and is NOT kept up to date."""
 
-    def __init__(self, checker, nodes, kept, edges, lengths, k, max_step, mask, check_kw):
+    def __init__(self, checker, nodes, kept, edges, lengths, k, max_step, mask, check_kw, lazy=False):
         from scipy.sparse import csr_matrix
         self.checker = checker if isinstance(checker, _Checker) else _Checker(checker)
         self.nodes, self.kept, self.edges, self.lengths = nodes, kept, edges, lengths
@@ -279,9 +364,13 @@ class Roadmap:
         self.graph = csr_matrix((np.concatenate([w, w]), (np.concatenate([e[:, 0], e[:, 1]]), np.concatenate([e[:, 1], e[:, 0]]))),
                                 shape=(n, n))
         self._csr = None
+        self.lazy = bool(lazy)
+        if self.lazy:
+            self.edge_state = torch.zeros(len(edges), dtype=torch.uint8, device=nodes.device)
+            self._lazy = None
 
     @classmethod
-    def build(cls, checker, nodes, k, max_step, wrap=None, max_dist=None, **check_kw):
+    def build(cls, checker, nodes, k, max_step, wrap=None, max_dist=None, lazy=False, **check_kw):
         ck = _Checker(checker)
         nodes = torch.as_tensor(nodes).detach()
         mask = _ops.wrap_mask(wrap, nodes.shape[1], ck.transform)
@@ -289,6 +378,8 @@ class Roadmap:
         nodes = nodes[kept]
         cand = knn_edges(nodes, k, wrap=mask, max_dist=max_dist)
         qa, qb = nodes[cand[:, 0]], nodes[cand[:, 1]]
+        if lazy:
+            return cls(ck, nodes, kept, cand, _ops.wrapped_delta(qa, qb, mask).norm(dim=1), int(k), max_step, mask, check_kw, lazy=True)
         free = ~ck.motions(qa, qb, max_step, mask, **check_kw)
         edges = cand[free]
         lengths = _ops.wrapped_delta(qa[free], qb[free], mask).norm(dim=1)
@@ -302,7 +393,9 @@ class Roadmap:
 
     def csr(self):
         """(rowptr int32 [n + 1], col int32 [nnz], weight float32 [nnz]) on the nodes' device: the roadmap as the symmetric CSR
-        dcx_sssp_run reads (every edge in both rows, each row sorted by col).  Built once from `edges` and `lengths`."""
+        dcx_sssp_run reads (every edge in both rows, each row sorted by col).  Built once from `edges` and `lengths`.
+        On a lazy roadmap `weight` is a buffer the roadmap changes: an entry holds its edge's length while the edge is unknown
+        or free and +inf once it is blocked."""
         if self._csr is None:
             n, dev = len(self.nodes), self.nodes.device
             e = self.edges.to(dev)
@@ -312,11 +405,49 @@ class Roadmap:
             rowptr = torch.zeros(n + 1, dtype=torch.int64, device=dev)
             rowptr[1:] = torch.cumsum(torch.bincount(i, minlength=n), dim=0)
             self._csr = (rowptr.to(torch.int32), j[order].to(torch.int32).contiguous(), torch.cat([w, w])[order].contiguous())
+            if self.lazy:
+                # entry p of the unsorted list belongs to edge p % M: p < M in row i, else in row j
+                M = len(e)
+                inv = torch.empty_like(order)
+                inv[order] = torch.arange(2 * M, device=dev)
+                self._lazy = ((order % max(M, 1)).to(torch.int32).contiguous(), torch.stack([inv[:M], inv[M:]], dim=1).to(torch.int32).contiguous(),
+                              e.to(torch.int32).contiguous())
         return self._csr
+
+    def lazy_arrays(self):
+        """(eid int32 [nnz]: CSR entry -> edge id; ent int32 [M, 2]: edge id -> its two CSR entries; ends int32 [M, 2]; edge_state):
+        what dcx_sssp_mark_routes and dcx_graph_apply_checks read beside csr() (include/dcx.h, "lazy roadmap queries")"""
+        if not self.lazy:
+            raise ValueError("lazy_arrays: the roadmap was built with lazy=False")
+        self.csr()
+        return self._lazy + (self.edge_state,)
+
+    def validate(self):
+        """checks every still unknown edge in one check_motions call: afterwards the roadmap holds exactly the information of
+        one built with lazy=False.  Returns the number of edges checked."""
+        _, _, weight = self.csr()
+        _, ent, _, state = self.lazy_arrays()
+        ids = (state == 0).nonzero().reshape(-1)
+        hit = self.checker.motions(self.nodes[self.edges[ids, 0]], self.nodes[self.edges[ids, 1]], self.max_step, self.wrap_mask, **self.check_kw)
+        host_apply_checks(weight, ent, state, ids, (len(ids), len(ids)), hit)
+        return len(ids)
+
+    def invalidate(self, edge_ids=None):
+        """sets the given edges (default: all) back to unknown and their weights back to their lengths: the call after the
+        checker changed (`checker.update(...)`).  The nodes' validity is NOT asked again: an edge check samples its endpoints,
+        so the edges of a node that now collides fall one by one as routes try them."""
+        _, _, weight = self.csr()
+        _, ent, _, state = self.lazy_arrays()
+        ids = torch.arange(len(state), device=state.device) if edge_ids is None else torch.as_tensor(edge_ids, device=state.device).to(torch.int64).reshape(-1)
+        state[ids] = 0
+        w = self.lengths.detach().to(device=weight.device, dtype=torch.float32)[ids]
+        e = ent.to(torch.int64)[ids]
+        weight[e[:, 0]], weight[e[:, 1]] = w, w
 
     STATE_BUDGET = 1 << 28   # bytes of relaxation state query_batch holds at a time: 12 bytes per (node, query)
 
-    def query_batch(self, starts, goals, k=None, rounds_per_call=8, max_rounds=None, max_waypoints=None, route=None):
+    def query_batch(self, starts, goals, k=None, rounds_per_call=8, max_rounds=None, max_waypoints=None, route=None, max_iters=None,
+                    check_capacity=None):
         """`query` for Q start/goal pairs at once, as a RoadmapPaths: the shortest routes over the roadmap in one
         [Q, W, dof] tensor that goes into shortcut_paths as it is.  The checker is called three times whatever Q is (the 2Q
         endpoints, the Q direct motions, the 2Qk links to each endpoint's k nearest nodes); the shortest paths are the fixed
@@ -327,7 +458,15 @@ class Roadmap:
         _ops.sssp_extract_paths), CPU tensors host_sssp and host_extract_paths; `route` ('fused' / 'host') forces one.
         `max_waypoints`: W; None sizes it by the longest route (one more number read back).  The queries are taken in chunks
         of Q such that the relaxation state (two float32 distance buffers and an int32 predecessor per node and query) stays
-        within STATE_BUDGET = 256 MiB."""
+        within STATE_BUDGET = 256 MiB.
+        On a lazy roadmap each chunk of queries loops: relax from round 0 to the fixed point over the current weights; mark the
+        still unknown edges of the routes found (_ops.sssp_mark_routes / host_mark_routes; their number is the one value read
+        back per pass, 0 ends the loop); check the first `check_capacity` (default: all M) of them, in edge-id order, in one
+        check_motions call; write the verdicts into the graph (_ops.graph_apply_checks / host_apply_checks), +inf for a blocked
+        edge.  The relaxation starts over each time, since distances only grow when edges go.  Every pass that marks anything
+        settles at least one edge, so the loop ends within M passes; `max_iters` cuts it earlier, and a query whose route still
+        stands on unknown edges then is reported unsettled, without a path.  The routes are those of the eager roadmap, bit
+        for bit, for the edges checked on the way; the states stay with the roadmap."""
         nodes, mask = self.nodes, self.wrap_mask
         dev, dof, n = nodes.device, nodes.shape[1], len(nodes)
         starts = torch.as_tensor(starts).reshape(-1, dof).to(device=dev, dtype=nodes.dtype)
@@ -374,6 +513,23 @@ class Roadmap:
         qchunk = max(1, self.STATE_BUDGET // (12 * max(n, 1)))
         qchunk -= qchunk % 64 if qchunk >= 64 else 0
         fused = route == "fused"
+        if max_iters is not None and int(max_iters) < 1:
+            raise ValueError("query_batch: max_iters must be >= 1")
+        lazy = self.lazy and len(self.edges) > 0
+        settled, iters, checked = torch.ones(Q, dtype=torch.bool, device=dev), 1, 0
+        if lazy:
+            M = len(self.edges)
+            eid, ent, ends_, state = self.lazy_arrays()
+            capn = M if check_capacity is None else min(int(check_capacity), M)
+            if capn < 1:
+                raise ValueError("query_batch: check_capacity must be >= 1")
+            if fused:
+                lz = (eid, ent, ends_, state)
+                # (list, qa, qb, n_out): written by every mark pass, read by the checker and the apply call
+                mark_out = (torch.zeros(capn, dtype=torch.int32, device=dev), torch.zeros((capn, dof), device=dev),
+                            torch.zeros((capn, dof), device=dev), torch.zeros(2, dtype=torch.int32, device=dev))
+                hitbuf = torch.zeros(capn, dtype=torch.uint8, device=dev)
+                flag = torch.zeros(1, dtype=torch.int32, device=dev)
         if fused:
             nodes32, starts32, goals32 = (t.to(torch.float32).contiguous() for t in (nodes, starts, goals))
         W = None if max_waypoints is None else int(max_waypoints)
@@ -381,28 +537,66 @@ class Roadmap:
         for q0 in range(0, Q, qchunk):
             s = slice(q0, q0 + qchunk)
             Qc = len(mode[s])
+            mode_c, it = mode[s], 0
             if fused:
                 dist = torch.empty((2, n, Qc), dtype=torch.float32, device=dev)
                 pred = torch.empty((n, Qc), dtype=torch.int32, device=dev)
-                done, took = 0, None
-                while done < cap and took is None:
-                    m = min(rpc, cap - done)
-                    flags = _ops.sssp_run(rowptr, col, weight, start_idx[s], start_len[s], dist, pred, done, m).tolist()
-                    if 0 in flags:
-                        took = done + flags.index(0) + 1
-                    done += m
-                args = (rowptr, col, weight, nodes32, dist, pred, done, mode[s], starts32[s], goals32[s], goal_idx[s], goal_len[s],
+                pending = torch.zeros(Qc, dtype=torch.int32, device=dev)
+                while True:
+                    done, took = 0, None
+                    while done < cap and took is None:
+                        m = min(rpc, cap - done)
+                        flags = _ops.sssp_run(rowptr, col, weight, start_idx[s], start_len[s], dist, pred, done, m).tolist()
+                        if 0 in flags:
+                            took = done + flags.index(0) + 1
+                        done += m
+                    it += 1
+                    if not lazy:
+                        break
+                    _, lst, ea, eb, n_out = _ops.sssp_mark_routes(rowptr, col, weight, lz, nodes32, dist, pred, done, mode_c, goal_idx[s],
+                                                                  goal_len[s], capn, out=(pending,) + mark_out)
+                    total, nn = n_out.tolist()
+                    if total == 0:
+                        break
+                    if nodes.dtype != torch.float32:   # (the checker sees the nodes' own bits, as an eager build's does)
+                        ids = lst[:nn].to(torch.int64)
+                        ea, eb = nodes[self.edges[ids, 0]], nodes[self.edges[ids, 1]]
+                    hitbuf[:nn] = self.checker.motions(ea[:nn], eb[:nn], self.max_step, mask, **self.check_kw)
+                    _ops.graph_apply_checks(rowptr, col, weight, lz, lst, n_out, hitbuf, any_blocked=flag)
+                    checked += nn
+                    if max_iters is not None and it >= int(max_iters):
+                        settled[s] = pending == 0
+                        mode_c = torch.where(pending == 0, mode_c, torch.zeros_like(mode_c))
+                        break
+                args = (rowptr, col, weight, nodes32, dist, pred, done, mode_c, starts32[s], goals32[s], goal_idx[s], goal_len[s],
                         direct_len[s])
                 Wc = W
                 if Wc is None:
                     Wc = max(-int(_ops.sssp_extract_paths(*args, 0)[1].min()), 2)
                 part = _ops.sssp_extract_paths(*args, Wc)
             else:
-                d, p, flags = host_sssp(rowptr, col, weight, start_idx[s], start_len[s], rounds=cap)
-                flags = flags.tolist()
-                took = flags.index(0) + 1 if 0 in flags else None
-                part = host_extract_paths(nodes, d, p, mode[s], starts[s], goals[s], goal_idx[s], goal_len[s], direct_len[s], W)
+                while True:
+                    d, p, flags = host_sssp(rowptr, col, weight, start_idx[s], start_len[s], rounds=cap)
+                    flags = flags.tolist()
+                    took = flags.index(0) + 1 if 0 in flags else None
+                    it += 1
+                    if not lazy:
+                        break
+                    pending, lst, ea, eb, n_out = host_mark_routes(rowptr, col, eid, ends_, state, nodes, d, p, mode_c, goal_idx[s],
+                                                                   goal_len[s], capn)
+                    total, nn = n_out.tolist()
+                    if total == 0:
+                        break
+                    hit = self.checker.motions(ea[:nn], eb[:nn], self.max_step, mask, **self.check_kw)
+                    host_apply_checks(weight, ent, state, lst, n_out, hit)
+                    checked += nn
+                    if max_iters is not None and it >= int(max_iters):
+                        settled[s] = pending == 0
+                        mode_c = torch.where(pending == 0, mode_c, torch.zeros_like(mode_c))
+                        break
+                part = host_extract_paths(nodes, d, p, mode_c, starts[s], goals[s], goal_idx[s], goal_len[s], direct_len[s], W)
             rounds = max(rounds, cap if took is None else took)
+            iters = max(iters, it)
             parts.append(part)
         if len(parts) == 1:
             path, count, length = parts[0]
@@ -415,11 +609,16 @@ class Roadmap:
                 q0 += len(p[0])
             count = torch.cat([p[1] for p in parts]) if parts else torch.zeros(0, dtype=torch.int32, device=dev)
             length = torch.cat([p[2] for p in parts]) if parts else torch.zeros(0, dtype=torch.float32, device=dev)
-        return RoadmapPaths(path, count, length, mode, rounds, route)
+        return RoadmapPaths(path, count, length, mode, rounds, route, settled, iters, checked)
 
     def query(self, start, goal, k=None):
         """(waypoints [W, dof], length) of the shortest route start -> goal over the roadmap, or None where an endpoint
-        collides or no route exists.  A free direct motion is returned as the two-point path."""
+        collides or no route exists.  A free direct motion is returned as the two-point path.  On a lazy roadmap this is
+        `query_batch` with one pair (its float32 relaxation, its lazy checks), the waypoints in the dtype query_batch returns."""
+        if self.lazy:
+            res = self.query_batch(torch.as_tensor(start).reshape(1, -1), torch.as_tensor(goal).reshape(1, -1), k=k)
+            n = int(res.count[0])
+            return (res.path[0, :n], float(res.length[0])) if n > 0 else None
         from scipy.sparse import coo_matrix, vstack, hstack, csr_matrix
         from scipy.sparse.csgraph import dijkstra
         nodes, mask = self.nodes, self.wrap_mask

@@ -913,6 +913,70 @@ int dcx_sssp_extract_paths(int device, const dcx_graph* graph, const float* node
                            const dcx_sssp_links* goal_links, const float* direct_len, float* path, int32_t* count, float* length,
                            int32_t W, void* stream);
 
+/* ---- lazy roadmap queries (added under DCX_VERSION 109) --------------------------------------------------- */
+/* A roadmap whose edges are checked only when a shortest route uses them (lazy PRM): the relaxation above runs over ALL
+ * candidate edges, dcx_sssp_mark_routes lists the still unchecked edges of the routes it found, ready for the motion checks, and
+ * dcx_graph_apply_checks writes the verdicts back into the graph: a blocked edge's weight becomes +inf, which the relaxation
+ * takes as "no edge" (an inf candidate never wins).  The caller repeats relax (from round 0: distances only grow when edges go,
+ * so an earlier state is no valid start) - mark - check - apply until a mark pass lists nothing.  On `device`, without a model.
+ * Edges (dcx_lazy_graph; caller-owned device memory) beside the CSR of a dcx_graph, M undirected edges with ids 0 .. M - 1:
+ *   eid   [nnz] int32      CSR entry -> edge id
+ *   ent   [M, 2] int32     edge id -> its two CSR entries (row ends[m, 0] and row ends[m, 1])
+ *   ends  [M, 2] int32     edge id -> its two nodes
+ *   state [M] uint8        0 unknown, 1 free, 2 blocked; any other value is read as "not unknown"
+ *   The calls do NOT check that the three index arrays agree with the CSR or with each other.  Memory safety alone is kept: an
+ *   index outside its range (an edge id outside 0 .. M - 1, an entry outside 0 .. nnz - 1, a node outside 0 .. N - 1) is skipped.
+ * dcx_sssp_mark_routes; graph, nodes [N, dof], state, rounds_done, Q, k, mode and goal_links exactly as dcx_sssp_extract_paths
+ * reads them (the graph's weight is not read).  For every query q:
+ *   mode[q] != 2: pending[q] = 0.
+ *   mode[q] == 2: the goal slot is dcx_sssp_extract_paths' (the first slot, in slot order, with the least dist + len, one rounded
+ *     fp32 add); pred is walked back from that node to -1, at most N steps.  No real slot, a sum that is not below +inf, a walk
+ *     that does not end by then or leaves 0 .. N - 1: no route, pending[q] = 0 and nothing is marked.  Otherwise, for every hop
+ *     (v, u = pred[v][q]) of the walk, e = the first entry of row v (the row's range clipped to 0 .. nnz) whose col is u and
+ *     m = eid[e]; where state[m] == 0 the edge is marked and counted in pending[q].  A hop without such an entry, or with m
+ *     outside 0 .. M - 1, is skipped.  The links (start and goal) are no edges of the graph and are never marked.
+ *   total = the number of marked edges (an edge on several routes counts once), n = min(total, capacity);
+ *   n_out[0] = total, n_out[1] = n;  list[0 .. n - 1] = the n smallest marked edge ids in ascending order;
+ *   qa[i] = nodes[ends[list[i], 0]] and qb[i] = nodes[ends[list[i], 1]] (the bits copied; an end that is no node leaves its row
+ *   as it is).  Entries i >= n of list, qa and qb are left as they are; capacity = 0 (list, qa, qb may then be NULL) counts alone.
+ *   pending [Q] int32, list [capacity] int32, qa / qb [capacity, dof] float, n_out [2] int32: device memory, written whatever
+ *   they held.  Neither state nor the graph is written.
+ *   work: dcx_sssp_mark_routes_work_bytes(M) bytes of device memory, 16-byte aligned, the caller's; initialised by the call
+ *   itself (one mark byte per edge, zeroed first, and one offset per 16 edges).
+ *   Launches: four (the marks zeroed; a wave per query making plain same-value stores into the marks; an ordered scan in one
+ *   workgroup; a scatter).  No allocation, no synchronisation, no atomic, nothing read back: the call can be captured, and the
+ *   same inputs give the same bits whatever the order the waves arrive in.
+ * dcx_graph_apply_checks; list and n_out as dcx_sssp_mark_routes left them, hit [at least n_out[1]] uint8 the checker's
+ * verdicts (non-zero = the motion collides).  n_out[1] is read on the device (values outside 0 .. M are clipped), so the host
+ * needs no second read-back.  For i < n_out[1], m = list[i]:
+ *   state[m] = hit[i] ? 2 : 1;  where hit[i]: weight[ent[m, 0]] = weight[ent[m, 1]] = +inf
+ *   any_blocked [1] int32: the call zeroes it, then 1 is stored (a plain store) by whoever saw a hit.
+ *   THE GRAPH'S weight IS WRITTEN, though dcx_graph declares it const: it must be memory the caller may change.  Nothing else of
+ *   the graph is read.  Launches: two (the flag zeroed; a thread per listed edge, striding).  Capturable as above.
+ * Argument errors (DCX_ERR_INVALID, before any device work): NULL graph / lazy / state / goal_links; a negative Q, N, nnz, M or
+ *   capacity; k outside 1 .. DCX_KNN_MAX_K; dof outside 1 .. 64; rounds_done < 1; a reserved field not 0; with Q > 0 and M > 0
+ *   (dcx_sssp_mark_routes) a NULL rowptr, col (nnz > 0), dist, pred (N > 0), nodes (N > 0), eid (nnz > 0), ent, ends, lazy
+ *   state, mode, link array, pending or n_out, a NULL list, qa or qb with capacity > 0, a NULL or misaligned work or work_bytes
+ *   below dcx_sssp_mark_routes_work_bytes(M); with M > 0 (dcx_graph_apply_checks) a NULL weight (nnz > 0), ent, lazy state,
+ *   list, n_out, hit or any_blocked.  N, nnz, M or N * Q beyond int32 indexing and a grid beyond one launch are
+ *   DCX_ERR_UNSUPPORTED.  Q == 0 or M == 0 returns 0 and touches nothing (no edge can be marked: the caller's total is 0).
+ *   dcx_sssp_mark_routes_work_bytes is 0 for M outside 1 .. INT32_MAX and non-decreasing in M.                              */
+typedef struct dcx_lazy_graph {
+    const int32_t* eid;      /* [nnz]                                                                       */
+    const int32_t* ent;      /* [M, 2]                                                                      */
+    const int32_t* ends;     /* [M, 2]                                                                      */
+    uint8_t*       state;    /* [M]: 0 unknown, 1 free, 2 blocked                                           */
+    int64_t  M;
+    int64_t  reserved[2];    /* 0                                                                           */
+} dcx_lazy_graph;
+size_t dcx_sssp_mark_routes_work_bytes(int64_t M);
+int dcx_sssp_mark_routes(int device, const dcx_graph* graph, const dcx_lazy_graph* lazy, const float* nodes, int32_t dof,
+                         const dcx_sssp_state* state, int32_t rounds_done, int64_t Q, int32_t k, const int32_t* mode,
+                         const dcx_sssp_links* goal_links, int32_t* pending, int32_t* list, float* qa, float* qb, int64_t capacity,
+                         int32_t* n_out, void* work, size_t work_bytes, void* stream);
+int dcx_graph_apply_checks(int device, const dcx_graph* graph, const dcx_lazy_graph* lazy, const int32_t* list,
+                           const int32_t* n_out, const uint8_t* hit, int32_t* any_blocked, void* stream);
+
 /* ---- batched path resampling (added under DCX_VERSION 109) ------------------------------------------------ */
 /* R piecewise-straight paths of uneven length resampled to T waypoints each, equally spaced in arc length under the motion
  * calls' metric: what joins the planners' paths (dcx_rrt_extract_paths, dcx_sssp_extract_paths, dcx_path_shortcut_run) to the
