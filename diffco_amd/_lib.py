@@ -91,6 +91,11 @@ SYMBOLS = {
     "dcx_rrt_work_bytes": (C.c_size_t, [C.c_void_p, C.c_int64, C.c_int32]),
     "dcx_rrt_connect_run": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, _c_fp, C.c_int32, C.c_int64, C.c_void_p, _c_fp, C.c_void_p,
                                       C.c_size_t, C.c_void_p]),
+    # batched RRT*: one tree per problem, parent choice and rewiring over a near set, and the paths to the goal nodes as one tensor
+    "dcx_rrtstar_work_bytes": (C.c_size_t, [C.c_void_p, C.c_int64, C.c_int32, C.c_int32]),
+    "dcx_rrtstar_run": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, _c_fp, _c_fp, C.c_int32, C.c_int64, C.c_void_p, _c_fp, C.c_void_p,
+                                  C.c_size_t, C.c_void_p]),
+    "dcx_rrtstar_extract_paths": (C.c_int, [C.c_int, C.c_void_p, C.c_int64, C.c_int32, C.c_int32, _c_fp, C.c_int32, _c_fp, C.c_void_p]),
     # batched path shortcutting over the motion checks, and the solved paths of an RRT state as one tensor
     "dcx_path_shortcut_work_bytes": (C.c_size_t, [C.c_void_p, C.c_int64, C.c_int32]),
     "dcx_path_shortcut_run": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, _c_fp, C.c_int32, C.c_void_p, _c_fp, C.c_void_p,
@@ -174,6 +179,22 @@ class RrtOpts(C.Structure):
     """ctypes mirror of dcx_rrt_opts (include/dcx.h)"""
     _fields_ = [("range", C.c_float), ("max_step", C.c_float), ("max_samples", C.c_int32), ("slots", C.c_int32), ("cap", C.c_int32),
                 ("reserved0", C.c_int32), ("wrap_mask", C.c_uint64), ("reserved", C.c_int64 * 2)]
+
+
+RRTSTAR_MAX_NEAR = 16     # DCX_RRTSTAR_MAX_NEAR
+RRTSTAR_MAX_CAP = 1 << 16  # DCX_RRTSTAR_MAX_CAP
+RRTSTAR_STATE = ("nodes", "parent", "elen", "cost", "count", "status", "goal_node", "first_round")
+
+
+class RrtStarState(C.Structure):
+    """ctypes mirror of dcx_rrtstar_state (include/dcx.h)"""
+    _fields_ = [(n, C.c_void_p) for n in RRTSTAR_STATE]
+
+
+class RrtStarOpts(C.Structure):
+    """ctypes mirror of dcx_rrtstar_opts (include/dcx.h)"""
+    _fields_ = [("range", C.c_float), ("max_step", C.c_float), ("radius", C.c_float), ("max_samples", C.c_int32), ("slots", C.c_int32),
+                ("near", C.c_int32), ("cap", C.c_int32), ("reserved0", C.c_int32), ("wrap_mask", C.c_uint64), ("reserved", C.c_int64 * 2)]
 
 
 SHORTCUT_MAX_SLOTS = 16           # DCX_SHORTCUT_MAX_SLOTS

@@ -349,6 +349,46 @@ def rrt_extract_paths(state, W, out=None):
     return path, count
 
 
+_RRTSTAR_KINDS = dict(nodes=torch.float32, parent=torch.int32, elen=torch.float32, cost=torch.float32, count=torch.int32,
+                      status=torch.int32, goal_node=torch.int32, first_round=torch.int32)
+
+
+def _rrtstar_state(label, state, dev):
+    """(dcx_rrtstar_state, R, cap, dof) of `state`: the eight tensors, contiguous on `dev`"""
+    nodes = state["nodes"]
+    if not isinstance(nodes, torch.Tensor) or nodes.dim() != 3 or nodes.device.type != "cuda":
+        raise ValueError(f"{label}: state['nodes'] must be a [R, cap, dof] tensor on a GPU")
+    dev = nodes.device if dev is None else dev
+    R, cap, dof = (int(v) for v in nodes.shape)
+    shapes = dict(nodes=(R, cap, dof), parent=(R, cap), elen=(R, cap), cost=(R, cap), count=(R,), status=(R,), goal_node=(R,),
+                  first_round=(R,))
+    for name, dt in _RRTSTAR_KINDS.items():
+        _check_tensor(f"{label}: state[{name!r}]", state[name], dt, shapes[name], dev)
+    return _lib.RrtStarState(*(state[n].data_ptr() for n in _lib.RRTSTAR_STATE)), R, cap, dof
+
+
+def rrtstar_extract_paths(state, W, out=None):
+    """the paths to the goal nodes of an RRT* state (dcx_rrtstar_extract_paths; `state` maps dcx_rrtstar_state's fields to
+    contiguous tensors on one GPU): (path [R, W, dof] float32, count [R] int32) there.  count[r] = n where problem r's n
+    waypoints fit and were written (root first), -n where n > W (the row is left as it is: zeros), 0 for a problem without a goal
+    node.  W = 0 asks for the sizes alone.  `out`: the [R, W, dof] tensor to write into.  One launch on torch's current stream,
+    nothing read back."""
+    lib = _lib.require_gpu()
+    st, R, cap, dof = _rrtstar_state("rrtstar_extract_paths", state, None)
+    dev = state["nodes"].device
+    W = int(W)
+    if W < 0:
+        raise ValueError("rrtstar_extract_paths: W must be >= 0")
+    if out is None:
+        path = torch.zeros((R, W, dof), device=dev, dtype=torch.float32)
+    else:
+        path = _check_tensor("rrtstar_extract_paths: out", out, torch.float32, (R, W, dof), dev, kind=f"float32 tensor {(R, W, dof)}")
+    count = torch.zeros(R, device=dev, dtype=torch.int32)
+    with _on_device(dev):
+        _lib.check(lib.dcx_rrtstar_extract_paths(dev.index, C.byref(st), R, cap, dof, _ptr(path), W, _ptr(count), _stream(dev)))
+    return path, count
+
+
 def path_resample(path, count, T, mask=0, out=None):
     """R paths resampled to T waypoints each, equally spaced in arc length (dcx_path_resample; path [R, W, dof] float32 and count
     [R] int32, contiguous on one GPU; mask: the wrap bitmask): (out [R, T, dof] float32, out_count [R] int32, length [R] float32)
@@ -803,6 +843,30 @@ class ScoreModel:
         with _on_device(self.dev):
             _lib.check(self._lib.dcx_rrt_connect_run(self._h, C.byref(st), R, _ptr(samples), T, int(round0), C.byref(opt), _ptr(mg),
                                                      _ptr(work), nbytes, self._st()))
+
+    def rrtstar_run(self, state, goals, samples, round0, range, max_step, radius, near, max_samples, margin=0., wrap=None):
+        """T rounds of batched RRT* (dcx_rrtstar_run) on the caller's state, in place: `state` maps dcx_rrtstar_state's fields
+        (nodes [R, cap, dof], elen and cost [R, cap] float32; parent [R, cap], count, status, goal_node, first_round [R] int32)
+        to contiguous tensors on the model's device; goals [R, dof] and samples [T, R, P, dof] float32 there.  `near`: K, the
+        near set's size (0: plain RRT with costs); `radius`: its radius.  Rounds round0 .. round0 + T - 1 are enqueued on
+        torch's current stream; nothing is read back (capturable).  `margin` as check_motions."""
+        if samples.dim() != 4:
+            raise ValueError("rrtstar_run: samples must be [T, R, P, dof]")
+        T, R, P = (int(v) for v in samples.shape[:3])
+        st, R0, cap, _ = _rrtstar_state("rrtstar_run", state, self.dev)
+        if R0 != R or int(state["nodes"].shape[2]) != self.dof:
+            raise ValueError(f"rrtstar_run: state['nodes'] must be [{R}, cap, {self.dof}]")
+        _check_tensor("rrtstar_run: samples", samples, torch.float32, (T, R, P, self.dof), self.dev,
+                      kind=f"float32 tensor [T, R, P, {self.dof}]")
+        _check_tensor("rrtstar_run: goals", goals, torch.float32, (R, self.dof), self.dev)
+        opt = _lib.RrtStarOpts(float(range), float(max_step), float(radius), int(max_samples), P, int(near), cap, 0,
+                               wrap_mask(wrap, self.dof), (C.c_int64 * 2)(0, 0))
+        mg = self._motion_margin(margin)
+        nbytes = self._lib.dcx_rrtstar_work_bytes(self._h, R, P, int(near))
+        work = self._work(nbytes)
+        with _on_device(self.dev):
+            _lib.check(self._lib.dcx_rrtstar_run(self._h, C.byref(st), R, _ptr(goals), _ptr(samples), T, int(round0), C.byref(opt),
+                                                 _ptr(mg), _ptr(work), nbytes, self._st()))
 
     def shortcut_run(self, state, draws, max_step, max_samples, margin=0., wrap=None, partial=False):
         """T rounds of batched path shortcutting (dcx_path_shortcut_run; partial=True: dcx_path_shortcut_partial_run, chords

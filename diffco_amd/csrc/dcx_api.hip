@@ -21,6 +21,7 @@
 #include "traj_dense.h"
 #include "knn_kernel.h"
 #include "rrt_kernel.h"
+#include "rrtstar_kernel.h"
 #include "shortcut_kernel.h"
 #include "shortcut_partial_kernel.h"
 #include "resample_kernel.h"
@@ -2638,6 +2639,7 @@ int dcx_rrt_connect_run(const dcx_model* m, const dcx_rrt_state* state, int64_t 
     a.P = opt->slots;
     a.cap = opt->cap;
     a.dof = m->fk.dof;
+    a.trees = 2;
     a.range = opt->range;
     a.wrap_mask = opt->wrap_mask;
     for (int32_t t = 0; t < T; ++t) {
@@ -2652,6 +2654,155 @@ int dcx_rrt_connect_run(const dcx_model* m, const dcx_rrt_state* state, int64_t 
             if (e != hipSuccess) return fail_hip(e, "rrt commit launch");
         }
     }
+    return DCX_OK;
+}
+
+// ---- batched RRT* (rrtstar_kernel.h): the size query and the call share the checks and rrtstar_plan ---------------------------
+namespace {
+constexpr PlannerCheck kRrtStarCheck{"rrtstar", DCX_RRT_MAX_SLOTS, "DCX_RRT_MAX_SLOTS", "phase"};
+// K and the place batches' size beside PlannerCheck::sizes (which has checked R * slots)
+int rrtstar_sizes(const dcx_model* m, int64_t R, int32_t slots, int32_t near) {
+    if (int rc = kRrtStarCheck.sizes(m, R, slots)) return rc;
+    if (near < 0 || near > DCX_RRTSTAR_MAX_NEAR) return fail(DCX_ERR_INVALID, "rrtstar: near must be in [0, DCX_RRTSTAR_MAX_NEAR]");
+    if (near > 1 && R * slots > INT32_MAX / near) return fail(DCX_ERR_UNSUPPORTED, "rrtstar: more than 2^31 - 1 edges per phase");
+    return DCX_OK;
+}
+}  // namespace
+
+size_t dcx_rrtstar_work_bytes(const dcx_model* m, int64_t R, int32_t slots, int32_t near) {
+    if (rrtstar_sizes(m, R, slots, near)) return 0;
+    return rrtstar_plan(R, slots, near, m->fk.dof, motion_work(R * slots * std::max(near, 1)).total).total;
+}
+
+int dcx_rrtstar_run(const dcx_model* m, const dcx_rrtstar_state* state, int64_t R, const float* goals, const float* samples, int32_t T,
+                    int64_t round0, const dcx_rrtstar_opts* opt, const float* margin, void* work, size_t work_bytes, void* stream) {
+    // every argument is checked before anything touches the model's device
+    if (!opt) return fail(DCX_ERR_INVALID, "rrtstar: options are NULL");
+    if (T < 0) return fail(DCX_ERR_INVALID, "rrtstar: T < 0");
+    if (int rc = rrtstar_sizes(m, R, opt->slots, opt->near)) return rc;
+    if (round0 < 0 || round0 > INT32_MAX - (int64_t)T) return fail(DCX_ERR_INVALID, "rrtstar: round0 < 0 or round0 + T above 2^31 - 1");
+    if (!(opt->range > 0.f)) return fail(DCX_ERR_INVALID, "rrtstar: range must be > 0");
+    if (!(opt->radius >= 0.f)) return fail(DCX_ERR_INVALID, "rrtstar: radius must be >= 0");
+    if (int rc = kRrtStarCheck.sampling(opt->max_step, opt->max_samples)) return rc;
+    if (opt->cap < 1 || opt->cap > DCX_RRTSTAR_MAX_CAP) return fail(DCX_ERR_INVALID, "rrtstar: cap must be in [1, DCX_RRTSTAR_MAX_CAP]");
+    if (opt->reserved0 || opt->reserved[0] || opt->reserved[1]) return fail(DCX_ERR_INVALID, "rrtstar: reserved fields must be 0");
+    if (int rc = MotionCheck{kRrtStarCheck.what}.mask(m, opt->wrap_mask)) return rc;
+    const bool state_ok = state && state->nodes && state->parent && state->elen && state->cost && state->count && state->status &&
+                          state->goal_node && state->first_round && goals;
+    if (int rc = kRrtStarCheck.buffers(R, T, state_ok, samples, "samples", work)) return rc;
+    const int32_t P = opt->slots, K = opt->near;
+    const int64_t E = R * P, EK = E * K;
+    // the extend batch and the place batches: both motion workspaces start at the head, the smaller one a prefix of the larger
+    const PlannerEdges ed{m, E, motion_work(E), {0, opt->max_step, opt->max_samples, 0}, margin, work, opt->wrap_mask, stream};
+    const PlannerEdges pl{m, EK, motion_work(EK), {0, opt->max_step, opt->max_samples, 0}, margin, work, opt->wrap_mask, stream};
+    const RrtStarPlan plan = rrtstar_plan(R, P, K, m->fk.dof, motion_work(E * std::max(K, 1)).total);
+    if (int rc = kRrtStarCheck.workspace(R, work_bytes, plan.total, "dcx_rrtstar_work_bytes")) return rc;
+    if (R == 0 || T == 0) return DCX_OK;
+    if (int rc = kRrtStarCheck.launchable(m, E * std::max(K, 1), opt->max_samples)) return rc;
+    if (int rc = set_device(m->device)) return rc;
+    hipStream_t st = (hipStream_t)stream;
+    char* base = (char*)work;
+    RrtArgs n{};   // the nearest + steer launch of RRT-Connect's phase 1 on the one tree
+    n.nodes = state->nodes;
+    n.count = state->count;
+    n.status = state->status;
+    n.qa = (float*)(base + plan.qa);
+    n.qb = (float*)(base + plan.qb);
+    n.near = (int32_t*)(base + plan.near);
+    n.R = (int32_t)R;
+    n.P = P;
+    n.cap = opt->cap;
+    n.dof = m->fk.dof;
+    n.trees = 1;
+    n.phase = 1;
+    n.tree = 0;
+    n.range = opt->range;
+    n.wrap_mask = opt->wrap_mask;
+    RrtStarArgs a{};
+    a.nodes = state->nodes;
+    a.parent = state->parent;
+    a.elen = state->elen;
+    a.cost = state->cost;
+    a.count = state->count;
+    a.status = state->status;
+    a.goal_node = state->goal_node;
+    a.first_round = state->first_round;
+    a.goals = goals;
+    a.qa = n.qa;
+    a.qb = n.qb;
+    a.near = n.near;
+    a.first_hit = (int32_t*)(base + plan.first_hit);
+    a.added = (int32_t*)(base + plan.added);
+    a.rewired = (int32_t*)(base + plan.rewired);
+    a.near_idx = (int32_t*)(base + plan.near_idx);
+    a.near_d2 = (float*)(base + plan.near_d2);
+    a.pqa = (float*)(base + plan.pqa);
+    a.pqb = (float*)(base + plan.pqb);
+    a.place_hit = (int32_t*)(base + plan.place_hit);
+    a.submitted = (int32_t*)(base + plan.submitted);
+    a.place_cost = (float*)(base + plan.place_cost);
+    a.place_len = (float*)(base + plan.place_len);
+    a.R = (int32_t)R;
+    a.P = P;
+    a.K = K;
+    a.cap = opt->cap;
+    a.dof = m->fk.dof;
+    a.max_d2 = opt->radius * opt->radius;
+    a.wrap_mask = opt->wrap_mask;
+    for (int32_t t = 0; t < T; ++t) {
+        a.round = n.round = (int32_t)(round0 + t);
+        n.samples = samples + (int64_t)t * E * a.dof;
+        hipError_t e = launch_rrt_nearest(n, st);
+        if (e != hipSuccess) return fail_hip(e, "rrtstar nearest launch");
+        if (int rc = ed.check(a.qa, a.qb, a.first_hit)) return rc;
+        if (K > 0) {
+            e = launch_rrtstar_near(a, st);
+            if (e != hipSuccess) return fail_hip(e, "rrtstar near launch");
+            e = launch_rrtstar_choose_prepare(a, st);
+            if (e != hipSuccess) return fail_hip(e, "rrtstar choose launch");
+            if (int rc = pl.check(a.pqa, a.pqb, a.place_hit)) return rc;
+        }
+        e = launch_rrtstar_commit(a, st);
+        if (e != hipSuccess) return fail_hip(e, "rrtstar commit launch");
+        if (K > 0) {
+            e = launch_rrtstar_rewire_prepare(a, st);
+            if (e != hipSuccess) return fail_hip(e, "rrtstar rewire launch");
+            if (int rc = pl.check(a.pqa, a.pqb, a.place_hit)) return rc;
+            e = launch_rrtstar_rewire_select(a, st);
+            if (e != hipSuccess) return fail_hip(e, "rrtstar select launch");
+        }
+        e = launch_rrtstar_refresh(a, st);   // (leaves at once where the round rewired nothing: always, with K = 0)
+        if (e != hipSuccess) return fail_hip(e, "rrtstar refresh launch");
+    }
+    return DCX_OK;
+}
+
+int dcx_rrtstar_extract_paths(int device, const dcx_rrtstar_state* state, int64_t R, int32_t cap, int32_t dof, float* path, int32_t W,
+                              int32_t* count_out, void* stream) {
+    if (R < 0) return fail(DCX_ERR_INVALID, "rrtstar extract: R < 0");
+    if (cap < 1 || cap > DCX_RRTSTAR_MAX_CAP) return fail(DCX_ERR_INVALID, "rrtstar extract: cap must be in [1, DCX_RRTSTAR_MAX_CAP]");
+    if (dof < 1) return fail(DCX_ERR_INVALID, "rrtstar extract: dof < 1");
+    if (W < 0) return fail(DCX_ERR_INVALID, "rrtstar extract: W < 0");
+    if (R > 0 && (!state || !state->nodes || !state->parent || !state->count || !state->goal_node))
+        return fail(DCX_ERR_INVALID, "rrtstar extract: state or one of its nodes, parent, count and goal_node pointers is NULL");
+    if (R > 0 && !count_out) return fail(DCX_ERR_INVALID, "rrtstar extract: count_out is NULL");
+    if (R > 0 && W > 0 && !path) return fail(DCX_ERR_INVALID, "rrtstar extract: path is NULL with W > 0");
+    if (R > INT32_MAX) return fail(DCX_ERR_UNSUPPORTED, "rrtstar extract: more than 2^31 - 1 problems");
+    if (R == 0) return DCX_OK;
+    if (int rc = set_device(device)) return rc;
+    RrtStarExtractArgs a{};
+    a.nodes = state->nodes;
+    a.parent = state->parent;
+    a.count = state->count;
+    a.goal_node = state->goal_node;
+    a.path = path;
+    a.count_out = count_out;
+    a.R = (int32_t)R;
+    a.cap = cap;
+    a.dof = dof;
+    a.W = W;
+    const hipError_t e = launch_rrtstar_extract(a, (hipStream_t)stream);
+    if (e != hipSuccess) return fail_hip(e, "rrtstar extract launch");
     return DCX_OK;
 }
 

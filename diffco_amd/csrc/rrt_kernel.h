@@ -46,10 +46,10 @@ inline RrtPlan rrt_plan(int64_t R, int32_t P, int32_t dof, size_t motion_bytes) 
 }
 
 struct RrtArgs {
-    // the caller's state (dcx_rrt_state)
-    float* nodes;             // [R, 2, cap, dof]
+    // the caller's state (dcx_rrt_state; RRT* searches and steers with trees = 1: nodes [R, cap, dof], count [R], phase 1 alone)
+    float* nodes;             // [R, trees, cap, dof]
     int32_t* parent;          // [R, 2, cap]
-    int32_t* count;           // [R, 2]
+    int32_t* count;           // [R, trees]
     int32_t* status;          // [R]
     int32_t* link;            // [R, 2]
     int32_t* solved_round;    // [R]
@@ -63,6 +63,7 @@ struct RrtArgs {
     int32_t* full;
     const float* frac;        // [E]: the motion prep's step fractions of the batch just checked (commit of phase 2)
     int32_t R, P, cap, dof;
+    int32_t trees;            // 2: RRT-Connect's pair;  1: RRT*'s one tree (rrtstar_kernel.h), nearest + steer only
     int32_t phase;            // 1: extend tree a towards the samples;  2: connect tree b to phase 1's new nodes
     int32_t tree;             // a = g & 1
     int32_t round;            // g

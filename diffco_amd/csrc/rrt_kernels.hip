@@ -76,11 +76,11 @@ __global__ __launch_bounds__(kRrtWaves * 64) void rrt_nearest_steer_kernel(const
     const int64_t r = blockIdx.x;
     const int P = a.P, dof = DOF > 0 ? DOF : a.dof, cap = a.cap;
     const int searched = a.phase == 1 ? a.tree : 1 - a.tree;
-    const float* const tree0 = a.nodes + r * 2 * (int64_t)cap * dof;            // the problem's tree 0; its node 0 is the start
+    const float* const tree0 = a.nodes + r * a.trees * (int64_t)cap * dof;      // the problem's tree 0; its node 0 is the start
     const float* const pts = tree0 + (int64_t)searched * cap * dof;
     const float* const grown = tree0 + (int64_t)a.tree * cap * dof;             // tree a: phase 1's new nodes live here
     const bool running = a.status[r] == 0;
-    const int n = running ? min(a.count[r * 2 + searched], cap) : 0;   // (a count beyond cap is the caller's error: never read past the tree)
+    const int n = running ? min(a.count[r * a.trees + searched], cap) : 0;   // (a count beyond cap is the caller's error: never read past the tree)
     const uint64_t mask = a.wrap_mask;
 
     // which slots search (block-uniform), and their queries

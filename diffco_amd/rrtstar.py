@@ -1,0 +1,347 @@
+"""Batched RRT* over a collision checker: R planning problems, one tree each, grown in lockstep with P extensions per problem
+and round; every new node picks the cheapest free parent among its K nearest within a radius and then rewires those of them it
+reaches more cheaply.  Only path length under the motion calls' metric is optimised.
+
+`rrt_star` runs the fused planner (dcx_rrtstar_run: the tree logic in HIP, the three edge batches of a round through the fused
+motion sweep, one status / goal read-back per chunk of rounds) where the checker's own `check_motions` would take the fused
+route, and `host_rrt_star` everywhere else.  `host_rrt_star` is the same contract (include/dcx.h, "batched RRT*") composed of the
+calls a user has without it - `roadmap.knn`, torch arithmetic one rounded operation at a time, the checker's
+`check_motions(..., return_first=True)` on the same fixed batches of R * P, R * P * K and R * P * K edges: the referee of the
+fused planner (equal state, bit for bit, for equal samples) and the baseline it is measured against.  It runs on CPU tensors
+with any checker that has such a `check_motions`.
+
+In lockstep RRT* the set of nodes does not depend on the parents: near = 0 (plain RRT with costs) grows the same nodes from the
+same samples, and no node's cost with near > 0 is above its cost with near = 0.
+"""
+import torch
+
+from . import _ops
+from .roadmap import knn
+from .rrt import (BLOCKED, FULL, RUNNING, _Edges, _FusedEdges, _Plan, _fused_model, _length, _nearest, _steer)
+
+__all__ = ["rrt_star", "host_rrt_star", "RRTStarResult", "RUNNING", "DIRECT", "FULL", "BLOCKED"]
+
+DIRECT = 1   # dcx_rrtstar_state's status 1: the direct motion start -> goal is free (RUNNING, FULL, BLOCKED: as rrt.py's)
+_STATE = ("nodes", "parent", "elen", "cost", "count", "status", "goal_node", "first_round")
+_NO_KEY = torch.iinfo(torch.int64).max
+
+
+class RRTStarResult:
+    """paths: per problem a [W, dof] tensor (start first, goal last) or None without a goal node;  costs [R]: the goal nodes'
+    cost-to-come (nan without one);  first_round [R]: the round that first reached the goal (-1: none, or a free direct motion);
+    status [R] (0 still running at max_rounds, 1 the direct motion is free, 2 full, 3 an endpoint collides);  rounds: the rounds
+    that were run;  route: "fused" or "host";  nodes, parent, elen, cost, count, goal_node: the raw state tensors."""
+
+    def __init__(self, route, state, paths, costs, rounds):
+        self.route, self.paths, self.costs, self.rounds = route, paths, costs, rounds
+        for name in _STATE:
+            setattr(self, name, state[name])
+
+    def state(self):
+        return {name: getattr(self, name) for name in _STATE}
+
+    def path_tensor(self, W=None):
+        """(path [R, W, dof] float32, count [R] int32) on the state's device: the rows of `paths` as one tensor, what
+        shortcut.shortcut_paths takes.  count[r] is the path's waypoints, 0 without a goal node, and -n where its n waypoints do
+        not fit into W (that row is left as it is: zeros).  A state on the GPU goes through dcx_rrtstar_extract_paths (one
+        launch, the parents never leave the device); W=None asks for the sizes first and reads their maximum back once.  A
+        state on the CPU is walked on the host."""
+        if self.nodes.device.type == "cuda":
+            st = self.state()
+            if W is None:
+                sizes = _ops.rrtstar_extract_paths(st, 0)[1]
+                W = int((-sizes).max()) if len(sizes) else 0
+            return _ops.rrtstar_extract_paths(st, W)
+        R, dof = len(self.status), self.nodes.shape[2]
+        rows = _walk_all(self.nodes, self.parent, self.goal_node)
+        if W is None:
+            W = max([0] + [len(p) for p in rows if p is not None])
+        path = torch.zeros((R, int(W), dof), dtype=torch.float32)
+        count = torch.zeros(R, dtype=torch.int32)
+        for r, p in enumerate(rows):
+            if p is not None:
+                count[r] = len(p) if len(p) <= W else -len(p)
+                if len(p) <= W:
+                    path[r, :len(p)] = p
+        return path, count
+
+
+def _walk_all(nodes, parent, goal_node):
+    """per problem the rows root .. goal node walked from `parent` on the host, None without a goal node"""
+    parent, goal = parent.cpu(), goal_node.tolist()
+    rows = []
+    for r, i in enumerate(goal):
+        walk = []
+        while i >= 0:
+            walk.append(i)
+            i = int(parent[r, i])
+        rows.append(nodes[r][torch.tensor(walk[::-1], dtype=torch.int64, device=nodes.device)] if walk else None)
+    return rows
+
+
+def _bits(x):
+    """a float32 tensor's bit patterns as non-negative int64: they order like the values of floats that are not negative"""
+    return x.contiguous().view(torch.int32).to(torch.int64) & 0xFFFFFFFF
+
+
+def _sqrt32(x):
+    return torch.sqrt(x.to(torch.float64)).to(torch.float32)   # correctly rounded (rrt._length has the argument)
+
+
+class _StarPlan(_Plan):
+    def __init__(self, checker, starts, goals, dev, reach, max_step, radius, near, wrap, slots, cap, max_rounds, rounds_per_call, sampler,
+                 goal_bias, limits, seed, max_samples):
+        own = sampler is None
+        super().__init__(checker, starts, goals, dev, reach, max_step, wrap, slots, cap, max_rounds, rounds_per_call,
+                         (lambda T, R, P: None) if own else sampler, limits, seed, max_samples)
+        self.K = int(near)
+        if not 0 <= self.K <= 16:
+            raise ValueError(f"rrt_star: near must be in [0, 16], got {near}")
+        if not 2 <= self.cap <= 65536:
+            raise ValueError(f"rrt_star: cap must be in [2, 65536], got {cap}")
+        self.radius = self.range if radius is None else float(radius)
+        if not self.radius >= 0:
+            raise ValueError("rrt_star: radius must be >= 0")
+        if own:
+            if self.limits is None:
+                raise ValueError("rrt_star: pass `limits` [dof, 2] or a `sampler`: the checker's robot has no joint limits")
+            gen = torch.Generator(device=dev)
+            gen.manual_seed(int(seed))
+            lo, span, bias = self.limits[:, 0], self.limits[:, 1] - self.limits[:, 0], float(goal_bias)
+
+            def default(T, R, P):   # one pair of draws per round: the stream of samples does not depend on rounds_per_call
+                out = []
+                for _ in range(T):
+                    u = lo + span * torch.rand((R, P, self.dof), generator=gen, device=dev)
+                    pick = torch.rand((R, P), generator=gen, device=dev) < bias
+                    out.append(torch.where(pick[..., None], self.goals[:, None, :], u))
+                return torch.stack(out) if T else torch.zeros((0, R, P, self.dof), device=dev)
+            self.sampler = default
+
+    def initial_state(self, edges):
+        """the roots, and the initial checks as ONE batch of 3 R edges: the zero-length edges on the starts and on the goals
+        (the point checks under the planner's own margin) and the direct motions start -> goal.  A free direct motion is the
+        optimum: node 1 is the goal"""
+        R, cap, dof, dev = self.R, self.cap, self.dof, self.dev
+        st = dict(nodes=torch.zeros((R, cap, dof), dtype=torch.float32, device=dev),
+                  parent=torch.full((R, cap), -1, dtype=torch.int32, device=dev),
+                  elen=torch.zeros((R, cap), dtype=torch.float32, device=dev),
+                  cost=torch.zeros((R, cap), dtype=torch.float32, device=dev),
+                  count=torch.ones(R, dtype=torch.int32, device=dev),
+                  status=torch.zeros(R, dtype=torch.int32, device=dev),
+                  goal_node=torch.full((R,), -1, dtype=torch.int32, device=dev),
+                  first_round=torch.full((R,), -1, dtype=torch.int32, device=dev))
+        st["nodes"][:, 0] = self.starts
+        if R:
+            qa, qb = torch.cat([self.starts, self.goals, self.starts]), torch.cat([self.starts, self.goals, self.goals])
+            first = edges.first_hit(qa, qb, self.starts[:1].expand(3 * R, dof))[0]
+            blocked = (first[:R] != -1) | (first[R:2 * R] != -1)
+            direct = (first[2 * R:] == -1) & ~blocked
+            L = _length(_ops.wrapped_delta(self.starts, self.goals, self.mask))
+            st["status"][blocked] = BLOCKED
+            st["status"][direct] = DIRECT
+            st["nodes"][direct, 1] = self.goals[direct]
+            st["parent"][direct, 1] = 0
+            st["elen"][direct, 1] = L[direct]
+            st["cost"][direct, 1] = L[direct]
+            st["count"][direct] = 2
+            st["goal_node"][direct] = 1
+        return st
+
+    def run(self, st, run_chunk, stop_on_first):
+        """chunks of rounds until no problem is running or max_rounds (stop_on_first: or every running problem has a goal node);
+        one status / goal_node read-back per chunk.  The rounds run."""
+        g = 0
+        while g < self.max_rounds:
+            status, goal = torch.stack([st["status"], st["goal_node"]]).cpu()
+            running = status == RUNNING
+            if not bool(running.any()) or (stop_on_first and bool((goal[running] >= 0).all())):
+                break
+            T = min(self.chunk, self.max_rounds - g)
+            samples = torch.as_tensor(self.sampler(T, self.R, self.P)).to(device=self.dev, dtype=torch.float32).contiguous()
+            if tuple(samples.shape) != (T, self.R, self.P, self.dof):
+                raise ValueError(f"rrt_star: the sampler returned {tuple(samples.shape)}, expected {(T, self.R, self.P, self.dof)}")
+            run_chunk(samples, g)
+            g += T
+        return g
+
+    def star_result(self, route, st, rounds_run):
+        paths = _walk_all(st["nodes"], st["parent"], st["goal_node"])
+        goal = st["goal_node"].to(torch.int64)
+        costs = st["cost"].gather(1, goal.clamp(min=0)[:, None])[:, 0] if self.R else st["cost"][:, 0]
+        costs = torch.where(goal >= 0, costs, torch.full_like(costs, float("nan")))
+        return RRTStarResult(route, st, paths, costs, rounds_run)
+
+
+def _host_round(pl, edges, st, s, g, trace=None):
+    """one round of the contract on the state tensors, in place (s [R, P, dof]: the round's samples).  `trace`: a dict that
+    takes what the round did (the events the tests count)."""
+    R, P, K, dof, cap, mask, dev = pl.R, pl.P, pl.K, pl.dof, pl.cap, pl.mask, pl.dev
+    r_all = torch.arange(R, device=dev)
+    r1, r2 = r_all[:, None], r_all[:, None, None]
+    running = st["status"] == RUNNING
+    counts = st["count"].tolist()   # the snapshot's
+    nodes, cost = st["nodes"], st["cost"]
+    root = nodes[:, 0][:, None, :].expand(R, P, dof)
+
+    def check(go, qa, qb, rt):
+        qa, qb = torch.where(go[..., None], qa, rt), torch.where(go[..., None], qb, rt)
+        return edges.first_hit(qa.reshape(-1, dof), qb.reshape(-1, dof), rt.reshape(-1, dof))[0].reshape(go.shape)
+
+    # 1. extend: RRT-Connect's phase 1 on the one tree
+    near = _nearest({"nodes": nodes[:, None]}, 0, s, running[:, None].expand(R, P), [[c] for c in counts], mask)
+    nc = near.clamp(min=0)
+    nq = nodes[r1, nc]
+    x, ok = _steer(nq, s, pl.range, mask)
+    go = (near >= 0) & ok
+    cand = go & (check(go, nq, x, root) == -1)
+    L0 = _length(_ops.wrapped_delta(nq, x, mask))
+    c0 = cost[r1, nc] + L0
+    par, elen, cnew = near.clone(), L0, c0
+
+    if K > 0:
+        # 2. the near sets over the snapshot
+        u = torch.full((R, P, K), -1, dtype=torch.int64, device=dev)
+        d2 = torch.full((R, P, K), float("inf"), dtype=torch.float32, device=dev)
+        for r in torch.nonzero(cand.any(dim=1)).reshape(-1).tolist():
+            idx, dist2 = knn(x[r], nodes[r, :counts[r]], K, wrap=mask, max_dist=pl.radius)
+            u[r], d2[r] = idx.to(torch.int64), dist2
+        u = torch.where(cand[..., None], u, torch.full_like(u, -1))
+        uc = u.clamp(min=0)
+        un = nodes[r2, uc]
+        rootk = root[:, :, None, :].expand(R, P, K, dof)
+        xk = x[:, :, None, :].expand(R, P, K, dof)
+        # 3. choose parent
+        Lj = _length(_ops.wrapped_delta(un, xk, mask))
+        cj = cost[r2, uc] + Lj
+        keyj = (_bits(cj) << 32) | uc
+        key0 = (_bits(c0) << 32) | nc
+        submit = (u >= 0) & (keyj < key0[..., None])
+        free = submit & (check(submit, un, xk, rootk) == -1)
+        keyj = torch.where(free, keyj, torch.full_like(keyj, _NO_KEY))
+        jb = keyj.argmin(dim=2, keepdim=True)
+        has = free.any(dim=2)
+        par = torch.where(has, uc.gather(2, jb)[..., 0], near)
+        elen = torch.where(has, Lj.gather(2, jb)[..., 0], L0)
+        cnew = torch.where(has, cj.gather(2, jb)[..., 0], c0)
+
+    # 4. append in slot order while count < cap
+    n0 = st["count"].to(torch.int64)
+    a64 = cand.to(torch.int64)
+    at = n0[:, None] + torch.cumsum(a64, dim=1) - a64
+    fits = cand & (at < cap)
+    rr = r1.expand_as(at)[fits]
+    st["nodes"][rr, at[fits]] = x[fits]
+    st["parent"][rr, at[fits]] = par[fits].to(torch.int32)
+    st["elen"][rr, at[fits]] = elen[fits]
+    st["cost"][rr, at[fits]] = cnew[fits]
+    total = n0 + a64.sum(dim=1)
+    st["count"][:] = total.clamp(max=cap).to(torch.int32)
+    over = total > cap
+    added = torch.where(fits, at, torch.full_like(at, -1))
+    is_goal = fits & (x.contiguous().view(torch.int32) == pl.goals.contiguous().view(torch.int32)[:, None, :]).all(dim=2)
+    found = is_goal.any(dim=1) & (st["goal_node"] == -1)
+    p0 = is_goal.to(torch.int64).argmax(dim=1)   # the lowest slot
+    st["goal_node"][found] = added[r_all, p0][found].to(torch.int32)
+    st["first_round"][found] = g
+    st["status"][running & over] = FULL
+    if trace is not None:
+        trace.update(chose_other=int((fits & (par != near)).sum()), dropped=int((cand & ~fits).sum()), rewires=0, contested=0,
+                     lowered_descendants=0, short_near=int((cand & (u[..., K - 1] < 0)).sum()) if K > 0 else 0)
+    if K == 0:
+        return
+
+    # 5. rewire: the new nodes against the snapshot's cost of their near nodes
+    ac = added.clamp(min=0)
+    Lp = _sqrt32(d2)
+    cp = cost[r1, ac][..., None] + Lp
+    submit = (added >= 0)[..., None] & (u >= 0) & (u != par[..., None]) & (cp < cost[r2, uc])
+    free = (submit & (check(submit, xk, un, rootk) == -1)).reshape(R, P * K)
+    v = uc.reshape(R, P * K)
+    key = ((_bits(cp) << 32) | torch.arange(P, device=dev)[None, :, None]).reshape(R, P * K)
+    rival = free[:, :, None] & free[:, None, :] & (v[:, :, None] == v[:, None, :]) & (key[:, None, :] < key[:, :, None])
+    win = free & ~rival.any(dim=2)
+    rw = r1.expand_as(v)[win]
+    st["parent"][rw, v[win]] = ac[:, :, None].expand(R, P, K).reshape(R, P * K)[win].to(torch.int32)
+    st["elen"][rw, v[win]] = Lp.reshape(R, P * K)[win]
+
+    # 6. refresh: the fixed point of cost = cost[parent] + elen from the roots' +0, where something was rewired
+    rows = torch.nonzero(win.any(dim=1)).reshape(-1)
+    before = st["cost"].clone() if trace is not None else None
+    if len(rows):
+        pr = st["parent"][rows].to(torch.int64)
+        live = (pr >= 0) & (torch.arange(cap, device=dev)[None, :] < st["count"][rows].to(torch.int64)[:, None])
+        while True:
+            cur = st["cost"][rows]
+            new = torch.where(live, cur.gather(1, pr.clamp(min=0)) + st["elen"][rows], cur)
+            if torch.equal(_bits(new), _bits(cur)):
+                break
+            st["cost"][rows] = new
+    if trace is not None:
+        target = torch.zeros((R, cap), dtype=torch.bool, device=dev)
+        target[rw, v[win]] = True
+        trace.update(rewires=int(win.sum()), contested=int((win & (free[:, None, :] & (v[:, :, None] == v[:, None, :])).sum(dim=2).gt(1)).sum()),
+                     lowered_descendants=int(((st["cost"] < before) & ~target).sum()))
+        assert not bool((st["cost"] > before).any())
+
+
+def host_rrt_star(checker, starts, goals, *, range, max_step, radius=None, near=8, wrap=None, slots=4, cap=4096, max_rounds=256,
+                  rounds_per_call=32, sampler=None, goal_bias=0.1, limits=None, seed=0, margin=0., max_samples=None,
+                  stop_on_first=False, _trace=None):
+    """rrt_star's contract as the loop a user would write from the library's other calls: per round one `knn` per running
+    problem for the nearest nodes and one for the near sets, the steering, costs and selections in torch, ONE
+    `checker.check_motions(..., return_first=True)` call per phase on the fixed batches of R * slots, R * slots * near and
+    R * slots * near edges, the appends and rewires as indexed assignments.  The state lives on the device of `starts`.
+    `margin` is passed on to the checker's check_motions only where it is not 0."""
+    dev = torch.as_tensor(starts).device
+    pl = _StarPlan(checker, starts, goals, dev, range, max_step, radius, near, wrap, slots, cap, max_rounds, rounds_per_call, sampler,
+                   goal_bias, limits, seed, max_samples)
+    edges = _Edges(checker, pl.max_step, pl.max_samples, pl.mask, margin)
+    st = pl.initial_state(edges)
+
+    def run_chunk(samples, g0):
+        for t, s in enumerate(samples):
+            ev = None if _trace is None else {"round": g0 + t}
+            _host_round(pl, edges, st, s, g0 + t, ev)
+            if _trace is not None:
+                ev["state"] = {k: v.clone() for k, v in st.items()}
+                _trace.append(ev)
+
+    return pl.star_result("host", st, pl.run(st, run_chunk, stop_on_first))
+
+
+def rrt_star(checker, starts, goals, *, range, max_step, radius=None, near=8, wrap=None, slots=4, cap=4096, max_rounds=256,
+             rounds_per_call=32, sampler=None, goal_bias=0.1, limits=None, seed=0, margin=0., max_samples=None, stop_on_first=False):
+    """Plan R motions starts[r] -> goals[r] ([R, dof] each) with batched RRT* under `checker`: an RRTStarResult.  Anytime: a
+    problem keeps improving its tree until max_rounds (stop_on_first: the loop ends at the first chunk after which every
+    running problem has reached its goal).
+    range: the longest extension; max_step: the stride of every edge check; radius: the near set's radius (None: range); near:
+    K, the most near nodes a new node looks at (0 .. 16; 0: plain RRT with costs); wrap (as check_motions): the circular
+    coordinates; slots: extensions per problem and round (1 .. 16); cap: nodes per tree (2 .. 65536); sampler(T, R, P) ->
+    [T, R, P, dof] (default: uniform in `limits` [dof, 2], taken from the checker's robot where it has them, and with probability
+    `goal_bias` the goal row itself, both drawn from one generator seeded by `seed`); margin: a sample collides where
+    score - margin > 0, on top of the checker's own threshold; max_samples: the most samples of one edge.
+    The fused planner (result.route == "fused") runs for kernel_perceptrons.DiffCo, RBFDiffCo and ForwardKinematicsDiffCo whose
+    transform fuses; every other checker is planned by host_rrt_star ("host")."""
+    dev0 = torch.as_tensor(starts).device
+    got = _fused_model(checker, dev0 if dev0.type == "cuda" else None)
+    if got is None:
+        return host_rrt_star(checker, starts, goals, range=range, max_step=max_step, radius=radius, near=near, wrap=wrap, slots=slots,
+                             cap=cap, max_rounds=max_rounds, rounds_per_call=rounds_per_call, sampler=sampler, goal_bias=goal_bias,
+                             limits=limits, seed=seed, margin=margin, max_samples=max_samples, stop_on_first=stop_on_first)
+    model, base = got
+    if isinstance(base, (int, float)) and isinstance(margin, (int, float)):
+        mg = float(base) + float(margin)
+    else:   # one per class on either side
+        mg = (torch.as_tensor(base, dtype=torch.float32).reshape(-1).to(model.dev)
+              + torch.as_tensor(margin, dtype=torch.float32).reshape(-1).to(model.dev))
+    pl = _StarPlan(checker, starts, goals, model.dev, range, max_step, radius, near, wrap, slots, cap, max_rounds, rounds_per_call,
+                   sampler, goal_bias, limits, seed, max_samples)
+    st = pl.initial_state(_FusedEdges(model, pl.max_step, pl.max_samples, pl.mask, mg))
+    mg_dev = model._motion_margin(mg)   # on the device once: no copy from the host per chunk
+
+    def run_chunk(samples, g0):
+        model.rrtstar_run(st, pl.goals, samples, g0, pl.range, pl.max_step, pl.radius, pl.K, pl.max_samples,
+                          margin=0. if mg_dev is None else mg_dev, wrap=pl.mask)
+
+    return pl.star_result("fused", st, pl.run(st, run_chunk, stop_on_first))

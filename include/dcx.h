@@ -726,6 +726,111 @@ size_t dcx_rrt_work_bytes(const dcx_model* m, int64_t R, int32_t slots);
 int dcx_rrt_connect_run(const dcx_model* m, const dcx_rrt_state* state, int64_t R, const float* samples, int32_t T, int64_t round0,
                         const dcx_rrt_opts* opts, const float* margin, void* work, size_t work_bytes, void* stream);
 
+/* ---- batched RRT* (added under DCX_VERSION 109) ----------------------------------------------------------- */
+/* R independent planning problems, one tree each, grown in lockstep with P = opts->slots extensions per problem and round: the
+ * asymptotically optimal tree planner over dcx_knn's metric and dcx_check_motions_ex's verdicts (the reference's
+ * misc/rrt_star.py grows one tree, links each new node and rewires every node within a fixed radius whose cost-to-come improves
+ * over a free line_collision motion).  Only path length under the motion calls' metric is optimised.  All tree logic runs on the
+ * device, the edge checks are dcx_check_motions_ex's own launches, and nothing is read back between rounds.
+ * State (dcx_rrtstar_state; caller-owned device memory, R problems, cap = opts->cap):
+ *   nodes [R, cap, dof] float       node 0 is the start
+ *   parent [R, cap] int32           the root's is -1
+ *   elen [R, cap] float             the length of the edge parent -> node; the root's is 0
+ *   cost [R, cap] float             the cost-to-come: cost[i] = cost[parent[i]] + elen[i] (one rounded fp32 sum); the root's is +0
+ *   count [R] int32                 the nodes in the tree (>= 1)
+ *   status [R] int32                0 running, 1 the direct motion start -> goal is free (set by the caller when it initialises
+ *                                   the state: node 1 is then the goal with parent 0, goal_node = 1, and that is the optimum),
+ *                                   2 full, 3 an endpoint collides (set by the caller, never by the kernels)
+ *   goal_node [R] int32             -1 until a node with the goal's bits is in the tree, then that node's index (the first one)
+ *   first_round [R] int32           the round that first reached the goal, else -1
+ * A problem's status is read at the start of the round and written only at its end; a problem that is not running (status != 0)
+ * is left as it is.  A running problem keeps running after it has found the goal: the planner is anytime.
+ * Round g = round0 + t, t = 0 .. T - 1, for a running problem r.  Every phase sees nodes, parent, cost and count as they stood
+ * at the start of the round (the snapshot).  Every arithmetic step is fp32 and rounded alone.  K = opts->near.
+ *   1. extend - slot p < P: dcx_rrt_connect_run's phase 1, steps 1 - 4, on the one tree: target s = samples[t, r, p, :], near =
+ *      the nearest node under dcx_knn's contract (query = s, k = 1), the steering to opts->range giving x, the edge near -> x
+ *      checked by dcx_check_motions_ex.  first_hit == -1 makes slot p a candidate with L0 = L(near -> x), the motion call's
+ *      own length bits: d_j = the motion calls' delta of the edge near -> x, l2 = l2 + d_j * d_j from +0 in coordinate order,
+ *      L = sqrtf(l2), correctly rounded.  Anything else (-2 included) leaves the slot idle for the rest of the round
+ *   2. near set (K > 0) - each candidate: the first K of dcx_knn's order for query = x over the snapshot's nodes with
+ *      max_dist2 = radius * radius (one rounded product): dist2_j and u_j, j < K; unfilled places are -1
+ *   3. choose parent - for each u_j: Lj = L(u_j -> x) formed as in 1 for that directed edge, cj = cost[u_j] + Lj.  The incumbent
+ *      is c0 = cost[near] + L0.  Place (r, p, j) submits the edge u_j -> x only where (bits(cj), u_j) < (bits(c0), near), in
+ *      lexicographic order of the two unsigned numbers; every other place is idle.  The parent of x is the submitted u_j with
+ *      first_hit == -1 and the least (bits(cj), u_j), with elen = Lj and cost = cj; without one it is near, with L0 and c0
+ *   4. append - the candidates are appended in ascending slot order while count < cap, with parent, elen and cost from 3; a
+ *      slot that does not fit is dropped and marks the problem full (status 2 at the end of the round).  With goal_node[r] == -1,
+ *      the appended node of the lowest slot whose dof words equal goals[r, :] bit for bit sets goal_node to its index and
+ *      first_round = g (the steering hands a sample within range through as given, so a goal-biased sampler puts the goal's own
+ *      bits into the tree).  Every other copy of the goal, of this round or a later one, is an ordinary node
+ *   5. rewire (K > 0) - for each appended x and each v = u_j >= 0 with v != parent(x): L' = sqrtf(dist2_j), correctly rounded:
+ *      the length of the directed edge x -> v, the bits dcx_knn documents;  c' = cost[x] + L'.  Place (r, p, j) submits the edge
+ *      x -> v only where c' < cost[v] on the snapshot's cost[v]; every other place is idle.  Of the submitted places with
+ *      first_hit == -1 for one v across the slots, the least (bits(c'), p) wins: parent[v] = x's index, elen[v] = L'.  The
+ *      selection is a compare-all in LDS, one block per problem
+ *   6. refresh - cost[i] = cost[parent[i]] + elen[i] for every node from the root's +0: the unique fixed point for the new
+ *      (parent, elen).  One block per problem repeats passes over its nodes until a pass changes nothing; skipped where the
+ *      round rewired nothing.  The parent graph stays a tree and no node's cost ever rises (DESIGN.md 3.4o has the argument)
+ * Fixed batch: the extend phase of every round submits exactly R * P edges in (r, p) order, the choose and the rewire phase
+ *   R * P * K edges each in (r, p, j) order.  Idle places submit the edge nodes[r, 0] -> nodes[r, 0] (one sample, its verdict
+ *   ignored), so the geometry of the motion sweeps never depends on the state: the call can be captured, and a referee that
+ *   submits the same batches to dcx_check_motions_ex gets the same verdicts.  K = 0 runs the extend, append and refresh phases
+ *   only: plain RRT with costs, on the same nodes as any K for equal samples - the set of nodes does not depend on the parents.
+ * dcx_rrtstar_run enqueues T rounds on the caller's stream.  No allocation, no synchronisation, no atomic decides any order,
+ *   nothing read back; repeated calls give the same bits, and T rounds in one call equal T calls of one round each.
+ *   goals [R, dof], samples [T, R, P, dof] device floats;  margin [C] device floats, NULL = 0.
+ * DCX_RRTSTAR_MAX_CAP: the refresh is ONE block of 1024 threads per problem that sweeps parent, elen and cost of the whole tree
+ *   once per pass, as many passes as the deepest rewired chain is long.  At 65536 nodes a pass is 64 nodes per thread over 768 KiB
+ *   of state, which an XCD's L2 still holds beside the other problems' trees; a larger tree would turn every pass of that single
+ *   block into a stream from HBM.  (The near search, a wave per slot, reads 1024 rows per lane at that size.)
+ * work: dcx_rrtstar_work_bytes(model, R, slots, near) bytes of device memory, the caller's (dcx_check_motions' workspace for
+ *   R * P * max(K, 1) edges, then the edge batches, their verdicts, the near lists and the candidates' costs); initialised by
+ *   the call itself.
+ * Argument errors (DCX_ERR_INVALID, before any device work): NULL model / opts; NULL state, state pointer, goals, samples (T > 0)
+ *   or work with R > 0; R < 0 or T < 0; round0 < 0 or round0 + T above 2^31 - 1; range or max_step <= 0 or NaN; radius negative
+ *   or NaN; max_samples < 1; slots outside 1 .. DCX_RRT_MAX_SLOTS; near outside 0 .. DCX_RRTSTAR_MAX_NEAR; cap outside
+ *   1 .. DCX_RRTSTAR_MAX_CAP; a wrap_mask bit at or above dof; a reserved field not 0; work_bytes below dcx_rrtstar_work_bytes.
+ *   R * slots * max(near, 1) above 2^31 - 1, R * slots * max(near, 1) * max_samples too large for one launch, dof above
+ *   DCX_MAX_DOF and a feature width without a motion kernel are DCX_ERR_UNSUPPORTED.  R = 0 or T = 0 launches nothing.
+ *   dcx_rrtstar_work_bytes is 0 for arguments the call refuses.                                                              */
+#define DCX_RRTSTAR_MAX_NEAR 16
+#define DCX_RRTSTAR_MAX_CAP 65536
+typedef struct dcx_rrtstar_state {
+    float*   nodes;         /* [R, cap, dof]                                                                */
+    int32_t* parent;        /* [R, cap]                                                                     */
+    float*   elen;          /* [R, cap]                                                                     */
+    float*   cost;          /* [R, cap]                                                                     */
+    int32_t* count;         /* [R]                                                                          */
+    int32_t* status;        /* [R]: 0 running, 1 the direct motion is free, 2 full, 3 an endpoint collides  */
+    int32_t* goal_node;     /* [R]                                                                          */
+    int32_t* first_round;   /* [R]                                                                          */
+} dcx_rrtstar_state;
+typedef struct dcx_rrtstar_opts {
+    float    range;        /* > 0: the longest extension                                                    */
+    float    max_step;     /* > 0: the sampling stride of every edge check                                  */
+    float    radius;       /* >= 0: the near set's radius                                                   */
+    int32_t  max_samples;  /* >= 1: an edge needing more samples is rejected; it sizes the sweep launches   */
+    int32_t  slots;        /* P, 1 .. DCX_RRT_MAX_SLOTS                                                     */
+    int32_t  near;         /* K, 0 .. DCX_RRTSTAR_MAX_NEAR; 0: no choose-parent, no rewiring                */
+    int32_t  cap;          /* nodes per tree, 1 .. DCX_RRTSTAR_MAX_CAP                                      */
+    int32_t  reserved0;    /* 0                                                                             */
+    uint64_t wrap_mask;    /* bit j: coordinate j is an angle, measured and walked along the shortest arc   */
+    int64_t  reserved[2];  /* 0                                                                             */
+} dcx_rrtstar_opts;
+size_t dcx_rrtstar_work_bytes(const dcx_model* m, int64_t R, int32_t slots, int32_t near);
+int dcx_rrtstar_run(const dcx_model* m, const dcx_rrtstar_state* state, int64_t R, const float* goals, const float* samples, int32_t T,
+                    int64_t round0, const dcx_rrtstar_opts* opts, const float* margin, void* work, size_t work_bytes, void* stream);
+/* The paths to the goal nodes of a dcx_rrtstar_state as rows of path [R, W, dof], one launch on `device`, without a model, with
+ * dcx_rrt_extract_paths' conventions: a wave per problem walks parent from goal_node[r], at most count[r] steps, and writes the
+ * n waypoints root first.  n <= W sets count_out[r] = n; n > W leaves the row untouched and sets count_out[r] = -n, so W = 0
+ * (path may then be NULL) is the size query.  goal_node[r] == -1: count_out[r] = 0.  A chain that leaves 0 .. count[r] - 1 or
+ * does not reach parent -1 within count[r] steps gives count_out[r] = 0, and nothing is read out of bounds.
+ * Argument errors (DCX_ERR_INVALID): R < 0; cap outside 1 .. DCX_RRTSTAR_MAX_CAP; dof < 1; W < 0; with R > 0 a NULL state,
+ *   nodes, parent, count, goal_node or count_out, or a NULL path with W > 0.  R above 2^31 - 1 is DCX_ERR_UNSUPPORTED.  R = 0
+ *   launches nothing.                                                                                                        */
+int dcx_rrtstar_extract_paths(int device, const dcx_rrtstar_state* state, int64_t R, int32_t cap, int32_t dof,
+                              float* path, int32_t W, int32_t* count_out, void* stream);
+
 /* ---- batched path shortcutting and RRT path extraction (added under DCX_VERSION 109) ---------------------- */
 /* R piecewise-straight paths simplified in lockstep, P = opts->slots shortcut attempts per path and round: try the straight
  * motion between two waypoints and cut out what lies between (the path simplifier a planner's user expects before the paths go
