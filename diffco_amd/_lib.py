@@ -96,6 +96,11 @@ SYMBOLS = {
     "dcx_rrtstar_run": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, _c_fp, _c_fp, C.c_int32, C.c_int64, C.c_void_p, _c_fp, C.c_void_p,
                                   C.c_size_t, C.c_void_p]),
     "dcx_rrtstar_extract_paths": (C.c_int, [C.c_int, C.c_void_p, C.c_int64, C.c_int32, C.c_int32, _c_fp, C.c_int32, _c_fp, C.c_void_p]),
+    # RRT*'s samples drawn on the device: one round's rows from the state as it stands, and the run that draws and plans
+    "dcx_rrtstar_sample": (C.c_int, [C.c_int, C.c_void_p, C.c_int64, _c_fp, C.c_void_p, C.c_int64, _c_fp, _c_fp, C.c_void_p]),
+    "dcx_rrtstar_sampled_work_bytes": (C.c_size_t, [C.c_void_p, C.c_int64, C.c_int32, C.c_int32]),
+    "dcx_rrtstar_run_sampled": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, _c_fp, C.c_void_p, C.c_int32, C.c_int64, C.c_void_p, _c_fp,
+                                          C.c_void_p, C.c_size_t, _c_fp, _c_fp, C.c_void_p]),
     # batched path shortcutting over the motion checks, and the solved paths of an RRT state as one tensor
     "dcx_path_shortcut_work_bytes": (C.c_size_t, [C.c_void_p, C.c_int64, C.c_int32]),
     "dcx_path_shortcut_run": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, _c_fp, C.c_int32, C.c_void_p, _c_fp, C.c_void_p,
@@ -195,6 +200,18 @@ class RrtStarOpts(C.Structure):
     """ctypes mirror of dcx_rrtstar_opts (include/dcx.h)"""
     _fields_ = [("range", C.c_float), ("max_step", C.c_float), ("radius", C.c_float), ("max_samples", C.c_int32), ("slots", C.c_int32),
                 ("near", C.c_int32), ("cap", C.c_int32), ("reserved0", C.c_int32), ("wrap_mask", C.c_uint64), ("reserved", C.c_int64 * 2)]
+
+
+RRTSTAR_MAX_TRIES = 16                    # DCX_RRTSTAR_MAX_TRIES
+RRTSTAR_SAMPLE_MODES = {"uniform": 0, "informed": 1}   # DCX_RRTSTAR_SAMPLE_UNIFORM, DCX_RRTSTAR_SAMPLE_INFORMED
+RRTSTAR_SAMPLE_MAX_PROBLEMS = 1 << 28     # DCX_RRTSTAR_SAMPLE_MAX_PROBLEMS
+
+
+class RrtStarSampleOpts(C.Structure):
+    """ctypes mirror of dcx_rrtstar_sample_opts (include/dcx.h)"""
+    _fields_ = [("limits", C.c_void_p), ("seed", C.c_uint64), ("goal_bias", C.c_float), ("uniform_mix", C.c_float), ("mode", C.c_int32),
+                ("tries", C.c_int32), ("slots", C.c_int32), ("cap", C.c_int32), ("dof", C.c_int32), ("reserved0", C.c_int32),
+                ("wrap_mask", C.c_uint64), ("reserved", C.c_int64 * 2)]
 
 
 SHORTCUT_MAX_SLOTS = 16           # DCX_SHORTCUT_MAX_SLOTS

@@ -389,6 +389,34 @@ def rrtstar_extract_paths(state, W, out=None):
     return path, count
 
 
+def _rrtstar_sample_opts(label, limits, dof, dev, seed, P, cap, mode, goal_bias, uniform_mix, tries, mask):
+    """dcx_rrtstar_sample_opts over `limits` ([dof, 2] float32, contiguous on `dev`)"""
+    _check_tensor(f"{label}: limits", limits, torch.float32, (dof, 2), dev)
+    if mode not in _lib.RRTSTAR_SAMPLE_MODES:
+        raise ValueError(f"{label}: mode must be one of {sorted(_lib.RRTSTAR_SAMPLE_MODES)}, got {mode!r}")
+    return _lib.RrtStarSampleOpts(limits.data_ptr(), int(seed) & 0xFFFFFFFFFFFFFFFF, float(goal_bias), float(uniform_mix),
+                                  _lib.RRTSTAR_SAMPLE_MODES[mode], int(tries), int(P), int(cap), int(dof), 0, mask, (C.c_int64 * 2)(0, 0))
+
+
+def rrtstar_sample(state, goals, limits, seed, g, P, mode="informed", goal_bias=0.1, uniform_mix=0., tries=8, wrap=None):
+    """round g's samples of an RRT* state drawn on the device (dcx_rrtstar_sample; `state` maps dcx_rrtstar_state's fields to
+    contiguous tensors on one GPU, goals [R, dof] and limits [dof, 2] float32 there): (samples [R, P, dof] float32, info [R, P]
+    int32) there.  info: -1 the problem is not running (its start row), 0 uniform in the limits, 1 the goal row, 2 + t informed
+    and accepted at try t, 2 + tries informed and fallen back to the uniform point.  `mode`: "uniform" or "informed".  One
+    launch on torch's current stream, nothing read back."""
+    lib = _lib.require_gpu()
+    st, R, cap, dof = _rrtstar_state("rrtstar_sample", state, None)
+    dev = state["nodes"].device
+    _check_tensor("rrtstar_sample: goals", goals, torch.float32, (R, dof), dev)
+    opt = _rrtstar_sample_opts("rrtstar_sample", limits, dof, dev, seed, P, cap, mode, goal_bias, uniform_mix, tries, wrap_mask(wrap, dof))
+    samples = torch.empty((R, int(P), dof), device=dev, dtype=torch.float32)
+    info = torch.empty((R, int(P)), device=dev, dtype=torch.int32)
+    with _on_device(dev):
+        _lib.check(lib.dcx_rrtstar_sample(dev.index, C.byref(st), R, _ptr(goals), C.byref(opt), int(g), _ptr(samples), _ptr(info),
+                                          _stream(dev)))
+    return samples, info
+
+
 def path_resample(path, count, T, mask=0, out=None):
     """R paths resampled to T waypoints each, equally spaced in arc length (dcx_path_resample; path [R, W, dof] float32 and count
     [R] int32, contiguous on one GPU; mask: the wrap bitmask): (out [R, T, dof] float32, out_count [R] int32, length [R] float32)
@@ -867,6 +895,37 @@ class ScoreModel:
         with _on_device(self.dev):
             _lib.check(self._lib.dcx_rrtstar_run(self._h, C.byref(st), R, _ptr(goals), _ptr(samples), T, int(round0), C.byref(opt),
                                                  _ptr(mg), _ptr(work), nbytes, self._st()))
+
+    def rrtstar_run_sampled(self, state, goals, limits, seed, T, slots, round0, range, max_step, radius, near, max_samples,
+                            mode="informed", goal_bias=0.1, uniform_mix=0., tries=8, margin=0., wrap=None, samples_out=None,
+                            info_out=None):
+        """T rounds of batched RRT* whose samples are drawn on the device at the start of each round (dcx_rrtstar_run_sampled:
+        per round rrtstar_sample's launch on the state as it stands, then rrtstar_run's round), in place on `state`; `state`,
+        goals, range .. max_samples, margin and wrap as rrtstar_run; limits [dof, 2] float32 on the model's device; seed, mode,
+        goal_bias, uniform_mix and tries as _ops.rrtstar_sample.  samples_out [T, R, slots, dof] float32 / info_out
+        [T, R, slots] int32: where the rounds' samples and info words are kept (None: nowhere).  Rounds round0 .. round0 + T - 1
+        are enqueued on torch's current stream; nothing is read back (capturable)."""
+        T, P = int(T), int(slots)
+        st, R, cap, _ = _rrtstar_state("rrtstar_run_sampled", state, self.dev)
+        if int(state["nodes"].shape[2]) != self.dof:
+            raise ValueError(f"rrtstar_run_sampled: state['nodes'] must be [R, cap, {self.dof}]")
+        _check_tensor("rrtstar_run_sampled: goals", goals, torch.float32, (R, self.dof), self.dev)
+        mask = wrap_mask(wrap, self.dof)
+        sopt = _rrtstar_sample_opts("rrtstar_run_sampled", limits, self.dof, self.dev, seed, P, cap, mode, goal_bias, uniform_mix, tries,
+                                    mask)
+        if samples_out is not None:
+            _check_tensor("rrtstar_run_sampled: samples_out", samples_out, torch.float32, (T, R, P, self.dof), self.dev)
+        if info_out is not None:
+            _check_tensor("rrtstar_run_sampled: info_out", info_out, torch.int32, (T, R, P), self.dev)
+        opt = _lib.RrtStarOpts(float(range), float(max_step), float(radius), int(max_samples), P, int(near), cap, 0, mask,
+                               (C.c_int64 * 2)(0, 0))
+        mg = self._motion_margin(margin)
+        nbytes = self._lib.dcx_rrtstar_sampled_work_bytes(self._h, R, P, int(near))
+        work = self._work(nbytes)
+        with _on_device(self.dev):
+            _lib.check(self._lib.dcx_rrtstar_run_sampled(self._h, C.byref(st), R, _ptr(goals), C.byref(sopt), T, int(round0),
+                                                         C.byref(opt), _ptr(mg), _ptr(work), nbytes, _ptr(samples_out),
+                                                         _ptr(info_out), self._st()))
 
     def shortcut_run(self, state, draws, max_step, max_samples, margin=0., wrap=None, partial=False):
         """T rounds of batched path shortcutting (dcx_path_shortcut_run; partial=True: dcx_path_shortcut_partial_run, chords

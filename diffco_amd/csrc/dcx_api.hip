@@ -2674,9 +2674,16 @@ size_t dcx_rrtstar_work_bytes(const dcx_model* m, int64_t R, int32_t slots, int3
     return rrtstar_plan(R, slots, near, m->fk.dof, motion_work(R * slots * std::max(near, 1)).total).total;
 }
 
-int dcx_rrtstar_run(const dcx_model* m, const dcx_rrtstar_state* state, int64_t R, const float* goals, const float* samples, int32_t T,
-                    int64_t round0, const dcx_rrtstar_opts* opt, const float* margin, void* work, size_t work_bytes, void* stream) {
-    // every argument is checked before anything touches the model's device
+size_t dcx_rrtstar_sampled_work_bytes(const dcx_model* m, int64_t R, int32_t slots, int32_t near) {
+    if (rrtstar_sizes(m, R, slots, near)) return 0;
+    return rrtstar_sampled_plan(R, slots, near, m->fk.dof, motion_work(R * slots * std::max(near, 1)).total).total;
+}
+
+namespace {
+// the argument checks dcx_rrtstar_run and dcx_rrtstar_run_sampled share, up to the buffers; `state_ok`: the state, every pointer
+// of it and the goals are there
+int rrtstar_run_checks(const dcx_model* m, const dcx_rrtstar_state* state, int64_t R, const float* goals, int32_t T, int64_t round0,
+                       const dcx_rrtstar_opts* opt, bool* state_ok) {
     if (!opt) return fail(DCX_ERR_INVALID, "rrtstar: options are NULL");
     if (T < 0) return fail(DCX_ERR_INVALID, "rrtstar: T < 0");
     if (int rc = rrtstar_sizes(m, R, opt->slots, opt->near)) return rc;
@@ -2687,71 +2694,76 @@ int dcx_rrtstar_run(const dcx_model* m, const dcx_rrtstar_state* state, int64_t 
     if (opt->cap < 1 || opt->cap > DCX_RRTSTAR_MAX_CAP) return fail(DCX_ERR_INVALID, "rrtstar: cap must be in [1, DCX_RRTSTAR_MAX_CAP]");
     if (opt->reserved0 || opt->reserved[0] || opt->reserved[1]) return fail(DCX_ERR_INVALID, "rrtstar: reserved fields must be 0");
     if (int rc = MotionCheck{kRrtStarCheck.what}.mask(m, opt->wrap_mask)) return rc;
-    const bool state_ok = state && state->nodes && state->parent && state->elen && state->cost && state->count && state->status &&
-                          state->goal_node && state->first_round && goals;
-    if (int rc = kRrtStarCheck.buffers(R, T, state_ok, samples, "samples", work)) return rc;
-    const int32_t P = opt->slots, K = opt->near;
-    const int64_t E = R * P, EK = E * K;
-    // the extend batch and the place batches: both motion workspaces start at the head, the smaller one a prefix of the larger
-    const PlannerEdges ed{m, E, motion_work(E), {0, opt->max_step, opt->max_samples, 0}, margin, work, opt->wrap_mask, stream};
-    const PlannerEdges pl{m, EK, motion_work(EK), {0, opt->max_step, opt->max_samples, 0}, margin, work, opt->wrap_mask, stream};
-    const RrtStarPlan plan = rrtstar_plan(R, P, K, m->fk.dof, motion_work(E * std::max(K, 1)).total);
-    if (int rc = kRrtStarCheck.workspace(R, work_bytes, plan.total, "dcx_rrtstar_work_bytes")) return rc;
-    if (R == 0 || T == 0) return DCX_OK;
-    if (int rc = kRrtStarCheck.launchable(m, E * std::max(K, 1), opt->max_samples)) return rc;
-    if (int rc = set_device(m->device)) return rc;
-    hipStream_t st = (hipStream_t)stream;
-    char* base = (char*)work;
-    RrtArgs n{};   // the nearest + steer launch of RRT-Connect's phase 1 on the one tree
-    n.nodes = state->nodes;
-    n.count = state->count;
-    n.status = state->status;
-    n.qa = (float*)(base + plan.qa);
-    n.qb = (float*)(base + plan.qb);
-    n.near = (int32_t*)(base + plan.near);
-    n.R = (int32_t)R;
-    n.P = P;
-    n.cap = opt->cap;
-    n.dof = m->fk.dof;
-    n.trees = 1;
-    n.phase = 1;
-    n.tree = 0;
-    n.range = opt->range;
-    n.wrap_mask = opt->wrap_mask;
-    RrtStarArgs a{};
-    a.nodes = state->nodes;
-    a.parent = state->parent;
-    a.elen = state->elen;
-    a.cost = state->cost;
-    a.count = state->count;
-    a.status = state->status;
-    a.goal_node = state->goal_node;
-    a.first_round = state->first_round;
-    a.goals = goals;
-    a.qa = n.qa;
-    a.qb = n.qb;
-    a.near = n.near;
-    a.first_hit = (int32_t*)(base + plan.first_hit);
-    a.added = (int32_t*)(base + plan.added);
-    a.rewired = (int32_t*)(base + plan.rewired);
-    a.near_idx = (int32_t*)(base + plan.near_idx);
-    a.near_d2 = (float*)(base + plan.near_d2);
-    a.pqa = (float*)(base + plan.pqa);
-    a.pqb = (float*)(base + plan.pqb);
-    a.place_hit = (int32_t*)(base + plan.place_hit);
-    a.submitted = (int32_t*)(base + plan.submitted);
-    a.place_cost = (float*)(base + plan.place_cost);
-    a.place_len = (float*)(base + plan.place_len);
-    a.R = (int32_t)R;
-    a.P = P;
-    a.K = K;
-    a.cap = opt->cap;
-    a.dof = m->fk.dof;
-    a.max_d2 = opt->radius * opt->radius;
-    a.wrap_mask = opt->wrap_mask;
-    for (int32_t t = 0; t < T; ++t) {
-        a.round = n.round = (int32_t)(round0 + t);
-        n.samples = samples + (int64_t)t * E * a.dof;
+    *state_ok = state && state->nodes && state->parent && state->elen && state->cost && state->count && state->status &&
+                state->goal_node && state->first_round && goals;
+    return DCX_OK;
+}
+
+// THE round of RRT*: the launches' arguments over a workspace laid out by rrtstar_plan, and one round on the caller's stream.
+// dcx_rrtstar_run feeds it the caller's samples, dcx_rrtstar_run_sampled the rows its sample launch has just written.
+struct RrtStarRound {
+    PlannerEdges ed, pl;   // the extend batch and the place batches: both motion workspaces start at the head, the smaller one a prefix of the larger
+    RrtArgs n;             // the nearest + steer launch of RRT-Connect's phase 1 on the one tree
+    RrtStarArgs a;
+    RrtStarRound(const dcx_model* m, const dcx_rrtstar_state* state, int64_t R, const float* goals, const dcx_rrtstar_opts* opt,
+                 const float* margin, void* work, const RrtStarPlan& plan, void* stream)
+        : ed{m, R * opt->slots, motion_work(R * opt->slots), {0, opt->max_step, opt->max_samples, 0}, margin, work, opt->wrap_mask, stream},
+          pl{m, R * opt->slots * opt->near, motion_work(R * opt->slots * opt->near), {0, opt->max_step, opt->max_samples, 0}, margin, work,
+             opt->wrap_mask, stream},
+          n{}, a{} {
+        char* base = (char*)work;
+        n.nodes = state->nodes;
+        n.count = state->count;
+        n.status = state->status;
+        n.qa = (float*)(base + plan.qa);
+        n.qb = (float*)(base + plan.qb);
+        n.near = (int32_t*)(base + plan.near);
+        n.R = (int32_t)R;
+        n.P = opt->slots;
+        n.cap = opt->cap;
+        n.dof = m->fk.dof;
+        n.trees = 1;
+        n.phase = 1;
+        n.tree = 0;
+        n.range = opt->range;
+        n.wrap_mask = opt->wrap_mask;
+        a.nodes = state->nodes;
+        a.parent = state->parent;
+        a.elen = state->elen;
+        a.cost = state->cost;
+        a.count = state->count;
+        a.status = state->status;
+        a.goal_node = state->goal_node;
+        a.first_round = state->first_round;
+        a.goals = goals;
+        a.qa = n.qa;
+        a.qb = n.qb;
+        a.near = n.near;
+        a.first_hit = (int32_t*)(base + plan.first_hit);
+        a.added = (int32_t*)(base + plan.added);
+        a.rewired = (int32_t*)(base + plan.rewired);
+        a.near_idx = (int32_t*)(base + plan.near_idx);
+        a.near_d2 = (float*)(base + plan.near_d2);
+        a.pqa = (float*)(base + plan.pqa);
+        a.pqb = (float*)(base + plan.pqb);
+        a.place_hit = (int32_t*)(base + plan.place_hit);
+        a.submitted = (int32_t*)(base + plan.submitted);
+        a.place_cost = (float*)(base + plan.place_cost);
+        a.place_len = (float*)(base + plan.place_len);
+        a.R = (int32_t)R;
+        a.P = opt->slots;
+        a.K = opt->near;
+        a.cap = opt->cap;
+        a.dof = m->fk.dof;
+        a.max_d2 = opt->radius * opt->radius;
+        a.wrap_mask = opt->wrap_mask;
+    }
+    // round g towards samples [R, P, dof]
+    int run(int32_t g, const float* samples) {
+        hipStream_t st = (hipStream_t)ed.stream;
+        const int K = a.K;
+        a.round = n.round = g;
+        n.samples = samples;
         hipError_t e = launch_rrt_nearest(n, st);
         if (e != hipSuccess) return fail_hip(e, "rrtstar nearest launch");
         if (int rc = ed.check(a.qa, a.qb, a.first_hit)) return rc;
@@ -2773,6 +2785,119 @@ int dcx_rrtstar_run(const dcx_model* m, const dcx_rrtstar_state* state, int64_t 
         }
         e = launch_rrtstar_refresh(a, st);   // (leaves at once where the round rewired nothing: always, with K = 0)
         if (e != hipSuccess) return fail_hip(e, "rrtstar refresh launch");
+        return DCX_OK;
+    }
+};
+
+// dcx_rrtstar_sample_opts' own value checks, `what` in front of every message (the sizes are each call's own)
+int rrtstar_sample_checks(const char* what, const dcx_rrtstar_sample_opts* so) {
+    const std::string w(what);
+    if (so->tries < 1 || so->tries > DCX_RRTSTAR_MAX_TRIES) return fail(DCX_ERR_INVALID, w + ": tries must be in [1, DCX_RRTSTAR_MAX_TRIES]");
+    if (!(so->goal_bias >= 0.f && so->goal_bias <= 1.f)) return fail(DCX_ERR_INVALID, w + ": goal_bias must be in [0, 1]");
+    if (!(so->uniform_mix >= 0.f && so->uniform_mix <= 1.f)) return fail(DCX_ERR_INVALID, w + ": uniform_mix must be in [0, 1]");
+    if (so->mode != DCX_RRTSTAR_SAMPLE_UNIFORM && so->mode != DCX_RRTSTAR_SAMPLE_INFORMED)
+        return fail(DCX_ERR_INVALID, w + ": mode must be DCX_RRTSTAR_SAMPLE_UNIFORM or DCX_RRTSTAR_SAMPLE_INFORMED");
+    if (so->reserved0 || so->reserved[0] || so->reserved[1]) return fail(DCX_ERR_INVALID, w + ": reserved fields of the sample options must be 0");
+    return DCX_OK;
+}
+
+RrtStarSampleArgs rrtstar_sample_args(const dcx_rrtstar_state* state, int64_t R, const float* goals, const dcx_rrtstar_sample_opts* so) {
+    RrtStarSampleArgs s{};
+    s.nodes = state->nodes;
+    s.cost = state->cost;
+    s.status = state->status;
+    s.goal_node = state->goal_node;
+    s.goals = goals;
+    s.limits = so->limits;
+    s.seed = so->seed;
+    s.wrap_mask = so->wrap_mask;
+    s.R = (int32_t)R;
+    s.P = so->slots;
+    s.cap = so->cap;
+    s.dof = so->dof;
+    s.mode = so->mode;
+    s.tries = so->tries;
+    s.goal_bias = so->goal_bias;
+    s.uniform_mix = so->uniform_mix;
+    return s;
+}
+}  // namespace
+
+int dcx_rrtstar_run(const dcx_model* m, const dcx_rrtstar_state* state, int64_t R, const float* goals, const float* samples, int32_t T,
+                    int64_t round0, const dcx_rrtstar_opts* opt, const float* margin, void* work, size_t work_bytes, void* stream) {
+    // every argument is checked before anything touches the model's device
+    bool state_ok = false;
+    if (int rc = rrtstar_run_checks(m, state, R, goals, T, round0, opt, &state_ok)) return rc;
+    if (int rc = kRrtStarCheck.buffers(R, T, state_ok, samples, "samples", work)) return rc;
+    const int32_t P = opt->slots, K = opt->near;
+    const int64_t E = R * P;
+    const RrtStarPlan plan = rrtstar_plan(R, P, K, m->fk.dof, motion_work(E * std::max(K, 1)).total);
+    if (int rc = kRrtStarCheck.workspace(R, work_bytes, plan.total, "dcx_rrtstar_work_bytes")) return rc;
+    if (R == 0 || T == 0) return DCX_OK;
+    if (int rc = kRrtStarCheck.launchable(m, E * std::max(K, 1), opt->max_samples)) return rc;
+    if (int rc = set_device(m->device)) return rc;
+    RrtStarRound round(m, state, R, goals, opt, margin, work, plan, stream);
+    for (int32_t t = 0; t < T; ++t)
+        if (int rc = round.run((int32_t)(round0 + t), samples + (int64_t)t * E * m->fk.dof)) return rc;
+    return DCX_OK;
+}
+
+int dcx_rrtstar_sample(int device, const dcx_rrtstar_state* state, int64_t R, const float* goals, const dcx_rrtstar_sample_opts* so,
+                       int64_t round, float* samples, int32_t* info, void* stream) {
+    const char* const what = "rrtstar sample";
+    if (!so) return fail(DCX_ERR_INVALID, "rrtstar sample: options are NULL");
+    if (R < 0) return fail(DCX_ERR_INVALID, "rrtstar sample: R < 0");
+    if (so->slots < 1 || so->slots > DCX_RRT_MAX_SLOTS) return fail(DCX_ERR_INVALID, "rrtstar sample: slots must be in [1, DCX_RRT_MAX_SLOTS]");
+    if (R > INT32_MAX / so->slots) return fail(DCX_ERR_UNSUPPORTED, "rrtstar sample: more than 2^31 - 1 slots");
+    if (R > DCX_RRTSTAR_SAMPLE_MAX_PROBLEMS) return fail(DCX_ERR_UNSUPPORTED, "rrtstar sample: more than DCX_RRTSTAR_SAMPLE_MAX_PROBLEMS problems");
+    if (round < 0 || round > INT32_MAX) return fail(DCX_ERR_INVALID, "rrtstar sample: round < 0 or above 2^31 - 1");
+    if (so->cap < 1 || so->cap > DCX_RRTSTAR_MAX_CAP) return fail(DCX_ERR_INVALID, "rrtstar sample: cap must be in [1, DCX_RRTSTAR_MAX_CAP]");
+    if (so->dof < 1 || so->dof > DCX_MAX_DOF) return fail(DCX_ERR_INVALID, "rrtstar sample: dof must be in [1, DCX_MAX_DOF]");
+    if (mask_beyond_dof(so->wrap_mask, so->dof)) return fail(DCX_ERR_INVALID, "rrtstar sample: wrap_mask has a bit at or above dof");
+    if (int rc = rrtstar_sample_checks(what, so)) return rc;
+    if (R > 0 && !(state && state->nodes && state->cost && state->status && state->goal_node && goals))
+        return fail(DCX_ERR_INVALID, "rrtstar sample: state, one of its nodes, cost, status and goal_node pointers, or goals is NULL");
+    if (R > 0 && !so->limits) return fail(DCX_ERR_INVALID, "rrtstar sample: limits is NULL");
+    if (R > 0 && !samples) return fail(DCX_ERR_INVALID, "rrtstar sample: samples is NULL");
+    if (R == 0) return DCX_OK;
+    if (int rc = set_device(device)) return rc;
+    RrtStarSampleArgs s = rrtstar_sample_args(state, R, goals, so);
+    s.round = (int32_t)round;
+    s.samples = samples;
+    s.info = info;
+    const hipError_t e = launch_rrtstar_sample(s, (hipStream_t)stream);
+    if (e != hipSuccess) return fail_hip(e, "rrtstar sample launch");
+    return DCX_OK;
+}
+
+int dcx_rrtstar_run_sampled(const dcx_model* m, const dcx_rrtstar_state* state, int64_t R, const float* goals,
+                            const dcx_rrtstar_sample_opts* so, int32_t T, int64_t round0, const dcx_rrtstar_opts* opt, const float* margin,
+                            void* work, size_t work_bytes, float* samples_out, int32_t* info_out, void* stream) {
+    // every argument is checked before anything touches the model's device
+    bool state_ok = false;
+    if (int rc = rrtstar_run_checks(m, state, R, goals, T, round0, opt, &state_ok)) return rc;
+    if (!so) return fail(DCX_ERR_INVALID, "rrtstar: sample options are NULL");
+    if (int rc = rrtstar_sample_checks(kRrtStarCheck.what, so)) return rc;
+    if (so->slots != opt->slots || so->cap != opt->cap || so->dof != m->fk.dof || so->wrap_mask != opt->wrap_mask)
+        return fail(DCX_ERR_INVALID, "rrtstar: slots, cap, dof or wrap_mask of the sample options differ from the options' or the model's");
+    if (R > DCX_RRTSTAR_SAMPLE_MAX_PROBLEMS) return fail(DCX_ERR_UNSUPPORTED, "rrtstar: more than DCX_RRTSTAR_SAMPLE_MAX_PROBLEMS problems");
+    if (int rc = kRrtStarCheck.buffers(R, 1, state_ok, so->limits, "limits", work)) return rc;
+    const int32_t P = opt->slots, K = opt->near, dof = m->fk.dof;
+    const int64_t E = R * P;
+    const RrtStarSampledPlan plan = rrtstar_sampled_plan(R, P, K, dof, motion_work(E * std::max(K, 1)).total);
+    if (int rc = kRrtStarCheck.workspace(R, work_bytes, plan.total, "dcx_rrtstar_sampled_work_bytes")) return rc;
+    if (R == 0 || T == 0) return DCX_OK;
+    if (int rc = kRrtStarCheck.launchable(m, E * std::max(K, 1), opt->max_samples)) return rc;
+    if (int rc = set_device(m->device)) return rc;
+    RrtStarRound round(m, state, R, goals, opt, margin, work, plan.run, stream);
+    RrtStarSampleArgs s = rrtstar_sample_args(state, R, goals, so);
+    for (int32_t t = 0; t < T; ++t) {
+        s.round = (int32_t)(round0 + t);
+        s.samples = samples_out ? samples_out + (int64_t)t * E * dof : (float*)((char*)work + plan.samples);
+        s.info = info_out ? info_out + (int64_t)t * E : nullptr;
+        const hipError_t e = launch_rrtstar_sample(s, (hipStream_t)stream);
+        if (e != hipSuccess) return fail_hip(e, "rrtstar sample launch");
+        if (int rc = round.run(s.round, s.samples)) return rc;
     }
     return DCX_OK;
 }

@@ -8,6 +8,7 @@
 //   rewire prepare -> dcx_check_motions_ex on the E * K edges x -> u_j -> rewire select (K > 0)
 //   refresh
 // Every batch has its fixed size; a place with nothing to check submits the zero-length edge on the problem's start node.
+// dcx_rrtstar_run_sampled puts the sample launch (rrtstar_sample_kernels.hip) in front of each round: the same round otherwise.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -20,6 +21,7 @@ namespace dcx {
 constexpr int kRrtStarMaxNear = DCX_RRTSTAR_MAX_NEAR;   // K: a lane of the near search keeps this many 64-bit keys in registers
 constexpr int kRrtStarPlaceThreads = 256;               // the per-place kernels' block; also the most places of one problem (16 * 16)
 constexpr int kRrtStarRefreshThreads = 1024;            // the refresh: one block per problem
+constexpr int kRrtStarSampleThreads = 256;              // the sample kernel's block: one thread per slot
 static_assert(kRrtMaxSlots * kRrtStarMaxNear <= kRrtStarPlaceThreads, "the rewire selection holds a problem's places in one block");
 
 // the workspace (work_layout.h): dcx_check_motions' for the larger batch first (motion_work's offsets; the smaller batch's layout
@@ -59,6 +61,23 @@ inline RrtStarPlan rrtstar_plan(int64_t R, int32_t P, int32_t K, int32_t dof, si
     w.submitted = c.take_n<int32_t>(EK);
     w.place_cost = c.take_n<float>(EK);
     w.place_len = c.take_n<float>(EK);
+    w.total = c.at;
+    return w;
+}
+
+// dcx_rrtstar_run_sampled's workspace: dcx_rrtstar_run's, then one round's sample rows (used where the caller keeps none)
+struct RrtStarSampledPlan {
+    RrtStarPlan run;
+    size_t samples;         // [E, dof] floats
+    size_t total;
+};
+
+inline RrtStarSampledPlan rrtstar_sampled_plan(int64_t R, int32_t P, int32_t K, int32_t dof, size_t motion_bytes) {
+    RrtStarSampledPlan w;
+    w.run = rrtstar_plan(R, P, K, dof, motion_bytes);
+    WorkCarve c;
+    c.take(w.run.total);
+    w.samples = c.take_n<float>((size_t)R * (size_t)P * dof);
     w.total = c.at;
     return w;
 }
@@ -105,6 +124,25 @@ struct RrtStarExtractArgs {
     int32_t R, cap, dof, W;
 };
 
+// one round's samples (rrtstar_sample_kernels.hip; include/dcx.h, "batched RRT*: samples drawn on the device")
+struct RrtStarSampleArgs {
+    const float* nodes;        // [R, cap, dof]: node 0 is the start
+    const float* cost;         // [R, cap]
+    const int32_t* status;     // [R]
+    const int32_t* goal_node;  // [R]
+    const float* goals;        // [R, dof]
+    const float* limits;       // [dof, 2]
+    float* samples;            // [R, P, dof]
+    int32_t* info;             // [R, P] or NULL
+    uint64_t seed;
+    uint64_t wrap_mask;
+    int32_t R, P, cap, dof;
+    int32_t round;             // g
+    int32_t mode, tries;
+    float goal_bias, uniform_mix;
+};
+
+hipError_t launch_rrtstar_sample(const RrtStarSampleArgs& a, hipStream_t stream);
 hipError_t launch_rrtstar_near(const RrtStarArgs& a, hipStream_t stream);
 hipError_t launch_rrtstar_choose_prepare(const RrtStarArgs& a, hipStream_t stream);
 hipError_t launch_rrtstar_commit(const RrtStarArgs& a, hipStream_t stream);

@@ -12,28 +12,41 @@ with any checker that has such a `check_motions`.
 
 In lockstep RRT* the set of nodes does not depend on the parents: near = 0 (plain RRT with costs) grows the same nodes from the
 same samples, and no node's cost with near > 0 is above its cost with near = 0.
+
+sampling="device" / "informed" draws each round's samples where the trees live (include/dcx.h, "batched RRT*: samples drawn on
+the device"; dcx_rrtstar_run_sampled), from the state as the round finds it: "informed" samples a problem that has reached its
+goal inside the ellipsoid of points that can still shorten its path.  `host_device_samples` restates that draw in torch on CPU
+tensors - the kernel's referee, and what host_rrt_star draws from in those modes.
 """
+import builtins
+import math
+
 import torch
 
 from . import _ops
 from .roadmap import knn
 from .rrt import (BLOCKED, FULL, RUNNING, _Edges, _FusedEdges, _Plan, _fused_model, _length, _nearest, _steer)
 
-__all__ = ["rrt_star", "host_rrt_star", "RRTStarResult", "RUNNING", "DIRECT", "FULL", "BLOCKED"]
+__all__ = ["rrt_star", "host_rrt_star", "host_device_samples", "philox4x32_10", "RRTStarResult", "RUNNING", "DIRECT", "FULL", "BLOCKED"]
 
 DIRECT = 1   # dcx_rrtstar_state's status 1: the direct motion start -> goal is free (RUNNING, FULL, BLOCKED: as rrt.py's)
 _STATE = ("nodes", "parent", "elen", "cost", "count", "status", "goal_node", "first_round")
 _NO_KEY = torch.iinfo(torch.int64).max
+_SAMPLING = {"host": None, "device": "uniform", "informed": "informed"}   # rrt_star's `sampling` -> the draw's mode
 
 
 class RRTStarResult:
     """paths: per problem a [W, dof] tensor (start first, goal last) or None without a goal node;  costs [R]: the goal nodes'
     cost-to-come (nan without one);  first_round [R]: the round that first reached the goal (-1: none, or a free direct motion);
     status [R] (0 still running at max_rounds, 1 the direct motion is free, 2 full, 3 an endpoint collides);  rounds: the rounds
-    that were run;  route: "fused" or "host";  nodes, parent, elen, cost, count, goal_node: the raw state tensors."""
+    that were run;  route: "fused" or "host";  nodes, parent, elen, cost, count, goal_node: the raw state tensors;  samples
+    [rounds, R, P, dof] and sample_info [rounds, R, P] (record_samples=True, else None): what every round was given, and for the
+    draws of sampling="device" / "informed" their info words (include/dcx.h: -1 not running, 0 uniform, 1 goal, 2 + t informed
+    at try t, 2 + tries fallen back)."""
 
-    def __init__(self, route, state, paths, costs, rounds):
+    def __init__(self, route, state, paths, costs, rounds, samples=None, sample_info=None):
         self.route, self.paths, self.costs, self.rounds = route, paths, costs, rounds
+        self.samples, self.sample_info = samples, sample_info
         for name in _STATE:
             setattr(self, name, state[name])
 
@@ -88,9 +101,123 @@ def _sqrt32(x):
     return torch.sqrt(x.to(torch.float64)).to(torch.float32)   # correctly rounded (rrt._length has the argument)
 
 
+_M32 = 0xFFFFFFFF
+
+
+def philox4x32_10(counter, key):
+    """Philox4x32-10 in int64 arithmetic: the four output words (int64 tensors holding 32-bit values) of `counter` (four
+    words) under `key` (two words); every word an int or an int64 tensor, broadcast together.  What csrc/philox_device.h
+    computes, word for word."""
+    c0, c1, c2, c3 = (torch.as_tensor(c, dtype=torch.int64) & _M32 for c in counter)
+    k0, k1 = (torch.as_tensor(k, dtype=torch.int64) & _M32 for k in key)
+
+    def mulhilo(m, b):   # the 64-bit product of two 32-bit words from 16-bit halves: nothing passes 2^63
+        ph, lo = m * (b >> 16), m * (b & 0xFFFF)
+        s = ((ph & 0xFFFF) << 16) + lo
+        return (ph >> 16) + (s >> 32), s & _M32
+
+    for _ in builtins.range(10):
+        hi0, lo0 = mulhilo(0xD2511F53, c0)
+        hi1, lo1 = mulhilo(0xCD9E8D57, c2)
+        c0, c1, c2, c3 = hi1 ^ c1 ^ k0, lo1, hi0 ^ c3 ^ k1, lo0
+        k0, k1 = (k0 + 0x9E3779B9) & _M32, (k1 + 0xBB67AE85) & _M32
+    return c0, c1, c2, c3
+
+
+def _u01(word):
+    return (word >> 8).to(torch.float32) * 2.0 ** -24   # exact
+
+
+def host_device_samples(state, goals, limits, seed, g, P, mode="informed", goal_bias=0.1, uniform_mix=0., tries=8, wrap=None):
+    """Round g's samples as dcx_rrtstar_sample draws them (include/dcx.h, "batched RRT*: samples drawn on the device"), in torch
+    ops on CPU tensors: (samples [R, P, dof] float32, info [R, P] int32, candidates [tries, R, P, dof] float64).  Philox in int64
+    arithmetic; the goal rows and the uniform points in float32, one rounded operation at a time: the kernel's bits.  The
+    informed draw in float64 from the same uniforms, the same float32 cost and c_min: every try's candidate is returned beside
+    the chosen sample (the first try whose float32 rounding lies inside the limits), so a checker can hold the kernel's float32
+    arithmetic to the candidate of the try the kernel names.  With circular coordinates (`wrap`) the ellipsoid is the one
+    around the shortest-arc image of the goal; every point of it meets the bound under the torus metric.
+    `state`: dcx_rrtstar_state's tensors, of which nodes, cost, status and goal_node are read; mode: "uniform" or "informed"."""
+    if mode not in ("uniform", "informed"):
+        raise ValueError(f"host_device_samples: mode must be 'uniform' or 'informed', got {mode!r}")
+    nodes, cost = state["nodes"].detach().cpu().to(torch.float32), state["cost"].detach().cpu().to(torch.float32)
+    status, gn = state["status"].cpu(), state["goal_node"].cpu().to(torch.int64)
+    R, cap, dof = nodes.shape
+    P, tries = int(P), int(tries)
+    goals = torch.as_tensor(goals).detach().cpu().to(torch.float32).reshape(R, dof)
+    lim = torch.as_tensor(limits).detach().cpu().to(torch.float32).reshape(dof, 2)
+    mask = _ops.wrap_mask(wrap, dof)
+    seed = int(seed) & 0xFFFFFFFFFFFFFFFF
+    slot = (torch.arange(R, dtype=torch.int64)[:, None] * 16 + torch.arange(P, dtype=torch.int64)[None, :]) & _M32
+
+    def block(t, b):
+        return philox4x32_10((int(g), slot, t, b), (seed & _M32, seed >> 32))
+
+    h0 = block(0, 0)
+    u_bias, u_mix = _u01(h0[0]), _u01(h0[1])
+    start = nodes[:, 0]
+    running, has = (status == 0)[:, None], ((gn >= 0) & (gn < cap))[:, None]
+    is_goal = running & (gn == -1)[:, None] & (u_bias < torch.tensor(float(goal_bias), dtype=torch.float32))
+    # step 2's point: one rounded product, one rounded sum
+    words = [block(0, 1 + b) for b in builtins.range((dof + 3) // 4)]
+    u = torch.stack([_u01(words[j // 4][j % 4]) for j in builtins.range(dof)], dim=-1)
+    lo, hi = lim[:, 0], lim[:, 1]
+    uniform = lo + (hi - lo) * u
+    # step 3 in float64
+    a32 = _ops.wrapped_delta(start, goals, mask)
+    cmin32 = _length(a32)
+    informed = running & has & ~is_goal & (cmin32 > 0)[:, None] & \
+        ~(u_mix < torch.tensor(float(uniform_mix), dtype=torch.float32)) & (mode == "informed")
+    a, cmin = a32.to(torch.float64), cmin32.to(torch.float64)
+    c = cost.gather(1, gn.clamp(0, cap - 1)[:, None])[:, 0].to(torch.float64)
+    ah = a / torch.where(cmin > 0, cmin, torch.ones_like(cmin))[:, None]
+    v = ah.clone()
+    v[:, 0] += torch.where(a[:, 0] < 0, -1.0, 1.0).to(torch.float64)
+    vv = (v * v).sum(dim=1)
+    centre = start.to(torch.float64) + a / 2
+    radii = (torch.sqrt(((c - cmin) * (c + cmin)).clamp(min=0)) / 2)[:, None].repeat(1, dof)
+    radii[:, 0] = c / 2
+    on = torch.tensor([bool((mask >> j) & 1) for j in builtins.range(dof)])
+    cand = torch.zeros((tries, R, P, dof), dtype=torch.float64)
+    chosen = torch.full((R, P), tries, dtype=torch.int64)
+    for t in builtins.range(tries):
+        z = torch.zeros((R, P, dof), dtype=torch.float64)
+        for b in builtins.range((dof + 3) // 4):
+            h = block(t, 10 + b)
+            for i in (0, 1):
+                rad = torch.sqrt(-2.0 * torch.log(((h[2 * i] >> 8) + 1).to(torch.float64) * 2.0 ** -24))
+                ang = 2.0 * math.pi * _u01(h[2 * i + 1]).to(torch.float64)
+                for j, val in ((4 * b + 2 * i, rad * torch.cos(ang)), (4 * b + 2 * i + 1, rad * torch.sin(ang))):
+                    if j < dof:
+                        z[..., j] = val
+        n = z.norm(dim=-1, keepdim=True)
+        ball = z / torch.where(n > 0, n, torch.ones_like(n)) * _u01(block(t, 9)[0]).to(torch.float64)[..., None] ** (1.0 / dof)
+        y = radii[:, None, :] * ball
+        x = centre[:, None, :] + y - 2.0 * v[:, None, :] * (v[:, None, :] * y).sum(dim=-1, keepdim=True) / vv[:, None, None]
+        x = torch.where(on, torch.remainder(x + math.pi, 2 * math.pi) - math.pi, x)
+        cand[t] = x
+        x32 = x.to(torch.float32)
+        inside = ((lo <= x32) & (x32 < hi)).all(dim=-1)
+        chosen = torch.where((chosen == tries) & inside, torch.full_like(chosen, t), chosen)
+    taken = cand.gather(0, chosen.clamp(max=tries - 1)[None, :, :, None].expand(1, R, P, dof))[0].to(torch.float32)
+    samples = torch.where((informed & (chosen < tries))[..., None], taken, uniform)
+    samples = torch.where(is_goal[..., None], goals[:, None, :].expand(R, P, dof), samples)
+    samples = torch.where(running[..., None], samples, start[:, None, :].expand(R, P, dof))
+    info = torch.where(informed, 2 + chosen, torch.zeros_like(chosen))
+    info = torch.where(is_goal, torch.ones_like(info), info)
+    info = torch.where(running, info, torch.full_like(info, -1))
+    return samples.contiguous(), info.to(torch.int32), cand
+
+
 class _StarPlan(_Plan):
     def __init__(self, checker, starts, goals, dev, reach, max_step, radius, near, wrap, slots, cap, max_rounds, rounds_per_call, sampler,
-                 goal_bias, limits, seed, max_samples):
+                 goal_bias, limits, seed, max_samples, sampling="host", uniform_mix=0., informed_tries=8, record_samples=False):
+        if sampling not in _SAMPLING:
+            raise ValueError(f"rrt_star: sampling must be one of {list(_SAMPLING)}, got {sampling!r}")
+        if sampling != "host" and sampler is not None:
+            raise ValueError(f"rrt_star: a `sampler` draws on the host: it cannot be combined with sampling={sampling!r}")
+        self.mode, self.seed, self.goal_bias = _SAMPLING[sampling], int(seed), float(goal_bias)
+        self.uniform_mix, self.tries = float(uniform_mix), int(informed_tries)
+        self.kept = ([], []) if record_samples else None   # the rounds' samples and info words, chunk by chunk
         own = sampler is None
         super().__init__(checker, starts, goals, dev, reach, max_step, wrap, slots, cap, max_rounds, rounds_per_call,
                          (lambda T, R, P: None) if own else sampler, limits, seed, max_samples)
@@ -102,7 +229,15 @@ class _StarPlan(_Plan):
         self.radius = self.range if radius is None else float(radius)
         if not self.radius >= 0:
             raise ValueError("rrt_star: radius must be >= 0")
-        if own:
+        if self.mode is not None:
+            if self.limits is None:
+                raise ValueError(f"rrt_star: sampling={sampling!r} needs `limits` [dof, 2]: the checker's robot has no joint limits")
+            if not 0 <= self.goal_bias <= 1 or not 0 <= self.uniform_mix <= 1:
+                raise ValueError("rrt_star: goal_bias and uniform_mix must be in [0, 1]")
+            if not 1 <= self.tries <= 16:
+                raise ValueError(f"rrt_star: informed_tries must be in [1, 16], got {informed_tries}")
+            self.limits = self.limits.contiguous()
+        elif own:
             if self.limits is None:
                 raise ValueError("rrt_star: pass `limits` [dof, 2] or a `sampler`: the checker's robot has no joint limits")
             gen = torch.Generator(device=dev)
@@ -158,9 +293,15 @@ class _StarPlan(_Plan):
             if not bool(running.any()) or (stop_on_first and bool((goal[running] >= 0).all())):
                 break
             T = min(self.chunk, self.max_rounds - g)
+            if self.mode is not None:   # the chunk draws its own samples, round by round
+                run_chunk(T, g)
+                g += T
+                continue
             samples = torch.as_tensor(self.sampler(T, self.R, self.P)).to(device=self.dev, dtype=torch.float32).contiguous()
             if tuple(samples.shape) != (T, self.R, self.P, self.dof):
                 raise ValueError(f"rrt_star: the sampler returned {tuple(samples.shape)}, expected {(T, self.R, self.P, self.dof)}")
+            if self.kept is not None:
+                self.kept[0].append(samples)
             run_chunk(samples, g)
             g += T
         return g
@@ -170,7 +311,11 @@ class _StarPlan(_Plan):
         goal = st["goal_node"].to(torch.int64)
         costs = st["cost"].gather(1, goal.clamp(min=0)[:, None])[:, 0] if self.R else st["cost"][:, 0]
         costs = torch.where(goal >= 0, costs, torch.full_like(costs, float("nan")))
-        return RRTStarResult(route, st, paths, costs, rounds_run)
+        samples = info = None
+        if self.kept is not None:
+            samples = torch.cat(self.kept[0]) if self.kept[0] else torch.zeros((0, self.R, self.P, self.dof), device=self.dev)
+            info = torch.cat(self.kept[1]) if self.kept[1] else None
+        return RRTStarResult(route, st, paths, costs, rounds_run, samples, info)
 
 
 def _host_round(pl, edges, st, s, g, trace=None):
@@ -287,21 +432,33 @@ def _host_round(pl, edges, st, s, g, trace=None):
 
 def host_rrt_star(checker, starts, goals, *, range, max_step, radius=None, near=8, wrap=None, slots=4, cap=4096, max_rounds=256,
                   rounds_per_call=32, sampler=None, goal_bias=0.1, limits=None, seed=0, margin=0., max_samples=None,
-                  stop_on_first=False, _trace=None):
+                  stop_on_first=False, sampling="host", uniform_mix=0., informed_tries=8, record_samples=False, _trace=None):
     """rrt_star's contract as the loop a user would write from the library's other calls: per round one `knn` per running
     problem for the nearest nodes and one for the near sets, the steering, costs and selections in torch, ONE
     `checker.check_motions(..., return_first=True)` call per phase on the fixed batches of R * slots, R * slots * near and
     R * slots * near edges, the appends and rewires as indexed assignments.  The state lives on the device of `starts`.
-    `margin` is passed on to the checker's check_motions only where it is not 0."""
+    `margin` is passed on to the checker's check_motions only where it is not 0.  sampling="device" / "informed" (rrt_star has
+    the options) draws every round from host_device_samples on the state as the round finds it."""
     dev = torch.as_tensor(starts).device
     pl = _StarPlan(checker, starts, goals, dev, range, max_step, radius, near, wrap, slots, cap, max_rounds, rounds_per_call, sampler,
-                   goal_bias, limits, seed, max_samples)
+                   goal_bias, limits, seed, max_samples, sampling, uniform_mix, informed_tries, record_samples)
     edges = _Edges(checker, pl.max_step, pl.max_samples, pl.mask, margin)
     st = pl.initial_state(edges)
 
     def run_chunk(samples, g0):
-        for t, s in enumerate(samples):
+        for t in builtins.range(samples if pl.mode is not None else len(samples)):
             ev = None if _trace is None else {"round": g0 + t}
+            if pl.mode is not None:
+                s, info, _ = host_device_samples(st, pl.goals, pl.limits, pl.seed, g0 + t, pl.P, pl.mode, pl.goal_bias, pl.uniform_mix,
+                                                 pl.tries, pl.mask)
+                s, info = s.to(dev), info.to(dev)
+                if pl.kept is not None:
+                    pl.kept[0].append(s[None])
+                    pl.kept[1].append(info[None])
+                if ev is not None:
+                    ev["samples"], ev["sample_info"] = s, info
+            else:
+                s = samples[t]
             _host_round(pl, edges, st, s, g0 + t, ev)
             if _trace is not None:
                 ev["state"] = {k: v.clone() for k, v in st.items()}
@@ -311,7 +468,8 @@ def host_rrt_star(checker, starts, goals, *, range, max_step, radius=None, near=
 
 
 def rrt_star(checker, starts, goals, *, range, max_step, radius=None, near=8, wrap=None, slots=4, cap=4096, max_rounds=256,
-             rounds_per_call=32, sampler=None, goal_bias=0.1, limits=None, seed=0, margin=0., max_samples=None, stop_on_first=False):
+             rounds_per_call=32, sampler=None, goal_bias=0.1, limits=None, seed=0, margin=0., max_samples=None, stop_on_first=False,
+             sampling="host", uniform_mix=0., informed_tries=8, record_samples=False):
     """Plan R motions starts[r] -> goals[r] ([R, dof] each) with batched RRT* under `checker`: an RRTStarResult.  Anytime: a
     problem keeps improving its tree until max_rounds (stop_on_first: the loop ends at the first chunk after which every
     running problem has reached its goal).
@@ -321,6 +479,15 @@ def rrt_star(checker, starts, goals, *, range, max_step, radius=None, near=8, wr
     [T, R, P, dof] (default: uniform in `limits` [dof, 2], taken from the checker's robot where it has them, and with probability
     `goal_bias` the goal row itself, both drawn from one generator seeded by `seed`); margin: a sample collides where
     score - margin > 0, on top of the checker's own threshold; max_samples: the most samples of one edge.
+    sampling: "host" (the default: `sampler`, a whole chunk of rounds drawn before the chunk runs), "device" (uniform in `limits`
+    with the goal bias, drawn on the device at the start of every round: Philox4x32-10 keyed by `seed`, no launch of torch's per
+    chunk) or "informed" (as "device" until a problem has a goal node of cost c; from then on its samples are uniform in the
+    ellipsoid d(start, x) + d(x, goal) <= c, the only points that can still shorten its path, `informed_tries` (1 .. 16) draws
+    before the uniform point is taken where the ellipsoid leaves the limits, and with probability `uniform_mix` a uniform sample
+    all the same).  With circular coordinates the ellipsoid is the one around the shortest-arc image of the goal: every point
+    of it meets the bound under the torus metric, and routes through other images of the goal are left to uniform_mix.  The
+    goal bias is off once a problem has a goal node.  Both need `limits`; a `sampler` together with either is a ValueError.
+    record_samples: keep every round's samples (and, for the device draws, their info words) on the result.
     The fused planner (result.route == "fused") runs for kernel_perceptrons.DiffCo, RBFDiffCo and ForwardKinematicsDiffCo whose
     transform fuses; every other checker is planned by host_rrt_star ("host")."""
     dev0 = torch.as_tensor(starts).device
@@ -328,7 +495,8 @@ def rrt_star(checker, starts, goals, *, range, max_step, radius=None, near=8, wr
     if got is None:
         return host_rrt_star(checker, starts, goals, range=range, max_step=max_step, radius=radius, near=near, wrap=wrap, slots=slots,
                              cap=cap, max_rounds=max_rounds, rounds_per_call=rounds_per_call, sampler=sampler, goal_bias=goal_bias,
-                             limits=limits, seed=seed, margin=margin, max_samples=max_samples, stop_on_first=stop_on_first)
+                             limits=limits, seed=seed, margin=margin, max_samples=max_samples, stop_on_first=stop_on_first,
+                             sampling=sampling, uniform_mix=uniform_mix, informed_tries=informed_tries, record_samples=record_samples)
     model, base = got
     if isinstance(base, (int, float)) and isinstance(margin, (int, float)):
         mg = float(base) + float(margin)
@@ -336,11 +504,22 @@ def rrt_star(checker, starts, goals, *, range, max_step, radius=None, near=8, wr
         mg = (torch.as_tensor(base, dtype=torch.float32).reshape(-1).to(model.dev)
               + torch.as_tensor(margin, dtype=torch.float32).reshape(-1).to(model.dev))
     pl = _StarPlan(checker, starts, goals, model.dev, range, max_step, radius, near, wrap, slots, cap, max_rounds, rounds_per_call,
-                   sampler, goal_bias, limits, seed, max_samples)
+                   sampler, goal_bias, limits, seed, max_samples, sampling, uniform_mix, informed_tries, record_samples)
     st = pl.initial_state(_FusedEdges(model, pl.max_step, pl.max_samples, pl.mask, mg))
     mg_dev = model._motion_margin(mg)   # on the device once: no copy from the host per chunk
 
     def run_chunk(samples, g0):
+        if pl.mode is not None:   # (samples: T)
+            keep = info = None
+            if pl.kept is not None:
+                keep = torch.empty((samples, pl.R, pl.P, pl.dof), dtype=torch.float32, device=pl.dev)
+                info = torch.empty((samples, pl.R, pl.P), dtype=torch.int32, device=pl.dev)
+                pl.kept[0].append(keep)
+                pl.kept[1].append(info)
+            return model.rrtstar_run_sampled(st, pl.goals, pl.limits, pl.seed, samples, pl.P, g0, pl.range, pl.max_step, pl.radius, pl.K,
+                                             pl.max_samples, mode=pl.mode, goal_bias=pl.goal_bias, uniform_mix=pl.uniform_mix,
+                                             tries=pl.tries, margin=0. if mg_dev is None else mg_dev, wrap=pl.mask,
+                                             samples_out=keep, info_out=info)
         model.rrtstar_run(st, pl.goals, samples, g0, pl.range, pl.max_step, pl.radius, pl.K, pl.max_samples,
                           margin=0. if mg_dev is None else mg_dev, wrap=pl.mask)
 

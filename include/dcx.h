@@ -831,6 +831,87 @@ int dcx_rrtstar_run(const dcx_model* m, const dcx_rrtstar_state* state, int64_t 
 int dcx_rrtstar_extract_paths(int device, const dcx_rrtstar_state* state, int64_t R, int32_t cap, int32_t dof,
                               float* path, int32_t W, int32_t* count_out, void* stream);
 
+/* ---- batched RRT*: samples drawn on the device (added under DCX_VERSION 109) ------------------------------ */
+/* The samples of a round drawn where the trees live, from each problem's state at the start of that round: uniform in the joint
+ * limits with a goal bias until the problem has a goal node, and from then on (mode informed) inside the set that can still
+ * shorten its path, { x : d(start, x) + d(x, goal) <= c_best } (Gammell, Srinivasa, Barfoot: Informed RRT*, IROS 2014).  One
+ * thread per slot (r, p); no scratch, no atomics, nothing read back.
+ * Random numbers: Philox4x32-10.  The key is (seed's low word, seed's high word); the counter is (g, r * 16 + p, t, b): round,
+ *   slot, try and block.  A uniform is (word >> 8) * 2^-24 in [0, 1); where a logarithm follows it is ((word >> 8) + 1) * 2^-24.
+ *   block 0, try 0:        word 0 = u_bias decides the goal bias, word 1 = u_mix decides the uniform mix
+ *   blocks 1 .. 8, try 0:  the uniform-in-limits coordinates: u_j is word j % 4 of block 1 + j / 4
+ *   blocks 9 .. 17, try t: the informed draw of try t.  Word 0 of block 9 is the radial uniform u_rad.  Blocks 10 .. 17 hold one
+ *                          Box-Muller pair per two coordinates: words (0, 1) of block 10 + j / 4 serve coordinates 4 b and 4 b + 1,
+ *                          words (2, 3) coordinates 4 b + 2 and 4 b + 3; with (w, w') the pair, rad = sqrt(-2 ln u(w)) (the
+ *                          logarithm's uniform) and (sn, cs) = sincospi(2 u(w')), the even coordinate is rad * cs, the odd rad * sn
+ *   A draw depends on (seed, g, r, p) and the snapshot alone: not on T, on the chunking of the rounds into calls, or on launch
+ *   geometry.
+ * Slot (r, p) of a running problem (status[r] == 0) in round g, in this order; lo_j = limits[j, 0], hi_j = limits[j, 1]:
+ *   1. goal     - with goal_node[r] == -1 and u_bias < goal_bias the sample is goals[r, :], bit for bit.  The bias is off once the
+ *                 problem has a goal node: the goal is then reached more cheaply by rewiring, and a copy would be an ordinary node
+ *   2. uniform  - otherwise, with goal_node[r] == -1, or mode == DCX_RRTSTAR_SAMPLE_UNIFORM, or u_mix < uniform_mix:
+ *                 x_j = lo_j + span_j * u_j with span_j = hi_j - lo_j: one rounded fp32 product and one rounded fp32 sum (never
+ *                 contracted), so a referee reproduces the bits
+ *   3. informed - otherwise c = cost[r, goal_node[r]] of the snapshot.  a = the motion calls' wrapped delta start -> goal with
+ *                 start = nodes[r, 0]; c_min = |a| (the motion calls' length of that edge), a^ = a / c_min, centre = start + a / 2;
+ *                 r1 = c / 2, r2 = sqrt(max(c^2 - c_min^2, 0)) / 2, the difference formed as (c - c_min) (c + c_min), which keeps
+ *                 its digits where c is close to c_min.  Try t = 0 .. tries - 1: z = the dof Gaussians of try t, u = z / |z| *
+ *                 u_rad^(1 / dof): a uniform point of the unit ball;  y = (r1 u_0, r2 u_1, .., r2 u_{dof-1});  x = centre + H y,
+ *                 H the Householder reflection that takes e_0 to -+a^: v = a^ + sign(a^_0) e_0 (sign(0) = +1),
+ *                 H y = y - 2 v (v.y) / (v.v).  O(dof) per try, no rotation matrix; v.v = 2 (1 + |a^_0|) >= 2, so it is stable
+ *                 everywhere, and the sign does not matter because the ball is symmetric.  Coordinates of the wrap mask are brought
+ *                 into [-pi, pi) as the steering step's.  The first try with lo_j <= x_j < hi_j for every j is the sample; without
+ *                 one the sample is step 2's uniform point.  c_min == 0 takes step 2.  (A free direct motion has status 1 and is
+ *                 never sampled.)  These steps are fp32 with the device's logf, sincospif and powf: they agree with an fp64
+ *                 restatement to rounding, not bit for bit
+ *   A problem that is not running gets its start row nodes[r, 0, :].  A goal_node outside -1 .. cap - 1 (the caller's error) is
+ *   sampled as in step 2 and nothing is read there.
+ * info [R, P] int32 (may be NULL): -1 not running, 0 uniform, 1 goal, 2 + t informed and accepted at try t, 2 + tries informed
+ *   and fallen back to the uniform point.
+ * Wrapped joints: the ellipsoid is the one around the shortest-arc image of the goal.  Every point of it satisfies the bound
+ *   under the torus metric, because the wrapped sum is at most the unwrapped one; routes through other images of the goal are
+ *   left to uniform_mix.
+ * dcx_rrtstar_sample draws round `round` for the R problems of `state` on `device`, without a model (as
+ *   dcx_rrtstar_extract_paths): one launch on the caller's stream; it reads nodes, cost, status and goal_node of the state.
+ * dcx_rrtstar_run_sampled enqueues T rounds g = round0 .. round0 + T - 1: per round the sample launch on the state as the round
+ *   finds it, then exactly the launches of dcx_rrtstar_run's round towards those rows - one round, shared by both calls.  With
+ *   samples_out [T, R, P, dof] (and info_out [T, R, P]) the rounds' samples (and info words) are written there; otherwise the
+ *   rows live in the work slot.  Capturable: no allocation, no synchronisation, nothing read back; equal seeds give equal bits,
+ *   and T rounds in one call equal T calls of one round each.  `opts`, `margin`: dcx_rrtstar_run's.
+ * work: dcx_rrtstar_sampled_work_bytes(model, R, slots, near) bytes: dcx_rrtstar_work_bytes' total, then one round's sample rows
+ *   [R, P, dof].  dcx_rrtstar_work_bytes itself is unchanged.
+ * Argument errors (DCX_ERR_INVALID, before any device work): NULL sample_opts; with R > 0 a NULL limits, state, nodes, cost,
+ *   status, goal_node, goals or (dcx_rrtstar_sample) samples; tries outside 1 .. DCX_RRTSTAR_MAX_TRIES; goal_bias or uniform_mix
+ *   outside [0, 1] or NaN; an unknown mode; a reserved field not 0; dcx_rrtstar_sample: R < 0, round < 0 or above 2^31 - 1, slots
+ *   outside 1 .. DCX_RRT_MAX_SLOTS, cap outside 1 .. DCX_RRTSTAR_MAX_CAP, dof outside 1 .. DCX_MAX_DOF, a wrap_mask bit at or
+ *   above dof; dcx_rrtstar_run_sampled: every error of dcx_rrtstar_run, and slots, cap, dof or wrap_mask that differ from opts'
+ *   or the model's.  More than DCX_RRTSTAR_SAMPLE_MAX_PROBLEMS problems (the slot word r * 16 + p has 32 bits) is
+ *   DCX_ERR_UNSUPPORTED.  R = 0 (or T = 0) launches nothing; dcx_rrtstar_sampled_work_bytes is 0 for arguments the call refuses. */
+#define DCX_RRTSTAR_MAX_TRIES 16
+#define DCX_RRTSTAR_SAMPLE_UNIFORM 0
+#define DCX_RRTSTAR_SAMPLE_INFORMED 1
+#define DCX_RRTSTAR_SAMPLE_MAX_PROBLEMS (1 << 28)
+typedef struct dcx_rrtstar_sample_opts {
+    const float* limits;   /* device [dof, 2]: lo_j, hi_j                                                   */
+    uint64_t seed;         /* the Philox key                                                                */
+    float    goal_bias;    /* in [0, 1]: the chance of the goal row while the problem has no goal node      */
+    float    uniform_mix;  /* in [0, 1]: the chance of a uniform sample once it has one (mode informed)     */
+    int32_t  mode;         /* DCX_RRTSTAR_SAMPLE_UNIFORM or DCX_RRTSTAR_SAMPLE_INFORMED                     */
+    int32_t  tries;        /* 1 .. DCX_RRTSTAR_MAX_TRIES: informed draws before the uniform fallback        */
+    int32_t  slots;        /* P: dcx_rrtstar_opts' slots                                                    */
+    int32_t  cap;          /* dcx_rrtstar_opts' cap                                                         */
+    int32_t  dof;          /* the model's dof                                                               */
+    int32_t  reserved0;    /* 0                                                                             */
+    uint64_t wrap_mask;    /* dcx_rrtstar_opts' wrap_mask                                                   */
+    int64_t  reserved[2];  /* 0                                                                             */
+} dcx_rrtstar_sample_opts;
+int dcx_rrtstar_sample(int device, const dcx_rrtstar_state* state, int64_t R, const float* goals,
+                       const dcx_rrtstar_sample_opts* sample_opts, int64_t round, float* samples, int32_t* info, void* stream);
+size_t dcx_rrtstar_sampled_work_bytes(const dcx_model* m, int64_t R, int32_t slots, int32_t near);
+int dcx_rrtstar_run_sampled(const dcx_model* m, const dcx_rrtstar_state* state, int64_t R, const float* goals,
+                            const dcx_rrtstar_sample_opts* sample_opts, int32_t T, int64_t round0, const dcx_rrtstar_opts* opts,
+                            const float* margin, void* work, size_t work_bytes, float* samples_out, int32_t* info_out, void* stream);
+
 /* ---- batched path shortcutting and RRT path extraction (added under DCX_VERSION 109) ---------------------- */
 /* R piecewise-straight paths simplified in lockstep, P = opts->slots shortcut attempts per path and round: try the straight
  * motion between two waypoints and cut out what lies between (the path simplifier a planner's user expects before the paths go
