@@ -839,7 +839,8 @@ int dcx_device_count(void) {
 
 // ---- the model's rows: storage for `cap` supports, filled from host staging or by the packing kernel ---------------------
 static constexpr double kXfRqRule = 32.0;   // RQ2 takes the expanded form iff gamma * max |s - c|^2 <= this (see model_fill_host)
-static size_t rows_tail_floats(const dcx_model* m) { return 8 * (size_t)m->RS + 16; }  // readable zeros behind the last row for the sweeps' look-ahead loads
+// readable zeros behind the last row for the sweeps' look-ahead loads (score_kernel.h kSweepLookahead: never more rows than this)
+static size_t rows_tail_floats(const dcx_model* m) { return kRowsTailRows * (size_t)m->RS + kRowsTailFloats; }
 
 static void model_free_rows(dcx_model* m) {
     if (m->rows_dev) (void)hipFree(m->rows_dev);

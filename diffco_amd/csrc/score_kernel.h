@@ -161,6 +161,15 @@ __device__ __forceinline__ void wave_slice(int wave, int nw, int s_chunk, int sk
 // at the memory-side atomic unit (~12 ns each; the count took 2.5 k cycles instead of ~0.7 k)
 constexpr int kCounterStride = 32;
 
+// The rows' storage ends in a readable tail of zeros, kRowsTailRows strides + kRowsTailFloats floats (dcx_api.hip rows_tail_floats:
+// every copy of the rows, both packing routes), because the sweeps' pipelines issue the loads of the NEXT rows before they know
+// whether those are consumed.  kSweepLookahead: how many rows past the end of its slice - at most the model's last row - the
+// four-row pipeline of sweep_rows may fetch (whole strides at most); pair2's look-ahead is one stage of two rows.
+constexpr int kRowsTailRows = 8;
+constexpr int kRowsTailFloats = 16;
+constexpr int kSweepLookahead = 2;
+static_assert(kSweepLookahead <= kRowsTailRows, "the look-ahead loads of the sweep stay inside the rows' tail");
+
 typedef const __attribute__((address_space(4))) float* cfloat_ptr;
 typedef float v2f __attribute__((ext_vector_type(2)));
 
@@ -943,8 +952,8 @@ __device__ __forceinline__ void sweep_rows(const ScoreArgs& a, const float (&x_i
 #ifdef DCX_EXP_NO_LOADS   // timing experiment only (wrong results): after the first few, a row "load" fetches nothing - the
     int exp_real_loads = 4;  // registers keep their values behind an opaque barrier - what do the scalar loads cost the stream?
 #endif
-    auto load_row = [&](float (&dst)[L::RS], int j) __attribute__((always_inline)) {
-        cfloat_ptr r = rows + (size_t)j * RSTRIDE;
+    // (r: the row's address - the four-row pipeline hands over its row pointer plus a compile-time number of strides)
+    auto load_row = [&](float (&dst)[L::RS], cfloat_ptr r, auto whole) __attribute__((always_inline)) {
 #ifdef DCX_EXP_NO_LOADS
         if (exp_real_loads <= 0) {
 #pragma unroll
@@ -955,12 +964,16 @@ __device__ __forceinline__ void sweep_rows(const ScoreArgs& a, const float (&x_i
 #endif
 #pragma unroll
         for (int e = 0; e < NLOAD; ++e) {
-            // (SP: the float between the weight and the operand pair is not fetched - 15 SGPRs per row, and the four rows in
-            // flight fit the wave's budget like the plain form's 16 + 16 + 14 + 14)
-            if (SP && e == D + 1) continue;
+            // (SP: the float between the weight and the operand pair is fetched with the rows that arrive whole - one
+            // s_load_dwordx16 - and left out of the other two - x8 + x4 + x1 + x2, 15 SGPRs: 16 + 16 + 15 + 15 in flight fit the
+            // wave's budget like the plain form's 16 + 16 + 14 + 14; four whole rows do not: Polyharmonic(1)'s loop parked 144
+            // SGPR values in VGPR lanes)
+            if (SP && !decltype(whole)::value && e == D + 1) continue;
             dst[e] = r[e];
         }
     };
+    constexpr std::true_type WHOLE{};
+    constexpr std::false_type LEAN{};
 
     // How many SGPRs a pipeline may keep in flight: ~100 exist, the kernel needs a dozen for itself.  Four whole rows
     // (the deepest pipeline) fit up to 22 floats per row; wider rows run a two-buffer pipeline over whole rows
@@ -1014,17 +1027,35 @@ __device__ __forceinline__ void sweep_rows(const ScoreArgs& a, const float (&x_i
     // Explicit software pipeline, two rows per stage (4 row buffers): the wait before a stage covers loads
     // issued TWO row bodies earlier, which is what hides an L2-latency scalar miss when only a few waves
     // share a SIMD (small batches).  wait -> issue {C,D} -> body(A), body(B) -> wait -> issue {A,B} -> body(C), body(D)
+    // Addresses: the wave carries ONE pointer, to row j, advanced once per iteration; every row of the iteration is loaded at a
+    // compile-time offset from it (immediate offsets on the scalar loads: no index -> address arithmetic per row).  The look-ahead
+    // is NOT clamped to the slice: the loads of an iteration reach rows j + 5 <= j1 + kSweepLookahead - 1.  Inside the model those
+    // are the next wave's rows; behind the model's last row the storage carries kRowsTailRows readable rows of zeros
+    // (dcx_api.hip rows_tail_floats, both packing routes; j1 <= S always: wave_slice).  What they fetch is never consumed.
     if (j0 < j1) {
         float rowA[L::RS], rowB[L::RS], rowC[L::RS], rowD[L::RS];
-        const int jl = j1 - 1;  // clamp target for the look-ahead loads (harmless re-reads at the end)
-        load_row(rowA, j0);
-        load_row(rowB, (j0 + 1 < j1) ? j0 + 1 : jl);
+        cfloat_ptr rp = rows + (size_t)j0 * RSTRIDE;
+        // The pointer is made opaque in front of every row's loads (an empty asm on the same register pair: no instruction).  Loop
+        // strength reduction leaves it alone either way - it stays an induction variable of its own, not one rebuilt from j -
+        // but with every row at a constant offset from ONE visible base the load vectoriser sees neighbouring rows as one run of
+        // memory and cuts that run into loads that straddle the rows, whose pieces reach their row's registers through copies
+        // (the RQ2 spare loop: 76 instead of 66 VALU with the pointer visible, and 82 VALU, 14 s_mov, 16 v_readlane /
+        // v_writelane with it opaque once per iteration only; Polyharmonic(1)'s loop happened to come out the same each time)
+        auto next_row = [&](int k) __attribute__((always_inline)) -> cfloat_ptr {
+            asm volatile("" : "+s"(rp));
+            return rp + k * RSTRIDE;
+        };
+        load_row(rowA, next_row(0), WHOLE);
+        load_row(rowB, next_row(1), WHOLE);
         int j = j0;
-        for (; j + 3 < j1; j += 4) {
+        const int jend = j1 - 3;
+        while (j < jend) {
             __builtin_amdgcn_s_waitcnt(0xC07F);
             __builtin_amdgcn_sched_barrier(0);
-            load_row(rowC, j + 2);
-            load_row(rowD, j + 3);
+            load_row(rowC, next_row(2), LEAN);
+            load_row(rowD, next_row(3), LEAN);
+            // (the stride's padding counts as read where whole rows are consumed, or their load is narrowed back into four pieces)
+            if constexpr (SP) asm volatile("" ::"s"(rowA[D + 1]), "s"(rowB[D + 1]));
             __builtin_amdgcn_sched_barrier(0);
             if constexpr (XFA) {
                 stage_x(rowA, rowB, rowC, rowD);
@@ -1035,8 +1066,9 @@ __device__ __forceinline__ void sweep_rows(const ScoreArgs& a, const float (&x_i
             __builtin_amdgcn_sched_barrier(0);
             __builtin_amdgcn_s_waitcnt(0xC07F);
             __builtin_amdgcn_sched_barrier(0);
-            load_row(rowA, (j + 4 < j1) ? j + 4 : jl);
-            load_row(rowB, (j + 5 < j1) ? j + 5 : jl);
+            load_row(rowA, next_row(4), WHOLE);
+            load_row(rowB, next_row(5), WHOLE);
+            static_assert(5 - 3 <= kSweepLookahead, "the look-ahead of the four-row loop: rows j + 4, j + 5 with j + 3 < j1");
             __builtin_amdgcn_sched_barrier(0);
             if constexpr (XFA) {
                 stage_x(rowC, rowD, rowA, rowB);
@@ -1045,9 +1077,11 @@ __device__ __forceinline__ void sweep_rows(const ScoreArgs& a, const float (&x_i
                 pair(rowD);
             }
             __builtin_amdgcn_sched_barrier(0);
+            rp += 4 * RSTRIDE;
             if constexpr (XFA && GRAD) {
                 if ((j & (DCX_XF_FLUSH - 4)) == 0) flush_x();  // once per DCX_XF_FLUSH rows, whatever j0's alignment
             }
+            j += 4;
         }
         // up to three rows left: rowA / rowB already hold rows j and j+1
         auto one = [&](const float (&r)[L::RS]) __attribute__((always_inline)) {
@@ -1057,7 +1091,7 @@ __device__ __forceinline__ void sweep_rows(const ScoreArgs& a, const float (&x_i
         if (j < j1) one(rowA);
         if (j + 1 < j1) one(rowB);
         if (j + 2 < j1) {
-            load_row(rowC, j + 2);
+            load_row(rowC, next_row(2), LEAN);
             one(rowC);
         }
     }

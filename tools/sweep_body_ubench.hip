@@ -1,8 +1,9 @@
 // tools/sweep_body_ubench.hip — developer tool (GPU box): what does the sweep's pair body cost by itself?  The product's own
 // sweep_rows<> (score_kernel.h) in a bare kernel: no FK, no fold, no J^T, every wave sweeps the same few rows (scalar-cache
 // hits), W waves per SIMD on every SIMD of the chip.  Reports shader cycles (clock64: the clock the SIMD really ran at) and
-// nanoseconds per wave-row per SIMD, for the one-class Polyharmonic(1) sweep of the headline and the five-class RQ2 sweep of
-// config #3, both in the expanded form.  The fused kernel's figure for the same quantity = launch time x SIMDs / wave-rows.
+// nanoseconds per wave-row per SIMD, for the one-class Polyharmonic(1) sweep of the headline (the plain expanded form and the
+// spare-slot form the headline really runs, pre-staged as score_body calls it) and the five-class RQ2 sweep of config #3 in the
+// expanded form.  The fused kernel's figure for the same quantity = launch time x SIMDs / wave-rows.
 // Build: hipcc --offload-arch=gfx950 -O3 -std=c++17 -Idiffco_amd/csrc tools/sweep_body_ubench.hip -o devlibs/sweep_body_ubench
 #include <hip/hip_runtime.h>
 #include <cstdio>
@@ -12,7 +13,7 @@
 
 using namespace dcx;
 
-template <int D, int KF, int CC, int MODE, int WPS>
+template <int D, int KF, int CC, int MODE, int WPS, bool SP = false>
 __global__ __launch_bounds__(256, WPS) void body_kernel(const ScoreArgs a, int rows_n, int reps, float* out, unsigned long long* ts) {
     float x[D], up[CC], sc[CC], gx[D];
     const int lane = threadIdx.x & 63;
@@ -24,7 +25,8 @@ __global__ __launch_bounds__(256, WPS) void body_kernel(const ScoreArgs a, int r
     for (int i = 0; i < (int)((blockIdx.x * 7u + (threadIdx.x >> 6) * 3u) & 15u); ++i) __builtin_amdgcn_s_sleep(UBENCH_SKEW);
 #endif
     const unsigned long long t0 = clock64();
-    for (int r = 0; r < reps; ++r) sweep_rows<D, KF, CC, MODE, true>(a, x, up, 0, rows_n, sc, gx);
+    // (SP: the spare-slot form as score_body runs it - features pre-staged, the agreed column last)
+    for (int r = 0; r < reps; ++r) sweep_rows<D, KF, CC, MODE, true, 0, false, SP, SP>(a, x, up, 0, rows_n, sc, gx);
     const unsigned long long t1 = clock64();
     float s = 0.f;
 #pragma unroll
@@ -154,7 +156,7 @@ void run_xf2(const char* name, int cus) {
     hipFree(d_rows); hipFree(d_out); hipFree(d_ts);
 }
 
-template <int D, int KF, int CC, int WPS>
+template <int D, int KF, int CC, int WPS, bool SP = false>
 void run(const char* name, int cus) {
     using L = RowLayout<D, CC>;
     const int rows_n = 96, reps = 400;
@@ -165,6 +167,13 @@ void run(const char* name, int cus) {
         for (int c = 0; c < CC; ++c) rows[(size_t)j * L::RS + L::W_OFF + c] = 0.01f * (float)((j + c) % 5 - 2);
         if (CC > 1) rows[(size_t)j * L::RS + L::WSUM_OFF] = 0.01f;
         rows[(size_t)j * L::RS + L::SS_OFF] = ss + (KF == KF_RQ2 ? 0.2f : 0.f);
+        if (SP) {   // the spare-slot row (score_kernel.h spare_applies): |s|^2 in the last feature's slot, {s_{D-2}, 1} behind the weight
+            float* y = &rows[(size_t)j * L::RS];
+            y[D - 1] = y[L::SS_OFF];
+            y[D + 1] = 0.f;
+            y[D + 2] = y[D - 2];
+            y[D + 3] = 1.f;
+        }
     }
     float *d_rows, *d_out;
     unsigned long long* d_ts;
@@ -181,7 +190,8 @@ void run(const char* name, int cus) {
     hipEvent_t e0, e1;
     hipEventCreate(&e0);
     hipEventCreate(&e1);
-    auto kern = body_kernel<D, KF, CC, MODE_GRAD_ROW, WPS>;
+    a.spare = SP ? D : 0;
+    auto kern = body_kernel<D, KF, CC, MODE_GRAD_ROW, WPS, SP>;
     for (int warm = 0; warm < 3; ++warm) kern<<<blocks, 256>>>(a, rows_n, reps, d_out, d_ts);
     hipDeviceSynchronize();
     hipEventRecord(e0);
@@ -210,6 +220,10 @@ int main() {
     run<12, KF_POLY1, 1, 2>("headline: D=12 C=1 POLY1 XF", cus);
     run<12, KF_POLY1, 1, 4>("headline: D=12 C=1 POLY1 XF", cus);
     run<12, KF_POLY1, 1, 8>("headline: D=12 C=1 POLY1 XF", cus);
+    run<12, KF_POLY1, 1, 1, true>("headline: D=12 C=1 POLY1 spare", cus);
+    run<12, KF_POLY1, 1, 2, true>("headline: D=12 C=1 POLY1 spare", cus);
+    run<12, KF_POLY1, 1, 4, true>("headline: D=12 C=1 POLY1 spare", cus);
+    run<12, KF_POLY1, 1, 8, true>("headline: D=12 C=1 POLY1 spare", cus);
     run_xf2<12, 2>("EXPERIMENT xf2: D=12 two rows/instr", cus);
     run_xf2<12, 4>("EXPERIMENT xf2: D=12 two rows/instr", cus);
     run_xf2<12, 7>("EXPERIMENT xf2: D=12 two rows/instr", cus);
