@@ -24,10 +24,10 @@ from .roadmap import Roadmap, knn, knn_edges  # noqa: F401
 from . import rrt  # noqa: F401
 from .rrt import rrt_connect, host_rrt_connect, RRTResult  # noqa: F401
 from . import rrtstar  # noqa: F401
-from .rrtstar import rrt_star, host_rrt_star, RRTStarResult  # noqa: F401
+from .rrtstar import rrt_star, host_rrt_star, clearance_cost_paths, RRTStarResult  # noqa: F401
 from . import shortcut  # noqa: F401
 from .shortcut import shortcut_paths, host_shortcut_paths, ShortcutResult  # noqa: F401
 from . import resample  # noqa: F401
 from .resample import resample_paths, host_resample_paths, ResampleResult  # noqa: F401
 
-__all__ = ["resample", "resample_paths", "host_resample_paths", "ResampleResult", "optimize_paths", "shortcut", "shortcut_paths", "host_shortcut_paths", "ShortcutResult", "rrt","rrt_connect", "host_rrt_connect", "RRTResult", "rrtstar", "rrt_star", "host_rrt_star", "RRTStarResult", "kernel", "model", "utils", "optim", "sharded", "traj", "escape", "fused_adam_traj_optimize", "roadmap", "Roadmap", "knn", "knn_edges", "urdf", "URDFRobotFK", "MultiURDFRobotFK", "collision_checkers", "RBFDiffCo", "ForwardKinematicsDiffCo", "HybridForwardKinematicsDiffCo", "deprecated", "DiffCo", "MultiDiffCo", "DiffCoBeta"]
+__all__ = ["resample", "resample_paths", "host_resample_paths", "ResampleResult", "optimize_paths", "shortcut", "shortcut_paths", "host_shortcut_paths", "ShortcutResult", "rrt","rrt_connect", "host_rrt_connect", "RRTResult", "rrtstar", "rrt_star", "host_rrt_star", "clearance_cost_paths", "RRTStarResult", "kernel", "model", "utils", "optim", "sharded", "traj", "escape", "fused_adam_traj_optimize", "roadmap", "Roadmap", "knn", "knn_edges", "urdf", "URDFRobotFK", "MultiURDFRobotFK", "collision_checkers", "RBFDiffCo", "ForwardKinematicsDiffCo", "HybridForwardKinematicsDiffCo", "deprecated", "DiffCo", "MultiDiffCo", "DiffCoBeta"]

@@ -101,6 +101,13 @@ SYMBOLS = {
     "dcx_rrtstar_sampled_work_bytes": (C.c_size_t, [C.c_void_p, C.c_int64, C.c_int32, C.c_int32]),
     "dcx_rrtstar_run_sampled": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, _c_fp, C.c_void_p, C.c_int32, C.c_int64, C.c_void_p, _c_fp,
                                           C.c_void_p, C.c_size_t, _c_fp, _c_fp, C.c_void_p]),
+    # RRT* under clearance-weighted edge costs: dcx_rrtstar_run / _run_sampled with dcx_rrtstar_cost_opts after the options
+    "dcx_rrtstar_cost_work_bytes": (C.c_size_t, [C.c_void_p, C.c_int64, C.c_int32, C.c_int32]),
+    "dcx_rrtstar_run_cost": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, _c_fp, _c_fp, C.c_int32, C.c_int64, C.c_void_p, C.c_void_p, _c_fp,
+                                       C.c_void_p, C.c_size_t, C.c_void_p]),
+    "dcx_rrtstar_sampled_cost_work_bytes": (C.c_size_t, [C.c_void_p, C.c_int64, C.c_int32, C.c_int32]),
+    "dcx_rrtstar_run_sampled_cost": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, _c_fp, C.c_void_p, C.c_int32, C.c_int64, C.c_void_p,
+                                               C.c_void_p, _c_fp, C.c_void_p, C.c_size_t, _c_fp, _c_fp, C.c_void_p]),
     # batched path shortcutting over the motion checks, and the solved paths of an RRT state as one tensor
     "dcx_path_shortcut_work_bytes": (C.c_size_t, [C.c_void_p, C.c_int64, C.c_int32]),
     "dcx_path_shortcut_run": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, _c_fp, C.c_int32, C.c_void_p, _c_fp, C.c_void_p,
@@ -205,6 +212,14 @@ class RrtStarOpts(C.Structure):
 RRTSTAR_MAX_TRIES = 16                    # DCX_RRTSTAR_MAX_TRIES
 RRTSTAR_SAMPLE_MODES = {"uniform": 0, "informed": 1}   # DCX_RRTSTAR_SAMPLE_UNIFORM, DCX_RRTSTAR_SAMPLE_INFORMED
 RRTSTAR_SAMPLE_MAX_PROBLEMS = 1 << 28     # DCX_RRTSTAR_SAMPLE_MAX_PROBLEMS
+
+
+RRTSTAR_COST_PEAK = 1   # dcx_rrtstar_cost_opts' mode
+
+
+class RrtStarCostOpts(C.Structure):
+    """ctypes mirror of dcx_rrtstar_cost_opts (include/dcx.h)"""
+    _fields_ = [("mode", C.c_int32), ("gain", C.c_float), ("band", C.c_float), ("reserved0", C.c_int32), ("reserved", C.c_int64 * 2)]
 
 
 class RrtStarSampleOpts(C.Structure):

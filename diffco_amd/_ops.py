@@ -872,7 +872,7 @@ class ScoreModel:
             _lib.check(self._lib.dcx_rrt_connect_run(self._h, C.byref(st), R, _ptr(samples), T, int(round0), C.byref(opt), _ptr(mg),
                                                      _ptr(work), nbytes, self._st()))
 
-    def rrtstar_run(self, state, goals, samples, round0, range, max_step, radius, near, max_samples, margin=0., wrap=None):
+    def rrtstar_run(self, state, goals, samples, round0, range, max_step, radius, near, max_samples, margin=0., wrap=None, _cost=None):
         """T rounds of batched RRT* (dcx_rrtstar_run) on the caller's state, in place: `state` maps dcx_rrtstar_state's fields
         (nodes [R, cap, dof], elen and cost [R, cap] float32; parent [R, cap], count, status, goal_node, first_round [R] int32)
         to contiguous tensors on the model's device; goals [R, dof] and samples [T, R, P, dof] float32 there.  `near`: K, the
@@ -890,15 +890,42 @@ class ScoreModel:
         opt = _lib.RrtStarOpts(float(range), float(max_step), float(radius), int(max_samples), P, int(near), cap, 0,
                                wrap_mask(wrap, self.dof), (C.c_int64 * 2)(0, 0))
         mg = self._motion_margin(margin)
+        if _cost is not None:   # (rrtstar_run_cost)
+            nbytes = self._lib.dcx_rrtstar_cost_work_bytes(self._h, R, P, int(near))
+            work = self._work(nbytes)
+            with _on_device(self.dev):
+                _lib.check(self._lib.dcx_rrtstar_run_cost(self._h, C.byref(st), R, _ptr(goals), _ptr(samples), T, int(round0),
+                                                          C.byref(opt), C.byref(_cost), _ptr(mg), _ptr(work), nbytes, self._st()))
+            return
         nbytes = self._lib.dcx_rrtstar_work_bytes(self._h, R, P, int(near))
         work = self._work(nbytes)
         with _on_device(self.dev):
             _lib.check(self._lib.dcx_rrtstar_run(self._h, C.byref(st), R, _ptr(goals), _ptr(samples), T, int(round0), C.byref(opt),
                                                  _ptr(mg), _ptr(work), nbytes, self._st()))
 
+    @staticmethod
+    def _rrtstar_cost_opts(gain, band):
+        return _lib.RrtStarCostOpts(_lib.RRTSTAR_COST_PEAK, float(gain), float(band), 0, (C.c_int64 * 2)(0, 0))
+
+    def rrtstar_run_cost(self, state, goals, samples, round0, range, max_step, radius, near, max_samples, gain, band, margin=0.,
+                         wrap=None):
+        """rrtstar_run under clearance-weighted edge costs (dcx_rrtstar_run_cost): an edge with peak w = max over its samples of
+        score - margin is free where w <= 0 and costs C = L * (1 + gain * max(w + band, 0)), every operation fp32 and rounded
+        alone; state['elen'] holds C.  gain, band >= 0; gain = 0 is rrtstar_run bit for bit.  Everything else as rrtstar_run."""
+        self.rrtstar_run(state, goals, samples, round0, range, max_step, radius, near, max_samples, margin=margin, wrap=wrap,
+                         _cost=self._rrtstar_cost_opts(gain, band))
+
+    def rrtstar_run_sampled_cost(self, state, goals, limits, seed, T, slots, round0, range, max_step, radius, near, max_samples, gain,
+                                 band, **kw):
+        """rrtstar_run_sampled under rrtstar_run_cost's objective (dcx_rrtstar_run_sampled_cost); `kw`: rrtstar_run_sampled's
+        mode, goal_bias, uniform_mix, tries, margin, wrap, samples_out and info_out.  The informed draw reads the goal node's
+        cost, which is never below its path's length: the ellipsoid stays admissible."""
+        self.rrtstar_run_sampled(state, goals, limits, seed, T, slots, round0, range, max_step, radius, near, max_samples,
+                                 _cost=self._rrtstar_cost_opts(gain, band), **kw)
+
     def rrtstar_run_sampled(self, state, goals, limits, seed, T, slots, round0, range, max_step, radius, near, max_samples,
                             mode="informed", goal_bias=0.1, uniform_mix=0., tries=8, margin=0., wrap=None, samples_out=None,
-                            info_out=None):
+                            info_out=None, _cost=None):
         """T rounds of batched RRT* whose samples are drawn on the device at the start of each round (dcx_rrtstar_run_sampled:
         per round rrtstar_sample's launch on the state as it stands, then rrtstar_run's round), in place on `state`; `state`,
         goals, range .. max_samples, margin and wrap as rrtstar_run; limits [dof, 2] float32 on the model's device; seed, mode,
@@ -920,6 +947,14 @@ class ScoreModel:
         opt = _lib.RrtStarOpts(float(range), float(max_step), float(radius), int(max_samples), P, int(near), cap, 0, mask,
                                (C.c_int64 * 2)(0, 0))
         mg = self._motion_margin(margin)
+        if _cost is not None:   # (rrtstar_run_sampled_cost)
+            nbytes = self._lib.dcx_rrtstar_sampled_cost_work_bytes(self._h, R, P, int(near))
+            work = self._work(nbytes)
+            with _on_device(self.dev):
+                _lib.check(self._lib.dcx_rrtstar_run_sampled_cost(self._h, C.byref(st), R, _ptr(goals), C.byref(sopt), T, int(round0),
+                                                                  C.byref(opt), C.byref(_cost), _ptr(mg), _ptr(work), nbytes,
+                                                                  _ptr(samples_out), _ptr(info_out), self._st()))
+            return
         nbytes = self._lib.dcx_rrtstar_sampled_work_bytes(self._h, R, P, int(near))
         work = self._work(nbytes)
         with _on_device(self.dev):

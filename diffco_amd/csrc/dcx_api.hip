@@ -22,6 +22,7 @@
 #include "knn_kernel.h"
 #include "rrt_kernel.h"
 #include "rrtstar_kernel.h"
+#include "rrtstar_cost_kernel.h"
 #include "shortcut_kernel.h"
 #include "shortcut_partial_kernel.h"
 #include "resample_kernel.h"
@@ -2891,6 +2892,183 @@ int dcx_rrtstar_run_sampled(const dcx_model* m, const dcx_rrtstar_state* state, 
     if (int rc = kRrtStarCheck.launchable(m, E * std::max(K, 1), opt->max_samples)) return rc;
     if (int rc = set_device(m->device)) return rc;
     RrtStarRound round(m, state, R, goals, opt, margin, work, plan.run, stream);
+    RrtStarSampleArgs s = rrtstar_sample_args(state, R, goals, so);
+    for (int32_t t = 0; t < T; ++t) {
+        s.round = (int32_t)(round0 + t);
+        s.samples = samples_out ? samples_out + (int64_t)t * E * dof : (float*)((char*)work + plan.samples);
+        s.info = info_out ? info_out + (int64_t)t * E : nullptr;
+        const hipError_t e = launch_rrtstar_sample(s, (hipStream_t)stream);
+        if (e != hipSuccess) return fail_hip(e, "rrtstar sample launch");
+        if (int rc = round.run(s.round, s.samples)) return rc;
+    }
+    return DCX_OK;
+}
+
+// ---- batched RRT* under clearance-weighted edge costs (rrtstar_cost_kernel.h): the size queries and the calls share the checks
+// and rrtstar_cost_plan; the length planner above is not touched ------------------------------------------------------------------
+namespace {
+// a round's edge batch through dcx_motion_worst: PlannerEdges with the peaks where the verdicts were
+struct PlannerPeaks {
+    const dcx_model* m;
+    int64_t E;
+    size_t work_bytes;
+    dcx_motion_opts mo;
+    const float* margin;
+    void* work;
+    uint64_t wrap_mask;
+    void* stream;
+    int worst(const float* qa, const float* qb, float* worst, int32_t* worst_idx) const {
+        return dcx_motion_worst(m, qa, qb, E, &mo, margin, worst, worst_idx, nullptr, nullptr, nullptr, nullptr, work, work_bytes,
+                                wrap_mask, stream);
+    }
+};
+
+// dcx_motion_worst's workspace for the larger batch of a round (the smaller batch's is no larger)
+size_t rrtstar_cost_head(const dcx_model* m, int64_t R, int32_t slots, int32_t near) {
+    return motion_worst_work(m, R * slots * std::max(near, 1)).total;
+}
+
+int rrtstar_cost_checks(const dcx_rrtstar_cost_opts* co) {
+    if (!co) return fail(DCX_ERR_INVALID, "rrtstar: cost options are NULL");
+    if (co->mode != DCX_RRTSTAR_COST_PEAK) return fail(DCX_ERR_INVALID, "rrtstar: the cost mode must be DCX_RRTSTAR_COST_PEAK");
+    if (!(co->gain >= 0.f)) return fail(DCX_ERR_INVALID, "rrtstar: the cost gain must be >= 0");
+    if (!(co->band >= 0.f)) return fail(DCX_ERR_INVALID, "rrtstar: the cost band must be >= 0");
+    if (co->reserved0 || co->reserved[0] || co->reserved[1]) return fail(DCX_ERR_INVALID, "rrtstar: reserved fields of the cost options must be 0");
+    return DCX_OK;
+}
+
+// what dcx_motion_worst could still refuse beyond PlannerCheck::launchable: refused before the first launch
+int rrtstar_cost_launchable(const dcx_model* m, int32_t max_samples) {
+    if (max_samples > kMotionWorstSampleLimit) return fail(DCX_ERR_UNSUPPORTED, "rrtstar: max_samples above 2^24 - 1 under a cost objective");
+    if (!motion_worst_for(m->Dt)) return fail(DCX_ERR_UNSUPPORTED, "rrtstar: no worst-sample kernel for this feature width");
+    return DCX_OK;
+}
+
+// THE round of RRT* under the objective: RrtStarRound's arguments over rrtstar_cost_plan's workspace, the three sweeps through
+// dcx_motion_worst, and the kernels of rrtstar_cost_kernels.hip between the length planner's own launches.  Both calls feed it.
+struct RrtStarCostRound {
+    RrtStarRound len;      // the length planner's arguments over plan.run (its edge batches are not used)
+    PlannerPeaks ed, pl;   // the extend batch and the place batches: both workspaces start at the head
+    RrtStarCostArgs c;
+    float* worst0;
+    int32_t* widx0;
+    float* place_worst;
+    int32_t* place_widx;
+    RrtStarCostRound(const dcx_model* m, const dcx_rrtstar_state* state, int64_t R, const float* goals, const dcx_rrtstar_opts* opt,
+                     const dcx_rrtstar_cost_opts* co, const float* margin, void* work, const RrtStarCostPlan& plan, void* stream)
+        : len(m, state, R, goals, opt, margin, work, plan.run, stream),
+          ed{m, R * opt->slots, motion_worst_work(m, R * opt->slots).total, {0, opt->max_step, opt->max_samples, 0}, margin, work,
+             opt->wrap_mask, stream},
+          pl{m, R * opt->slots * opt->near, motion_worst_work(m, R * opt->slots * opt->near).total, {0, opt->max_step, opt->max_samples, 0},
+             margin, work, opt->wrap_mask, stream},
+          c{} {
+        char* base = (char*)work;
+        worst0 = (float*)(base + plan.worst0);
+        widx0 = (int32_t*)(base + plan.widx0);
+        place_worst = (float*)(base + plan.place_worst);
+        place_widx = (int32_t*)(base + plan.place_widx);
+        c.a = len.a;
+        c.first_hit = (int32_t*)(base + plan.run.first_hit);
+        c.place_hit = (int32_t*)(base + plan.run.place_hit);
+        c.worst0 = worst0;
+        c.slot_len = (float*)(base + plan.slot_len);
+        c.slot_cost = (float*)(base + plan.slot_cost);
+        c.place_worst = place_worst;
+        c.gain = co->gain;
+        c.band = co->band;
+    }
+    // round g towards samples [R, P, dof]
+    int run(int32_t g, const float* samples) {
+        hipStream_t st = (hipStream_t)ed.stream;
+        RrtStarArgs& a = c.a;
+        const int K = a.K;
+        a.round = len.n.round = g;
+        len.n.samples = samples;
+        hipError_t e = launch_rrt_nearest(len.n, st);
+        if (e != hipSuccess) return fail_hip(e, "rrtstar nearest launch");
+        if (int rc = ed.worst(a.qa, a.qb, worst0, widx0)) return rc;
+        e = launch_rrtstar_cost_extend_settle(c, st);
+        if (e != hipSuccess) return fail_hip(e, "rrtstar cost extend launch");
+        if (K > 0) {
+            e = launch_rrtstar_near(a, st);
+            if (e != hipSuccess) return fail_hip(e, "rrtstar near launch");
+            e = launch_rrtstar_cost_choose_prepare(c, st);
+            if (e != hipSuccess) return fail_hip(e, "rrtstar cost choose launch");
+            if (int rc = pl.worst(a.pqa, a.pqb, place_worst, place_widx)) return rc;
+        }
+        e = launch_rrtstar_cost_commit(c, st);
+        if (e != hipSuccess) return fail_hip(e, "rrtstar cost commit launch");
+        if (K > 0) {
+            e = launch_rrtstar_rewire_prepare(a, st);   // its test cost[x] + L' < cost[v] is the objective's lower bound
+            if (e != hipSuccess) return fail_hip(e, "rrtstar rewire launch");
+            if (int rc = pl.worst(a.pqa, a.pqb, place_worst, place_widx)) return rc;
+            e = launch_rrtstar_cost_rewire_settle(c, st);
+            if (e != hipSuccess) return fail_hip(e, "rrtstar cost rewire launch");
+            e = launch_rrtstar_rewire_select(a, st);
+            if (e != hipSuccess) return fail_hip(e, "rrtstar select launch");
+        }
+        e = launch_rrtstar_refresh(a, st);
+        if (e != hipSuccess) return fail_hip(e, "rrtstar refresh launch");
+        return DCX_OK;
+    }
+};
+}  // namespace
+
+size_t dcx_rrtstar_cost_work_bytes(const dcx_model* m, int64_t R, int32_t slots, int32_t near) {
+    if (rrtstar_sizes(m, R, slots, near)) return 0;
+    return rrtstar_cost_plan(R, slots, near, m->fk.dof, rrtstar_cost_head(m, R, slots, near)).total;
+}
+
+size_t dcx_rrtstar_sampled_cost_work_bytes(const dcx_model* m, int64_t R, int32_t slots, int32_t near) {
+    if (rrtstar_sizes(m, R, slots, near)) return 0;
+    return rrtstar_sampled_cost_plan(R, slots, near, m->fk.dof, rrtstar_cost_head(m, R, slots, near)).total;
+}
+
+int dcx_rrtstar_run_cost(const dcx_model* m, const dcx_rrtstar_state* state, int64_t R, const float* goals, const float* samples,
+                         int32_t T, int64_t round0, const dcx_rrtstar_opts* opt, const dcx_rrtstar_cost_opts* co, const float* margin,
+                         void* work, size_t work_bytes, void* stream) {
+    // every argument is checked before anything touches the model's device
+    bool state_ok = false;
+    if (int rc = rrtstar_run_checks(m, state, R, goals, T, round0, opt, &state_ok)) return rc;
+    if (int rc = rrtstar_cost_checks(co)) return rc;
+    if (int rc = kRrtStarCheck.buffers(R, T, state_ok, samples, "samples", work)) return rc;
+    const int32_t P = opt->slots, K = opt->near;
+    const int64_t E = R * P;
+    const RrtStarCostPlan plan = rrtstar_cost_plan(R, P, K, m->fk.dof, rrtstar_cost_head(m, R, P, K));
+    if (int rc = kRrtStarCheck.workspace(R, work_bytes, plan.total, "dcx_rrtstar_cost_work_bytes")) return rc;
+    if (R == 0 || T == 0) return DCX_OK;
+    if (int rc = kRrtStarCheck.launchable(m, E * std::max(K, 1), opt->max_samples)) return rc;
+    if (int rc = rrtstar_cost_launchable(m, opt->max_samples)) return rc;
+    if (int rc = set_device(m->device)) return rc;
+    RrtStarCostRound round(m, state, R, goals, opt, co, margin, work, plan, stream);
+    for (int32_t t = 0; t < T; ++t)
+        if (int rc = round.run((int32_t)(round0 + t), samples + (int64_t)t * E * m->fk.dof)) return rc;
+    return DCX_OK;
+}
+
+int dcx_rrtstar_run_sampled_cost(const dcx_model* m, const dcx_rrtstar_state* state, int64_t R, const float* goals,
+                                 const dcx_rrtstar_sample_opts* so, int32_t T, int64_t round0, const dcx_rrtstar_opts* opt,
+                                 const dcx_rrtstar_cost_opts* co, const float* margin, void* work, size_t work_bytes, float* samples_out,
+                                 int32_t* info_out, void* stream) {
+    // every argument is checked before anything touches the model's device
+    bool state_ok = false;
+    if (int rc = rrtstar_run_checks(m, state, R, goals, T, round0, opt, &state_ok)) return rc;
+    if (int rc = rrtstar_cost_checks(co)) return rc;
+    if (!so) return fail(DCX_ERR_INVALID, "rrtstar: sample options are NULL");
+    if (int rc = rrtstar_sample_checks(kRrtStarCheck.what, so)) return rc;
+    if (so->slots != opt->slots || so->cap != opt->cap || so->dof != m->fk.dof || so->wrap_mask != opt->wrap_mask)
+        return fail(DCX_ERR_INVALID, "rrtstar: slots, cap, dof or wrap_mask of the sample options differ from the options' or the model's");
+    if (R > DCX_RRTSTAR_SAMPLE_MAX_PROBLEMS) return fail(DCX_ERR_UNSUPPORTED, "rrtstar: more than DCX_RRTSTAR_SAMPLE_MAX_PROBLEMS problems");
+    if (int rc = kRrtStarCheck.buffers(R, 1, state_ok, so->limits, "limits", work)) return rc;
+    const int32_t P = opt->slots, K = opt->near, dof = m->fk.dof;
+    const int64_t E = R * P;
+    const RrtStarSampledCostPlan plan = rrtstar_sampled_cost_plan(R, P, K, dof, rrtstar_cost_head(m, R, P, K));
+    if (int rc = kRrtStarCheck.workspace(R, work_bytes, plan.total, "dcx_rrtstar_sampled_cost_work_bytes")) return rc;
+    if (R == 0 || T == 0) return DCX_OK;
+    if (int rc = kRrtStarCheck.launchable(m, E * std::max(K, 1), opt->max_samples)) return rc;
+    if (int rc = rrtstar_cost_launchable(m, opt->max_samples)) return rc;
+    if (int rc = set_device(m->device)) return rc;
+    RrtStarCostRound round(m, state, R, goals, opt, co, margin, work, plan.run, stream);
     RrtStarSampleArgs s = rrtstar_sample_args(state, R, goals, so);
     for (int32_t t = 0; t < T; ++t) {
         s.round = (int32_t)(round0 + t);

@@ -1,6 +1,9 @@
 """Batched RRT* over a collision checker: R planning problems, one tree each, grown in lockstep with P extensions per problem
 and round; every new node picks the cheapest free parent among its K nearest within a radius and then rewires those of them it
-reaches more cheaply.  Only path length under the motion calls' metric is optimised.
+reaches more cheaply.  objective="length" (the default) optimises path length under the motion calls' metric;
+objective="clearance" charges an edge its length times 1 + clearance_gain * max(w + clearance_band, 0), w the peak of score -
+margin along it (include/dcx.h, "batched RRT*: clearance-weighted edge costs"): the tree then prefers motions that keep away
+from the obstacle boundary, which no shortcutter can do.  `clearance_cost_paths` prices any piecewise-straight path under it.
 
 `rrt_star` runs the fused planner (dcx_rrtstar_run: the tree logic in HIP, the three edge batches of a round through the fused
 motion sweep, one status / goal read-back per chunk of rounds) where the checker's own `check_motions` would take the fused
@@ -25,9 +28,9 @@ import torch
 
 from . import _ops
 from .roadmap import knn
-from .rrt import (BLOCKED, FULL, RUNNING, _Edges, _FusedEdges, _Plan, _fused_model, _length, _nearest, _steer)
+from .rrt import (BLOCKED, FULL, RUNNING, _Edges, _FusedEdges, _Plan, _edge_plan, _fused_model, _length, _nearest, _steer)
 
-__all__ = ["rrt_star", "host_rrt_star", "host_device_samples", "philox4x32_10", "RRTStarResult", "RUNNING", "DIRECT", "FULL", "BLOCKED"]
+__all__ = ["rrt_star", "host_rrt_star", "clearance_cost_paths", "host_device_samples", "philox4x32_10", "RRTStarResult", "RUNNING", "DIRECT", "FULL", "BLOCKED"]
 
 DIRECT = 1   # dcx_rrtstar_state's status 1: the direct motion start -> goal is free (RUNNING, FULL, BLOCKED: as rrt.py's)
 _STATE = ("nodes", "parent", "elen", "cost", "count", "status", "goal_node", "first_round")
@@ -37,7 +40,8 @@ _SAMPLING = {"host": None, "device": "uniform", "informed": "informed"}   # rrt_
 
 class RRTStarResult:
     """paths: per problem a [W, dof] tensor (start first, goal last) or None without a goal node;  costs [R]: the goal nodes'
-    cost-to-come (nan without one);  first_round [R]: the round that first reached the goal (-1: none, or a free direct motion);
+    cost-to-come (nan without one);  first_round [R]: the round that first reached the goal (-1: none, or a free direct motion -
+    under objective="clearance" also one that is penalised, which seeds the tree with status 0 and is improved on);
     status [R] (0 still running at max_rounds, 1 the direct motion is free, 2 full, 3 an endpoint collides);  rounds: the rounds
     that were run;  route: "fused" or "host";  nodes, parent, elen, cost, count, goal_node: the raw state tensors;  samples
     [rounds, R, P, dof] and sample_info [rounds, R, P] (record_samples=True, else None): what every round was given, and for the
@@ -208,6 +212,65 @@ def host_device_samples(state, goals, limits, seed, g, P, mode="informed", goal_
     return samples.contiguous(), info.to(torch.int32), cand
 
 
+class _Objective:
+    """the clearance objective of include/dcx.h in torch ops, one rounded float32 operation at a time:
+    C = L * (1 + gain * max(w + band, 0))"""
+
+    def __init__(self, gain, band, submit_all=False):
+        self.gain, self.band, self.submit_all = float(gain), float(band), bool(submit_all)
+
+    def pen(self, w):
+        return torch.clamp(w + torch.tensor(self.band, dtype=torch.float32, device=w.device), min=0)
+
+    def price(self, L, w):
+        f = 1 + torch.tensor(self.gain, dtype=torch.float32, device=w.device) * self.pen(w)
+        return L * f
+
+
+def _objective(name, objective, gain, band, submit_all=False):
+    """None for objective="length", else the _Objective of "clearance" (its arguments checked)"""
+    if objective == "length":
+        return None
+    if objective != "clearance":
+        raise ValueError(f"{name}: objective must be 'length' or 'clearance', got {objective!r}")
+    if band is None or not float(band) > 0:
+        raise ValueError(f"{name}: objective='clearance' needs clearance_band > 0 (how far below the margin a peak starts to cost)")
+    if not float(gain) >= 0:
+        raise ValueError(f"{name}: clearance_gain must be >= 0")
+    return _Objective(gain, band, submit_all)
+
+
+class _PeakEdges:
+    """the checker's motion_worst on the fixed batch, as rrt._Edges is its check_motions"""
+
+    def __init__(self, name, checker, max_step, max_samples, mask, margin):
+        if not callable(getattr(checker, "motion_worst", None)):
+            raise TypeError(f"{name}: the clearance objective needs a checker with motion_worst(qa, qb, max_step=, max_samples=, wrap=)")
+        self.checker, self.max_step, self.max_samples, self.mask = checker, float(max_step), int(max_samples), int(mask)
+        self.kw = {} if (isinstance(margin, (int, float)) and float(margin) == 0.0) else {"margin": margin}
+
+    def worst(self, qa, qb, root):
+        """worst [E] float32 of the edges qa -> qb; an edge over max_samples is answered NaN without being submitted (a facade
+        raises for it): its place in the batch takes `root` -> `root`, as an idle slot's"""
+        over = _edge_plan(qa, qb, self.max_step, self.max_samples, self.mask)[2]
+        qa_s, qb_s = torch.where(over[:, None], root, qa), torch.where(over[:, None], root, qb)
+        w = self.checker.motion_worst(qa_s, qb_s, max_step=self.max_step, wrap=self.mask if self.mask else None,
+                                      max_samples=self.max_samples, **self.kw)[0]
+        w = torch.as_tensor(w).detach().to(device=qa.device, dtype=torch.float32).reshape(-1)
+        return torch.where(over, torch.full_like(w, float("nan")), w)
+
+
+class _FusedPeakEdges:
+    """the same on a ScoreModel (the initial checks of the fused planner)"""
+
+    def __init__(self, model, max_step, max_samples, mask, margin):
+        self.model, self.max_step, self.max_samples, self.mask, self.margin = model, float(max_step), int(max_samples), int(mask), margin
+
+    def worst(self, qa, qb, root):
+        return self.model.motion_worst_raw(qa, qb, max_step=self.max_step, margin=self.margin, max_samples=self.max_samples,
+                                           wrap=self.mask)[0]
+
+
 class _StarPlan(_Plan):
     def __init__(self, checker, starts, goals, dev, reach, max_step, radius, near, wrap, slots, cap, max_rounds, rounds_per_call, sampler,
                  goal_bias, limits, seed, max_samples, sampling="host", uniform_mix=0., informed_tries=8, record_samples=False):
@@ -253,10 +316,12 @@ class _StarPlan(_Plan):
                 return torch.stack(out) if T else torch.zeros((0, R, P, self.dof), device=dev)
             self.sampler = default
 
-    def initial_state(self, edges):
+    def initial_state(self, edges, obj=None):
         """the roots, and the initial checks as ONE batch of 3 R edges: the zero-length edges on the starts and on the goals
         (the point checks under the planner's own margin) and the direct motions start -> goal.  A free direct motion is the
-        optimum: node 1 is the goal"""
+        optimum: node 1 is the goal.  Under an objective (`edges` then answers peaks) a free direct motion is node 1 with its
+        cost C all the same, but the optimum (status 1) only where C has its length's bits; a penalised one keeps status 0
+        and first_round -1, and the rounds improve on it"""
         R, cap, dof, dev = self.R, self.cap, self.dof, self.dev
         st = dict(nodes=torch.zeros((R, cap, dof), dtype=torch.float32, device=dev),
                   parent=torch.full((R, cap), -1, dtype=torch.int32, device=dev),
@@ -269,16 +334,21 @@ class _StarPlan(_Plan):
         st["nodes"][:, 0] = self.starts
         if R:
             qa, qb = torch.cat([self.starts, self.goals, self.starts]), torch.cat([self.starts, self.goals, self.goals])
-            first = edges.first_hit(qa, qb, self.starts[:1].expand(3 * R, dof))[0]
-            blocked = (first[:R] != -1) | (first[R:2 * R] != -1)
-            direct = (first[2 * R:] == -1) & ~blocked
-            L = _length(_ops.wrapped_delta(self.starts, self.goals, self.mask))
+            L = C = _length(_ops.wrapped_delta(self.starts, self.goals, self.mask))
+            if obj is None:
+                free = edges.first_hit(qa, qb, self.starts[:1].expand(3 * R, dof))[0] == -1
+            else:
+                w = edges.worst(qa, qb, self.starts[:1].expand(3 * R, dof))
+                free = w <= 0
+                C = obj.price(L, w[2 * R:])
+            blocked = ~free[:R] | ~free[R:2 * R]
+            direct = free[2 * R:] & ~blocked
             st["status"][blocked] = BLOCKED
-            st["status"][direct] = DIRECT
+            st["status"][direct & (_bits(C) == _bits(L))] = DIRECT
             st["nodes"][direct, 1] = self.goals[direct]
             st["parent"][direct, 1] = 0
-            st["elen"][direct, 1] = L[direct]
-            st["cost"][direct, 1] = L[direct]
+            st["elen"][direct, 1] = C[direct]
+            st["cost"][direct, 1] = C[direct]
             st["count"][direct] = 2
             st["goal_node"][direct] = 1
         return st
@@ -318,9 +388,10 @@ class _StarPlan(_Plan):
         return RRTStarResult(route, st, paths, costs, rounds_run, samples, info)
 
 
-def _host_round(pl, edges, st, s, g, trace=None):
+def _host_round(pl, edges, st, s, g, trace=None, obj=None):
     """one round of the contract on the state tensors, in place (s [R, P, dof]: the round's samples).  `trace`: a dict that
-    takes what the round did (the events the tests count)."""
+    takes what the round did (the events the tests count).  `obj`: None, or the _Objective of the clearance round (`edges`
+    then answers peaks): verdicts from w <= 0, every edge priced C = L * f(w), the places submitted on the lower bound L."""
     R, P, K, dof, cap, mask, dev = pl.R, pl.P, pl.K, pl.dof, pl.cap, pl.mask, pl.dev
     r_all = torch.arange(R, device=dev)
     r1, r2 = r_all[:, None], r_all[:, None, None]
@@ -329,9 +400,20 @@ def _host_round(pl, edges, st, s, g, trace=None):
     nodes, cost = st["nodes"], st["cost"]
     root = nodes[:, 0][:, None, :].expand(R, P, dof)
 
-    def check(go, qa, qb, rt):
+    def check(go, qa, qb, rt, L):
+        """(free, C) of the batch's edges: the verdicts and the edges' costs; the trace counts the free edges of `go` that cost
+        more than their length"""
         qa, qb = torch.where(go[..., None], qa, rt), torch.where(go[..., None], qb, rt)
-        return edges.first_hit(qa.reshape(-1, dof), qb.reshape(-1, dof), rt.reshape(-1, dof))[0].reshape(go.shape)
+        if obj is None:
+            return edges.first_hit(qa.reshape(-1, dof), qb.reshape(-1, dof), rt.reshape(-1, dof))[0].reshape(go.shape) == -1, L
+        w = edges.worst(qa.reshape(-1, dof), qb.reshape(-1, dof), rt.reshape(-1, dof)).reshape(go.shape)
+        if trace is not None:
+            seen["penalised"] += int((go & (w <= 0) & (obj.pen(w) > 0)).sum())
+        return w <= 0, obj.price(L, w)
+
+    seen = dict(penalised=0, pruned_after=0, rewire_rejected_after=0)   # (counted for a trace only: each is a read-back)
+
+    every = obj is not None and obj.submit_all   # (a test's: every near place submitted, the lower bounds ignored)
 
     # 1. extend: RRT-Connect's phase 1 on the one tree
     near = _nearest({"nodes": nodes[:, None]}, 0, s, running[:, None].expand(R, P), [[c] for c in counts], mask)
@@ -339,10 +421,11 @@ def _host_round(pl, edges, st, s, g, trace=None):
     nq = nodes[r1, nc]
     x, ok = _steer(nq, s, pl.range, mask)
     go = (near >= 0) & ok
-    cand = go & (check(go, nq, x, root) == -1)
     L0 = _length(_ops.wrapped_delta(nq, x, mask))
-    c0 = cost[r1, nc] + L0
-    par, elen, cnew = near.clone(), L0, c0
+    free, C0 = check(go, nq, x, root, L0)
+    cand = go & free
+    c0 = cost[r1, nc] + C0
+    par, elen, cnew = near.clone(), C0, c0
 
     if K > 0:
         # 2. the near sets over the snapshot
@@ -358,16 +441,20 @@ def _host_round(pl, edges, st, s, g, trace=None):
         xk = x[:, :, None, :].expand(R, P, K, dof)
         # 3. choose parent
         Lj = _length(_ops.wrapped_delta(un, xk, mask))
-        cj = cost[r2, uc] + Lj
+        key0 = ((_bits(c0) << 32) | nc)[..., None]
+        submit = (u >= 0) & ((((_bits(cost[r2, uc] + Lj) << 32) | uc) < key0) | every)   # the lower bound: Cj >= Lj
+        free, Cj = check(submit, un, xk, rootk, Lj)
+        cj = cost[r2, uc] + Cj
         keyj = (_bits(cj) << 32) | uc
-        key0 = (_bits(c0) << 32) | nc
-        submit = (u >= 0) & (keyj < key0[..., None])
-        free = submit & (check(submit, un, xk, rootk) == -1)
+        free = submit & free
+        if trace is not None:
+            seen["pruned_after"] = int((free & ~(keyj < key0)).sum())
+        free = free & (keyj < key0)
         keyj = torch.where(free, keyj, torch.full_like(keyj, _NO_KEY))
         jb = keyj.argmin(dim=2, keepdim=True)
         has = free.any(dim=2)
         par = torch.where(has, uc.gather(2, jb)[..., 0], near)
-        elen = torch.where(has, Lj.gather(2, jb)[..., 0], L0)
+        elen = torch.where(has, Cj.gather(2, jb)[..., 0], C0)
         cnew = torch.where(has, cj.gather(2, jb)[..., 0], c0)
 
     # 4. append in slot order while count < cap
@@ -392,23 +479,29 @@ def _host_round(pl, edges, st, s, g, trace=None):
     st["status"][running & over] = FULL
     if trace is not None:
         trace.update(chose_other=int((fits & (par != near)).sum()), dropped=int((cand & ~fits).sum()), rewires=0, contested=0,
-                     lowered_descendants=0, short_near=int((cand & (u[..., K - 1] < 0)).sum()) if K > 0 else 0)
+                     lowered_descendants=0, short_near=int((cand & (u[..., K - 1] < 0)).sum()) if K > 0 else 0,
+                     **seen)
     if K == 0:
         return
 
     # 5. rewire: the new nodes against the snapshot's cost of their near nodes
     ac = added.clamp(min=0)
     Lp = _sqrt32(d2)
-    cp = cost[r1, ac][..., None] + Lp
-    submit = (added >= 0)[..., None] & (u >= 0) & (u != par[..., None]) & (cp < cost[r2, uc])
-    free = (submit & (check(submit, xk, un, rootk) == -1)).reshape(R, P * K)
+    cx = cost[r1, ac][..., None]
+    submit = (added >= 0)[..., None] & (u >= 0) & (u != par[..., None]) & ((cx + Lp < cost[r2, uc]) | every)   # the lower bound
+    free, Cp = check(submit, xk, un, rootk, Lp)
+    cp = cx + Cp
+    free = submit & free
+    if trace is not None:
+        seen["rewire_rejected_after"] = int((free & ~(cp < cost[r2, uc])).sum())
+    free = (free & (cp < cost[r2, uc])).reshape(R, P * K)
     v = uc.reshape(R, P * K)
     key = ((_bits(cp) << 32) | torch.arange(P, device=dev)[None, :, None]).reshape(R, P * K)
     rival = free[:, :, None] & free[:, None, :] & (v[:, :, None] == v[:, None, :]) & (key[:, None, :] < key[:, :, None])
     win = free & ~rival.any(dim=2)
     rw = r1.expand_as(v)[win]
     st["parent"][rw, v[win]] = ac[:, :, None].expand(R, P, K).reshape(R, P * K)[win].to(torch.int32)
-    st["elen"][rw, v[win]] = Lp.reshape(R, P * K)[win]
+    st["elen"][rw, v[win]] = Cp.reshape(R, P * K)[win]
 
     # 6. refresh: the fixed point of cost = cost[parent] + elen from the roots' +0, where something was rewired
     rows = torch.nonzero(win.any(dim=1)).reshape(-1)
@@ -426,24 +519,31 @@ def _host_round(pl, edges, st, s, g, trace=None):
         target = torch.zeros((R, cap), dtype=torch.bool, device=dev)
         target[rw, v[win]] = True
         trace.update(rewires=int(win.sum()), contested=int((win & (free[:, None, :] & (v[:, :, None] == v[:, None, :])).sum(dim=2).gt(1)).sum()),
-                     lowered_descendants=int(((st["cost"] < before) & ~target).sum()))
+                     lowered_descendants=int(((st["cost"] < before) & ~target).sum()), **seen)
         assert not bool((st["cost"] > before).any())
 
 
 def host_rrt_star(checker, starts, goals, *, range, max_step, radius=None, near=8, wrap=None, slots=4, cap=4096, max_rounds=256,
                   rounds_per_call=32, sampler=None, goal_bias=0.1, limits=None, seed=0, margin=0., max_samples=None,
-                  stop_on_first=False, sampling="host", uniform_mix=0., informed_tries=8, record_samples=False, _trace=None):
+                  stop_on_first=False, sampling="host", uniform_mix=0., informed_tries=8, record_samples=False, objective="length",
+                  clearance_gain=1.0, clearance_band=None, _trace=None, _submit_all=False):
     """rrt_star's contract as the loop a user would write from the library's other calls: per round one `knn` per running
     problem for the nearest nodes and one for the near sets, the steering, costs and selections in torch, ONE
     `checker.check_motions(..., return_first=True)` call per phase on the fixed batches of R * slots, R * slots * near and
     R * slots * near edges, the appends and rewires as indexed assignments.  The state lives on the device of `starts`.
     `margin` is passed on to the checker's check_motions only where it is not 0.  sampling="device" / "informed" (rrt_star has
-    the options) draws every round from host_device_samples on the state as the round finds it."""
+    the options) draws every round from host_device_samples on the state as the round finds it.
+    objective="clearance" (rrt_star has the arguments): the same round with ONE `checker.motion_worst(...)` call per phase on
+    the same batches in place of check_motions; a checker without motion_worst is a TypeError.  `_trace` then also counts
+    `penalised` (free edges that cost more than their length), `pruned_after` (places submitted on the lower bound and free,
+    but no longer below the incumbent once priced) and `rewire_rejected_after` (the same for rewires)."""
     dev = torch.as_tensor(starts).device
+    obj = _objective("host_rrt_star", objective, clearance_gain, clearance_band, _submit_all)
     pl = _StarPlan(checker, starts, goals, dev, range, max_step, radius, near, wrap, slots, cap, max_rounds, rounds_per_call, sampler,
                    goal_bias, limits, seed, max_samples, sampling, uniform_mix, informed_tries, record_samples)
-    edges = _Edges(checker, pl.max_step, pl.max_samples, pl.mask, margin)
-    st = pl.initial_state(edges)
+    edges = _Edges(checker, pl.max_step, pl.max_samples, pl.mask, margin) if obj is None else \
+        _PeakEdges("host_rrt_star", checker, pl.max_step, pl.max_samples, pl.mask, margin)
+    st = pl.initial_state(edges, obj)
 
     def run_chunk(samples, g0):
         for t in builtins.range(samples if pl.mode is not None else len(samples)):
@@ -459,7 +559,7 @@ def host_rrt_star(checker, starts, goals, *, range, max_step, radius=None, near=
                     ev["samples"], ev["sample_info"] = s, info
             else:
                 s = samples[t]
-            _host_round(pl, edges, st, s, g0 + t, ev)
+            _host_round(pl, edges, st, s, g0 + t, ev, obj)
             if _trace is not None:
                 ev["state"] = {k: v.clone() for k, v in st.items()}
                 _trace.append(ev)
@@ -469,7 +569,8 @@ def host_rrt_star(checker, starts, goals, *, range, max_step, radius=None, near=
 
 def rrt_star(checker, starts, goals, *, range, max_step, radius=None, near=8, wrap=None, slots=4, cap=4096, max_rounds=256,
              rounds_per_call=32, sampler=None, goal_bias=0.1, limits=None, seed=0, margin=0., max_samples=None, stop_on_first=False,
-             sampling="host", uniform_mix=0., informed_tries=8, record_samples=False):
+             sampling="host", uniform_mix=0., informed_tries=8, record_samples=False, objective="length", clearance_gain=1.0,
+             clearance_band=None):
     """Plan R motions starts[r] -> goals[r] ([R, dof] each) with batched RRT* under `checker`: an RRTStarResult.  Anytime: a
     problem keeps improving its tree until max_rounds (stop_on_first: the loop ends at the first chunk after which every
     running problem has reached its goal).
@@ -488,15 +589,24 @@ def rrt_star(checker, starts, goals, *, range, max_step, radius=None, near=8, wr
     of it meets the bound under the torus metric, and routes through other images of the goal are left to uniform_mix.  The
     goal bias is off once a problem has a goal node.  Both need `limits`; a `sampler` together with either is a ValueError.
     record_samples: keep every round's samples (and, for the device draws, their info words) on the result.
+    objective: "length" (the default) or "clearance": an edge then costs C = L * (1 + clearance_gain * max(w + clearance_band,
+    0)), L its length and w the peak of score - margin over its samples (motion_worst's), every operation fp32 and rounded
+    alone - a hinge, so that the fused planner and host_rrt_star agree bit for bit.  clearance_band > 0 (required; in score
+    units) is how far below the margin a peak starts to cost, clearance_gain >= 0 the slope.  costs, cost and elen then hold
+    these costs (never below the lengths); clearance_cost_paths prices other paths the same way.  A free direct motion is final
+    (status 1) only where it is not penalised; otherwise it seeds the tree (first_round stays -1) and the rounds improve on it.
+    clearance_gain = 0 plans exactly as objective="length".
     The fused planner (result.route == "fused") runs for kernel_perceptrons.DiffCo, RBFDiffCo and ForwardKinematicsDiffCo whose
     transform fuses; every other checker is planned by host_rrt_star ("host")."""
     dev0 = torch.as_tensor(starts).device
+    obj = _objective("rrt_star", objective, clearance_gain, clearance_band)
     got = _fused_model(checker, dev0 if dev0.type == "cuda" else None)
     if got is None:
         return host_rrt_star(checker, starts, goals, range=range, max_step=max_step, radius=radius, near=near, wrap=wrap, slots=slots,
                              cap=cap, max_rounds=max_rounds, rounds_per_call=rounds_per_call, sampler=sampler, goal_bias=goal_bias,
                              limits=limits, seed=seed, margin=margin, max_samples=max_samples, stop_on_first=stop_on_first,
-                             sampling=sampling, uniform_mix=uniform_mix, informed_tries=informed_tries, record_samples=record_samples)
+                             sampling=sampling, uniform_mix=uniform_mix, informed_tries=informed_tries, record_samples=record_samples,
+                             objective=objective, clearance_gain=clearance_gain, clearance_band=clearance_band)
     model, base = got
     if isinstance(base, (int, float)) and isinstance(margin, (int, float)):
         mg = float(base) + float(margin)
@@ -505,8 +615,9 @@ def rrt_star(checker, starts, goals, *, range, max_step, radius=None, near=8, wr
               + torch.as_tensor(margin, dtype=torch.float32).reshape(-1).to(model.dev))
     pl = _StarPlan(checker, starts, goals, model.dev, range, max_step, radius, near, wrap, slots, cap, max_rounds, rounds_per_call,
                    sampler, goal_bias, limits, seed, max_samples, sampling, uniform_mix, informed_tries, record_samples)
-    st = pl.initial_state(_FusedEdges(model, pl.max_step, pl.max_samples, pl.mask, mg))
+    st = pl.initial_state((_FusedEdges if obj is None else _FusedPeakEdges)(model, pl.max_step, pl.max_samples, pl.mask, mg), obj)
     mg_dev = model._motion_margin(mg)   # on the device once: no copy from the host per chunk
+    cost_kw = {} if obj is None else dict(gain=obj.gain, band=obj.band)
 
     def run_chunk(samples, g0):
         if pl.mode is not None:   # (samples: T)
@@ -516,11 +627,54 @@ def rrt_star(checker, starts, goals, *, range, max_step, radius=None, near=8, wr
                 info = torch.empty((samples, pl.R, pl.P), dtype=torch.int32, device=pl.dev)
                 pl.kept[0].append(keep)
                 pl.kept[1].append(info)
-            return model.rrtstar_run_sampled(st, pl.goals, pl.limits, pl.seed, samples, pl.P, g0, pl.range, pl.max_step, pl.radius, pl.K,
-                                             pl.max_samples, mode=pl.mode, goal_bias=pl.goal_bias, uniform_mix=pl.uniform_mix,
-                                             tries=pl.tries, margin=0. if mg_dev is None else mg_dev, wrap=pl.mask,
-                                             samples_out=keep, info_out=info)
-        model.rrtstar_run(st, pl.goals, samples, g0, pl.range, pl.max_step, pl.radius, pl.K, pl.max_samples,
-                          margin=0. if mg_dev is None else mg_dev, wrap=pl.mask)
+            run = model.rrtstar_run_sampled if obj is None else model.rrtstar_run_sampled_cost
+            return run(st, pl.goals, pl.limits, pl.seed, samples, pl.P, g0, pl.range, pl.max_step, pl.radius, pl.K, pl.max_samples,
+                       mode=pl.mode, goal_bias=pl.goal_bias, uniform_mix=pl.uniform_mix, tries=pl.tries,
+                       margin=0. if mg_dev is None else mg_dev, wrap=pl.mask, samples_out=keep, info_out=info, **cost_kw)
+        run = model.rrtstar_run if obj is None else model.rrtstar_run_cost
+        run(st, pl.goals, samples, g0, pl.range, pl.max_step, pl.radius, pl.K, pl.max_samples,
+            margin=0. if mg_dev is None else mg_dev, wrap=pl.mask, **cost_kw)
 
     return pl.star_result("fused", st, pl.run(st, run_chunk, stop_on_first))
+
+
+def clearance_cost_paths(checker, paths, counts, *, max_step, gain=1.0, band, wrap=None, margin=0., max_samples=None):
+    """(cost [R], length [R], peak [R]) float32 of R piecewise-straight paths under rrt_star's clearance objective, whatever made
+    them (RRTStarResult.path_tensor(), shortcut_paths, query_batch): paths [R, W, dof], counts [R] the waypoints of each (a row
+    with fewer than two has cost and length 0 and peak nan).  ONE `checker.motion_worst` call on the consecutive pairs; a
+    segment costs C = L * (1 + gain * max(w + band, 0)), L the motion calls' length bits and w its peak of score - margin, and a
+    path's cost is the sum of its segments' from the root on, one float32 sum per segment - the goal node's cost of a tree that
+    holds these edges, to the bits of w.  length sums the L the same way; peak is the largest w (> 0: the path collides).
+    max_samples=None: from the longest segment."""
+    obj = _objective("clearance_cost_paths", "clearance", gain, band)
+    paths = torch.as_tensor(paths).detach().to(torch.float32)
+    if paths.dim() != 3:
+        raise ValueError("clearance_cost_paths: paths must be [R, W, dof]")
+    R, W, dof = paths.shape
+    dev = paths.device
+    n = torch.as_tensor(counts).to(device=dev, dtype=torch.int64).reshape(R)
+    cost = torch.zeros(R, dtype=torch.float32, device=dev)
+    length = torch.zeros(R, dtype=torch.float32, device=dev)
+    peak = torch.full((R,), float("nan"), dtype=torch.float32, device=dev)
+    if R == 0 or W < 2:
+        return cost, length, peak
+    mask = _ops.wrap_mask(wrap, dof, getattr(checker, "transform", None) or
+                          getattr(getattr(checker, "perceptron", None), "transform", None))
+    live = torch.arange(W - 1, device=dev)[None, :] + 1 < n[:, None]   # segment s of path r: waypoints s -> s + 1
+    qa, qb = paths[:, :-1][live], paths[:, 1:][live]
+    if len(qa) == 0:
+        return cost, length, peak
+    L = _length(_ops.wrapped_delta(qa, qb, mask))
+    if max_samples is None:
+        max_samples = min(_ops.MOTION_MAX_SAMPLES, int(math.ceil(float(L.max()) / float(max_step))) + 2)
+    edges = _PeakEdges("clearance_cost_paths", checker, max_step, max_samples, mask, margin)
+    w = edges.worst(qa, qb, qa[:1].expand_as(qa))
+    Cs, Ls, ws = (torch.zeros((R, W - 1), dtype=torch.float32, device=dev) for _ in builtins.range(3))
+    Cs[live], Ls[live] = obj.price(L, w), L
+    ws = torch.full_like(ws, -float("inf"))
+    ws[live] = torch.where(torch.isnan(w), torch.full_like(w, float("inf")), w)   # (a segment over max_samples: not priced)
+    for k in builtins.range(W - 1):   # (a dead segment adds +0: the sum keeps its bits)
+        cost, length = cost + Cs[:, k], length + Ls[:, k]
+    has = live.any(dim=1)
+    peak = torch.where(has, ws.max(dim=1).values, peak)
+    return cost, length, peak

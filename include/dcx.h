@@ -912,6 +912,68 @@ int dcx_rrtstar_run_sampled(const dcx_model* m, const dcx_rrtstar_state* state, 
                             const dcx_rrtstar_sample_opts* sample_opts, int32_t T, int64_t round0, const dcx_rrtstar_opts* opts,
                             const float* margin, void* work, size_t work_bytes, float* samples_out, int32_t* info_out, void* stream);
 
+/* ---- batched RRT*: clearance-weighted edge costs (added under DCX_VERSION 109) ---------------------------- */
+/* The same planner under an objective a shortcutter cannot optimise: an edge costs its length times a factor that grows with the
+ * peak score along it, so the tree prefers motions that keep away from the obstacle boundary.  The reference's
+ * misc/rrt_star.py does this in score_dist, length * (1 + a penalty of the worst sample's score), and scripts/motion_planner.py
+ * hands OMPL a custom motionCost.  The objective travels in a struct of its own and through entry points of its own:
+ * dcx_rrtstar_opts, its reserved fields and dcx_rrtstar_run are unchanged.
+ * The objective (mode DCX_RRTSTAR_COST_PEAK) of a directed edge a -> b of a batch submitted to dcx_motion_worst with the closed
+ * max_step rule, max_samples, margin, wrap_mask of the options and no gradients; w = its worst, L = the motion calls' own length
+ * bits of a -> b as "batched RRT*" step 1 forms them:
+ *   free  <=>  w <= 0          (NaN, an edge over max_samples, is not free: what first_hit -2 is to dcx_rrtstar_run)
+ *   pen = fmaxf(w + band, +0)  band >= 0: how far below the margin a peak starts to cost, in score units
+ *   f   = 1 + gain * pen       gain >= 0
+ *   C   = L * f                the edge's cost
+ * every operation fp32 and rounded alone, never contracted.  The shape is score_dist's with a hinge where the reference has exp:
+ * with a hinge each step is one correctly rounded operation that a host referee reproduces, so the two agree bit for bit; an expf
+ * would agree to rounding only.  free is dcx_check_motions_ex's verdict on the same batch (dcx_motion_worst documents that).
+ * The round keeps dcx_rrtstar_run's numbering, its phases 1 (up to the check), 2, 4 and 6, its state and its fixed batches.  elen
+ * holds C (the edge's cost, no longer its length); cost[i] = cost[parent[i]] + elen[i] as before.
+ *   sweeps        - the three batches (R * P, R * P * K, R * P * K edges in (r, p[, j]) order, idle places nodes[r, 0] ->
+ *                   nodes[r, 0]) go through dcx_motion_worst in place of dcx_check_motions_ex; one worst array per batch
+ *   extend        - a slot is a candidate where its edge is free;  C0 = L0 * f(w0),  c0 = cost[near] + C0
+ *   choose parent - place (r, p, j) submits u_j -> x where the lower bound (bits(cost[u_j] + Lj), u_j) < (bits(c0), near).  After
+ *                   the sweep Cj = Lj * f(wj), cj = cost[u_j] + Cj: the parent is the free submitted u_j with the least
+ *                   (bits(cj), u_j) that is still < (bits(c0), near); without one it is near, with C0 and c0
+ *   rewire        - place (r, p, j) submits x -> v where the lower bound cost[x] + L' < cost[v].  After the sweep C' = L' * f(w'),
+ *                   c' = cost[x] + C': the place stays in only where it is free and c' < cost[v]; the least (bits(c'), p) per v
+ *                   wins and sets parent[v] = x, elen[v] = C'
+ * The pruning by the lower bounds is exact: f >= 1 and fp32 products and sums are monotone, so C >= L and cost + C >= cost + L in
+ * bits; a place the bound leaves out could not have won.  gain == 0 gives f == 1 and C == L bit for bit: the submissions, verdicts
+ * and state are dcx_rrtstar_run's own.  No node's cost ever rises and the parent graph stays a tree (the rewire test is still
+ * strict), and the set of nodes still does not depend on the parents.
+ * Status 1 (the caller's, when it initialises the state): a free direct motion is the optimum only where its C has L's bits.  A
+ * caller seeds a free but penalised direct motion as node 1 = goal with elen = cost = C, goal_node = 1, first_round -1 and status
+ * 0: the problem keeps improving on it.
+ * dcx_rrtstar_run_sampled_cost: dcx_rrtstar_run_sampled's sample launch in front of every round.  The informed sampler reads
+ *   state.cost as it does there; its set d(start, x) + d(x, goal) <= c_best stays admissible because C >= L: a path through a
+ *   point outside it is longer than c_best and therefore costs more.
+ * Launches on the caller's stream only, no allocation, no synchronisation, no atomic decides any order, nothing read back: the
+ *   calls can be captured; repeated calls give the same bits, and T rounds in one call equal T calls of one round each.
+ * work: dcx_rrtstar_cost_work_bytes / dcx_rrtstar_sampled_cost_work_bytes: dcx_rrtstar_work_bytes' layout with
+ *   dcx_motion_worst_work_bytes of the larger batch at its head, then the batches' worst arrays and the slots' C0 and c0.
+ * Argument errors: those of dcx_rrtstar_run (dcx_rrtstar_run_sampled); and DCX_ERR_INVALID for NULL cost_opts, an unknown mode,
+ *   gain or band negative or NaN, a reserved field not 0 - all before any device work.  max_samples above 2^24 - 1 and a feature
+ *   width without a worst-sample kernel are DCX_ERR_UNSUPPORTED.  The size queries are 0 for arguments the calls refuse.      */
+#define DCX_RRTSTAR_COST_PEAK 1
+typedef struct dcx_rrtstar_cost_opts {
+    int32_t mode;         /* DCX_RRTSTAR_COST_PEAK, the only mode                                           */
+    float   gain;         /* >= 0: the cost factor's slope per score unit of the hinge                      */
+    float   band;         /* >= 0: how far below the margin a peak starts to cost                           */
+    int32_t reserved0;    /* 0                                                                              */
+    int64_t reserved[2];  /* 0                                                                              */
+} dcx_rrtstar_cost_opts;
+size_t dcx_rrtstar_cost_work_bytes(const dcx_model* m, int64_t R, int32_t slots, int32_t near);
+int dcx_rrtstar_run_cost(const dcx_model* m, const dcx_rrtstar_state* state, int64_t R, const float* goals, const float* samples,
+                         int32_t T, int64_t round0, const dcx_rrtstar_opts* opts, const dcx_rrtstar_cost_opts* cost_opts,
+                         const float* margin, void* work, size_t work_bytes, void* stream);
+size_t dcx_rrtstar_sampled_cost_work_bytes(const dcx_model* m, int64_t R, int32_t slots, int32_t near);
+int dcx_rrtstar_run_sampled_cost(const dcx_model* m, const dcx_rrtstar_state* state, int64_t R, const float* goals,
+                                 const dcx_rrtstar_sample_opts* sample_opts, int32_t T, int64_t round0, const dcx_rrtstar_opts* opts,
+                                 const dcx_rrtstar_cost_opts* cost_opts, const float* margin, void* work, size_t work_bytes,
+                                 float* samples_out, int32_t* info_out, void* stream);
+
 /* ---- batched path shortcutting and RRT path extraction (added under DCX_VERSION 109) ---------------------- */
 /* R piecewise-straight paths simplified in lockstep, P = opts->slots shortcut attempts per path and round: try the straight
  * motion between two waypoints and cut out what lies between (the path simplifier a planner's user expects before the paths go
