@@ -117,6 +117,14 @@ SYMBOLS = {
     "dcx_path_shortcut_partial_work_bytes": (C.c_size_t, [C.c_void_p, C.c_int64, C.c_int32, C.c_int32]),
     "dcx_path_shortcut_partial_run": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, _c_fp, C.c_int32, C.c_void_p, _c_fp, C.c_void_p,
                                                 C.c_size_t, C.c_void_p]),
+    # shortcuts under the clearance objective: both modes with the caller's seg [R, W] after the state and dcx_rrtstar_cost_opts
+    # after the options
+    "dcx_path_shortcut_cost_work_bytes": (C.c_size_t, [C.c_void_p, C.c_int64, C.c_int32]),
+    "dcx_path_shortcut_run_cost": (C.c_int, [C.c_void_p, C.c_void_p, _c_fp, C.c_int64, _c_fp, C.c_int32, C.c_void_p, C.c_void_p, _c_fp,
+                                             C.c_void_p, C.c_size_t, C.c_void_p]),
+    "dcx_path_shortcut_partial_cost_work_bytes": (C.c_size_t, [C.c_void_p, C.c_int64, C.c_int32, C.c_int32]),
+    "dcx_path_shortcut_partial_run_cost": (C.c_int, [C.c_void_p, C.c_void_p, _c_fp, C.c_int64, _c_fp, C.c_int32, C.c_void_p, C.c_void_p,
+                                                     _c_fp, C.c_void_p, C.c_size_t, C.c_void_p]),
     # roadmap queries: min-plus relaxation over the roadmap's CSR for Q start/goal pairs, and their routes as one tensor
     "dcx_sssp_run": (C.c_int, [C.c_int, C.c_void_p, C.c_int64, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p,
                                C.c_void_p]),

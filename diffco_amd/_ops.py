@@ -962,14 +962,19 @@ class ScoreModel:
                                                          C.byref(opt), _ptr(mg), _ptr(work), nbytes, _ptr(samples_out),
                                                          _ptr(info_out), self._st()))
 
-    def shortcut_run(self, state, draws, max_step, max_samples, margin=0., wrap=None, partial=False):
+    def shortcut_run(self, state, draws, max_step, max_samples, margin=0., wrap=None, partial=False, cost=None, seg=None):
         """T rounds of batched path shortcutting (dcx_path_shortcut_run; partial=True: dcx_path_shortcut_partial_run, chords
         between points inside segments, W also the capacity a path may grow into) on the caller's state, in place: `state` maps
         path [R, W, dof] float32, count [R] and accepted [R] (int32) to contiguous tensors on the model's device; draws
         [T, R, P, 2] float32 there.  The rounds are enqueued on torch's current stream; nothing is read back (capturable).
-        `margin` as check_motions."""
+        `margin` as check_motions.
+        cost=(gain, band): the rounds under the clearance objective (dcx_path_shortcut_run_cost / _partial_run_cost: a chord is
+        kept only if it is free and costs less than what it removes, C = L * (1 + gain * max(w + band, 0)) per edge); `seg`
+        [R, W] float32 on the model's device then holds the segments' costs, in place as the rest of the state."""
         if draws.dim() != 4:
             raise ValueError("shortcut_run: draws must be [T, R, P, 2]")
+        if (cost is None) != (seg is None):
+            raise ValueError("shortcut_run: cost=(gain, band) and seg [R, W] go together")
         T, R, P = (int(v) for v in draws.shape[:3])
         path = state["path"]
         if path.dim() != 3:
@@ -983,6 +988,19 @@ class ScoreModel:
         st = _lib.ShortcutState(*(state[n].data_ptr() for n in kinds))
         opt = _lib.ShortcutOpts(float(max_step), int(max_samples), P, W, wrap_mask(wrap, self.dof), (C.c_int64 * 2)(0, 0))
         mg = self._motion_margin(margin)
+        if cost is not None:
+            _check_tensor("shortcut_run: seg", seg, torch.float32, (R, W), self.dev)
+            co = self._rrtstar_cost_opts(*cost)
+            if partial:
+                nbytes = self._lib.dcx_path_shortcut_partial_cost_work_bytes(self._h, R, P, W)
+                run = self._lib.dcx_path_shortcut_partial_run_cost
+            else:
+                nbytes, run = self._lib.dcx_path_shortcut_cost_work_bytes(self._h, R, P), self._lib.dcx_path_shortcut_run_cost
+            work = self._work(nbytes)
+            with _on_device(self.dev):
+                _lib.check(run(self._h, C.byref(st), _ptr(seg), R, _ptr(draws), T, C.byref(opt), C.byref(co), _ptr(mg), _ptr(work),
+                               nbytes, self._st()))
+            return
         if partial:
             nbytes, run = self._lib.dcx_path_shortcut_partial_work_bytes(self._h, R, P, W), self._lib.dcx_path_shortcut_partial_run
         else:

@@ -96,6 +96,26 @@ __device__ __forceinline__ int arc_locate(const float* const c, const int n, con
     return lo;
 }
 
+// THE pick of the partial shortcuts (include/dcx.h, "Partial shortcuts" step 2): the two arc lengths sa <= sb of the draws
+// (u0, u1) on a path of total length L and the segments ea <= eb they fall into; false for an idle slot (a path without an arc
+// length to draw on, a spoilt draw, or ea == eb: a chord inside one straight segment gains nothing)
+template <bool kLds>
+__device__ __forceinline__ bool arc_pick(const float* const c, const int n, const bool live, const float L, const float u0, const float u1,
+                                         int& ea, int& eb, float& sa, float& sb) {
+#pragma clang fp contract(off)
+    ea = -1;
+    eb = -1;
+    sa = 0.0f;
+    sb = 0.0f;
+    if (!(live && u0 >= 0.0f && u0 < 1.0f && u1 >= 0.0f && u1 < 1.0f)) return false;   // (a NaN fails the comparisons)
+    const float s0 = u0 * L, s1 = u1 * L;
+    sa = fminf(s0, s1);
+    sb = fmaxf(s0, s1);
+    ea = arc_locate<kLds>(c, n, sa);
+    eb = arc_locate<kLds>(c, n, sb);
+    return ea != eb;
+}
+
 // coordinate j of that point on segment e: the contract's interpolation (the bits of the segment's end where !(arc < len))
 template <bool kLds>
 __device__ __forceinline__ float arc_point(const float* const row, const float* const c, const float* const ln, const int dof,

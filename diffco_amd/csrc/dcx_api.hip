@@ -25,6 +25,7 @@
 #include "rrtstar_cost_kernel.h"
 #include "shortcut_kernel.h"
 #include "shortcut_partial_kernel.h"
+#include "shortcut_cost_kernel.h"
 #include "resample_kernel.h"
 #include "sssp_kernel.h"
 #include "sssp_lazy_kernel.h"
@@ -2928,19 +2929,21 @@ size_t rrtstar_cost_head(const dcx_model* m, int64_t R, int32_t slots, int32_t n
     return motion_worst_work(m, R * slots * std::max(near, 1)).total;
 }
 
-int rrtstar_cost_checks(const dcx_rrtstar_cost_opts* co) {
-    if (!co) return fail(DCX_ERR_INVALID, "rrtstar: cost options are NULL");
-    if (co->mode != DCX_RRTSTAR_COST_PEAK) return fail(DCX_ERR_INVALID, "rrtstar: the cost mode must be DCX_RRTSTAR_COST_PEAK");
-    if (!(co->gain >= 0.f)) return fail(DCX_ERR_INVALID, "rrtstar: the cost gain must be >= 0");
-    if (!(co->band >= 0.f)) return fail(DCX_ERR_INVALID, "rrtstar: the cost band must be >= 0");
-    if (co->reserved0 || co->reserved[0] || co->reserved[1]) return fail(DCX_ERR_INVALID, "rrtstar: reserved fields of the cost options must be 0");
+// `what`: the caller in the messages (the shortcuts under the objective take the same struct with the same validation)
+int rrtstar_cost_checks(const dcx_rrtstar_cost_opts* co, const char* what = "rrtstar") {
+    const std::string who = std::string(what) + ": ";
+    if (!co) return fail(DCX_ERR_INVALID, who + "cost options are NULL");
+    if (co->mode != DCX_RRTSTAR_COST_PEAK) return fail(DCX_ERR_INVALID, who + "the cost mode must be DCX_RRTSTAR_COST_PEAK");
+    if (!(co->gain >= 0.f)) return fail(DCX_ERR_INVALID, who + "the cost gain must be >= 0");
+    if (!(co->band >= 0.f)) return fail(DCX_ERR_INVALID, who + "the cost band must be >= 0");
+    if (co->reserved0 || co->reserved[0] || co->reserved[1]) return fail(DCX_ERR_INVALID, who + "reserved fields of the cost options must be 0");
     return DCX_OK;
 }
 
 // what dcx_motion_worst could still refuse beyond PlannerCheck::launchable: refused before the first launch
-int rrtstar_cost_launchable(const dcx_model* m, int32_t max_samples) {
-    if (max_samples > kMotionWorstSampleLimit) return fail(DCX_ERR_UNSUPPORTED, "rrtstar: max_samples above 2^24 - 1 under a cost objective");
-    if (!motion_worst_for(m->Dt)) return fail(DCX_ERR_UNSUPPORTED, "rrtstar: no worst-sample kernel for this feature width");
+int rrtstar_cost_launchable(const dcx_model* m, int32_t max_samples, const char* what = "rrtstar") {
+    if (max_samples > kMotionWorstSampleLimit) return fail(DCX_ERR_UNSUPPORTED, std::string(what) + ": max_samples above 2^24 - 1 under a cost objective");
+    if (!motion_worst_for(m->Dt)) return fail(DCX_ERR_UNSUPPORTED, std::string(what) + ": no worst-sample kernel for this feature width");
     return DCX_OK;
 }
 
@@ -3127,47 +3130,119 @@ size_t dcx_path_shortcut_partial_work_bytes(const dcx_model* m, int64_t R, int32
     return shortcut_partial_plan(R, slots, W, m->fk.dof, motion_work(R * slots).total).total;
 }
 
+// the clearance objective of a shortcut call: the cost options and the caller's seg (NULL members are the call's errors)
+struct ShortcutObjective {
+    const dcx_rrtstar_cost_opts* co;
+    float* seg;
+};
+
+// the sizes of the calls under the objective: PlannerCheck::sizes, and the swept batch of R * slots * pieces edges
+static int shortcut_cost_sizes(const dcx_model* m, int64_t R, int32_t slots, int32_t pieces) {
+    if (int rc = kShortcutCheck.sizes(m, R, slots)) return rc;
+    if (R * slots > INT32_MAX / pieces) return fail(DCX_ERR_UNSUPPORTED, "shortcut: more than 2^31 - 1 edges per round");
+    return DCX_OK;
+}
+
+size_t dcx_path_shortcut_cost_work_bytes(const dcx_model* m, int64_t R, int32_t slots) {
+    if (shortcut_cost_sizes(m, R, slots, 1)) return 0;
+    return shortcut_cost_plan(R, slots, 0, m->fk.dof, 1, motion_worst_work(m, R * slots).total).total;
+}
+
+size_t dcx_path_shortcut_partial_cost_work_bytes(const dcx_model* m, int64_t R, int32_t slots, int32_t W) {
+    if (shortcut_cost_sizes(m, R, slots, 3) || shortcut_check_W(W)) return 0;
+    return shortcut_cost_plan(R, slots, W, m->fk.dof, 3, motion_worst_work(m, R * slots * 3).total).total;
+}
+
+// The workspace of a shortcut call, resolved: the offsets the rounds' arguments take, whichever of the three plans laid them out
+// (shortcut_plan, shortcut_partial_plan, shortcut_cost_plan), its size, the size query's name for the message, and the sweep's
+// own workspace at the head
+struct ShortcutWork {
+    size_t qa, qb, first_hit, picks, stage, arc_c, arc_len, total, sweep_bytes;
+    ShortcutCostPlan cost;   // under the objective: worst, widx, len and stage_seg beside the above
+    const char* size_fn;
+};
+
+static ShortcutWork shortcut_work(bool partial, bool priced, const dcx_model* m, int64_t R, const dcx_shortcut_opts* opt, int32_t pieces) {
+    const int64_t E = R * opt->slots * pieces;
+    ShortcutWork w{};
+    if (priced) {
+        w.sweep_bytes = motion_worst_work(m, E).total;
+        const ShortcutCostPlan c = w.cost = shortcut_cost_plan(R, opt->slots, partial ? opt->W : 0, m->fk.dof, pieces, w.sweep_bytes);
+        w.qa = c.qa, w.qb = c.qb, w.picks = c.picks, w.stage = c.stage, w.arc_c = c.arc_c, w.arc_len = c.arc_len, w.total = c.total;
+        w.size_fn = partial ? "dcx_path_shortcut_partial_cost_work_bytes" : "dcx_path_shortcut_cost_work_bytes";
+        return w;
+    }
+    w.sweep_bytes = motion_work(E).total;
+    ShortcutPartialPlan p{};   // (vertex mode: the slot part alone)
+    if (partial) p = shortcut_partial_plan(R, opt->slots, opt->W, m->fk.dof, w.sweep_bytes);
+    else p.total = (p.slot = shortcut_plan(R, opt->slots, m->fk.dof, w.sweep_bytes)).total;
+    w.qa = p.slot.qa, w.qb = p.slot.qb, w.first_hit = p.slot.first_hit, w.picks = p.slot.picks;
+    w.stage = p.stage, w.arc_c = p.c, w.arc_len = p.len, w.total = p.total;
+    w.size_fn = partial ? "dcx_path_shortcut_partial_work_bytes" : "dcx_path_shortcut_work_bytes";
+    return w;
+}
+
+// `obj`: NULL for the length modes (dcx_check_motions_ex between pick and commit), else the objective (dcx_motion_worst between
+// the cost modes' pick and their price-and-commit)
 static int shortcut_run(bool partial, const dcx_model* m, const dcx_shortcut_state* state, int64_t R, const float* draws, int32_t T,
-                        const dcx_shortcut_opts* opt, const float* margin, void* work, size_t work_bytes, void* stream) {
+                        const dcx_shortcut_opts* opt, const float* margin, void* work, size_t work_bytes, void* stream,
+                        const ShortcutObjective* obj = nullptr) {
     // every argument is checked before anything touches the model's device; the partial mode's size query takes W, so it checks
     // W with the sizes, the vertex mode behind max_samples
+    const int32_t pieces = obj && partial ? 3 : 1;
     if (!opt) return fail(DCX_ERR_INVALID, "shortcut: options are NULL");
     if (T < 0) return fail(DCX_ERR_INVALID, "shortcut: T < 0");
-    if (int rc = kShortcutCheck.sizes(m, R, opt->slots)) return rc;
+    if (int rc = obj ? shortcut_cost_sizes(m, R, opt->slots, pieces) : kShortcutCheck.sizes(m, R, opt->slots)) return rc;
     if (int rc = partial ? shortcut_check_W(opt->W) : DCX_OK) return rc;
     if (int rc = kShortcutCheck.sampling(opt->max_step, opt->max_samples)) return rc;
     if (int rc = partial ? DCX_OK : shortcut_check_W(opt->W)) return rc;
     if (opt->reserved[0] || opt->reserved[1]) return fail(DCX_ERR_INVALID, "shortcut: reserved fields must be 0");
     if (int rc = MotionCheck{kShortcutCheck.what}.mask(m, opt->wrap_mask)) return rc;
+    if (int rc = obj ? rrtstar_cost_checks(obj->co, kShortcutCheck.what) : DCX_OK) return rc;
     if (int rc = kShortcutCheck.buffers(R, T, state && state->path && state->count && state->accepted, draws, "draws", work)) return rc;
-    const PlannerEdges ed{m, R * opt->slots, motion_work(R * opt->slots), {0, opt->max_step, opt->max_samples, 0}, margin, work,
-                          opt->wrap_mask, stream};
-    ShortcutPartialPlan plan{};   // (vertex mode: the slot part alone)
-    if (partial) plan = shortcut_partial_plan(R, opt->slots, opt->W, m->fk.dof, ed.mw.total);
-    else plan.total = (plan.slot = shortcut_plan(R, opt->slots, m->fk.dof, ed.mw.total)).total;
-    if (int rc = kShortcutCheck.workspace(R, work_bytes, plan.total,
-                                          partial ? "dcx_path_shortcut_partial_work_bytes" : "dcx_path_shortcut_work_bytes")) return rc;
+    if (obj && R > 0 && !obj->seg) return fail(DCX_ERR_INVALID, "shortcut: seg is NULL");
+    const int64_t E = R * opt->slots * pieces;   // the swept batch
+    const ShortcutWork w = shortcut_work(partial, obj != nullptr, m, R, opt, pieces);
+    if (int rc = kShortcutCheck.workspace(R, work_bytes, w.total, w.size_fn)) return rc;
     if (R == 0 || T == 0) return DCX_OK;
-    if (int rc = kShortcutCheck.launchable(m, ed.E, opt->max_samples)) return rc;
+    if (int rc = obj ? rrtstar_cost_launchable(m, opt->max_samples, kShortcutCheck.what) : DCX_OK) return rc;
+    if (int rc = kShortcutCheck.launchable(m, E, opt->max_samples)) return rc;
     if (int rc = set_device(m->device)) return rc;
     hipStream_t st = (hipStream_t)stream;
     char* base = (char*)work;
+    const dcx_motion_opts mo{0, opt->max_step, opt->max_samples, 0};
     ShortcutPartialArgs a{};
     a.path = state->path;
     a.count = state->count;
     a.accepted = state->accepted;
-    a.qa = (float*)(base + plan.slot.qa);
-    a.qb = (float*)(base + plan.slot.qb);
-    a.first_hit = (int32_t*)(base + plan.slot.first_hit);
-    a.picks = (int32_t*)(base + plan.slot.picks);
-    a.stage = (float*)(base + plan.stage);   // (stage, work_c, work_len, wrap_mask: the partial mode's alone)
-    a.work_c = (float*)(base + plan.c);
-    a.work_len = (float*)(base + plan.len);
+    a.qa = (float*)(base + w.qa);
+    a.qb = (float*)(base + w.qb);
+    a.first_hit = obj ? nullptr : (int32_t*)(base + w.first_hit);   // (the cost modes read the peaks instead)
+    a.picks = (int32_t*)(base + w.picks);
+    a.stage = (float*)(base + w.stage);   // (stage, work_c, work_len: the partial modes' alone)
+    a.work_c = (float*)(base + w.arc_c);
+    a.work_len = (float*)(base + w.arc_len);
     a.wrap_mask = opt->wrap_mask;
     a.R = (int32_t)R;
     a.P = opt->slots;
     a.W = opt->W;
     a.dof = m->fk.dof;
+    if (obj) {
+        const PlannerPeaks pk{m, E, w.sweep_bytes, mo, margin, work, opt->wrap_mask, stream};
+        float* const worst = (float*)(base + w.cost.worst);
+        int32_t* const widx = (int32_t*)(base + w.cost.widx);
+        ShortcutCostArgs c{a, obj->seg, (float*)(base + w.cost.len), worst, (float*)(base + w.cost.stage_seg), obj->co->gain, obj->co->band};
+        for (int32_t t = 0; t < T; ++t) {
+            c.a.draws = draws + (int64_t)t * R * opt->slots * 2;
+            hipError_t e = partial ? launch_shortcut_partial_cost_pick(c, st) : launch_shortcut_cost_pick(c, st);
+            if (e != hipSuccess) return fail_hip(e, partial ? "partial shortcut cost pick launch" : "shortcut cost pick launch");
+            if (int rc = pk.worst(c.a.qa, c.a.qb, worst, widx)) return rc;
+            e = partial ? launch_shortcut_partial_cost_commit(c, st) : launch_shortcut_cost_commit(c, st);
+            if (e != hipSuccess) return fail_hip(e, partial ? "partial shortcut cost commit launch" : "shortcut cost commit launch");
+        }
+        return DCX_OK;
+    }
+    const PlannerEdges ed{m, E, motion_work(E), mo, margin, work, opt->wrap_mask, stream};
     ShortcutArgs v{a.path, a.count, a.accepted, nullptr, a.qa, a.qb, a.first_hit, a.picks, a.R, a.P, a.W, a.dof};   // the vertex mode's
     for (int32_t t = 0; t < T; ++t) {
         a.draws = v.draws = draws + (int64_t)t * ed.E * 2;
@@ -3188,6 +3263,20 @@ int dcx_path_shortcut_run(const dcx_model* m, const dcx_shortcut_state* state, i
 int dcx_path_shortcut_partial_run(const dcx_model* m, const dcx_shortcut_state* state, int64_t R, const float* draws, int32_t T,
                                   const dcx_shortcut_opts* opt, const float* margin, void* work, size_t work_bytes, void* stream) {
     return shortcut_run(true, m, state, R, draws, T, opt, margin, work, work_bytes, stream);
+}
+
+int dcx_path_shortcut_run_cost(const dcx_model* m, const dcx_shortcut_state* state, float* seg, int64_t R, const float* draws, int32_t T,
+                               const dcx_shortcut_opts* opt, const dcx_rrtstar_cost_opts* co, const float* margin, void* work,
+                               size_t work_bytes, void* stream) {
+    const ShortcutObjective obj{co, seg};
+    return shortcut_run(false, m, state, R, draws, T, opt, margin, work, work_bytes, stream, &obj);
+}
+
+int dcx_path_shortcut_partial_run_cost(const dcx_model* m, const dcx_shortcut_state* state, float* seg, int64_t R, const float* draws,
+                                       int32_t T, const dcx_shortcut_opts* opt, const dcx_rrtstar_cost_opts* co, const float* margin,
+                                       void* work, size_t work_bytes, void* stream) {
+    const ShortcutObjective obj{co, seg};
+    return shortcut_run(true, m, state, R, draws, T, opt, margin, work, work_bytes, stream, &obj);
 }
 
 int dcx_rrt_extract_paths(int device, const dcx_rrt_state* state, int64_t R, int32_t cap, int32_t dof, float* path, int32_t* count,

@@ -65,6 +65,59 @@ struct ExtractArgs {
     int32_t R, cap, dof, W;
 };
 
+// THE pick of include/dcx.h's step 1 (dcx_path_shortcut_run and dcx_path_shortcut_run_cost draw the same (i, j) from the same
+// draws): (-1, -1) for an idle slot
+__device__ __forceinline__ void shortcut_pick_ij(const int n, const float u0, const float u1, int& i, int& j) {
+#pragma clang fp contract(off)
+    i = -1;
+    j = -1;
+    if (n >= 3 && u0 >= 0.0f && u0 < 1.0f && u1 >= 0.0f && u1 < 1.0f) {   // (a NaN fails the comparisons)
+        i = min((int)(u0 * (float)(n - 2)), n - 3);
+        const int m = n - 2 - i;
+        j = i + 2 + min((int)(u1 * (float)m), m - 1);
+    }
+}
+
+// THE in-place compaction of the vertex modes: the floats [begin, end) of `row`, `width` floats per entry, moved down past the
+// applied intervals (si, sj) (INT_MAX, INT_MAX where a slot is not applied) in ascending chunks - a chunk is read into registers,
+// one barrier, then written.  An entry never moves up, so what a chunk overwrites has been read by then, by this chunk or an
+// earlier one; an entry's new index is a closed form of the intervals: no scan.  Waypoint k dies where si < k < sj; with
+// kSegments the entries are segments k -> k + 1, which die where si <= k < sj (the chord's own cost goes to si afterwards).
+// Every thread of the block calls it (begin and end are block-uniform).  On return every read of the row is done.
+template <bool kSegments>
+__device__ __forceinline__ void shortcut_compact(float* const row, const int begin, const int end, const int width,
+                                                 const int (&si)[kShortcutMaxSlots], const int (&sj)[kShortcutMaxSlots]) {
+    const int tid = threadIdx.x;
+    for (int base = begin; base < end; base += kShortcutThreads * kShortcutChunk) {
+        float v[kShortcutChunk];
+        int dst[kShortcutChunk];
+#pragma unroll
+        for (int u = 0; u < kShortcutChunk; ++u) {
+            const int at = base + u * kShortcutThreads + tid;
+            dst[u] = -1;
+            v[u] = 0.0f;
+            if (at < end) {
+                const int k = at / width;
+                bool dead = false;
+                int shift = 0;
+#pragma unroll
+                for (int p = 0; p < kShortcutMaxSlots; ++p) {
+                    dead = dead || ((kSegments ? si[p] <= k : si[p] < k) && k < sj[p]);
+                    shift += sj[p] <= k ? sj[p] - si[p] - 1 : 0;
+                }
+                if (!dead) {
+                    v[u] = row[at];
+                    dst[u] = at - shift * width;
+                }
+            }
+        }
+        __syncthreads();
+#pragma unroll
+        for (int u = 0; u < kShortcutChunk; ++u)
+            if (dst[u] >= 0) row[dst[u]] = v[u];
+    }
+}
+
 hipError_t launch_shortcut_pick(const ShortcutArgs& a, hipStream_t stream);
 hipError_t launch_shortcut_commit(const ShortcutArgs& a, hipStream_t stream);
 hipError_t launch_rrt_extract(const ExtractArgs& a, hipStream_t stream);

@@ -6,7 +6,9 @@
 //            slot order by itself (at most 16 * 15 / 2 interval comparisons on uniform values).  A block with nothing applied
 //            leaves at once.  The survivors are moved down in place, in ascending chunks: a chunk is read into registers, one
 //            barrier, then written.  A waypoint never moves up, so what a chunk overwrites has been read by then - by this
-//            chunk or an earlier one - and a waypoint's new index is a closed form of the applied intervals: no scan.
+//            chunk or an earlier one - and a waypoint's new index is a closed form of the applied intervals: no scan.  (The pick
+//            and this compaction are shortcut_kernel.h's shortcut_pick_ij and shortcut_compact: the rounds under the clearance
+//            objective, shortcut_cost_kernels.hip, run the same definitions.)
 //   extract: one wave per problem, a half-wave per tree: each chain is walked once for its depth and once more to write its
 //            rows, the half's lanes across the coordinates.
 // Waypoints are copied, never recomputed, and no atomic decides anything: the state after a round is a function of the state
@@ -26,12 +28,8 @@ __global__ __launch_bounds__(kShortcutThreads) void shortcut_pick_kernel(const S
     const int dof = a.dof;
     const int n = max(0, min(a.count[r], a.W));   // (a count beyond W is the caller's error: never read past the row)
     const float u0 = a.draws[e * 2], u1 = a.draws[e * 2 + 1];
-    int i = -1, j = -1;
-    if (n >= 3 && u0 >= 0.0f && u0 < 1.0f && u1 >= 0.0f && u1 < 1.0f) {   // (a NaN fails the comparisons)
-        i = min((int)(u0 * (float)(n - 2)), n - 3);
-        const int m = n - 2 - i;
-        j = i + 2 + min((int)(u1 * (float)m), m - 1);
-    }
+    int i, j;
+    shortcut_pick_ij(n, u0, u1, i, j);
     // an idle slot: the zero-length edge on the path's first row, one sample, its verdict ignored
     const float* const row = a.path + r * (int64_t)a.W * dof;
     const float* const wa = row + (int64_t)max(i, 0) * dof;
@@ -79,35 +77,7 @@ __global__ __launch_bounds__(kShortcutThreads) void shortcut_commit_kernel(const
 
     // waypoints 0 .. lo stay where they are; the floats of the rest in ascending chunks
     float* const row = a.path + r * (int64_t)a.W * dof;
-    const int end = n * dof;   // (W * dof <= 65536 * DCX_MAX_DOF)
-    for (int base = (lo + 1) * dof; base < end; base += kShortcutThreads * kShortcutChunk) {
-        float v[kShortcutChunk];
-        int dst[kShortcutChunk];
-#pragma unroll
-        for (int u = 0; u < kShortcutChunk; ++u) {
-            const int at = base + u * kShortcutThreads + tid;
-            dst[u] = -1;
-            v[u] = 0.0f;
-            if (at < end) {
-                const int k = at / dof;
-                bool dead = false;
-                int shift = 0;
-#pragma unroll
-                for (int p = 0; p < kShortcutMaxSlots; ++p) {
-                    dead = dead || (si[p] < k && k < sj[p]);
-                    shift += sj[p] <= k ? sj[p] - si[p] - 1 : 0;
-                }
-                if (!dead) {
-                    v[u] = row[at];
-                    dst[u] = at - shift * dof;
-                }
-            }
-        }
-        __syncthreads();
-#pragma unroll
-        for (int u = 0; u < kShortcutChunk; ++u)
-            if (dst[u] >= 0) row[dst[u]] = v[u];
-    }
+    shortcut_compact<false>(row, (lo + 1) * dof, n * dof, dof, si, sj);   // (W * dof <= 65536 * DCX_MAX_DOF)
     __syncthreads();   // every thread has read count[r]
     if (tid == 0) {
         a.count[r] = n - removed;

@@ -39,17 +39,9 @@ __device__ __forceinline__ void partial_slots(const ShortcutPartialArgs& a, cons
         const int end = rem / dof, j = rem - end * dof;
         const int64_t e = r * P + p;
         const float u0 = a.draws[e * 2], u1 = a.draws[e * 2 + 1];
-        bool ok = live && u0 >= 0.0f && u0 < 1.0f && u1 >= 0.0f && u1 < 1.0f;   // (a NaN fails the comparisons)
-        int ea = -1, eb = -1;
-        float sa = 0.0f, sb = 0.0f;
-        if (ok) {
-            const float s0 = u0 * L, s1 = u1 * L;
-            sa = fminf(s0, s1);
-            sb = fmaxf(s0, s1);
-            ea = arc_locate<kLds>(c, n, sa);
-            eb = arc_locate<kLds>(c, n, sb);
-            ok = ea != eb;   // a chord inside one straight segment gains nothing
-        }
+        int ea, eb;
+        float sa, sb;
+        const bool ok = arc_pick<kLds>(c, n, live, L, u0, u1, ea, eb, sa, sb);
         // an idle slot: the zero-length edge on the path's first row, one sample, its verdict ignored
         float v = row[j];
         if (ok) v = end ? arc_point<kLds>(row, c, ln, dof, mask, eb, sb, j) : arc_point<kLds>(row, c, ln, dof, mask, ea, sa, j);

@@ -13,6 +13,13 @@ positions on the path and tries the chord between the two points, inside segment
 removed.  A slot inside two neighbouring segments adds a waypoint: the state's W is then the `capacity` the paths may grow into.
 Only the chord is checked; the two end pieces lie on segments the path already had (the header says what that does not promise).
 
+`objective="clearance"` is both modes under rrt_star's clearance objective (include/dcx.h, "Path shortcuts under the clearance
+objective"; dcx_path_shortcut_run_cost, dcx_path_shortcut_partial_run_cost): an edge with peak w of score - margin costs
+C = L * (1 + gain * max(w + band, 0)), the state carries the segments' costs `seg`, and a slot is applied only where every piece
+it inserts is free and together they cost less than the segments it removes - so the paths keep their distance where the length
+modes skim the obstacle boundary, the partial mode's three pieces are all swept, and a segment that is not free (seg = +inf) is
+repaired by any free chord across it.  The edge sweeps are `motion_worst`'s on either route.
+
 The paths of `rrt.rrt_connect` come as one tensor from `RRTResult.path_tensor()`; what leaves here - one [R, W, dof] tensor with a
 count per path - is what `resample.resample_paths` brings to one waypoint count and `traj.optimize_paths` optimises as R problems
 at once (a single path, read back, is still a valid `init_solution` of `fused_adam_traj_optimize`).
@@ -23,6 +30,7 @@ import torch
 
 from . import _ops
 from .rrt import _Edges, _edge_plan, _f32, _div, _fma32, _fused_model, _length, _sample, _transform_of, _wrap
+from .rrtstar import _FusedPeakEdges, _PeakEdges, _objective
 
 __all__ = ["shortcut_paths", "host_shortcut_paths", "ShortcutResult"]
 
@@ -35,11 +43,14 @@ class ShortcutResult:
     """path [R, W, dof]: row k < count[r] is waypoint k of path r (rows beyond are unspecified);  count [R] int32;  accepted [R]
     int32: the shortcuts applied;  paths: per path a [count, dof] tensor or None where count < 2;  lengths_before, lengths [R]:
     the paths' lengths under the checks' metric before (after `subdivide`, which does not change them) and after (nan without a
-    path);  route: "fused" or "host"."""
+    path);  route: "fused" or "host".  Under objective="clearance" (None under "length"): seg [R, W] float32: for
+    k < count[r] - 1 the cost of segment k -> k + 1 (+inf where it is not free);  costs_before, costs [R] on the CPU: the paths'
+    costs before and after, the serial float32 sum of seg[r, :count[r] - 1] from +0 (clearance_cost_paths' own sum)."""
 
-    def __init__(self, route, path, count, accepted, lengths_before, lengths):
+    def __init__(self, route, path, count, accepted, lengths_before, lengths, seg=None, costs_before=None, costs=None):
         self.route, self.path, self.count, self.accepted = route, path, count, accepted
         self.lengths_before, self.lengths = lengths_before, lengths
+        self.seg, self.costs_before, self.costs = seg, costs_before, costs
         self.paths = [path[r, :n] if n >= 2 else None for r, n in enumerate(count.tolist())]
 
 
@@ -53,6 +64,17 @@ def _lengths(path, count, mask):
     live = torch.arange(W - 1, device=path.device)[None, :] < (count.to(torch.int64)[:, None] - 1)
     total = torch.where(live, seg, torch.zeros_like(seg)).sum(dim=1).cpu()
     return torch.where(count.cpu() >= 2, total, out)
+
+
+def _costs(seg, count):
+    """[R] float32 on the CPU: seg[r, 0] + ... + seg[r, count[r] - 2] added to +0 in ascending order, one float32 sum at a time
+    (a dead entry adds +0: the sum keeps its bits)"""
+    seg, n = seg.cpu(), count.cpu().to(torch.int64)
+    total = torch.zeros(len(seg), dtype=torch.float32)
+    zero = torch.zeros((), dtype=torch.float32)
+    for k in range(max(int(n.max()) - 1, 0) if len(n) else 0):
+        total = total + torch.where(k < n - 1, seg[:, k], zero)
+    return total
 
 
 def _subdivide(p, step, mask):
@@ -113,7 +135,8 @@ class _Pass:
     """what both routes share: the arguments, the state, the draws, the loop"""
 
     def __init__(self, checker, paths, counts, dev, max_step, wrap, slots, rounds, rounds_per_call, sampler, seed, max_samples,
-                 subdivide, partial=False, capacity=None):
+                 subdivide, partial=False, capacity=None, obj=None):
+        self.obj = obj
         self.max_step = float(max_step)
         if not self.max_step > 0:
             raise ValueError("shortcut_paths: max_step must be > 0")
@@ -179,10 +202,25 @@ class _Pass:
             run_chunk(draws)
             g += T
 
+    def form_seg(self, peaks):
+        """the state's seg [R, W] under the objective: ONE motion_worst call (`peaks`: the route's) on the consecutive waypoint
+        pairs, priced by the objective, +inf where a segment is not free (w > 0, or NaN for one over max_samples)"""
+        path, n = self.st["path"], self.st["count"].to(torch.int64)
+        seg = torch.zeros((self.R, self.W), dtype=torch.float32, device=self.dev)
+        live = torch.arange(self.W - 1, device=self.dev)[None, :] + 1 < n[:, None]   # segment k of path r: waypoints k -> k + 1
+        qa, qb = path[:, :-1][live], path[:, 1:][live]
+        if len(qa):
+            w = peaks.worst(qa, qb, qa[:1].expand_as(qa))
+            C = self.obj.price(_length(_ops.wrapped_delta(qa, qb, self.mask)), w)
+            seg[:, :-1][live] = torch.where(w <= 0, C, torch.full_like(C, float("inf")))
+        self.st["seg"] = seg
+        self.costs_before = _costs(seg, self.st["count"])
+
     def result(self, route):
         st = self.st
+        cost = () if self.obj is None else (st["seg"], self.costs_before, _costs(st["seg"], st["count"]))
         return ShortcutResult(route, st["path"], st["count"], st["accepted"], self.lengths_before,
-                              _lengths(st["path"], st["count"], self.mask))
+                              _lengths(st["path"], st["count"], self.mask), *cost)
 
 
 def _pick(count, u):
@@ -337,19 +375,148 @@ def _host_round_partial(ps, edges, u, record=None):
     st["accepted"] += applied.sum(dim=1).to(torch.int32)
 
 
+def _span_cost(seg, a, b, live):
+    """old [R, P]: seg[r, a] + seg[r, a + 1] + ... + seg[r, b] where `live` (a <= b there), ascending from seg[r, a], one float32
+    sum at a time; +0 elsewhere (two read-backs: the columns the live spans cover)"""
+    old = torch.zeros(a.shape, dtype=torch.float32, device=seg.device)
+    if not bool(live.any()):
+        return old
+    lo, hi = int(a[live].min()), int(b[live].max())
+    for k in range(lo, hi + 1):
+        s = seg[:, k:k + 1].expand_as(old)
+        old = torch.where(live & (a == k), s, torch.where(live & (a < k) & (k <= b), old + s, old))
+    return old
+
+
+def _host_round_cost(ps, peaks, u, record=None):
+    """one round of the vertex contract under the objective on the state tensors, in place"""
+    st, R, P, W, dof = ps.st, ps.R, ps.P, ps.W, ps.dof
+    path, seg, dev = st["path"], st["seg"], ps.dev
+    i, j, live = _pick(st["count"], u)
+    r_all = torch.arange(R, device=dev)[:, None]
+    root = path[:, :1].expand(R, P, dof)
+    qa = torch.where(live[..., None], path[r_all, i], root)
+    qb = torch.where(live[..., None], path[r_all, j], root)
+    w = peaks.worst(qa.reshape(-1, dof), qb.reshape(-1, dof), root.reshape(-1, dof)).reshape(R, P)
+    C = ps.obj.price(_length(_ops.wrapped_delta(qa, qb, ps.mask)), w)
+    old = _span_cost(seg, i, j - 1, live)
+    free = live & (w <= 0)
+    gainful = free & (C < old)                                                       # (strict: a NaN fails it)
+    applied = torch.zeros_like(free)
+    for p in range(P):   # slot order: a gainful slot is applied iff it crosses none that was applied before it
+        ok = gainful[:, p].clone()
+        for q in range(p):
+            ok &= ~applied[:, q] | (j[:, p] <= i[:, q]) | (j[:, q] <= i[:, p])
+        applied[:, p] = ok
+    if record is not None:
+        record(live, w, free, applied, dict(i=i, j=j, cost=C, old=old, gainful=gainful))
+    n = st["count"].to(torch.int64)[:, None]
+    k = torch.arange(W, device=dev)[None, :, None]                                   # [1, W, 1]
+    ia, ja, on = i[:, None, :], j[:, None, :], applied[:, None, :]                   # [R, 1, P]
+    dead = (on & (ia < k) & (k < ja)).any(dim=2)                                     # [R, W]
+    shift = torch.where(on & (ja <= k), ja - ia - 1, torch.zeros_like(ja)).sum(dim=2)
+    keep = ~dead & (k[:, :, 0] < n)
+    keep_seg = keep & ~(on & (ia == k)).any(dim=2) & (k[:, :, 0] < n - 1)            # both ends survive, and not an applied i
+    rr, kk = torch.nonzero(keep, as_tuple=True)
+    moved = path[rr, kk]   # (a copy: read before anything is written)
+    rs, ks = torch.nonzero(keep_seg, as_tuple=True)
+    moved_seg = seg[rs, ks]
+    ra, pa = torch.nonzero(applied, as_tuple=True)
+    path[rr, kk - shift[rr, kk]] = moved
+    seg[rs, ks - shift[rs, ks]] = moved_seg
+    seg[ra, i[ra, pa] - shift[ra, i[ra, pa]]] = C[ra, pa]
+    st["count"].copy_(keep.sum(dim=1).to(torch.int32))
+    st["accepted"] += applied.sum(dim=1).to(torch.int32)
+
+
+def _host_round_partial_cost(ps, peaks, u, record=None):
+    """one round of the partial contract under the objective on the state tensors, in place"""
+    st, R, P, W, dof = ps.st, ps.R, ps.P, ps.W, ps.dof
+    path, seg, dev = st["path"], st["seg"], ps.dev
+    n = st["count"].to(torch.int64).clamp(min=0, max=W)
+    arc = _arc_length(path, n, ps.mask)
+    L = arc[3].gather(1, (n - 1).clamp(min=0)[:, None])[:, 0]
+    has = (n >= 3) & (L > 0) & (L < float("inf"))                                    # (a NaN fails it)
+    u0, u1 = u[..., 0], u[..., 1]
+    drawn = has[:, None] & (u0 >= 0) & (u0 < 1) & (u1 >= 0) & (u1 < 1)
+    zero = torch.zeros((), dtype=torch.float32, device=dev)
+    Lz = torch.where(has, L, zero)[:, None]
+    s0, s1 = torch.where(drawn, u0, zero) * Lz, torch.where(drawn, u1, zero) * Lz
+    sa, sb = torch.minimum(s0, s1), torch.maximum(s0, s1)
+    e, pts = _arc_points(path, n, arc, torch.cat([sa, sb], dim=1), has, ps.mask)
+    ea, eb, xa, xb = e[:, :P], e[:, P:], pts[:, :P], pts[:, P:]
+    live = drawn & (ea != eb)
+    r_all = torch.arange(R, device=dev)[:, None]
+    root = path[:, :1].expand(R, P, dof)
+    wa, wb = path[r_all, ea], path[r_all, (eb + 1).clamp(max=W - 1)]
+    # the three pieces of a slot: path[ea] -> xa, xa -> xb, xb -> path[eb + 1]
+    qa = torch.where(live[..., None, None], torch.stack([wa, xa, xb], dim=2), root[:, :, None, :])   # [R, P, 3, dof]
+    qb = torch.where(live[..., None, None], torch.stack([xa, xb, wb], dim=2), root[:, :, None, :])
+    w = peaks.worst(qa.reshape(-1, dof), qb.reshape(-1, dof), root[:, :, None, :].expand(R, P, 3, dof).reshape(-1, dof)).reshape(R, P, 3)
+    C = ps.obj.price(_length(_ops.wrapped_delta(qa, qb, ps.mask)), w)                # [R, P, 3]
+    new = (C[..., 0] + C[..., 1]) + C[..., 2]
+    old = _span_cost(seg, ea, eb, live)
+    free = live & (w <= 0).all(dim=2)
+    gainful = free & (new < old)                                                     # (strict: a NaN fails it)
+    applied, apart, cnt = torch.zeros_like(free), torch.zeros_like(free), n.clone()
+    grow = 2 - (eb - ea)
+    for p in range(P):   # slot order: a gainful slot is applied iff it shares no segment with an applied one and the path has room
+        ok = gainful[:, p].clone()
+        for q in range(p):
+            ok &= ~applied[:, q] | (eb[:, p] < ea[:, q]) | (eb[:, q] < ea[:, p])
+        apart[:, p] = ok
+        ok = ok & (cnt + grow[:, p] <= W)
+        applied[:, p] = ok
+        cnt = torch.where(ok, cnt + grow[:, p], cnt)
+    if record is not None:
+        record(live, w, free, applied, dict(drawn=drawn, ea=ea, eb=eb, apart=apart, has=has, xa=xa, xb=xb, cost=new, pieces=C, old=old,
+                                               gainful=gainful))
+    k = torch.arange(W, device=dev)[None, :, None]                                   # [1, W, 1]
+    a3, b3, on = ea[:, None, :], eb[:, None, :], applied[:, None, :]                 # [R, 1, P]
+    dead = (on & (a3 < k) & (k <= b3)).any(dim=2)                                    # [R, W]
+    shift = torch.where(on & (b3 < k), 2 - (b3 - a3), torch.zeros_like(b3)).sum(dim=2)
+    keep = ~dead & (k[:, :, 0] < n[:, None])
+    keep_seg = ~(on & (a3 <= k) & (k <= b3)).any(dim=2) & (k[:, :, 0] < n[:, None] - 1)
+    rr, kk = torch.nonzero(keep, as_tuple=True)
+    moved = path[rr, kk]   # (a copy: read before anything is written; xa and xb are no views of the path either)
+    rs, ks = torch.nonzero(keep_seg, as_tuple=True)
+    moved_seg = seg[rs, ks]
+    ra, pa = torch.nonzero(applied, as_tuple=True)
+    at = ea[ra, pa] + shift[ra, ea[ra, pa]]   # the new index of waypoint ea
+    path[rr, kk + shift[rr, kk]] = moved
+    path[ra, at + 1] = xa[ra, pa]
+    path[ra, at + 2] = xb[ra, pa]
+    seg[rs, ks + shift[rs, ks]] = moved_seg
+    for piece in range(3):
+        seg[ra, at + piece] = C[ra, pa, piece]
+    st["count"].copy_(cnt.to(torch.int32))
+    st["accepted"] += applied.sum(dim=1).to(torch.int32)
+
+
 def host_shortcut_paths(checker, paths, counts=None, *, max_step, wrap=None, slots=4, rounds=64, rounds_per_call=32, sampler=None,
-                        seed=0, margin=0., max_samples=None, subdivide=None, partial=False, capacity=None, _record=None):
+                        seed=0, margin=0., max_samples=None, subdivide=None, partial=False, capacity=None, objective="length",
+                        clearance_gain=1.0, clearance_band=None, _record=None):
     """shortcut_paths' contract as the loop a user would write from the library's other calls: per round the pick and the
     compaction as torch indexing, ONE `checker.check_motions(..., return_first=True)` call on the fixed batch of R * slots
     edges.  The state lives on the device of the paths.  `margin` is passed on to the checker's check_motions only where it is
     not 0.  partial, capacity: as shortcut_paths' (the partial contract in torch ops, one rounded fp32 operation at a time and
-    the arc length in the resampler's association; `_record` then gets a fifth argument, the round's drawn, ea, eb, apart, has)."""
+    the arc length in the resampler's association; `_record` then gets a fifth argument, the round's drawn, ea, eb, apart, has).
+    objective, clearance_gain, clearance_band: as shortcut_paths'; under "clearance" the one call per round is
+    `checker.motion_worst` (a TypeError for a checker without it) on the R * slots (partial: R * slots * 3) edges, every cost one
+    rounded fp32 operation at a time, and `_record` gets (live, worst, free, applied, info): info holds the round's cost (C, or
+    new = (C0 + C1) + C2), old and the gainful mask beside the picks."""
+    obj = _objective("shortcut_paths", objective, clearance_gain, clearance_band)
     first = paths if torch.is_tensor(paths) else next((p for p in paths if p is not None), None)
     dev = torch.as_tensor(first).device if first is not None else torch.device("cpu")
     ps = _Pass(checker, paths, counts, dev, max_step, wrap, slots, rounds, rounds_per_call, sampler, seed, max_samples, subdivide,
-               partial, capacity)
-    edges = _Edges(checker, ps.max_step, ps.max_samples, ps.mask, margin)
-    one_round = _host_round_partial if ps.partial else _host_round
+               partial, capacity, obj)
+    if obj is None:
+        edges = _Edges(checker, ps.max_step, ps.max_samples, ps.mask, margin)
+        one_round = _host_round_partial if ps.partial else _host_round
+    else:
+        edges = _PeakEdges("shortcut_paths", checker, ps.max_step, ps.max_samples, ps.mask, margin)
+        ps.form_seg(edges)
+        one_round = _host_round_partial_cost if ps.partial else _host_round_cost
 
     def run_chunk(draws):
         for u in draws:
@@ -360,7 +527,8 @@ def host_shortcut_paths(checker, paths, counts=None, *, max_step, wrap=None, slo
 
 
 def shortcut_paths(checker, paths, counts=None, *, max_step, wrap=None, slots=4, rounds=64, rounds_per_call=32, sampler=None,
-                   seed=0, margin=0., max_samples=None, subdivide=None, partial=False, capacity=None):
+                   seed=0, margin=0., max_samples=None, subdivide=None, partial=False, capacity=None, objective="length",
+                   clearance_gain=1.0, clearance_band=None):
     """Shorten R piecewise-straight paths under `checker` by random shortcuts - between waypoints, or with partial=True between
     points inside segments: a ShortcutResult.
     paths: a list of [W_r, dof] tensors or None, or a [R, W, dof] tensor with counts [R];  max_step: the stride of every edge
@@ -373,6 +541,12 @@ def shortcut_paths(checker, paths, counts=None, *, max_step, wrap=None, slots=4,
     the chord between the two points (it cuts corners; only the chord is checked, the end pieces lie on segments the path had);
     capacity (partial only): the rows W of a path, which a slot inside two neighbouring segments grows by one - at least the
     longest path, at most 65536, default the longest path + 16.
+    objective="clearance" (with clearance_gain >= 0 and clearance_band > 0, rrt_star's names and meaning): an edge with peak w of
+    score - margin costs L * (1 + clearance_gain * max(w + clearance_band, 0)), and a slot is applied only where every piece it
+    inserts is free and together they cost less than the segments they replace (in the partial mode all three pieces are swept).
+    The result then carries seg, costs_before and costs; a segment that is not free costs +inf, so any free chord across it
+    repairs it.  clearance_gain=0 prices length alone but is not objective="length": that applies every free chord, this only
+    those that shorten the path.  The checker needs `motion_worst`.
     The fused pass (result.route == "fused") runs for kernel_perceptrons.DiffCo, RBFDiffCo and ForwardKinematicsDiffCo whose
     transform fuses, on paths that are on the GPU; everything else goes through host_shortcut_paths ("host")."""
     first = paths if torch.is_tensor(paths) else next((p for p in paths if p is not None), None)
@@ -381,7 +555,9 @@ def shortcut_paths(checker, paths, counts=None, *, max_step, wrap=None, slots=4,
     if got is None:
         return host_shortcut_paths(checker, paths, counts, max_step=max_step, wrap=wrap, slots=slots, rounds=rounds,
                                    rounds_per_call=rounds_per_call, sampler=sampler, seed=seed, margin=margin,
-                                   max_samples=max_samples, subdivide=subdivide, partial=partial, capacity=capacity)
+                                   max_samples=max_samples, subdivide=subdivide, partial=partial, capacity=capacity,
+                                   objective=objective, clearance_gain=clearance_gain, clearance_band=clearance_band)
+    obj = _objective("shortcut_paths", objective, clearance_gain, clearance_band)
     model, base = got
     if isinstance(base, (int, float)) and isinstance(margin, (int, float)):
         mg = float(base) + float(margin)
@@ -389,12 +565,16 @@ def shortcut_paths(checker, paths, counts=None, *, max_step, wrap=None, slots=4,
         mg = (torch.as_tensor(base, dtype=torch.float32).reshape(-1).to(model.dev)
               + torch.as_tensor(margin, dtype=torch.float32).reshape(-1).to(model.dev))
     ps = _Pass(checker, paths, counts, model.dev, max_step, wrap, slots, rounds, rounds_per_call, sampler, seed, max_samples, subdivide,
-               partial, capacity)
+               partial, capacity, obj)
     mg_dev = model._motion_margin(mg)   # on the device once: no copy from the host per chunk
+    cost_kw = {}
+    if obj is not None:
+        ps.form_seg(_FusedPeakEdges(model, ps.max_step, ps.max_samples, ps.mask, 0. if mg_dev is None else mg_dev))
+        cost_kw = dict(cost=(obj.gain, obj.band), seg=ps.st["seg"])
 
     def run_chunk(draws):
         model.shortcut_run(ps.st, draws, ps.max_step, ps.max_samples, margin=0. if mg_dev is None else mg_dev, wrap=ps.mask,
-                           partial=ps.partial)
+                           partial=ps.partial, **cost_kw)
 
     ps.loop(run_chunk)
     return ps.result("fused")

@@ -1092,6 +1092,77 @@ size_t dcx_path_shortcut_partial_work_bytes(const dcx_model* m, int64_t R, int32
 int dcx_path_shortcut_partial_run(const dcx_model* m, const dcx_shortcut_state* state, int64_t R, const float* draws, int32_t T,
                                   const dcx_shortcut_opts* opts, const float* margin, void* work, size_t work_bytes, void* stream);
 
+/* Path shortcuts under the clearance objective: both modes above with a round that prices what it removes against what it
+ * inserts and keeps a chord only if it costs less.  The length modes skim the obstacle boundary - they optimise length alone; here
+ * a chord that runs closer to an obstacle than the corner it cuts is turned down.  The objective is "batched RRT*:
+ * clearance-weighted edge costs"' own and travels in its struct, dcx_rrtstar_cost_opts, with its validation (mode
+ * DCX_RRTSTAR_COST_PEAK, gain >= 0, band >= 0, reserved fields 0): an edge submitted to dcx_motion_worst with the closed max_step
+ * rule, max_samples, margin and wrap_mask of the options and no gradients, w = its worst, L = the motion calls' own length bits
+ * (wrapped deltas, squares summed from +0 in coordinate order, a correctly rounded sqrt), is free iff w <= 0 and costs
+ *   C = L * (1 + gain * fmaxf(w + band, +0))
+ * every operation fp32 and rounded alone, never contracted.  dcx_path_shortcut_run, dcx_path_shortcut_partial_run, their state, their
+ * options and their workspaces are unchanged.
+ * State: dcx_shortcut_state, and one more caller-owned device array
+ *   seg [R, W] float                for k < count[r] - 1 the cost of segment k -> k + 1; entries at and beyond count[r] - 1 are
+ *                                   unspecified
+ * which the caller initialises from ONE dcx_motion_worst call on the consecutive waypoint pairs (same rule, max_samples, margin,
+ * wrap_mask, no gradients): seg = C where the segment is free, +inf where it is not (w > 0, or NaN for a segment over max_samples).
+ * An unfree segment therefore costs more than any free replacement: the rounds repair a path as well as improve it.  A NaN in seg
+ * is the caller's error; no slot whose removed span holds one is applied (C < old is false).
+ * The bits of a seg entry are those of the batch that priced it.  dcx_motion_worst derives its launch geometry from the batch's
+ * size and max_samples, and on models large enough for that to change how a score is summed, the same edge swept in a batch of
+ * another size can answer a peak a few units in the last place away.  An entry is thus, bit for bit, the price of its segment
+ * swept in a batch of the size of the call that formed seg or of a round's batch (R * P, R * P * 3 edges) under the same
+ * max_samples - which of the two, the rounds decide; a referee that submits the same batches gets the same bits.
+ * Vertex mode, dcx_path_shortcut_run_cost; round t, path r, slot p:
+ *   1. pick: dcx_path_shortcut_run's step 1, word for word: the same draws give the same (i, j), an idle slot (-1, -1).
+ *   2. sweep: the R * P edges path[r, i] -> path[r, j] in (r, p) order go through dcx_motion_worst; an idle slot submits
+ *      path[r, 0] -> path[r, 0].  A fixed batch: the launch geometry does not depend on the state.
+ *   3. price: w = the edge's worst; the slot is free iff w <= 0.  C as above.  old = seg[i] + seg[i + 1] + ... + seg[j - 1], added
+ *      in ascending order starting from seg[i].  The slot is gainful iff it is free and C < old (strict: a NaN fails it).
+ *   4. apply: slots are taken in ascending order; a gainful slot is applied iff it satisfies step 3's disjointness rule of
+ *      dcx_path_shortcut_run against every slot already applied: j_p <= i_q || j_q <= i_p.
+ *   5. compact: the waypoints move exactly as in dcx_path_shortcut_run's step 4, and seg with them: segment k survives iff both its
+ *      ends survive and it is not the i of an applied slot, and moves to the new index of waypoint k; the segment at the new index
+ *      of an applied i takes that slot's C.  count and accepted as there.
+ * Partial mode, dcx_path_shortcut_partial_run_cost: steps 1 and 2 (arc length, pick) are dcx_path_shortcut_partial_run's, word for
+ * word, and give (ea, xa), (eb, xb).  Then
+ *   3. sweep: three edges per slot, R * P * 3 in (r, p, piece) order: piece 0 path[ea] -> xa, piece 1 xa -> xb, piece 2
+ *      xb -> path[eb + 1]; an idle slot submits path[r, 0] -> path[r, 0] three times.
+ *   4. price: new = (C0 + C1) + C2; old = seg[ea] + ... + seg[eb], ascending from seg[ea].  The slot is gainful iff all three pieces
+ *      are free and new < old.  A zero-length piece (xa with the bits of a waypoint) prices as L = 0, C = 0 and is free iff the
+ *      score at that point is <= 0.
+ *   5. apply and rewrite: dcx_path_shortcut_partial_run's steps 4 and 5 (no shared segment, the capacity bound, slot order) with
+ *      "gainful" for "free".  seg is rewritten with the rows: a surviving segment moves with its first waypoint, the three new
+ *      segments take C0, C1, C2 at the new indices of ea, xa and xb.
+ *   All three pieces are swept and priced, so what "Only the new middle edge is checked" says of the length mode does not hold
+ *   here: a path whose seg is finite keeps every segment free under the sweep that priced it.
+ * gain == 0 gives C == L bit for bit.  The rounds are still not the length modes': those apply every free chord, these apply only
+ *   chords with C < old - the never-lengthening variant (a free chord between two points of a polyline is never longer than the
+ *   polyline in exact arithmetic, but the length modes also apply one that ties, or loses by a rounding, or replaces unfree
+ *   segments; here the comparison decides).
+ * Both calls enqueue T rounds on the caller's stream: per round one pick launch, the launches of dcx_motion_worst, one
+ *   price-and-commit launch.  No allocation, no synchronisation, no atomic decides any order, nothing read back: the calls can be
+ *   captured; repeated calls give the same bits, and T rounds in one call equal T calls of one round each.  draws and margin as
+ *   dcx_path_shortcut_run's.
+ * work: dcx_path_shortcut_cost_work_bytes(model, R, slots) / dcx_path_shortcut_partial_cost_work_bytes(model, R, slots, W) bytes
+ *   of device memory, the caller's: dcx_motion_worst_work_bytes of the batch (R * slots, R * slots * 3 edges) at the head, then
+ *   the edge batch, its worst and worst_idx, the pieces' L and the picks; the partial mode adds the [R, W, dof] stage of the
+ *   rewritten rows, the [R, W] stage of their seg and, for W above what a block's LDS holds, c and len [R, W].  Both are 0 for
+ *   arguments the calls refuse and non-decreasing in their arguments.
+ * Argument errors, all before any device work: everything dcx_path_shortcut_run (dcx_path_shortcut_partial_run) refuses, with
+ *   work_bytes below the size query of the call; DCX_ERR_INVALID for NULL seg with R > 0, for NULL cost_opts, an unknown mode, gain
+ *   or band negative or NaN, a reserved field of it not 0.  max_samples above 2^24 - 1, a feature width without a worst-sample
+ *   kernel and more than 2^31 - 1 swept edges per round are DCX_ERR_UNSUPPORTED.  R = 0 or T = 0 launches nothing.             */
+size_t dcx_path_shortcut_cost_work_bytes(const dcx_model* m, int64_t R, int32_t slots);
+int dcx_path_shortcut_run_cost(const dcx_model* m, const dcx_shortcut_state* state, float* seg, int64_t R, const float* draws, int32_t T,
+                               const dcx_shortcut_opts* opts, const dcx_rrtstar_cost_opts* cost_opts, const float* margin, void* work,
+                               size_t work_bytes, void* stream);
+size_t dcx_path_shortcut_partial_cost_work_bytes(const dcx_model* m, int64_t R, int32_t slots, int32_t W);
+int dcx_path_shortcut_partial_run_cost(const dcx_model* m, const dcx_shortcut_state* state, float* seg, int64_t R, const float* draws,
+                                       int32_t T, const dcx_shortcut_opts* opts, const dcx_rrtstar_cost_opts* cost_opts,
+                                       const float* margin, void* work, size_t work_bytes, void* stream);
+
 /* ---- roadmap queries (added under DCX_VERSION 109) -------------------------------------------------------- */
 /* Shortest paths over a roadmap for Q start/goal pairs at once: synchronous min-plus relaxation in fp32 without atomics
  * (dcx_sssp_run), then the routes as rows of one [Q, W, dof] tensor (dcx_sssp_extract_paths), on `device`, without a model.
