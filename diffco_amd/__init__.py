@@ -29,5 +29,8 @@ from . import shortcut  # noqa: F401
 from .shortcut import shortcut_paths, host_shortcut_paths, ShortcutResult  # noqa: F401
 from . import resample  # noqa: F401
 from .resample import resample_paths, host_resample_paths, ResampleResult  # noqa: F401
+from . import geometry  # noqa: F401
+from .geometry import (World, RobotSpheres, SphereWorldChecker, host_clearance_points, spheres_on_control_points,  # noqa: F401
+                       spheres_along_links)
 
-__all__ = ["resample", "resample_paths", "host_resample_paths", "ResampleResult", "optimize_paths", "shortcut", "shortcut_paths", "host_shortcut_paths", "ShortcutResult", "rrt","rrt_connect", "host_rrt_connect", "RRTResult", "rrtstar", "rrt_star", "host_rrt_star", "clearance_cost_paths", "RRTStarResult", "kernel", "model", "utils", "optim", "sharded", "traj", "escape", "fused_adam_traj_optimize", "roadmap", "Roadmap", "knn", "knn_edges", "urdf", "URDFRobotFK", "MultiURDFRobotFK", "collision_checkers", "RBFDiffCo", "ForwardKinematicsDiffCo", "HybridForwardKinematicsDiffCo", "deprecated", "DiffCo", "MultiDiffCo", "DiffCoBeta"]
+__all__ = ["geometry", "World", "RobotSpheres", "SphereWorldChecker", "host_clearance_points", "spheres_on_control_points", "spheres_along_links", "resample", "resample_paths", "host_resample_paths", "ResampleResult", "optimize_paths", "shortcut", "shortcut_paths", "host_shortcut_paths", "ShortcutResult", "rrt","rrt_connect", "host_rrt_connect", "RRTResult", "rrtstar", "rrt_star", "host_rrt_star", "clearance_cost_paths", "RRTStarResult", "kernel", "model", "utils", "optim", "sharded", "traj", "escape", "fused_adam_traj_optimize", "roadmap", "Roadmap", "knn", "knn_edges", "urdf", "URDFRobotFK", "MultiURDFRobotFK", "collision_checkers", "RBFDiffCo", "ForwardKinematicsDiffCo", "HybridForwardKinematicsDiffCo", "deprecated", "DiffCo", "MultiDiffCo", "DiffCoBeta"]

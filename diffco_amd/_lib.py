@@ -87,6 +87,9 @@ SYMBOLS = {
     "dcx_knn_work_bytes": (C.c_size_t, [C.c_int64, C.c_int64, C.c_int32, C.c_int32]),
     "dcx_knn": (C.c_int, [C.c_int, _c_fp, C.c_int64, _c_fp, C.c_int64, C.c_int32, C.c_void_p, _c_fp, _c_fp, C.c_void_p, C.c_size_t,
                           C.c_void_p]),
+    # geometric ground truth: the robot's spheres against a world of primitives (no model)
+    "dcx_geom_clearance": (C.c_int, [C.c_int, C.POINTER(FkDesc), _c_fp, C.c_void_p, C.c_int64, _c_fp, C.c_int64, C.c_void_p, _c_fp,
+                                     C.c_void_p, _c_fp, C.c_void_p]),
     # batched RRT-Connect: R trees grown in lockstep over the kNN metric and the motion checks
     "dcx_rrt_work_bytes": (C.c_size_t, [C.c_void_p, C.c_int64, C.c_int32]),
     "dcx_rrt_connect_run": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, _c_fp, C.c_int32, C.c_int64, C.c_void_p, _c_fp, C.c_void_p,
@@ -184,6 +187,19 @@ class KnnOpts(C.Structure):
     """ctypes mirror of dcx_knn_opts (include/dcx.h)"""
     _fields_ = [("k", C.c_int32), ("reserved0", C.c_int32), ("wrap_mask", C.c_uint64), ("max_dist2", C.c_float),
                 ("reserved1", C.c_int32), ("self_offset", C.c_int64), ("reserved", C.c_int64 * 2)]
+
+
+GEOM_SPHERE, GEOM_BOX, GEOM_CAPSULE, GEOM_CYLINDER = range(4)   # DCX_GEOM_*
+
+
+class GeomObstacle(C.Structure):
+    """ctypes mirror of dcx_geom_obstacle (include/dcx.h): one 64-byte row"""
+    _fields_ = [("type_group", C.c_int32), ("rt", C.c_float * 9), ("c", C.c_float * 3), ("p", C.c_float * 3)]
+
+
+class GeomOpts(C.Structure):
+    """ctypes mirror of dcx_geom_opts (include/dcx.h)"""
+    _fields_ = [("n_groups", C.c_int32), ("sphere_base", C.c_int32), ("accumulate", C.c_int32), ("reserved", C.c_int32)]
 
 
 RRT_MAX_SLOTS = 16        # DCX_RRT_MAX_SLOTS

@@ -312,6 +312,44 @@ def knn(queries, points, k, wrap=None, max_dist=None, exclude_self=False, self_o
     return idx, dist2
 
 
+def geom_clearance(desc: FkDesc, radii, obstacles, q, n_groups=1, sphere_base=0, accumulate=False, clearance=None, witness=None,
+                   grad=None, want_witness=True, want_grad=False, check_groups=True):
+    """dcx_geom_clearance: the spheres of `desc` (its control points, radii [M] float32 on the device) against `obstacles`
+    ([O, 16] float32 rows of dcx_geom_obstacle on the device) for q [B, dof] float32 on the device ->
+    (clearance [B, G] float32, witness [B, G, 2] int32 or None, grad [B, dof] float32 or None).  `accumulate`: the three
+    tensors are an earlier chunk's results and are updated in place (entries only where this chunk is strictly smaller).
+    `check_groups`: the rows' group ids are read back (one small reduction) and one at or above n_groups raises - the kernel
+    would ignore such rows; pass False where the groups are known (geometry.SphereWorldChecker checks its World on the host)
+    or where the call must not synchronise."""
+    lib = _lib.require_gpu()
+    dev = q.device
+    B, G, O = len(q), int(n_groups), len(obstacles)
+    _check_tensor("geom_clearance: q", q, torch.float32, (B, desc.dof), dev)
+    _check_tensor("geom_clearance: radii", radii, torch.float32, (desc.n_points,), dev)
+    _check_tensor("geom_clearance: obstacles", obstacles, torch.float32, (O, 16), dev)
+    if accumulate and clearance is None:
+        raise ValueError("geom_clearance: accumulate needs the earlier call's tensors")
+    if clearance is None:
+        clearance = torch.empty((B, G), device=dev, dtype=torch.float32)
+        witness = torch.empty((B, G, 2), device=dev, dtype=torch.int32) if want_witness else None
+        grad = torch.empty((B, desc.dof), device=dev, dtype=torch.float32) if want_grad else None
+    _check_tensor("geom_clearance: clearance", clearance, torch.float32, (B, G), dev)
+    if witness is not None:
+        _check_tensor("geom_clearance: witness", witness, torch.int32, (B, G, 2), dev)
+    if grad is not None:
+        _check_tensor("geom_clearance: grad", grad, torch.float32, (B, desc.dof), dev)
+    if check_groups and O:
+        top = int((obstacles.view(torch.int32)[:, 0] >> 8).max())
+        low = int((obstacles.view(torch.int32)[:, 0] >> 8).min())
+        if top >= G or low < 0:
+            raise ValueError(f"geom_clearance: an obstacle row has group {top if top >= G else low}, outside [0, n_groups = {G})")
+    opt = _lib.GeomOpts(G, int(sphere_base), int(bool(accumulate)), 0)
+    with _on_device(dev):
+        _lib.check(lib.dcx_geom_clearance(dev.index, C.byref(desc), _ptr(radii), _ptr(obstacles), O, _ptr(q), B, C.byref(opt),
+                                          _ptr(clearance), _ptr(witness), _ptr(grad), _stream(dev)))
+    return clearance, witness, grad
+
+
 def _check_tensor(label, t, dtype, shape, dev, kind=None):
     """raises ValueError unless t is a contiguous `dtype` tensor of `shape` on `dev`.  `label`: how the message names it;
     `kind`: how it names the expected tensor where that is not "<dtype> tensor <shape>"."""

@@ -9,9 +9,10 @@ tutorial's
     fkdc.collision_score(q)                   # differentiable, one fused HIP launch
 
 runs with `perceptron.train` on the device trainer, `fit_poly` on HIP kernel rows and `poly_score` on the fused
-kernel with the URDF tree inside it.  What is NOT here is the ground truth: the reference derives labels from
-FCL/trimesh collision geometry (`robot.collision(q, other=environment)`); diffco_amd has no geometry engine, so the
-caller passes labels or a `gt_check_func(q) -> {0,1}[N]`.
+kernel with the URDF tree inside it.  The ground truth enters as labels or as a `gt_check_func(q) -> {0,1}[N]`: the
+reference derives labels from FCL/trimesh collision geometry (`robot.collision(q, other=environment)`); here
+`diffco_amd.geometry.SphereWorldChecker` - a sphere model of the robot against a world of primitives, one fused HIP
+launch - is such a callable (meshes and `environment=` stay out of scope).
 """
 import os
 import time
@@ -41,8 +42,8 @@ class CollisionChecker:
 
     def _ground_truth(self, q):
         if self.gt_check_func is None:
-            raise ValueError("no ground truth available: diffco_amd has no geometric collision checker, pass labels "
-                             "or construct the checker with gt_check_func")
+            raise ValueError("no ground truth available: pass labels or construct the checker with gt_check_func "
+                             "(diffco_amd.geometry.SphereWorldChecker is one)")
         return self.gt_check_func(q)
 
     def collision(self, q):

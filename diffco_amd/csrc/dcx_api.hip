@@ -20,6 +20,7 @@
 #include "solve_kernels.h"
 #include "traj_dense.h"
 #include "knn_kernel.h"
+#include "geom_kernel.h"
 #include "rrt_kernel.h"
 #include "rrtstar_kernel.h"
 #include "rrtstar_cost_kernel.h"
@@ -2483,6 +2484,57 @@ int dcx_kernel_matrix(int device, int kernel_kind, const float* kparams, const f
                                             (hipStream_t)stream);
         if (e != hipSuccess) return fail_hip(e, "kernel_matrix launch");
     }
+    return DCX_OK;
+}
+
+// ---- geometric ground truth (geom_kernel.h): a sphere model of the robot against a world of primitives --------------------------
+int dcx_geom_clearance(int device, const dcx_fk_desc* spheres_fk, const float* radii, const dcx_geom_obstacle* obstacles, int64_t O,
+                       const float* q, int64_t B, const dcx_geom_opts* opt, float* clearance, int32_t* witness, float* grad,
+                       void* stream) {
+    if (!spheres_fk) return fail(DCX_ERR_INVALID, "geom: spheres_fk is NULL");
+    if (!opt) return fail(DCX_ERR_INVALID, "geom: options are NULL");
+    if (B < 0 || O < 0) return fail(DCX_ERR_INVALID, "geom: B < 0 or O < 0");
+    if (opt->reserved) return fail(DCX_ERR_INVALID, "geom: reserved fields must be 0");
+    if (opt->n_groups < 1 || opt->n_groups > DCX_MAX_C) return fail(DCX_ERR_INVALID, "geom: n_groups must be in [1, DCX_MAX_C]");
+    if (opt->sphere_base < 0) return fail(DCX_ERR_INVALID, "geom: sphere_base < 0");
+    if (opt->accumulate != 0 && opt->accumulate != 1) return fail(DCX_ERR_INVALID, "geom: accumulate must be 0 or 1");
+    const dcx_fk_desc& fk = *spheres_fk;
+    if (fk.kind == DCX_FK_NONE || (fk.point_dim != 2 && fk.point_dim != 3) || fk.n_points < 1 || fk.n_points > DCX_MAX_POINTS)
+        return fail(DCX_ERR_INVALID, "geom: the spheres' description needs 1 .. DCX_MAX_POINTS points of dimension 2 or 3");
+    if (int rc = check_fk(fk)) return rc;
+    if (B > 0 && (!radii || !q || !clearance)) return fail(DCX_ERR_INVALID, "geom: radii / q / clearance is NULL");
+    if (B > 0 && O > 0 && !obstacles) return fail(DCX_ERR_INVALID, "geom: obstacles is NULL");
+    if (O > INT32_MAX) return fail(DCX_ERR_UNSUPPORTED, "geom: more than 2^31 - 1 obstacles");
+    if ((B + 63) / 64 > INT32_MAX) return fail(DCX_ERR_UNSUPPORTED, "geom: B too large for one launch");
+    const size_t lds = geom_lds_bytes(fk, opt->n_groups);
+    if (lds > kGeomMaxLdsBytes) return fail(DCX_ERR_UNSUPPORTED, "geom: the description needs more than 64 KiB of LDS per block");
+    if (B == 0) return DCX_OK;
+    if (int rc = set_device(device)) return rc;
+    FkProg* dev = nullptr;
+    if (int rc = fk_device_copy(device, fk, &dev)) return rc;
+    GeomArgs a{};
+    a.fk = dev;
+    a.radii = radii;
+    a.obst = reinterpret_cast<const float*>(obstacles);
+    a.O = O;
+    a.q = q;
+    a.B = B;
+    a.clearance = clearance;
+    a.witness = witness;
+    a.grad = grad;
+    a.dof = fk.dof;
+    a.n_points = fk.n_points;
+    a.point_dim = fk.point_dim;
+    a.d_fk = fk.n_points * fk.point_dim;
+    a.frame_floats = fk_frame_floats(fk);
+    const bool coord_major = fk.kind == DCX_FK_TREE && fk.t_coord_major;
+    a.pt_stride = coord_major ? 1 : fk.point_dim;
+    a.coord_stride = coord_major ? fk.n_points : 1;
+    a.n_groups = opt->n_groups;
+    a.sphere_base = opt->sphere_base;
+    a.accumulate = opt->accumulate;
+    const hipError_t e = launch_geom_clearance(a, lds, (hipStream_t)stream);
+    if (e != hipSuccess) return fail_hip(e, "geom_clearance launch");
     return DCX_OK;
 }
 

@@ -7,7 +7,8 @@ BaxterDualArmFK 310-386, PandaFK 390-453 (robot_fkine.py:388-444 for the 5-point
 DualPandaFK 456-502, PointRobot1D 505-.  The numbers below (link lengths, DH tables, joint limits)
 restate the reference's robot definitions; the FK itself runs in HIP (`dcx_fkine`, differentiable
 through `dcx_fkine_vjp`), and when a robot's `fkine` is handed to DiffCo as `transform` the chain is
-fused into the score kernel.  Ground-truth geometry (`update_polygons`, FCL) is out of scope.
+fused into the score kernel.  Ground-truth geometry as the reference has it (`update_polygons`, FCL) is out of scope;
+`diffco_amd.geometry` puts spheres on these robots' frames and checks them against a world of primitives.
 """
 import math
 

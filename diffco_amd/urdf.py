@@ -271,7 +271,8 @@ class URDFRobotFK:
         robot.fkine(q)            # [B, 3, L] link-origin features, HIP forward + vjp; pass `robot.fkine` as
                                   # DiffCo's `transform` and the tree is fused into the score kernel
 
-    Ground-truth collision geometry (meshes, FCL) is outside diffco_amd's scope."""
+    Ground-truth collision geometry as the URDF states it (meshes, FCL) is outside diffco_amd's scope;
+    `diffco_amd.geometry.RobotSpheres` attaches spheres to any link of this robot."""
 
     def __init__(self, urdf, name="", base_transform=None, coord_major=True):
         self.name = name

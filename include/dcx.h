@@ -1401,6 +1401,47 @@ int dcx_euler_frames_vjp(int device, const float* phi, const float* gR, int64_t 
 int dcx_kernel_matrix(int device, int kernel_kind, const float* kparams, const float* x, int64_t B,
                       const float* s, int64_t S, int32_t D, float* K, void* stream);
 
+/* ---- geometric ground truth (added under DCX_VERSION 109) -------------------------------------------------- */
+/* A sphere model of the robot against a world of primitives: the true collision labels the proxy is trained on and verified
+ * against, computed on the device.  The reference takes them from FCL / trimesh (ShapeEnv, collision_interfaces/
+ * env_interface.py:35-122: Box, Sphere, Cylinder, Capsule by `extents` / `radius` / `height` and a 4x4 transform) through its
+ * checkers (collision_checkers.py:28-125); meshes are not part of this library.
+ *
+ * The robot's spheres are the control points of `spheres_fk` (M = n_points <= DCX_MAX_POINTS, point_dim 2 or 3; 2 means z = 0)
+ * with radii[k]; an obstacle is one 64-byte row: with the local point l = R^T (p - c),
+ *   DCX_GEOM_SPHERE    p = (rho, -, -)          d = |l| - rho
+ *   DCX_GEOM_BOX       p = half extents h       u = |l| - h (per axis);  d = |max(u, 0)| + min(max(u_x, u_y, u_z), 0)
+ *   DCX_GEOM_CAPSULE   p = (rho, hl, -)         d = |l - (0, 0, clamp(l_z, -hl, hl))| - rho     (hl: half the axis segment, local z)
+ *   DCX_GEOM_CYLINDER  p = (rho, hl, -)         a = hypot(l_x, l_y) - rho, b = |l_z| - hl;  d = min(max(a, b), 0) + |max((a, b), 0)|
+ * type_group = DCX_GEOM_TYPE_GROUP(type, group); rt: the rows of R^T, row-major.
+ *
+ * clearance[b, g] = min over spheres k and obstacles o of group g of d_o(p_k(q_b)) - radii[k]; witness[b, g] = (o, k +
+ * opt->sphere_base) of the first pair, in (obstacle, sphere) loop order, that attains it under a strict <.  A group without
+ * obstacles (O = 0 as well) gives +inf and (-1, -1); rows whose group is outside [0, n_groups) or whose type is unknown are
+ * ignored.  grad[b] = d min_g clearance[b, g] / d q_b: the unit normal of the witness pair's solid at the sphere's centre through
+ * the transform's J^T, in the same launch; where the normal is undefined (|l| = 0 for a sphere or on a capsule's axis segment, a
+ * point on a cylinder's axis, a box's medial planes) a fixed choice or zero, never NaN; zeros where there is no witness.
+ * opt->accumulate = 1: clearance / witness / grad hold an earlier call's results for the same q and obstacles (another chunk of
+ * the robot's spheres); an entry is overwritten only where this call's is strictly smaller, the gradient row only where this
+ * call's overall minimum is strictly smaller than the one there.  Robots with more than DCX_MAX_POINTS spheres take one call
+ * per chunk on one stream.
+ * No allocation, no synchronisation, no atomics, nothing read back: capturable once `spheres_fk`'s program is on the device (the
+ * first call with a description uploads it, as dcx_fkine).  DCX_ERR_INVALID: a NULL argument that is needed, B < 0, O < 0, a
+ * reserved field not 0, n_groups outside [1, DCX_MAX_C], sphere_base < 0, accumulate not 0 / 1, a description whose points are
+ * not 2- or 3-dimensional.  DCX_ERR_UNSUPPORTED: O above 2^31 - 1, a description whose block needs more than 64 KiB of LDS. */
+#define DCX_GEOM_SPHERE 0
+#define DCX_GEOM_BOX 1
+#define DCX_GEOM_CAPSULE 2
+#define DCX_GEOM_CYLINDER 3
+#define DCX_GEOM_TYPE_GROUP(type, group) ((int32_t)(type) | ((int32_t)(group) << 8))
+typedef struct dcx_geom_obstacle { int32_t type_group; float rt[9]; float c[3]; float p[3]; } dcx_geom_obstacle;   /* 64 bytes */
+typedef struct dcx_geom_opts { int32_t n_groups, sphere_base, accumulate, reserved; } dcx_geom_opts;
+/* stands in for ShapeEnv's collision queries (env_interface.py:35-122) as the checkers call them (collision_checkers.py:28-125) */
+int dcx_geom_clearance(int device, const dcx_fk_desc* spheres_fk, const float* radii /*[M] device*/,
+                       const dcx_geom_obstacle* obstacles /*[O] device*/, int64_t O, const float* q, int64_t B,
+                       const dcx_geom_opts* opt, float* clearance /*[B, G]*/, int32_t* witness /*[B, G, 2] or NULL*/,
+                       float* grad /*[B, dof] or NULL*/, void* stream);
+
 /* x with A x = B: the S x S system fit_poly ends in (torch.linalg.solve at kernel_perceptrons.py:283, deprecated/DiffCo.py:162,
  * deprecated/MultiDiffCo.py:151 - add `reg` to A's diagonal first).  LU with partial pivoting in fp64, ONE launch.
  * A [n, n], B [n, nrhs] -> X [n, nrhs], all row-major fp32 on the device; 1 <= n <= DCX_SOLVE_MAX_N, 1 <= nrhs <= 64.
